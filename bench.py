@@ -324,6 +324,67 @@ def self_launch(args):
     return rc
 
 
+DUMP_SAMPLE = 1 << 18  # elements kept of a longer per-chunk / per-block output
+DUMP_BYTES_SAMPLE = 1 << 20  # bytes kept of each serialized index
+DUMP_IMAGE_BYTES = 1 << 20  # bytes kept of the last codec batch's stored-block images
+
+
+def dump_sample(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k out of n (all of them when n <= k): the same n gives the same sample."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, ing, res, total, out_offs, out_lens, out_hash, first, h_vi, h_si, comp_sizes, arena):
+    """--dump-outputs: what the timed path delivered in its last step, as DIR/<name>.npy in float64 (float32 for bytes), under
+    64 MB in all (checked).  Unsigned integers up to 32 bits are exact in float64, so a 64-bit chunk hash is written as its two 32-bit
+    halves; a longer output is a fixed, seeded sample whose indices are written beside it (<name>_index).
+      summary              chunks_all, unique_all, blocks, raw_bytes, compressed_bytes, version_index_size, store_index_size
+      chunk_*              this rank's chunks (lthip_chunk_hash): offset into the input, length, hash [lo, hi]; part_first_chunk
+      version_index_bytes  the serialized VersionIndex (host memory), store_index_bytes the serialized StoreIndex
+      block_compressed_sizes  every block's payload size; image_bytes  the stored-block images of the last codec batch (device arena)"""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"summary": np.array([res.chunks_all, res.unique_all, res.blocks, res.raw_bytes, res.compressed_bytes,
+                                   res.version_index_size, res.store_index_size], dtype=np.float64),
+              "part_first_chunk": first.astype(np.float64)}
+    import torch
+
+    def gather(t, i):  # elements i of a device tensor, on the host (indices checked here, not by a device-side assert)
+        assert len(i) == 0 or (int(i.min()) >= 0 and int(i.max()) < t.numel()), "--dump-outputs: sample index out of range"
+        return t[torch.from_numpy(i).to(t.device)].cpu().numpy()
+
+    idx = dump_sample(total, DUMP_SAMPLE, 1)
+    h = gather(out_hash, idx).view(np.uint64)
+    arrays.update(chunk_index=idx.astype(np.float64), chunk_offsets=gather(out_offs, idx).astype(np.float64),
+                  chunk_lengths=gather(out_lens, idx).view(np.uint32).astype(np.float64),
+                  chunk_hashes=np.stack([h & np.uint64(0xFFFFFFFF), h >> np.uint64(32)], axis=1).astype(np.float64))
+    for name, host, size, seed in (("version_index", h_vi, res.version_index_size, 2), ("store_index", h_si, res.store_index_size, 3)):
+        if host is None:
+            continue
+        i = dump_sample(int(size), DUMP_BYTES_SAMPLE, seed)
+        arrays[f"{name}_bytes"] = host.numpy()[i].astype(np.float32)
+        arrays[f"{name}_bytes_index"] = i.astype(np.float64)
+    i = dump_sample(len(comp_sizes), DUMP_SAMPLE, 4)
+    arrays["block_compressed_sizes"] = comp_sizes[i].astype(np.float64)
+    arrays["block_compressed_sizes_index"] = i.astype(np.float64)
+    first_block, img_off, img_size = ing.images()
+    ends = np.cumsum(img_size.astype(np.int64))
+    i = dump_sample(int(ends[-1]) if len(ends) else 0, DUMP_IMAGE_BYTES, 5)  # positions in the images laid end to end
+    which = np.searchsorted(ends, i, side="right")
+    at = img_off.astype(np.int64)[which] + i - (ends[which] - img_size.astype(np.int64)[which]) if len(i) else i
+    arrays["image_first_block"] = np.array([first_block], dtype=np.float64)
+    arrays["image_sizes"] = img_size.astype(np.float64)
+    arrays["image_bytes"] = gather(arena, at).astype(np.float32)
+    arrays["image_bytes_index"] = i.astype(np.float64)
+    total_bytes = sum(a.nbytes for a in arrays.values())
+    assert total_bytes <= 64 << 20, f"--dump-outputs: {total_bytes} bytes, over the 64 MB bound"
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return sorted(arrays)
+
+
 class Bench:
     """Device buffers shared by the configurations measured in one process."""
 
@@ -720,8 +781,9 @@ class Bench:
         return out
 
     # ------------------------------------------------------------------------------------------------------------
-    def run(self, cfg, steps, warmup):
-        """cfg: dict(tree, kind, codec, gib, file_mib, scaling, partition).  Returns the measurements of this configuration."""
+    def run(self, cfg, steps, warmup, dump_dir=None):
+        """cfg: dict(tree, kind, codec, gib, file_mib, scaling, partition).  Returns the measurements of this configuration.
+        dump_dir: write what the last timed step computed there (rank 0; dump_outputs)."""
         torch, args, ctx, world, rank = self.torch, self.args, self.ctx, self.world, self.rank
         from longtail_amd.dist import JobPartition, exchange_chunks, sharded_first_seen
         from longtail_amd.lib import Ingest, chunker_params
@@ -833,7 +895,7 @@ class Bench:
             t4 = time.perf_counter()
             if os.environ.get("LTHIP_BENCH_TRACE"):
                 print(f"step: write (host) {1e3*(t3b-t3):.2f} finish {1e3*(t4-t3b):.2f} ms", file=sys.stderr)
-            stats.update(res=res, t=(t1 - t0, t2 - t1, t3 - t2, t4 - t3))
+            stats.update(res=res, t=(t1 - t0, t2 - t1, t3 - t2, t4 - t3), total=total)
 
         for _ in range(warmup):
             step()
@@ -860,6 +922,9 @@ class Bench:
             elapsed = float(self.reduce([elapsed], "max")[0])
             comp, blocks, raw = (int(round(x)) for x in self.reduce([comp, blocks, raw]))
         sizes = ing.compressed_sizes(res.blocks)
+        if dump_dir is not None and rank == 0:
+            first = h_first.numpy()[: len(mine) + 1].view(np.uint32)
+            dump_outputs(dump_dir, ing, res, stats["total"], out_offs, out_lens, out_hash, first, h_vi, h_si, sizes, arena)
         ing.close()
         plan.close()
 
@@ -1049,6 +1114,9 @@ def make_parser():
     ap.add_argument("--handshake-only", action="store_true",
                     help="plain launch only: id file + lthip_comm_create + barrier + reductions + one all-to-all, then a JSON line; no kernels")
     ap.add_argument("--cpu-gib", type=float, default=8.0, help="sample size of the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed (chunk hashes, lengths and offsets, the "
+                         "serialized indexes, block sizes, stored-block image bytes; seeded samples of long ones) as DIR/<name>.npy")
     ap.add_argument("--exchange-profile", action="store_true",
                     help="N > 1: split the exchange + index phases of every step into host / device / transport time (waits for the device at "
                          "every mark: a breakdown, not the metric; tools/exchange_cost.py)")
@@ -1083,7 +1151,7 @@ def main():
                partition=args.partition, dups=args.dups)
     if b.world == 1 and not under_profiler:
         b.measure_peak(4 if args.gib >= 8 else 1)
-    main_res = b.run(cfg, args.steps, args.warmup)
+    main_res = b.run(cfg, args.steps, args.warmup, dump_dir=args.dump_outputs)
     secondary = None
     default_headline = args.tree == "files" and args.kind == "random" and args.codec == "lz4" and not args.no_compress
     # the reference's CPU path beside EVERY number ("same tree on W cores"): one CpuReference for the headline and the

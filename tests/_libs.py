@@ -356,3 +356,57 @@ def ref() -> Ref:
     if _ref is None:
         _ref = Ref()
     return _ref
+
+
+# ---- reference results that travel with the repository ----
+REF_RESULTS = GOLDEN / "ref_results.json"
+
+
+def digest(*parts) -> str:
+    """sha256 (hex, 32 digits) of numpy arrays (bytes + dtype + shape) and plain values, in order."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for p in parts:
+        if isinstance(p, np.ndarray):
+            a = np.ascontiguousarray(p)
+            h.update(f"{a.dtype.str}{a.shape}".encode())
+            h.update(a.tobytes())
+        else:
+            h.update(repr(p).encode())
+        h.update(b"\0")
+    return h.hexdigest()[:32]
+
+
+class RefResults:
+    """One small result of the reference library per call: computed by oracle/_ref where it was built (and written to
+    tests/golden/ref_results.json with LTHIP_RECORD_REF=1), read back from that file everywhere else.  A call is keyed by its
+    name and a digest of its inputs; the callable returns a JSON value (digests stand in for long arrays)."""
+
+    def __init__(self):
+        import json
+        import os
+
+        self.table = json.loads(REF_RESULTS.read_text()) if REF_RESULTS.exists() else {}
+        self.live = ref() if have_ref() else None
+        self.record = self.live is not None and os.environ.get("LTHIP_RECORD_REF") == "1"
+
+    def __call__(self, name: str, inputs, fn):
+        import json
+
+        key = f"{name}:{digest(*inputs)}"
+        if self.live is not None:
+            value = json.loads(json.dumps(fn(self.live)))
+            if self.record:
+                self.table[key] = value
+            return value
+        if key not in self.table:
+            raise AssertionError(f"no recorded reference result for {key}: the inputs changed, record them again where oracle/_ref is "
+                                 "built (LTHIP_RECORD_REF=1 python -m pytest tests -m 'not gpu')")
+        return self.table[key]
+
+    def save(self):
+        import json
+
+        if self.record:
+            REF_RESULTS.write_text(json.dumps(self.table, indent=0, sort_keys=True) + "\n")

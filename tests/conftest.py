@@ -31,6 +31,16 @@ def ref():
 
 
 @pytest.fixture(scope="session")
+def refcall():
+    """Results of the reference library: live where oracle/_ref is built, else from tests/golden/ref_results.json (tests._libs.RefResults)."""
+    from tests._libs import RefResults
+
+    r = RefResults()
+    yield r
+    r.save()
+
+
+@pytest.fixture(scope="session")
 def golden():
     import json
 

@@ -24,15 +24,16 @@ def test_plugin_layer_is_clean_under_asan_and_ubsan():
     assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr
 
 
-def test_plugin_layer_is_clean_under_tsan():
+def test_plugin_layer_is_clean_under_tsan(tmp_path):
     """The same driver under ThreadSanitizer: 12 threads on one chunker API with a tiny window pool, the two batchers' hand-overs, the
     codec dispatcher, and chunkers DISPOSED FROM ANOTHER THREAD while the thread that drew their last chunk goes on calling HashBuffer
     (the registry's lock-free look-up counts itself in before it reads a slot; a writer waits for the count to drain)."""
     if not shutil.which("gcc"):
         pytest.skip("no gcc")
-    probe = subprocess.run(["gcc", "-fsanitize=thread", "-x", "c", "-", "-o", "/tmp/lthip_tsan_probe"], input="int main(){return 0;}",
+    exe = tmp_path / "tsan_probe"  # (a fixed name in /tmp may belong to another user)
+    probe = subprocess.run(["gcc", "-fsanitize=thread", "-x", "c", "-", "-o", str(exe)], input="int main(){return 0;}",
                            capture_output=True, text=True)
-    if probe.returncode != 0 or subprocess.run(["/tmp/lthip_tsan_probe"]).returncode != 0:
+    if probe.returncode != 0 or subprocess.run([str(exe)]).returncode != 0:
         pytest.skip("gcc lacks a working ThreadSanitizer runtime here")
     out = subprocess.run(["make", "-C", str(SAN), "run-tsan"], capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
