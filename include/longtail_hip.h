@@ -44,6 +44,15 @@ LTHIP_EXPORT struct Longtail_ChunkerAPI* Longtail_CreateHipChunkerAPI(void);
  * GPU already computed; any other buffer is hashed on the GPU on demand. */
 LTHIP_EXPORT struct Longtail_HashAPI* Longtail_CreateHipBlake3HashAPI(void);
 
+/* Replaces Longtail_CreateBlake2HashAPI() (lib/blake2/longtail_blake2.h, implementation longtail_blake2.c).  GetIdentifier ->
+ * 0x626c6b32 ('blk2'); digests are unkeyed BLAKE2s with an 8-byte output read as a little-endian u64 (blake2s(out, 8, data, len,
+ * 0, 0), longtail_blake2.c).  HashBuffer, BeginContext / Hash / EndContext behave as the BLAKE3 object's: O(1) host state per
+ * context, EndContext failures latched for Longtail_Hip_GetLastError.  Paired with a HIP chunker: the window's chunks get a BLAKE2
+ * digest table, filled by the first HashBuffer of one of them (one lthip_blake2s_ranges over the whole window, from the window's
+ * device copy or uploaded again from the pinned window); later HashBuffer calls of the window read it.  Other buffers are hashed on
+ * the GPU one by one (lthip_blake2s_one up to 64 KiB).  The chunker itself still computes BLAKE3 digests, unused here. */
+LTHIP_EXPORT struct Longtail_HashAPI* Longtail_CreateHipBlake2HashAPI(void);
+
 /* WHEN TO CONSTRUCT THE CODEC OBJECTS.  One stored block per Compress call crosses the link twice: the HIP codec objects pay on data that
  * compresses -- WriteContent at 32 bikeshed workers: LZ4 31-47 GB/s against the reference codec's 22-25, ZStd 33-35 against 7-14 -- and
  * lose on incompressible bytes, where the CPU's LZ4 is a memcpy (25-29 against 56-105 GB/s): there bind the reference's own LZ4 beside
@@ -156,7 +165,8 @@ enum lthip_kernel_id
     LTHIP_K_OTHER = 7,
     LTHIP_K_ZSTD_ENC = 8, /* zstd entropy stage (Huffman literals, FSE sequences), one wave per 128 KiB piece */
     LTHIP_K_GATHER = 9,   /* device block assembly: chunk ranges -> contiguous block images (src/longtail.c:4640-4721) */
-    LTHIP_K_COUNT = 10
+    LTHIP_K_BLAKE2S = 10, /* BLAKE2s-64 ('blk2'): ranges, one input, streaming (lib/blake2/longtail_blake2.c) */
+    LTHIP_K_COUNT = 11
 };
 LTHIP_EXPORT int lthip_timing_enable(lthip_ctx* ctx, int on);
 LTHIP_EXPORT int lthip_timing_reset(lthip_ctx* ctx);
@@ -239,6 +249,39 @@ LTHIP_EXPORT int lthip_hash_runs_u64_bounded(lthip_ctx* ctx, const uint64_t* d_v
                                              uint64_t total_values_bound, uint64_t run_values_bound, uint64_t* d_out);
 LTHIP_EXPORT int lthip_hash_runs_u64(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count,
                                      uint64_t* d_out);
+
+/* ---- BLAKE2s-64, the 'blk2' hash type (k_blake2s.hip) ----------------------------------------------------------------------
+ * Digest = the first 8 bytes of unkeyed BLAKE2s with outlen 8, as a little-endian u64 (longtail_blake2.c: blake2s(out, 8, data, len,
+ * 0, 0)); == int.from_bytes(hashlib.blake2s(data, digest_size=8).digest(), "little").  Same contracts as the BLAKE3 entry points above.
+ * lthip_blake2s_ranges: d_hashes[i] = blake2s(d_data + d_offsets[i], d_lens[i]); len 0 is legal, ranges may overlap and start at any
+ * byte.  max_len is accepted for symmetry with lthip_hash_ranges and may be 0.  Never waits for the device.
+ * lthip_blake2s_ranges_dev: the number of ranges is min(count_bound, *d_count) with d_count on the device -- e.g. d_part_first +
+ * part_count of lthip_chunk_hash(..., d_chunk_hashes = NULL, ...) with count_bound = lthip_plan_chunk_capacity: BLAKE2 chunk hashes
+ * queued behind the chunker without a host synchronisation. */
+LTHIP_EXPORT int lthip_blake2s_ranges(lthip_ctx* ctx, const void* d_data, uint64_t range_count, const uint64_t* d_offsets,
+                                      const uint32_t* d_lens, uint32_t max_len, uint64_t* d_hashes);
+LTHIP_EXPORT int lthip_blake2s_ranges_dev(lthip_ctx* ctx, const void* d_data, uint64_t count_bound, const uint32_t* d_count,
+                                          const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t max_len, uint64_t* d_hashes);
+/* ONE input of at most 64 KiB read where it lies, as lthip_hash_one (pinned host or device memory for `in` and `out`, any alignment);
+ * EINVAL above 64 KiB.  Asynchronous on the context's stream. */
+LTHIP_EXPORT int lthip_blake2s_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
+/* BLAKE2s-64 of runs of 64-bit values, the contracts of lthip_hash_runs_u64[_bounded] (the bounds only spare the BLAKE3 call its read-back;
+ * the BLAKE2s call never reads back and ignores them). */
+LTHIP_EXPORT int lthip_blake2s_runs_u64_bounded(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count,
+                                                uint64_t total_values_bound, uint64_t run_values_bound, uint64_t* d_out);
+LTHIP_EXPORT int lthip_blake2s_runs_u64(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count,
+                                        uint64_t* d_out);
+/* Streaming BLAKE2s-64 with O(1) state (Blake2Hash_BeginContext/_Hash/_EndContext).  The state is LTHIP_B2S_STREAM_STATE_BYTES of
+ * device memory ({h[8], bytes so far}; no initialisation needed).  The caller cuts the stream into batches of LTHIP_B2S_STREAM_BATCH
+ * bytes (device memory, 16-byte aligned) and calls lthip_b2s_stream_batch for them in order -- a batch only when at least one byte
+ * follows it, because BLAKE2 marks the LAST block of the stream -- then lthip_b2s_stream_final with the rest (1 .. one batch of bytes,
+ * or 0 bytes after 0 batches: the empty stream).  d_out: device or pinned host memory.  Asynchronous on the context's stream.  One
+ * stream is one serial chain of 64-byte compressions on one quad of lanes: a batch costs its 16 384 compressions back to back. */
+#define LTHIP_B2S_STREAM_BATCH (1u << 20)
+#define LTHIP_B2S_STREAM_STATE_BYTES 64u
+LTHIP_EXPORT int lthip_b2s_stream_batch(lthip_ctx* ctx, const void* d_data, uint64_t batch_index, void* d_state);
+LTHIP_EXPORT int lthip_b2s_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint64_t batch_count, void* d_state,
+                                        uint64_t* d_out);
 
 /* ---- phase 2: per-block compression ----------------------------------------------------------------
  * One call compresses a batch of stored blocks (the unit of CompressBlock, compressblockstore.c:67-141).
@@ -368,8 +411,10 @@ LTHIP_EXPORT int lthip_dedup_min_ordinal(lthip_ctx* ctx, uint64_t count, const u
 /* ---- bulk Longtail_CreateVersionIndex tail (src/longtail.c:2808-3017, layout :2551-2584, :2709-2806) ---
  * From the device-resident chunk lists of lthip_chunk_hash -- all assets' chunks concatenated in (asset, part, chunk) order,
  * asset a owning asset_chunk_counts[a] of them -- to the SERIALIZED VersionIndex (the bytes Longtail_WriteVersionIndexToBuffer
- * produces, :3415): first-seen unique chunk list + per-asset-chunk indexes, content hash per asset (BLAKE3 of its chunk-hash
- * array), path hashes.  The file list is a struct Longtail_FileInfos taken apart (src/longtail.h:1684-1692); directories are
+ * produces, :3415): first-seen unique chunk list + per-asset-chunk indexes, content hash per asset (hash of its chunk-hash
+ * array), path hashes.  HASH TYPE: path, content and block hashes of this and the two builders below are BLAKE2s-64 when
+ * hash_identifier is 'blk2' (0x626c6b32) and BLAKE3-64 for any other identifier ('blk3' and, as before, everything else); the
+ * chunk hashes are the caller's and must be of the same type.  The file list is a struct Longtail_FileInfos taken apart (src/longtail.h:1684-1692); directories are
  * assets with zero chunks.  Host arrays unless marked d_.  Returns ENOMEM with *out_size set when `out` is too small. */
 LTHIP_EXPORT size_t lthip_version_index_size(uint32_t asset_count, uint64_t unique_chunk_count, uint64_t asset_chunk_index_count,
                                              uint32_t path_data_size);
@@ -398,7 +443,8 @@ LTHIP_EXPORT int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block
  * Longtail_CreateStoreIndex :6745-6880) -------------------------------------------------------------------------------
  * Which of the version's chunks (unique list, version order: device hashes + sizes, host tags or NULL) does a store holding
  * d_existing_hashes lack, and how are they packed into blocks?  Output: the serialized StoreIndex of the missing content
- * (the bytes Longtail_WriteStoreIndexToBuffer produces: blocks with their BLAKE3 block hashes, chunk lists, tags).
+ * (the bytes Longtail_WriteStoreIndexToBuffer produces: blocks with their block hashes -- of hash_identifier's type, see above --,
+ * chunk lists, tags).
  * Returns ENOMEM with *out_size set when `out` is too small. */
 LTHIP_EXPORT int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_count, const uint64_t* d_existing_hashes,
                                               uint64_t chunk_count, const uint64_t* d_chunk_hashes, const uint32_t* d_chunk_lens,
@@ -446,7 +492,8 @@ typedef struct lthip_ingest lthip_ingest;
 typedef struct lthip_ingest_config
 {
     uint32_t target_chunk_size;    /* recorded in the VersionIndex */
-    uint32_t hash_identifier;      /* 0x626c6b33 */
+    uint32_t hash_identifier;      /* 0x626c6b33 'blk3', or 0x626c6b32 'blk2': path / content / block hashes with BLAKE2s (the caller's
+                                      chunk hashes then come from lthip_blake2s_ranges[_dev]) */
     uint32_t max_block_size;       /* cmd/main.c:3006-3009 defaults: 8 MiB */
     uint32_t max_chunks_per_block; /*                                 1024  */
     uint32_t compression_type;     /* the tag stored with chunks and blocks: 'lz42', 'ztd1'..'ztd5' */

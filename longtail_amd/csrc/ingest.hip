@@ -411,7 +411,7 @@ static int ingest_blocks_done(lthip_ingest* g)
         }
         if ((err = lthip_stage_upload(ctx, g->d_boff.p, o.data(), nb * 8, s)) || (err = lthip_stage_upload(ctx, g->d_blen.p, l.data(), nb * 4, s)))
             return err;
-        if ((err = lthip_hash_ranges_known(ctx, g->d_mu_hash.p, nb, (const uint64_t*)g->d_boff.p, (const uint32_t*)g->d_blen.p, max_len, leaves,
+        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, g->d_mu_hash.p, nb, (const uint64_t*)g->d_boff.p, (const uint32_t*)g->d_blen.p, max_len, leaves,
                                            (uint64_t*)g->d_bhash.p)))
             return err;
         LTHIP_CHECK(ctx, hipMemcpyAsync(g->h_bhash.p, g->d_bhash.p, nb * 8, hipMemcpyDeviceToHost, s));
@@ -454,8 +454,8 @@ static int ingest_vi_work(lthip_ingest* g, lthip_ctx* ctx)
         if ((err = lthip_stage_upload(ctx, g->d_aoff.p, h_off.data(), (size_t)na * 8, s)) ||
             (err = lthip_stage_upload(ctx, g->d_alen.p, h_len.data(), (size_t)na * 4, s)))
             return err;
-        if ((err = lthip_hash_ranges(ctx, n ? (const void*)d_all_hashes : g->d_paths.p, na, (const uint64_t*)g->d_aoff.p,
-                                     (const uint32_t*)g->d_alen.p, max_len, (uint64_t*)g->d_ch.p)))
+        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, n ? (const void*)d_all_hashes : g->d_paths.p, na, (const uint64_t*)g->d_aoff.p,
+                                     (const uint32_t*)g->d_alen.p, max_len, 0u, (uint64_t*)g->d_ch.p)))
             return err;
         max_len = 0;
         for (uint32_t a = 0; a < na; ++a)
@@ -472,7 +472,7 @@ static int ingest_vi_work(lthip_ingest* g, lthip_ctx* ctx)
             (err = lthip_stage_upload(ctx, g->d_aoff.p, h_off.data(), (size_t)na * 8, s)) ||
             (err = lthip_stage_upload(ctx, g->d_alen.p, h_len.data(), (size_t)na * 4, s)))
             return err;
-        if ((err = lthip_hash_ranges(ctx, g->d_paths.p, na, (const uint64_t*)g->d_aoff.p, (const uint32_t*)g->d_alen.p, max_len,
+        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, g->d_paths.p, na, (const uint64_t*)g->d_aoff.p, (const uint32_t*)g->d_alen.p, max_len, 0u,
                                      (uint64_t*)g->d_ph.p)))
             return err;
     }

@@ -108,6 +108,7 @@ enum ScratchSlot
     S_SLICE_LENS,
     S_SLICE_HASH,
     S_SLICE_FIRST,
+    S_B2_ORDER,     // BLAKE2s ranges: class histogram, cursors and the length-class order of the ranges
     S_COUNT
 };
 
@@ -276,6 +277,20 @@ int lthip_launch_blake3_stream_batch(lthip_ctx* ctx, const void* d_data, uint32_
 int lthip_launch_blake3_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint32_t leaf0, const uint32_t* d_stack,
                                      uint32_t depth, uint64_t* d_out);
 int lthip_launch_blake3_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
+
+// BLAKE2s-64 (k_blake2s.hip) of count ranges (count = min(count_bound, *d_count) when d_count != null); never reads anything back
+int lthip_launch_blake2s(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
+                         uint64_t count_bound, uint64_t* d_hashes);
+int lthip_launch_blake2s_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
+int lthip_launch_blake2s_stream(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out);
+
+// The hash of a longtail hash type over device ranges: what the index builders call for path hashes, asset content hashes and block
+// hashes.  'blk2' (LTHIP_HASH_BLAKE2) runs BLAKE2s; every other identifier runs BLAKE3, exactly the code path of lthip_hash_ranges /
+// lthip_hash_ranges_known (leaf_total 0 = unknown).
+constexpr uint32_t LTHIP_HASH_BLAKE3 = 0x626c6b33u; // 'blk3', lib/blake3/longtail_blake3.c
+constexpr uint32_t LTHIP_HASH_BLAKE2 = 0x626c6b32u; // 'blk2', lib/blake2/longtail_blake2.c
+int lthip_hash_ranges_by_id(lthip_ctx* ctx, uint32_t hash_identifier, const void* d_data, uint64_t range_count, const uint64_t* d_offsets,
+                            const uint32_t* d_lens, uint32_t max_len, uint64_t leaf_total, uint64_t* d_hashes);
 
 int lthip_launch_from_buffer(lthip_ctx* ctx, const uint8_t* d_data, uint32_t n, uint32_t min_chunk, const DivTest& dv,
                              uint64_t* d_out);

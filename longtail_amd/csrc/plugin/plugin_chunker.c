@@ -149,6 +149,7 @@ static int chunker_refill(struct HipChunker* c, Longtail_Chunker_Feeder feeder, 
             return err;
         if (total > w->ccap)
             return EIO;
+        w->d_resident = 0; /* chunked in the batcher's arena */
     }
     else
     {
@@ -167,6 +168,7 @@ static int chunker_refill(struct HipChunker* c, Longtail_Chunker_Feeder feeder, 
         if (!err) err = lthip_ctx_sync(ctx);
         if (err)
             return err;
+        w->d_resident = 1;
     }
     c->ntotal = (uint32_t)total;
     if (c->eof)
@@ -187,6 +189,8 @@ static int chunker_refill(struct HipChunker* c, Longtail_Chunker_Feeder feeder, 
     c->pub.lens = w->h_len;
     c->pub.hashes = w->h_hash;
     c->pub.count = c->nfinal;
+    c->pub.owner = w;
+    w->b2_ready = 0;
     ltp_window_publish(c->slot, &c->pub);
     ltp_window_set_current(c->slot);
     return 0;

@@ -248,6 +248,44 @@ void ltp_window_set_current(int slot)
         t_current_seq = atomic_load_explicit(&g_window_seq[slot], memory_order_acquire);
 }
 
+static int window_index(const struct ltp_window* w, const uint8_t* p, uint32_t len)
+{
+    const uint64_t rel = (uint64_t)(p - w->base);
+    uint32_t lo = 0, hi = w->count;
+    while (lo < hi)
+    {
+        uint32_t mid = lo + (hi - lo) / 2;
+        if (w->offsets[mid] < rel)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo < w->count && w->offsets[lo] == rel && w->lens[lo] == len ? (int)lo : -1;
+}
+
+int ltp_window_with_current(const void* data, uint32_t len, int (*fn)(const struct ltp_window* w, uint32_t index, void* arg), void* arg)
+{
+    const uint8_t* p = (const uint8_t*)data;
+    const int slot = t_current_slot;
+    int res = -1;
+    if (slot < 0 || (t_current_seq & 1u))
+        return -1;
+    /* the reader count of ltp_window_lookup's fast path: writers of the slot wait until it drains */
+    atomic_fetch_add_explicit(&g_window_readers[slot].n, 1, memory_order_seq_cst);
+    if (atomic_load_explicit(&g_window_seq[slot], memory_order_seq_cst) == t_current_seq)
+    {
+        const struct ltp_window* cur = &g_windows[slot];
+        if (cur->base && cur->owner && p >= cur->base && p < cur->base + cur->size)
+        {
+            const int idx = window_index(cur, p, len);
+            if (idx >= 0)
+                res = fn(cur, (uint32_t)idx, arg);
+        }
+    }
+    atomic_fetch_sub_explicit(&g_window_readers[slot].n, 1, memory_order_release);
+    return res;
+}
+
 static int window_find(const struct ltp_window* w, const uint8_t* p, uint32_t len, uint64_t* out_hash)
 {
     const uint64_t rel = (uint64_t)(p - w->base);
@@ -360,6 +398,7 @@ static void window_destroy(struct ltp_chunk_window* w)
     lthip_free_pinned(0, w->h_off);
     lthip_free_pinned(0, w->h_len);
     lthip_free_pinned(0, w->h_hash);
+    lthip_free_pinned(0, w->h_hash2);
     free(w);
 }
 

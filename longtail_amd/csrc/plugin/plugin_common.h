@@ -46,6 +46,7 @@ struct ltp_window
     const uint32_t* lens;
     const uint64_t* hashes;
     uint32_t count;
+    struct ltp_chunk_window* owner; /* the pooled window the tables belong to (its BLAKE2 table, its device copy) */
 };
 /* slot = ltp_window_register(); update with ltp_window_publish(slot, &w); remove with ltp_window_unregister(slot) */
 int ltp_window_register(void);
@@ -53,6 +54,10 @@ void ltp_window_publish(int slot, const struct ltp_window* w);
 void ltp_window_unregister(int slot);
 /* returns 1 and the digest when (data,len) is exactly a chunk of a published window */
 int ltp_window_lookup(const void* data, uint32_t len, uint64_t* out_hash);
+/* When (data,len) is exactly a chunk of the window the CALLING thread's chunker published last: fn(window, chunk index, arg) while
+ * the window is held stable (no writer can change or recycle it until fn returns), and its result.  -1 otherwise.  The other hash
+ * types' digests (plugin_blake2.c) are computed for the whole window by the first fn that wants them. */
+int ltp_window_with_current(const void* data, uint32_t len, int (*fn)(const struct ltp_window* w, uint32_t index, void* arg), void* arg);
 /* The window the CALLING thread's chunker handed ranges out of last (DynamicChunking calls NextChunk and HashBuffer alternately on
  * one thread, src/longtail.c:2231-2296): looked at first, without any lock.  -1 clears it. */
 void ltp_window_set_current(int slot);
@@ -80,6 +85,9 @@ struct ltp_chunk_window
     uint32_t* h_len;
     uint64_t* h_hash;
     lthip_plan* plan; /* one part of `cap` bytes, re-aimed per refill (lthip_plan_resize_single) */
+    int d_resident;   /* d_win / d_off / d_len hold the published bytes and chunk lists (the direct path, not the batcher's arena) */
+    int b2_ready;     /* h_hash2 holds the BLAKE2 digests of the published chunks (reset at every publish) */
+    uint64_t* h_hash2; /* pinned, ccap entries, allocated by the first BLAKE2 look-up */
     int cls;          /* 0 small, 1 large, 2 private */
     struct ltp_chunk_window* next;
 };
@@ -101,6 +109,26 @@ int ltp_memo_get(const void* data, uint32_t length, uint64_t* out_hash);
  * blocks other threads have queued; *produced as the bulk entry points report it ---- */
 int ltp_codec_batch(int codec, int decompress, int quality, const void* d_in, uint32_t n, void* d_out, uint32_t cap, uint32_t* produced);
 void ltp_codec_batch_shutdown(void);
+
+/* ---- plugin_hash.c: the HashAPI object over a table of device calls (BLAKE3 there, BLAKE2s in plugin_blake2.c).  The streaming
+ * context collects batches of LTHIP_B3_STREAM_BATCH bytes on the host for every kind; stream_state_bytes of device memory per stream.
+ * use_windows: the chunk windows' digests and the batcher's memo are of this kind (BLAKE3 only) ---- */
+struct ltp_chunk_window;
+struct ltp_hash_kind
+{
+    uint32_t id;
+    int (*one)(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
+    int (*ranges)(lthip_ctx* ctx, const void* d_data, uint64_t range_count, const uint64_t* d_offsets, const uint32_t* d_lens,
+                  uint32_t max_len, uint64_t* d_hashes);
+    int (*stream_batch)(lthip_ctx* ctx, const void* d_data, uint64_t batch_index, void* d_state);
+    int (*stream_final)(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint64_t batch_count, void* d_state, uint64_t* d_out);
+    uint32_t stream_state_bytes;
+    int use_windows;
+    /* kinds without window digests (use_windows 0): the digest of a chunk of the calling thread's current window, computed for the
+     * whole window on first use -- 1 + *out_hash, 0 (not such a chunk) or -errno; may be NULL */
+    int (*window_lookup)(const void* data, uint32_t len, uint64_t* out_hash);
+};
+struct Longtail_HashAPI* ltp_create_hash_api(const struct ltp_hash_kind* kind);
 
 /* ---- error latch: void / value-returning entry points of the plugin structs (HashAPI.Hash, EndContext) cannot report failure;
  * the first errno of such a call on a thread is kept until read.  Exported as Longtail_Hip_GetLastError(). ---- */

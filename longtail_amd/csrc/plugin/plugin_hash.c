@@ -1,4 +1,4 @@
-/* plugin_hash.c -- Longtail_HashAPI (BLAKE3, 64-bit) on the GPU; C99 host code over the lthip_* C ABI.
+/* plugin_hash.c -- Longtail_HashAPI (BLAKE3 and BLAKE2s, 64-bit) on the GPU; C99 host code over the lthip_* C ABI.
  *
  * Mirrors lib/blake3/longtail_blake3.c of the reference:
  *   Longtail_CreateHipBlake3HashAPI <-> Longtail_CreateBlake3HashAPI (:124-141)
@@ -11,6 +11,9 @@
  * bytes again.  Anything else (path strings src/longtail.c:1272, per-asset chunk-hash arrays :2522, block hash
  * arrays :3757, ranges from a CPU chunker) is copied to the device and hashed there; there is no CPU
  * implementation of BLAKE3 in this library.
+ *
+ * The object is written once over a table of device calls (struct ltp_hash_kind): BLAKE3's is below, BLAKE2s's -- the 'blk2'
+ * object, Longtail_CreateHipBlake2HashAPI -- in plugin_blake2.c.
  */
 #include "plugin_common.h"
 
@@ -19,6 +22,7 @@
 struct HipHashAPI
 {
     struct Longtail_HashAPI api;
+    const struct ltp_hash_kind* kind;
 };
 
 /* Streaming context: O(1) host memory whatever the stream's length (the reference's blake3_hasher is 1 912 bytes; round 2 buffered the
@@ -30,14 +34,15 @@ struct HipHashContext
     uint8_t* buf;      /* LTHIP_B3_STREAM_BATCH bytes, allocated with the first Hash() call */
     uint32_t have;     /* bytes in buf */
     uint64_t batches;  /* batches already on the device */
-    void* d_stack;     /* device: the stream's subtree stack, allocated with the first batch */
+    void* d_stack;     /* device: the stream's subtree stack (BLAKE3) or chaining state (BLAKE2s), allocated with the first batch */
     void* d_batch;     /* device: one batch */
     int err; /* first failure of a Hash() call on this context: EndContext reports it through the error latch */
+    const struct ltp_hash_kind* kind;
 };
 
 #define LTP_HASH_ONE_MAX 65536u
 
-static int gpu_hash(const void* data, uint32_t length, uint64_t* out_hash)
+static int gpu_hash(const struct ltp_hash_kind* kind, const void* data, uint32_t length, uint64_t* out_hash)
 {
     struct ltp_thread_state* ts = ltp_thread_state_get();
     if (!ts)
@@ -55,7 +60,7 @@ static int gpu_hash(const void* data, uint32_t length, uint64_t* out_hash)
         if (length)
             memcpy(h, data, length);
         uint64_t* res = (uint64_t*)(h + data_bytes);
-        err = lthip_hash_one(ctx, h, length, res);
+        err = kind->one(ctx, h, length, res);
         if (!err)
             err = lthip_ctx_sync(ctx);
         if (err)
@@ -78,8 +83,8 @@ static int gpu_hash(const void* data, uint32_t length, uint64_t* out_hash)
     if (!err)
         err = lthip_copy_h2d(ctx, d + data_bytes, h_tab, 16);
     if (!err)
-        err = lthip_hash_ranges(ctx, d, 1, (const uint64_t*)(d + data_bytes), (const uint32_t*)(d + data_bytes + 8), length,
-                                (uint64_t*)(d + data_bytes + 16));
+        err = kind->ranges(ctx, d, 1, (const uint64_t*)(d + data_bytes), (const uint32_t*)(d + data_bytes + 8), length,
+                           (uint64_t*)(d + data_bytes + 16));
     if (!err)
         err = lthip_copy_d2h(ctx, &h_tab[4], d + data_bytes + 16, 8);
     if (!err)
@@ -90,10 +95,17 @@ static int gpu_hash(const void* data, uint32_t length, uint64_t* out_hash)
     return 0;
 }
 
+static int b3_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint64_t batch_count, void* d_stack, uint64_t* d_out)
+{
+    return lthip_b3_stream_final(ctx, d_tail, tail_len, batch_count, d_stack, d_out);
+}
+
+static const struct ltp_hash_kind g_blake3 = {LONGTAIL_HIP_BLAKE3_ID, lthip_hash_one, lthip_hash_ranges, lthip_b3_stream_batch,
+                                              b3_stream_final, LTHIP_B3_STREAM_STACK_BYTES, 1, 0};
+
 static uint32_t HipHash_GetIdentifier(struct Longtail_HashAPI* hash_api)
 {
-    (void)hash_api;
-    return LONGTAIL_HIP_BLAKE3_ID;
+    return hash_api ? ((struct HipHashAPI*)hash_api)->kind->id : 0;
 }
 
 static int HipHash_BeginContext(struct Longtail_HashAPI* hash_api, Longtail_HashAPI_HContext* out_context)
@@ -104,6 +116,7 @@ static int HipHash_BeginContext(struct Longtail_HashAPI* hash_api, Longtail_Hash
     if (!c)
         return ENOMEM;
     memset(c, 0, sizeof *c);
+    c->kind = ((struct HipHashAPI*)hash_api)->kind;
     *out_context = (Longtail_HashAPI_HContext)c;
     return 0;
 }
@@ -114,11 +127,11 @@ static int stream_flush_batch(struct HipHashContext* c, lthip_ctx* ctx)
     if (!c->d_batch)
         err = lthip_malloc_device(ctx, LTHIP_B3_STREAM_BATCH, &c->d_batch);
     if (!err && !c->d_stack)
-        err = lthip_malloc_device(ctx, LTHIP_B3_STREAM_STACK_BYTES, &c->d_stack);
+        err = lthip_malloc_device(ctx, c->kind->stream_state_bytes, &c->d_stack);
     if (!err)
         err = lthip_copy_h2d(ctx, c->d_batch, c->buf, LTHIP_B3_STREAM_BATCH);
     if (!err)
-        err = lthip_b3_stream_batch(ctx, c->d_batch, c->batches, c->d_stack);
+        err = c->kind->stream_batch(ctx, c->d_batch, c->batches, c->d_stack);
     if (!err)
         err = lthip_ctx_sync(ctx); /* the host buffer is refilled next, and the next call may come from another thread */
     if (!err)
@@ -187,7 +200,7 @@ static uint64_t HipHash_EndContext(struct Longtail_HashAPI* hash_api, Longtail_H
         if (!ctx)
             err = ENODEV;
         else if (c->batches == 0 && c->have <= LTP_HASH_ONE_MAX)
-            err = gpu_hash(c->buf ? c->buf : (const uint8_t*)"", c->have, &h); /* a short stream is a HashBuffer */
+            err = gpu_hash(c->kind, c->buf ? c->buf : (const uint8_t*)"", c->have, &h); /* a short stream is a HashBuffer */
         else
         {
             /* the rest of the stream (1 .. one batch of bytes) and the fold of the stack, digest into the thread's pinned block */
@@ -198,7 +211,7 @@ static uint64_t HipHash_EndContext(struct Longtail_HashAPI* hash_api, Longtail_H
             if (!err)
                 err = lthip_copy_h2d(ctx, c->d_batch, c->buf, c->have);
             if (!err)
-                err = lthip_b3_stream_final(ctx, c->d_batch, c->have, c->batches, c->d_stack, (uint64_t*)ts->h_pin.p);
+                err = c->kind->stream_final(ctx, c->d_batch, c->have, c->batches, c->d_stack, (uint64_t*)ts->h_pin.p);
             if (!err)
                 err = lthip_ctx_sync(ctx);
             if (!err)
@@ -227,22 +240,32 @@ static int HipHash_HashBuffer(struct Longtail_HashAPI* hash_api, uint32_t length
 {
     if (!hash_api || !data || !out_hash)
         return EINVAL; /* longtail_blake3.c:94-96 */
+    const struct ltp_hash_kind* kind = ((struct HipHashAPI*)hash_api)->kind;
+    if (!kind->use_windows)
+    {
+        /* the window registry and the memo hold BLAKE3 digests: the kind's own table of the chunker's window, else the GPU */
+        const int hit = kind->window_lookup && length ? kind->window_lookup(data, length, out_hash) : 0;
+        if (hit < 0)
+            return -hit;
+        return hit ? 0 : gpu_hash(kind, data, length, out_hash);
+    }
     if (length && ltp_window_lookup(data, length, out_hash))
         return 0;
     if (ltp_memo_get(data, length, out_hash)) /* an asset's digest array the batcher has hashed on the GPU already */
         return 0;
-    return gpu_hash(data, length, out_hash);
+    return gpu_hash(kind, data, length, out_hash);
 }
 
 static void HipHash_Dispose(struct Longtail_API* api) { ltp_free(api); }
 
-struct Longtail_HashAPI* Longtail_CreateHipBlake3HashAPI(void)
+struct Longtail_HashAPI* ltp_create_hash_api(const struct ltp_hash_kind* kind)
 {
     if (lthip_device_count() <= 0)
         return 0; /* no GPU: fail loudly */
-    struct HipHashAPI* a = (struct HipHashAPI*)ltp_alloc("HipBlake3HashAPI", sizeof *a);
+    struct HipHashAPI* a = (struct HipHashAPI*)ltp_alloc("HipHashAPI", sizeof *a);
     if (!a)
         return 0;
+    a->kind = kind;
     a->api.m_API.Dispose = HipHash_Dispose;
     a->api.GetIdentifier = HipHash_GetIdentifier;
     a->api.BeginContext = HipHash_BeginContext;
@@ -251,3 +274,5 @@ struct Longtail_HashAPI* Longtail_CreateHipBlake3HashAPI(void)
     a->api.HashBuffer = HipHash_HashBuffer;
     return &a->api;
 }
+
+struct Longtail_HashAPI* Longtail_CreateHipBlake3HashAPI(void) { return ltp_create_hash_api(&g_blake3); }

@@ -112,8 +112,8 @@ extern "C" int lthip_build_version_index(lthip_ctx* ctx, uint32_t asset_count, c
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, h_off.data(), (size_t)asset_count * 8, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_len.p, h_len.data(), (size_t)asset_count * 4, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // h_off / h_len are reused below
-        if ((err = lthip_hash_ranges(ctx, d_chunk_hashes ? (const void*)d_chunk_hashes : d_paths.p, asset_count, (const uint64_t*)d_off.p,
-                                     (const uint32_t*)d_len.p, max_len, (uint64_t*)d_ch.p)))
+        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes ? (const void*)d_chunk_hashes : d_paths.p, asset_count, (const uint64_t*)d_off.p,
+                                     (const uint32_t*)d_len.p, max_len, 0u, (uint64_t*)d_ch.p)))
             return err;
         max_len = 0;
         for (uint32_t a = 0; a < asset_count; ++a)
@@ -128,7 +128,7 @@ extern "C" int lthip_build_version_index(lthip_ctx* ctx, uint32_t asset_count, c
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, h_off.data(), (size_t)asset_count * 8, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_len.p, h_len.data(), (size_t)asset_count * 4, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        if ((err = lthip_hash_ranges(ctx, d_paths.p, asset_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, max_len,
+        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_paths.p, asset_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, max_len, 0u,
                                      (uint64_t*)d_ph.p)))
             return err;
     }
@@ -227,7 +227,7 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_raw.p, raw_sizes, (size_t)block_count * 4, hipMemcpyHostToDevice, ctx->stream));
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_img.p, image_offsets, (size_t)block_count * 8, hipMemcpyHostToDevice, ctx->stream));
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // host vectors go out of scope
-    if ((err = lthip_hash_ranges(ctx, d_chunk_hashes, block_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, max_len,
+    if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes, block_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, max_len, 0u,
                                  (uint64_t*)d_bh.p)))
         return err;
     LaunchTimer t(ctx, LTHIP_K_OTHER);
@@ -326,7 +326,7 @@ extern "C" int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_co
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_o.p, o.data(), nb * 8, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_l.p, l.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        if ((err = lthip_hash_ranges(ctx, d_mh.p, nb, (const uint64_t*)d_o.p, (const uint32_t*)d_l.p, max_len, (uint64_t*)d_bh.p)))
+        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_mh.p, nb, (const uint64_t*)d_o.p, (const uint32_t*)d_l.p, max_len, 0u, (uint64_t*)d_bh.p)))
             return err;
         LTHIP_CHECK(ctx, hipMemcpyAsync(b_hash.data(), d_bh.p, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));

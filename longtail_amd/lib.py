@@ -28,6 +28,12 @@ KERNEL_IDS = {
     "zstd_encode": 8,
     "gather": 9,
 }
+# BLAKE2s ('blk2') kernels, kept out of KERNEL_IDS (bench.py reports every key of that dict): read with Context.timing_get_blake2s()
+BLAKE2S_KERNEL_ID = 10
+HASH_BLAKE3 = 0x626C6B33  # 'blk3', lib/blake3/longtail_blake3.c
+HASH_BLAKE2 = 0x626C6B32  # 'blk2', lib/blake2/longtail_blake2.c
+B2S_STREAM_BATCH = 1 << 20  # include/longtail_hip.h LTHIP_B2S_STREAM_BATCH
+B2S_STREAM_STATE_BYTES = 64
 
 
 class LongtailHipError(RuntimeError):
@@ -78,6 +84,7 @@ class HipLib:
         # --- plugin constructors ---
         sig("Longtail_CreateHipChunkerAPI", vp, [])
         sig("Longtail_CreateHipBlake3HashAPI", vp, [])
+        sig("Longtail_CreateHipBlake2HashAPI", vp, [])
         sig("Longtail_CreateHipLZ4CompressionAPI", vp, [])
         sig("Longtail_CompressionRegistry_CreateForHipLZ4", vp, [u32, P(u32)])
         sig("Longtail_GetHipLZ4DefaultQuality", u32, [])
@@ -146,6 +153,13 @@ class HipLib:
         sig("lthip_hash_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
         sig("lthip_b3_stream_batch", i32, [vp, vp, u64, vp])
         sig("lthip_b3_stream_final", i32, [vp, vp, u32, u64, vp, vp])
+        sig("lthip_blake2s_ranges", i32, [vp, vp, u64, vp, vp, u32, vp])
+        sig("lthip_blake2s_ranges_dev", i32, [vp, vp, u64, vp, vp, vp, u32, vp])
+        sig("lthip_blake2s_one", i32, [vp, vp, u32, vp])
+        sig("lthip_blake2s_runs_u64", i32, [vp, vp, vp, u32, vp])
+        sig("lthip_blake2s_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
+        sig("lthip_b2s_stream_batch", i32, [vp, vp, u64, vp])
+        sig("lthip_b2s_stream_final", i32, [vp, vp, u32, u64, vp, vp])
         sig("lthip_dedup_first_seen_range", i32, [vp, u64, vp, u64, u64, vp, vp])
         sig("lthip_gather_ranges", i32, [vp, vp, u64, vp, vp, vp, vp])
         sig("lthip_pack_blocks", i32, [u64, vp, u32, u32, vp, u64, P(u64)])
@@ -321,6 +335,50 @@ class Context:
             "lthip_hash_ranges",
         )
         return out[:n]
+
+    # -- BLAKE2s-64 ('blk2') --
+    def blake2s_ranges(self, data, offsets, lens, max_len: int = 0, out=None, count_bound: Optional[int] = None, d_count=None):
+        """d_hashes[i] = blake2s-64 of the range; with d_count (device u32) the number of ranges is min(count_bound, *d_count)."""
+        torch = self.torch
+        n = int(offsets.numel()) if count_bound is None else int(count_bound)
+        if out is None:
+            out = torch.empty(max(1, n), dtype=torch.int64, device=self._dev())
+        if d_count is None:
+            err = self.lib.dll.lthip_blake2s_ranges(self.h, _ptr(data), n, _ptr(offsets), _ptr(lens), max_len, _ptr(out))
+        else:
+            err = self.lib.dll.lthip_blake2s_ranges_dev(self.h, _ptr(data), n, _ptr(d_count), _ptr(offsets), _ptr(lens), max_len, _ptr(out))
+        self._check(err, "lthip_blake2s_ranges")
+        return out[:n]
+
+    def blake2s_one(self, data, length: int, out) -> None:
+        """One input of at most 64 KiB (device or pinned memory); the digest lands in `out` (device or pinned) on the stream."""
+        self._check(self.lib.dll.lthip_blake2s_one(self.h, _ptr(data), length, _ptr(out)), "lthip_blake2s_one")
+
+    def blake2s_runs_u64(self, values, first, run_count: int, out=None):
+        if out is None:
+            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
+        self._check(self.lib.dll.lthip_blake2s_runs_u64(self.h, _ptr(values), _ptr(first), run_count, _ptr(out)), "lthip_blake2s_runs_u64")
+        return out[:run_count]
+
+    def b2s_stream(self, data, length: int) -> int:
+        """Streaming BLAKE2s-64 of the first `length` bytes of a device tensor, batch by batch (lthip_b2s_stream_batch / _final)."""
+        torch = self.torch
+        state = torch.empty(B2S_STREAM_STATE_BYTES, dtype=torch.uint8, device=self._dev())
+        out = torch.zeros(1, dtype=torch.int64, device=self._dev())
+        base = _ptr(data)
+        batches = max(0, (length - 1) // B2S_STREAM_BATCH)
+        for b in range(batches):
+            self._check(self.lib.dll.lthip_b2s_stream_batch(self.h, base + b * B2S_STREAM_BATCH, b, _ptr(state)), "lthip_b2s_stream_batch")
+        tail = length - batches * B2S_STREAM_BATCH
+        self._check(self.lib.dll.lthip_b2s_stream_final(self.h, base + batches * B2S_STREAM_BATCH if tail else None, tail, batches,
+                                                        _ptr(state), _ptr(out)), "lthip_b2s_stream_final")
+        return int(out.cpu().numpy().view(np.uint64)[0])
+
+    def timing_get_blake2s(self):
+        """(total ms, launches) of the BLAKE2s kernels since the last timing_reset."""
+        ms, n = C.c_double(0), C.c_uint64(0)
+        self._check(self.lib.dll.lthip_timing_get(self.h, BLAKE2S_KERNEL_ID, C.byref(ms), C.byref(n)), "lthip_timing_get")
+        return ms.value, n.value
 
     def chunk_from_buffer(self, data, size: int, min_chunk: int, avg_chunk: int, max_chunk: int) -> int:
         out = C.c_uint64(0)
