@@ -192,9 +192,10 @@ LTHIP_EXPORT int lthip_plan_reaim(lthip_ctx* ctx, lthip_plan* plan, uint32_t par
 LTHIP_EXPORT void lthip_plan_destroy(lthip_ctx* ctx, lthip_plan* plan);
 /* upper bound on the number of chunks the plan can produce (size the output arrays with it) */
 LTHIP_EXPORT uint64_t lthip_plan_chunk_capacity(const lthip_plan* plan);
-/* 2 when lthip_chunk_hash runs this plan as two slices on two streams (plans of >= 1 GiB in >= 2 parts: the candidate scan of the
- * second half of the parts beside the leaf hashing of the first; results identical to the single pass), else 1.  Per-kernel timings
- * (lthip_timing_get) of the scan and the leaf hashing then OVERLAP: their sum exceeds the wall time of the call. */
+/* The number of slices the next lthip_chunk_hash with hashes runs this plan in, 1 .. 8: plans of >= 1 GiB in >= 2 parts run as slices
+ * on two streams (the candidate scan of slice k + 1 beside the leaf hashing of slice k; results identical to the single pass), 2 in
+ * the product build, LTHIP_SLICES in the ablation build; 1 = the single pass.  Per-kernel timings (lthip_timing_get) of the scan and
+ * the leaf hashing of a sliced call OVERLAP: their sum exceeds the wall time of the call. */
 LTHIP_EXPORT uint32_t lthip_plan_slices(const lthip_plan* plan);
 
 /* Runs buzhash scan -> cut selection -> compaction -> (if d_chunk_hashes) BLAKE3 on the stream.

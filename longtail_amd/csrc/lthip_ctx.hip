@@ -450,7 +450,7 @@ extern "C" int lthip_timing_get(lthip_ctx* ctx, int kernel_id, double* out_total
     int err = timing_collect(ctx);
     double ms = ctx->total_ms[kernel_id];
     uint64_t n = ctx->launches[kernel_id];
-    if (ctx->slice_ctx) // (the second slice of lthip_chunk_hash runs on a context of its own: its launches count here)
+    if (ctx->slice_ctx) // (slices 1 .. S-1 of lthip_chunk_hash run on a context of their own: their launches count here)
     {
         double ms2 = 0;
         uint64_t n2 = 0;
@@ -597,9 +597,6 @@ extern "C" int lthip_divtest_eval(uint32_t discriminator, uint32_t hash)
     return r <= t.qlim;
 }
 
-static int plan_create_impl(lthip_ctx* ctx, uint32_t part_count, const uint64_t* part_offsets, const uint64_t* part_sizes,
-                            uint32_t min_chunk, uint32_t avg_chunk, uint32_t max_chunk, lthip_plan** out_plan);
-
 // where a plan's parts are cut into S runs of about equal bytes: first[0] = 0 < first[1] < ... < first[S] = n; returns S (0 = do not slice)
 static uint32_t plan_slice_points(uint32_t part_count, const uint64_t* part_sizes, uint32_t want, uint32_t* first)
 {
@@ -632,42 +629,35 @@ static uint32_t plan_slice_points(uint32_t part_count, const uint64_t* part_size
     return S;
 }
 
-extern "C" int lthip_plan_create(lthip_ctx* ctx, uint32_t part_count, const uint64_t* part_offsets,
-                                 const uint64_t* part_sizes, uint32_t min_chunk, uint32_t avg_chunk, uint32_t max_chunk,
-                                 lthip_plan** out_plan)
+// The one place a plan's layout is computed: checks the parts and fills their device table `parts` and the extents.  `what` is the
+// entry point the errors name.
+static int plan_layout(lthip_ctx* ctx, const char* what, uint32_t min_chunk, uint32_t part_count, const uint64_t* part_offsets,
+                       const uint64_t* part_sizes, PartDev* parts, PlanExtents& x)
 {
-    int err = plan_create_impl(ctx, part_count, part_offsets, part_sizes, min_chunk, avg_chunk, max_chunk, out_plan);
-    if (err)
-        return err;
-    // the slices (lthip_chunk_hash): plans of their own over the same bytes.  Optional: a slice that cannot be made leaves the plan
-    // unsliced, it is never an error of the call.
-    lthip_plan* plan = *out_plan;
-    int want = LTHIP_SLICES;
-    LTHIP_ABLATION_ENV(env_slices, "LTHIP_SLICES"); // (ablation build: 1 = the single pass, for profiles of K1 / K3 alone; 2..8)
-    if (env_slices.get() > 0)
-        want = env_slices.get() > 8 ? 8 : env_slices.get();
-    uint32_t first[9];
-    const uint32_t S = plan_slice_points(part_count, part_sizes, (uint32_t)want, first);
-    if (S)
+    memset(&x, 0, sizeof x);
+    x.nparts = part_count;
+    for (uint32_t p = 0; p < part_count; ++p)
     {
-        bool ok = true;
-        for (uint32_t k = 0; k < S && ok; ++k)
-            ok = plan_create_impl(ctx, first[k + 1] - first[k], part_offsets + first[k], part_sizes + first[k], min_chunk, avg_chunk, max_chunk, &plan->slice[k]) == 0;
-        if (ok)
-        {
-            memcpy(plan->slice_first, first, sizeof(uint32_t) * (S + 1));
-            plan->nslices = S;
-            plan->sliced = true;
-        }
-        else
-        {
-            for (uint32_t k = 0; k < S; ++k)
-            {
-                lthip_plan_destroy(ctx, plan->slice[k]);
-                plan->slice[k] = nullptr;
-            }
-            ctx->err[0] = 0;
-        }
+        const uint64_t sz = part_sizes[p];
+        if ((part_offsets[p] & 15u) != 0 || sz > 0xFFFFFFFFull)
+            return lthip_fail(ctx, EINVAL, what, "part offsets must be 16-byte aligned, sizes < 4 GiB");
+        PartDev& pd = parts[p];
+        memset(&pd, 0, sizeof pd);
+        pd.off = part_offsets[p];
+        pd.size = sz;
+        pd.bm0_base = x.bm0_words;
+        pd.bm1_base = x.bm1_words;
+        pd.region_base = x.chunk_cap;
+        pd.tile_base = (uint32_t)x.ntiles;
+        const uint64_t cap = sz ? sz / min_chunk + 1 : 0; // every chunk but the last is >= min bytes
+        pd.region_cap = (uint32_t)cap;
+        const uint64_t t = div_up_u64(sz, 16384);
+        x.ntiles += t;
+        x.bm0_words += t * 256; // one 64-bit word per 64-byte run, whole tiles
+        x.bm1_words += t * 4;   // one 64-bit word per 4 KiB
+        x.chunk_cap += cap;
+        x.total_bytes += sz;
+        x.leaf_cap += div_up_u64(sz, 1024) + cap;
     }
     return 0;
 }
@@ -685,63 +675,31 @@ static int plan_create_impl(lthip_ctx* ctx, uint32_t part_count, const uint64_t*
     if (d == 0)
         return lthip_fail(ctx, EINVAL, "lthip_plan_create", "discriminator is zero");
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::vector<PartDev> parts(part_count);
+    PlanExtents x;
+    int err = plan_layout(ctx, "lthip_plan_create", min_chunk, part_count, part_offsets, part_sizes, parts.data(), x);
+    if (err)
+        return err;
+    if (x.ntiles > 0xFFFFFFF0ull)
+        return lthip_fail(ctx, EINVAL, "lthip_plan_create", "batch too large");
 
     lthip_plan* plan = new (std::nothrow) lthip_plan();
     if (!plan)
         return ENOMEM;
     memset(plan, 0, sizeof *plan);
-    plan->nparts = part_count;
+    static_cast<PlanExtents&>(*plan) = x;
     plan->device = ctx->device;
     plan->min_chunk = min_chunk;
     plan->avg_chunk = avg_chunk;
     plan->max_chunk = max_chunk;
     plan->div = make_div_test(d);
-
-    std::vector<PartDev> parts(part_count ? part_count : 1);
-    uint64_t tiles = 0, bm0 = 0, bm1 = 0, region = 0, bytes = 0, leaves = 0;
-    for (uint32_t p = 0; p < part_count; ++p)
-    {
-        uint64_t sz = part_sizes[p];
-        if ((part_offsets[p] & 15u) != 0 || sz > 0xFFFFFFFFull)
-        {
-            delete plan;
-            return lthip_fail(ctx, EINVAL, "lthip_plan_create", "part offsets must be 16-byte aligned, sizes < 4 GiB");
-        }
-        PartDev& pd = parts[p];
-        pd.off = part_offsets[p];
-        pd.size = sz;
-        pd.bm0_base = bm0;
-        pd.bm1_base = bm1;
-        pd.region_base = region;
-        pd.tile_base = (uint32_t)tiles;
-        uint64_t cap = sz ? sz / min_chunk + 1 : 0; // every chunk but the last is >= min bytes
-        pd.region_cap = (uint32_t)cap;
-        uint64_t t = div_up_u64(sz, 16384);
-        tiles += t;
-        bm0 += t * 256; // one 64-bit word per 64-byte run, whole tiles
-        bm1 += t * 4;   // one 64-bit word per 4 KiB
-        region += cap;
-        bytes += sz;
-        leaves += div_up_u64(sz, 1024) + cap;
-    }
-    if (tiles > 0xFFFFFFF0ull)
-    {
-        delete plan;
-        return lthip_fail(ctx, EINVAL, "lthip_plan_create", "batch too large");
-    }
-    plan->ntiles = tiles;
-    plan->bm0_words = bm0;
-    plan->bm1_words = bm1;
-    plan->chunk_cap = region;
-    plan->total_bytes = bytes;
-    plan->leaf_cap = leaves;
-    plan->capacity_bytes = bytes;
+    plan->capacity_bytes = x.total_bytes;
     plan->cap_parts = part_count ? part_count : 1;
-    plan->cap_tiles = tiles ? tiles : 1;
+    plan->cap_tiles = x.ntiles ? x.ntiles : 1;
 
-    hipError_t e = lthip_hip_malloc((void**)&plan->d_parts, sizeof(PartDev) * (part_count ? part_count : 1));
+    hipError_t e = lthip_hip_malloc((void**)&plan->d_parts, sizeof(PartDev) * plan->cap_parts);
     if (e == hipSuccess)
-        e = lthip_hip_malloc((void**)&plan->d_tile_part, sizeof(uint32_t) * (tiles ? tiles : 1));
+        e = lthip_hip_malloc((void**)&plan->d_tile_part, sizeof(uint32_t) * plan->cap_tiles);
     if (e == hipSuccess && part_count)
         e = hipMemcpyAsync(plan->d_parts, parts.data(), sizeof(PartDev) * part_count, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
@@ -751,13 +709,82 @@ static int plan_create_impl(lthip_ctx* ctx, uint32_t part_count, const uint64_t*
         lthip_plan_destroy(ctx, plan);
         return lthip_fail(ctx, e == hipErrorOutOfMemory ? ENOMEM : EIO, "lthip_plan_create", hipGetErrorString(e));
     }
-    int err = lthip_launch_tile_table(ctx, plan);
-    if (err)
+    if ((err = lthip_launch_tile_table(ctx, plan)))
     {
         lthip_plan_destroy(ctx, plan);
         return err;
     }
     *out_plan = plan;
+    return 0;
+}
+
+// aims a plan at a layout that fits its tables: the part table goes through the pinned staging ring, the tile -> part table is
+// rebuilt by its kernel on the stream
+static int plan_aim(lthip_ctx* ctx, lthip_plan* plan, const PlanExtents& x, const PartDev* parts)
+{
+    static_cast<PlanExtents&>(*plan) = x;
+    const int err = lthip_stage_upload(ctx, plan->d_parts, parts, sizeof(PartDev) * x.nparts, ctx->stream);
+    return err ? err : lthip_launch_tile_table(ctx, plan);
+}
+
+// The slices of a plan (lthip_chunk_hash): plans of their own over the same bytes, `want` runs of its parts of about equal bytes.
+// The first aim that slices creates them; a later aim re-aims them when the new parts fit them (they do when the layout is the one
+// the plan was created with: bench.py's steps), otherwise that aim runs as one.  Optional: a slice that cannot be made or aimed
+// leaves the plan unsliced and ctx->err clear, it is never an error of the call.
+static void plan_aim_slices(lthip_ctx* ctx, lthip_plan* plan, uint32_t want, const uint64_t* part_offsets, const uint64_t* part_sizes)
+{
+    plan->sliced = false;
+    uint32_t first[9];
+    const uint32_t S = plan_slice_points(plan->nparts, part_sizes, want, first);
+    if (S == 0 || (plan->nslices && S != plan->nslices))
+        return;
+    bool ok = true;
+    if (!plan->nslices)
+        for (uint32_t k = 0; k < S && ok; ++k)
+            ok = plan_create_impl(ctx, first[k + 1] - first[k], part_offsets + first[k], part_sizes + first[k], plan->min_chunk,
+                                  plan->avg_chunk, plan->max_chunk, &plan->slice[k]) == 0;
+    else
+    {
+        std::vector<PartDev> parts(plan->nparts); // slice k's table at first[k]
+        PlanExtents x[8];
+        for (uint32_t k = 0; k < S && ok; ++k)
+        {
+            const uint32_t n = first[k + 1] - first[k];
+            ok = plan_layout(ctx, "lthip_plan_reaim", plan->min_chunk, n, part_offsets + first[k], part_sizes + first[k], &parts[first[k]],
+                             x[k]) == 0 &&
+                 n <= plan->slice[k]->cap_parts && x[k].ntiles <= plan->slice[k]->cap_tiles;
+        }
+        for (uint32_t k = 0; k < S && ok; ++k)
+            ok = plan_aim(ctx, plan->slice[k], x[k], &parts[first[k]]) == 0;
+    }
+    if (!ok)
+    {
+        if (!plan->nslices) // (slices that were never aimed together: nothing to keep)
+            for (uint32_t k = 0; k < S; ++k)
+            {
+                lthip_plan_destroy(ctx, plan->slice[k]);
+                plan->slice[k] = nullptr;
+            }
+        ctx->err[0] = 0;
+        return;
+    }
+    memcpy(plan->slice_first, first, sizeof(uint32_t) * (S + 1));
+    plan->nslices = S;
+    plan->sliced = true;
+}
+
+extern "C" int lthip_plan_create(lthip_ctx* ctx, uint32_t part_count, const uint64_t* part_offsets,
+                                 const uint64_t* part_sizes, uint32_t min_chunk, uint32_t avg_chunk, uint32_t max_chunk,
+                                 lthip_plan** out_plan)
+{
+    int err = plan_create_impl(ctx, part_count, part_offsets, part_sizes, min_chunk, avg_chunk, max_chunk, out_plan);
+    if (err)
+        return err;
+    int want = LTHIP_SLICES;
+    LTHIP_ABLATION_ENV(env_slices, "LTHIP_SLICES"); // (ablation build: 1 = the single pass, for profiles of K1 / K3 alone; 2..8)
+    if (env_slices.get() > 0)
+        want = env_slices.get() > 8 ? 8 : env_slices.get();
+    plan_aim_slices(ctx, *out_plan, (uint32_t)want, part_offsets, part_sizes);
     return 0;
 }
 
@@ -771,104 +798,43 @@ extern "C" int lthip_plan_resize_single(lthip_ctx* ctx, lthip_plan* plan, uint64
     if (size > plan->capacity_bytes)
         return lthip_fail(ctx, EINVAL, "lthip_plan_resize_single", "size above the capacity the plan was created with");
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const uint64_t off = 0;
     PartDev pd;
-    memset(&pd, 0, sizeof pd);
-    pd.off = 0;
-    pd.size = size;
-    const uint64_t cap = size ? size / plan->min_chunk + 1 : 0;
-    pd.region_cap = (uint32_t)cap;
-    const uint64_t t = div_up_u64(size, 16384);
-    plan->ntiles = t;
-    plan->bm0_words = t * 256;
-    plan->bm1_words = t * 4;
-    plan->chunk_cap = cap;
-    plan->total_bytes = size;
-    plan->leaf_cap = div_up_u64(size, 1024) + cap;
+    PlanExtents x;
+    const int err = plan_layout(ctx, "lthip_plan_resize_single", plan->min_chunk, 1, &off, &size, &pd, x);
+    if (err)
+        return err;
+    static_cast<PlanExtents&>(*plan) = x;
     return lthip_stage_upload(ctx, plan->d_parts, &pd, sizeof pd, ctx->stream);
 }
 
 // A plan re-aimed at ANOTHER set of parts (any count up to the one it was created with, any layout whose tiles fit the tile
-// table it was created with): no allocation and no synchronisation -- the part table goes through the pinned staging ring, the
-// tile -> part table is rebuilt by its kernel on the stream.  What the plugin layer's batcher needs: one plan, a different set of
-// windows in every submission (plugin_batch.c).
-static int plan_reaim_impl(lthip_ctx* ctx, lthip_plan* plan, uint32_t part_count, const uint64_t* part_offsets, const uint64_t* part_sizes);
-
+// table it was created with): no allocation and no synchronisation.  What the plugin layer's batcher needs: one plan, a different
+// set of windows in every submission (plugin_batch.c).
 extern "C" int lthip_plan_reaim(lthip_ctx* ctx, lthip_plan* plan, uint32_t part_count, const uint64_t* part_offsets,
                                 const uint64_t* part_sizes)
-{
-    int err = plan_reaim_impl(ctx, plan, part_count, part_offsets, part_sizes);
-    if (err || !plan->nslices)
-        return err;
-    // the slices follow when the new parts fit them (they do when the layout is the one the plan was created with: bench.py's
-    // steps); otherwise this aim runs as one
-    plan->sliced = false;
-    uint32_t first[9];
-    if (plan_slice_points(part_count, part_sizes, plan->nslices, first) != plan->nslices)
-        return 0;
-    for (uint32_t k = 0; k < plan->nslices; ++k)
-    {
-        uint64_t tiles = 0;
-        for (uint32_t p = first[k]; p < first[k + 1]; ++p)
-            tiles += div_up_u64(part_sizes[p], 16384);
-        if (first[k + 1] - first[k] > plan->slice[k]->cap_parts || tiles > plan->slice[k]->cap_tiles)
-            return 0;
-    }
-    for (uint32_t k = 0; k < plan->nslices; ++k)
-        if (plan_reaim_impl(ctx, plan->slice[k], first[k + 1] - first[k], part_offsets + first[k], part_sizes + first[k]))
-        {
-            ctx->err[0] = 0;
-            return 0;
-        }
-    memcpy(plan->slice_first, first, sizeof(uint32_t) * (plan->nslices + 1));
-    plan->sliced = true;
-    return 0;
-}
-
-static int plan_reaim_impl(lthip_ctx* ctx, lthip_plan* plan, uint32_t part_count, const uint64_t* part_offsets, const uint64_t* part_sizes)
 {
     if (!ctx || !plan || (part_count && (!part_offsets || !part_sizes)))
         return EINVAL;
     if (part_count == 0 || part_count > plan->cap_parts)
         return lthip_fail(ctx, EINVAL, "lthip_plan_reaim", "part count outside 1 .. the count the plan was created with");
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::vector<PartDev> parts(part_count);
-    uint64_t tiles = 0, bm0 = 0, bm1 = 0, region = 0, bytes = 0, leaves = 0;
-    for (uint32_t p = 0; p < part_count; ++p)
     {
-        const uint64_t sz = part_sizes[p];
-        if ((part_offsets[p] & 15u) != 0 || sz > 0xFFFFFFFFull)
-            return lthip_fail(ctx, EINVAL, "lthip_plan_reaim", "part offsets must be 16-byte aligned, sizes < 4 GiB");
-        PartDev& pd = parts[p];
-        memset(&pd, 0, sizeof pd);
-        pd.off = part_offsets[p];
-        pd.size = sz;
-        pd.bm0_base = bm0;
-        pd.bm1_base = bm1;
-        pd.region_base = region;
-        pd.tile_base = (uint32_t)tiles;
-        const uint64_t cap = sz ? sz / plan->min_chunk + 1 : 0;
-        pd.region_cap = (uint32_t)cap;
-        const uint64_t t = div_up_u64(sz, 16384);
-        tiles += t;
-        bm0 += t * 256;
-        bm1 += t * 4;
-        region += cap;
-        bytes += sz;
-        leaves += div_up_u64(sz, 1024) + cap;
+        // (gone before the slices' table is laid out: with both 3 MB tables of the headline plan alive at once, the C library handed
+        // their pages back after every aim and the next aim faulted them in again -- 1-2 ms of every step, +30 ms in some)
+        std::vector<PartDev> parts(part_count);
+        PlanExtents x;
+        int err = plan_layout(ctx, "lthip_plan_reaim", plan->min_chunk, part_count, part_offsets, part_sizes, parts.data(), x);
+        if (err)
+            return err;
+        if (x.ntiles > plan->cap_tiles)
+            return lthip_fail(ctx, EINVAL, "lthip_plan_reaim", "more 16 KiB tiles than the plan was created with");
+        if ((err = plan_aim(ctx, plan, x, parts.data())))
+            return err;
     }
-    if (tiles > plan->cap_tiles)
-        return lthip_fail(ctx, EINVAL, "lthip_plan_reaim", "more 16 KiB tiles than the plan was created with");
-    plan->nparts = part_count;
-    plan->ntiles = tiles;
-    plan->bm0_words = bm0;
-    plan->bm1_words = bm1;
-    plan->chunk_cap = region;
-    plan->total_bytes = bytes;
-    plan->leaf_cap = leaves;
-    int err = lthip_stage_upload(ctx, plan->d_parts, parts.data(), sizeof(PartDev) * part_count, ctx->stream);
-    if (err)
-        return err;
-    return lthip_launch_tile_table(ctx, plan);
+    if (plan->nslices)
+        plan_aim_slices(ctx, plan, plan->nslices, part_offsets, part_sizes);
+    return 0;
 }
 
 extern "C" void lthip_plan_destroy(lthip_ctx* ctx, lthip_plan* plan)
@@ -892,13 +858,41 @@ extern "C" void lthip_plan_destroy(lthip_ctx* ctx, lthip_plan* plan)
 }
 
 extern "C" uint64_t lthip_plan_chunk_capacity(const lthip_plan* plan) { return plan ? plan->chunk_cap : 0; }
-extern "C" uint32_t lthip_plan_slices(const lthip_plan* plan) { return plan && plan->sliced && plan->nslices ? plan->nslices : 1u; }
+extern "C" uint32_t lthip_plan_slices(const lthip_plan* plan) { return plan && plan->sliced ? plan->nslices : 1u; }
 
 // ---------------------------------------------------------------------------------------------------
 // phase 1
 // ---------------------------------------------------------------------------------------------------
-static int chunk_scan_one(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, uint64_t* d_chunk_offsets, uint32_t* d_chunk_lens,
-                          uint32_t* d_part_first);
+// the candidate bitmaps of a whole plan (the slices' lie back to back in them)
+static int chunk_bitmaps(lthip_ctx* ctx, const lthip_plan* plan, uint64_t** bm0, uint64_t** bm1)
+{
+    const int err = lthip_scratch(ctx, S_BM0, plan->bm0_words * 8, (void**)bm0);
+    return err ? err : lthip_scratch(ctx, S_BM1, plan->bm1_words * 8, (void**)bm1);
+}
+
+// The phase-1 sequence of a plan, in two halves that the sliced pass runs on two streams: the candidate scan into bm0 / bm1 ...
+static int chunk_scan(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, uint64_t* bm0, uint64_t* bm1)
+{
+    return plan->nparts ? lthip_launch_buzhash(ctx, plan, (const uint8_t*)d_data, bm0, bm1) : 0;
+}
+
+// ... then cut selection, compaction and (with d_hashes) the BLAKE3 of the chunks, on ctx's stream behind the scan
+static int chunk_cut_hash(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, const uint64_t* bm0, const uint64_t* bm1,
+                          uint64_t* d_offsets, uint32_t* d_lens, uint64_t* d_hashes, uint32_t* d_part_first)
+{
+    void *region, *pcount;
+    int err;
+    if ((err = lthip_scratch(ctx, S_REGION, plan->chunk_cap * sizeof(uint2), &region)) ||
+        (err = lthip_scratch(ctx, S_PART_COUNT, ((size_t)plan->nparts + 1) * 4, &pcount)))
+        return err;
+    if (plan->nparts && (err = lthip_launch_select(ctx, plan, bm0, bm1, (uint2*)region, (uint32_t*)pcount)))
+        return err;
+    if ((err = lthip_launch_compact(ctx, plan, (const uint2*)region, (const uint32_t*)pcount, d_part_first, d_offsets, d_lens)))
+        return err;
+    return d_hashes ? lthip_launch_blake3(ctx, (const uint8_t*)d_data, d_offsets, d_lens, d_part_first + plan->nparts, plan->chunk_cap,
+                                          plan->leaf_cap, plan->max_chunk, d_hashes)
+                    : 0;
+}
 
 // a slice's lists behind the slices before it: base = part_first[0] (= the chunk count of everything before the slice, final by now),
 // its lists go to [base, base + total), its part table is shifted by base
@@ -918,6 +912,98 @@ __global__ void k_slice_join(const uint64_t* __restrict__ b_off, const uint32_t*
         part_first[i] = b_first[i] + base;
 }
 
+// Phase 1 in slices on two streams (plans of >= 1 GiB in >= 2 parts, with hashes).  The candidate scan (K1: four waves per SIMD, its
+// issue slots 72 % used, LDS-heavy) and the leaf hashing (K3: VALU bound, no LDS) are both bound by instruction issue and leave each
+// other room: with the parts cut into S slices, the scans of the slices run one after the other on the context's stream (scan k + 1
+// takes the CUs the moment scan k leaves them: its one workgroup per CU needs 117 KiB of LDS and four waves per SIMD, and would wait
+// for a whole grid of hashing workgroups to drain if those got there first) and cut selection, compaction and hashing of every slice
+// behind its scan on the slice context's stream -- scan k + 1 beside hashing k.  The lists are the ones of the single pass, bit for
+// bit: slice 0 writes the caller's arrays, the others go to scratch and are joined behind it in order (their place depends on the
+// counts before them).  tools/k1k3_overlap_probe.py, DESIGN.md §3.
+// *taken = false: the plan is not sliced, or what the pass needs could not be had -- nothing was queued, the caller runs the single
+// pass.  Once anything is queued every exit joins the second stream into the context's stream, also after a failure.
+static int chunk_hash_sliced(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, uint64_t* d_chunk_offsets, uint32_t* d_chunk_lens, uint64_t* d_chunk_hashes, uint32_t* d_part_first,
+                             bool* taken)
+{
+    *taken = false;
+    if (!plan->sliced || !d_chunk_hashes)
+        return 0;
+    if (!ctx->slice_ctx && lthip_ctx_create(ctx->device, LTHIP_STREAM_PRIVATE, &ctx->slice_ctx) != 0)
+        return 0;
+    lthip_ctx* c2 = ctx->slice_ctx;
+    const uint32_t S = plan->nslices;
+    uint64_t cap_rest = 0, parts_rest = 0; // slices 1 .. S-1 in scratch, back to back
+    for (uint32_t k = 1; k < S; ++k)
+    {
+        cap_rest += plan->slice[k]->chunk_cap + 1;
+        parts_rest += (uint64_t)plan->slice[k]->nparts + 1;
+    }
+    void *x_off, *x_len, *x_hash, *x_first;
+    uint64_t *bm0, *bm1;
+    if (lthip_scratch(ctx, S_SLICE_OFFS, cap_rest * 8, &x_off) || lthip_scratch(ctx, S_SLICE_LENS, cap_rest * 4, &x_len) ||
+        lthip_scratch(ctx, S_SLICE_HASH, cap_rest * 8, &x_hash) || lthip_scratch(ctx, S_SLICE_FIRST, parts_rest * 4, &x_first) ||
+        chunk_bitmaps(ctx, plan, &bm0, &bm1))
+    {
+        ctx->err[0] = 0;
+        return 0;
+    }
+    *taken = true;
+    c2->timing = ctx->timing;
+
+    int err = 0;
+    uint64_t co = 0, po = 0;
+    uint64_t *offs_k[8], *hash_k[8];
+    uint32_t *lens_k[8], *first_k[8];
+    for (uint32_t k = 0; k < S && !err; ++k)
+    {
+        const lthip_plan* pk = plan->slice[k];
+        offs_k[k] = k ? (uint64_t*)x_off + co : d_chunk_offsets;
+        lens_k[k] = k ? (uint32_t*)x_len + co : d_chunk_lens;
+        hash_k[k] = k ? (uint64_t*)x_hash + co : d_chunk_hashes;
+        first_k[k] = k ? (uint32_t*)x_first + po : d_part_first;
+        co += k ? pk->chunk_cap + 1 : 0;
+        po += k ? (uint64_t)pk->nparts + 1 : 0;
+        if ((err = chunk_scan(ctx, pk, d_data, bm0, bm1)))
+            break;
+        hipEvent_t scanned = lthip_sync_event(ctx);
+        hipError_t e = hipEventRecord(scanned, ctx->stream);
+        if (e == hipSuccess)
+            e = hipStreamWaitEvent(c2->stream, scanned, 0);
+        if (e != hipSuccess)
+            err = lthip_fail(ctx, EIO, "lthip_chunk_hash (the wait of the second stream for a scan)", hipGetErrorString(e));
+        else if ((err = chunk_cut_hash(c2, pk, d_data, bm0, bm1, offs_k[k], lens_k[k], hash_k[k], first_k[k])))
+            (void)lthip_fail(ctx, err, "lthip_chunk_hash (a slice on the second stream)", c2->err);
+        bm0 += pk->bm0_words;
+        bm1 += pk->bm1_words;
+    }
+    // the join (also after a failure: the context's stream never runs ahead of the second one)
+    hipEvent_t hashed = lthip_sync_event(ctx);
+    hipError_t e = hipEventRecord(hashed, c2->stream);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(ctx->stream, hashed, 0);
+    if (e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(c2->stream);
+        if (!err)
+            err = lthip_fail(ctx, EIO, "lthip_chunk_hash (the join of the second stream)", hipGetErrorString(e));
+    }
+    if (!err)
+    {
+        LaunchTimer t(ctx, LTHIP_K_COMPACT);
+        for (uint32_t k = 1; k < S; ++k) // in order: slice k's base is the total behind slice k - 1's join
+        {
+            const lthip_plan* pk = plan->slice[k];
+            const uint64_t n = pk->chunk_cap > (uint64_t)pk->nparts + 1 ? pk->chunk_cap : (uint64_t)pk->nparts + 1;
+            hipLaunchKernelGGL(k_slice_join, dim3((uint32_t)div_up_u64(n, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)offs_k[k], (const uint32_t*)lens_k[k],
+                               (const uint64_t*)hash_k[k], (const uint32_t*)first_k[k], pk->nparts, d_part_first + plan->slice_first[k], d_chunk_offsets,
+                               d_chunk_lens, d_chunk_hashes);
+        }
+        if ((e = hipGetLastError()) != hipSuccess)
+            err = lthip_fail(ctx, EIO, "kernel launch", hipGetErrorString(e));
+    }
+    return err;
+}
+
 extern "C" int lthip_chunk_hash(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, uint64_t* d_chunk_offsets,
                                 uint32_t* d_chunk_lens, uint64_t* d_chunk_hashes, uint32_t* d_part_first,
                                 uint64_t* out_total)
@@ -925,104 +1011,11 @@ extern "C" int lthip_chunk_hash(lthip_ctx* ctx, const lthip_plan* plan, const vo
     if (!ctx || !plan || !d_chunk_offsets || !d_chunk_lens || !d_part_first || (plan->total_bytes && !d_data))
         return EINVAL;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    int err = 0;
-    bool done = false;
-    // ---- slices on two streams (plans of >= 1 GiB in >= 2 parts, with hashes).  The candidate scan (K1: four waves per SIMD, its issue
-    // slots 72 % used, LDS-heavy) and the leaf hashing (K3: VALU bound, no LDS) are both bound by instruction issue and leave each other
-    // room: with the parts cut into S slices, the scans (+ cut selection + compaction) of the slices run one after the other on the
-    // context's stream and the hashing of every slice behind its scan on a second stream -- scan i + 1 beside hashing i; the scan
-    // takes its residency first (one persistent workgroup per CU), the hashing's workgroups fill what is left.  The lists are the
-    // ones of the single pass, bit for bit: slice 0 writes the caller's arrays, the others go to scratch and are joined behind it in
-    // order (their place depends on the counts before them).  tools/k1k3_overlap_probe.py, DESIGN.md §3.
-    if (plan->sliced && plan->nslices >= 2 && d_chunk_hashes)
-    {
-        if (!ctx->slice_ctx && lthip_ctx_create(ctx->device, LTHIP_STREAM_PRIVATE, &ctx->slice_ctx) != 0)
-            ctx->slice_ctx = nullptr;
-        lthip_ctx* c2 = ctx->slice_ctx;
-        const uint32_t S = plan->nslices;
-        uint64_t cap_rest = 0, parts_rest = 0; // slices 1 .. S-1 in scratch, back to back
-        for (uint32_t k = 1; k < S; ++k)
-        {
-            cap_rest += plan->slice[k]->chunk_cap + 1;
-            parts_rest += (uint64_t)plan->slice[k]->nparts + 1;
-        }
-        void *x_off = nullptr, *x_len = nullptr, *x_hash = nullptr, *x_first = nullptr;
-        if (c2 && !lthip_scratch(ctx, S_SLICE_OFFS, cap_rest * 8, &x_off) && !lthip_scratch(ctx, S_SLICE_LENS, cap_rest * 4, &x_len) &&
-            !lthip_scratch(ctx, S_SLICE_HASH, cap_rest * 8, &x_hash) && !lthip_scratch(ctx, S_SLICE_FIRST, parts_rest * 4, &x_first))
-        {
-            c2->timing = ctx->timing;
-            // all candidate scans back to back on the context's stream (scan k + 1 takes the CUs the moment scan k leaves them: its one
-            // workgroup per CU needs 117 KiB of LDS and four waves per SIMD, and would wait for a whole grid of hashing workgroups to
-            // drain if those got there first); cut selection, compaction and hashing of slice k on the second stream behind scan k
-            void *bm0 = nullptr, *bm1 = nullptr;
-            if ((err = lthip_scratch(ctx, S_BM0, plan->bm0_words * 8, &bm0)) || (err = lthip_scratch(ctx, S_BM1, plan->bm1_words * 8, &bm1)))
-                return err;
-            uint64_t co = 0, po = 0, b0 = 0, b1 = 0;
-            uint64_t* offs_k[8];
-            uint32_t *lens_k[8], *first_k[8];
-            uint64_t* hash_k[8];
-            for (uint32_t k = 0; k < S && !err; ++k)
-            {
-                const lthip_plan* pk = plan->slice[k];
-                offs_k[k] = k ? (uint64_t*)x_off + co : d_chunk_offsets;
-                lens_k[k] = k ? (uint32_t*)x_len + co : d_chunk_lens;
-                hash_k[k] = k ? (uint64_t*)x_hash + co : d_chunk_hashes;
-                first_k[k] = k ? (uint32_t*)x_first + po : d_part_first;
-                if (k)
-                {
-                    co += pk->chunk_cap + 1;
-                    po += (uint64_t)pk->nparts + 1;
-                }
-                uint64_t* bm0_k = (uint64_t*)bm0 + b0;
-                uint64_t* bm1_k = (uint64_t*)bm1 + b1;
-                b0 += pk->bm0_words;
-                b1 += pk->bm1_words;
-                if (pk->nparts && (err = lthip_launch_buzhash(ctx, pk, (const uint8_t*)d_data, bm0_k, bm1_k)))
-                    break;
-                hipEvent_t scanned = lthip_sync_event(ctx);
-                LTHIP_CHECK(ctx, hipEventRecord(scanned, ctx->stream));
-                LTHIP_CHECK(ctx, hipStreamWaitEvent(c2->stream, scanned, 0));
-                void *region = nullptr, *pcount = nullptr;
-                if ((err = lthip_scratch(c2, S_REGION, pk->chunk_cap * sizeof(uint2), &region)) ||
-                    (err = lthip_scratch(c2, S_PART_COUNT, ((size_t)pk->nparts + 1) * 4, &pcount)))
-                    break;
-                if (pk->nparts)
-                    err = lthip_launch_select(c2, pk, bm0_k, bm1_k, (uint2*)region, (uint32_t*)pcount);
-                if (!err)
-                    err = lthip_launch_compact(c2, pk, (const uint2*)region, (const uint32_t*)pcount, first_k[k], offs_k[k], lens_k[k]);
-                if (!err)
-                    err = lthip_launch_blake3(c2, (const uint8_t*)d_data, offs_k[k], lens_k[k], first_k[k] + pk->nparts, pk->chunk_cap, pk->leaf_cap,
-                                              pk->max_chunk, hash_k[k]);
-                if (err)
-                    (void)lthip_fail(ctx, err, "lthip_chunk_hash (a slice on the second stream)", c2->err);
-            }
-            hipEvent_t hashed = lthip_sync_event(ctx); // (also after a failure: the first stream never runs ahead of the second)
-            LTHIP_CHECK(ctx, hipEventRecord(hashed, c2->stream));
-            LTHIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, hashed, 0));
-            if (err)
-                return err;
-            LaunchTimer t(ctx, LTHIP_K_COMPACT);
-            for (uint32_t k = 1; k < S; ++k) // in order: slice k's base is the total behind slice k - 1's join
-            {
-                const lthip_plan* pk = plan->slice[k];
-                const uint64_t n = pk->chunk_cap > (uint64_t)pk->nparts + 1 ? pk->chunk_cap : (uint64_t)pk->nparts + 1;
-                hipLaunchKernelGGL(k_slice_join, dim3((uint32_t)div_up_u64(n, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)offs_k[k], (const uint32_t*)lens_k[k],
-                                   (const uint64_t*)hash_k[k], (const uint32_t*)first_k[k], pk->nparts, d_part_first + plan->slice_first[k], d_chunk_offsets,
-                                   d_chunk_lens, d_chunk_hashes);
-            }
-            LTHIP_LAUNCH_CHECK(ctx);
-            done = true;
-        }
-        else
-            ctx->err[0] = 0; // (no second context / scratch: the single pass)
-    }
-    if (!done)
-    {
-        err = chunk_scan_one(ctx, plan, d_data, d_chunk_offsets, d_chunk_lens, d_part_first);
-        if (!err && d_chunk_hashes)
-            err = lthip_launch_blake3(ctx, (const uint8_t*)d_data, d_chunk_offsets, d_chunk_lens, d_part_first + plan->nparts, plan->chunk_cap,
-                                      plan->leaf_cap, plan->max_chunk, d_chunk_hashes);
-    }
+    bool sliced;
+    int err = chunk_hash_sliced(ctx, plan, d_data, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first, &sliced);
+    uint64_t *bm0, *bm1;
+    if (!sliced && !(err = chunk_bitmaps(ctx, plan, &bm0, &bm1)) && !(err = chunk_scan(ctx, plan, d_data, bm0, bm1)))
+        err = chunk_cut_hash(ctx, plan, d_data, bm0, bm1, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first);
     if (err)
         return err;
     if (out_total)
@@ -1032,35 +1025,6 @@ extern "C" int lthip_chunk_hash(lthip_ctx* ctx, const lthip_plan* plan, const vo
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
         *out_total = total;
     }
-    return 0;
-}
-
-// candidate scan + cut selection + compaction of one plan on the context's stream
-static int chunk_scan_one(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, uint64_t* d_chunk_offsets, uint32_t* d_chunk_lens,
-                          uint32_t* d_part_first)
-{
-    void *bm0, *bm1, *region, *pcount;
-    int err;
-    if ((err = lthip_scratch(ctx, S_BM0, plan->bm0_words * 8, &bm0)))
-        return err;
-    if ((err = lthip_scratch(ctx, S_BM1, plan->bm1_words * 8, &bm1)))
-        return err;
-    if ((err = lthip_scratch(ctx, S_REGION, plan->chunk_cap * sizeof(uint2), &region)))
-        return err;
-    if ((err = lthip_scratch(ctx, S_PART_COUNT, ((size_t)plan->nparts + 1) * 4, &pcount)))
-        return err;
-
-    if (plan->nparts)
-    {
-        if ((err = lthip_launch_buzhash(ctx, plan, (const uint8_t*)d_data, (uint64_t*)bm0, (uint64_t*)bm1)))
-            return err;
-        if ((err = lthip_launch_select(ctx, plan, (const uint64_t*)bm0, (const uint64_t*)bm1, (uint2*)region,
-                                       (uint32_t*)pcount)))
-            return err;
-    }
-    if ((err = lthip_launch_compact(ctx, plan, (const uint2*)region, (const uint32_t*)pcount, d_part_first,
-                                    d_chunk_offsets, d_chunk_lens)))
-        return err;
     return 0;
 }
 

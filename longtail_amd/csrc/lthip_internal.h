@@ -40,18 +40,23 @@ struct DivTest
     uint32_t pow2; // d is a power of two: test (h & (d-1)) == d-1 instead
 };
 
-struct lthip_plan
+// what the parts a plan is aimed at come to (plan_layout, lthip_ctx.hip): the launches are sized by these
+struct PlanExtents
 {
-    int device;
     uint32_t nparts;
-    uint32_t min_chunk, avg_chunk, max_chunk;
-    DivTest div;
     uint64_t total_bytes;
     uint64_t ntiles;
     uint64_t chunk_cap;
     uint64_t bm0_words;
     uint64_t bm1_words;
     uint64_t leaf_cap;
+};
+
+struct lthip_plan : PlanExtents
+{
+    int device;
+    uint32_t min_chunk, avg_chunk, max_chunk;
+    DivTest div;
     uint64_t capacity_bytes; // bytes the plan was created for (lthip_plan_resize_single may aim it at fewer)
     uint32_t cap_parts;      // parts / tiles the device tables were allocated for (lthip_plan_reaim)
     uint64_t cap_tiles;
@@ -104,7 +109,7 @@ enum ScratchSlot
     S_Z_PERM,       // zstd decoder: the items in piece-major order, per-row counters, per-item done flags
     S_XCHG,         // multi-GPU exchange: range tables of lthip_exchange_reorder
     S_XCHG2,        // ... and the job tables of lthip_job_ordinals
-    S_SLICE_OFFS,   // lthip_chunk_hash in two slices: the second slice's chunk offsets / lengths / hashes / part table before the join
+    S_SLICE_OFFS,   // lthip_chunk_hash in slices: the chunk offsets / lengths / hashes / part tables of slices 1 .. S-1 before the join
     S_SLICE_LENS,
     S_SLICE_HASH,
     S_SLICE_FIRST,
@@ -123,7 +128,7 @@ struct lthip_ctx
     int device;
     hipStream_t stream;
     bool own_stream;
-    lthip_ctx* slice_ctx;                // lazily created: context (private stream, scratch of its own) of lthip_chunk_hash's second slice
+    lthip_ctx* slice_ctx;                // lazily created: context (private stream, scratch of its own) of lthip_chunk_hash's slices 1 .. S-1
     hipStream_t stream2;                 // lazily created side stream (non-blocking), see lthip_second_stream
     std::vector<hipEvent_t> sync_events; // ordering events between the two streams, reused round-robin
     size_t sync_next;

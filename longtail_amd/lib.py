@@ -757,7 +757,8 @@ class Plan:
 
     @property
     def slices(self) -> int:
-        """2 when chunk_hash runs this plan as two slices on two streams (per-kernel timings of scan and leaf hashing then overlap)."""
+        """How many slices chunk_hash runs this plan in on two streams (1 = the single pass; 2 in the product build, LTHIP_SLICES in the
+        ablation build): per-kernel timings of scan and leaf hashing of a sliced call overlap."""
         return int(self.ctx.lib.dll.lthip_plan_slices(self.h))
 
     def reaim(self, part_offsets, part_sizes):
