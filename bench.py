@@ -20,11 +20,14 @@ Workload (default = BASELINE.json configs[2]): a tree of 1 MiB random files, 64 
 N x 64 GiB) or in total (--scaling strong, configs[3]); the tree's jobs are assigned to ranks by lthip_partition_jobs
 (byte-balanced contiguous ranges by default: an asset's parts may straddle ranks, configs[4]); every rank synthesizes only its own
 parts.  value = bytes of the whole tree / max-over-ranks wall time of K steps (barrier + synchronize on both sides).
-The default run also measures, after the headline, the compressible variant, the north-star mixed-size tree, the zstd codec and
-BASELINE.json configs[4]'s shape (4 x 16 GiB files, ZStd) on compressible bytes ("secondary"; at N=1 also "restore": the device
-decoders' GB/s on 512 stored blocks of the compressible workload, round trip verified, and "host_fed": the session fed from pinned
-host memory), and times the reference's bikeshed-threaded CPU path on a bounded sample of EVERY one of those trees ("cpu_baseline",
-with the reference codec's ratio and the container's CPU quota beside it; class CpuReference) -- plus, in a process of its own
+A plain run does only that: set-up, warm-up, the K timed steps, --dump-outputs, the JSON line (per-kernel times from the timed
+steps' own events, roofline traffic from the committed profiles/*xtraffic*.json).  --full adds everything that takes runs of its
+own: first the memory-side traffic measured live under rocprofv3 and the box's measured copy / read peak, then, after the
+headline, the compressible variant, the north-star mixed-size tree, the zstd codec and BASELINE.json configs[4]'s shape
+(4 x 16 GiB files, ZStd) on compressible bytes ("secondary"; at N=1 also "restore": the device decoders' GB/s on 512 stored
+blocks of the compressible workload, round trip verified, and "host_fed": the session fed from pinned host memory), and the
+reference's bikeshed-threaded CPU path on a bounded sample of EVERY one of those trees ("cpu_baseline", with the reference
+codec's ratio and the container's CPU quota beside it; class CpuReference) -- plus, in a process of its own
 (tools/drop_in_child.py), the unmodified reference core with this library's plugin objects on the same sample ("drop_in").
 """
 from __future__ import annotations
@@ -1096,16 +1099,19 @@ def make_parser():
     ap.add_argument("--zstd-settings", type=int, choices=[2, 3, 4], default=2,
                     help="the reference's zstd settings id 'ztd2' (default) / 'ztd3' (max) / 'ztd4' (high): the parse the session runs")
     ap.add_argument("--no-compress", action="store_true", help="diagnostic: skip WriteContent (the line is then not the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: live traffic, measured peak, secondary workloads, restore / host-fed rates, CPU baseline and "
+                         "drop-in legs (a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / drop-in legs")
     ap.add_argument("--dedup", choices=["sharded", "replicated"], default="sharded",
                     help="N > 1: first-seen table sharded by hash (all-to-all, every rank inserts 1/N of the chunks) or rebuilt on every rank")
     ap.add_argument("--collective", choices=["torch", "c"], default="torch",
                     help="N > 1: the exchange's all-gathers by torch.distributed (RCCL backend) or by the C ABI's lthip_comm_allgather")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="roofline.traffic from the newest profiles/*xtraffic*.json instead of a live rocprofv3 --pmc run of this script on 8 GiB")
+                    help="--full: roofline.traffic from the newest profiles/*xtraffic*.json instead of a live rocprofv3 --pmc run of this script on 8 GiB")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: print how the tree's (asset, part) jobs fall onto --gpus ranks and what the exchange moves")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the compressible / mixed-size-tree measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the compressible / mixed-size-tree measurements")
     ap.add_argument("--dups", action="store_true", help="a quarter of the tree's files repeat earlier ones (whole-file and shifted duplicates)")
     ap.add_argument("--launch", choices=["torch", "plain"], default="torch",
                     help="--gpus N > 1 started without a launcher (WORLD_SIZE unset): how this process starts its N ranks -- 'torch': the "
@@ -1113,7 +1119,7 @@ def make_parser():
                          "every collective through the C ABI (lthip_comm_*), the id through a file (what tools/run8.sh does)")
     ap.add_argument("--handshake-only", action="store_true",
                     help="plain launch only: id file + lthip_comm_create + barrier + reductions + one all-to-all, then a JSON line; no kernels")
-    ap.add_argument("--cpu-gib", type=float, default=8.0, help="sample size of the CPU baseline")
+    ap.add_argument("--cpu-gib", type=float, default=8.0, help="sample size of the CPU baseline (--full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline's last step computed (chunk hashes, lengths and offsets, the "
                          "serialized indexes, block sizes, stored-block image bytes; seeded samples of long ones) as DIR/<name>.npy")
@@ -1136,30 +1142,30 @@ def main():
         handshake_only(args)
         return
 
-    # the traffic leg runs FIRST, in a child process under rocprofv3 (a profiler cannot wrap the process it runs in), rank 0 of a
-    # single-GPU run only; --no-live-traffic (and the child itself) take the committed measurement instead
+    # --full: the traffic leg runs FIRST, in a child process under rocprofv3 (a profiler cannot wrap the process it runs in), rank 0 of
+    # a single-GPU run only; a plain run, --no-live-traffic (and the child itself) take the committed measurement instead
     traffic = None
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
-    plain_default = (args.tree == "files" and args.kind == "random" and args.codec == "lz4" and not args.no_compress and not args.no_secondary
-                     and not args.no_cpu_baseline)  # the driver's command; every tool / test / profiler run passes one of these flags
+    full_default = (args.full and args.tree == "files" and args.kind == "random" and args.codec == "lz4" and not args.no_compress
+                    and not args.no_secondary and not args.no_cpu_baseline)
     under_profiler = any(k.startswith(("ROCP", "ROCPROF")) for k in os.environ)
-    if world_env == 1 and not args.no_live_traffic and plain_default and not under_profiler:
+    if world_env == 1 and not args.no_live_traffic and full_default and not under_profiler:
         traffic = live_traffic(args)
     b = Bench(args)
     b.traffic, b.traffic_cfg = traffic, dict(kind=args.kind, codec=args.codec, tree=args.tree)
     cfg = dict(tree=args.tree, kind=args.kind, codec=args.codec, gib=args.gib, file_mib=args.file_mib, scaling=args.scaling,
                partition=args.partition, dups=args.dups)
-    if b.world == 1 and not under_profiler:
+    if args.full and b.world == 1 and not under_profiler:
         b.measure_peak(4 if args.gib >= 8 else 1)
     main_res = b.run(cfg, args.steps, args.warmup, dump_dir=args.dump_outputs)
     secondary = None
     default_headline = args.tree == "files" and args.kind == "random" and args.codec == "lz4" and not args.no_compress
-    # the reference's CPU path beside EVERY number ("same tree on W cores"): one CpuReference for the headline and the
-    # secondary workloads, rank 0 of a single-GPU run only
-    cr = CpuReference(b, args) if (b.rank == 0 and b.world == 1 and not args.no_cpu_baseline) else None
+    # --full: the reference's CPU path beside EVERY number ("same tree on W cores"): one CpuReference for the headline
+    # and the secondary workloads, rank 0 of a single-GPU run only
+    cr = CpuReference(b, args) if (args.full and b.rank == 0 and b.world == 1 and not args.no_cpu_baseline) else None
     cpu_baseline = None
     try:
-        if not args.no_secondary and default_headline:
+        if args.full and not args.no_secondary and default_headline:
             # "report both" -- the compressible variant (match path + a real ratio) and the north-star tree; and
             # BASELINE.json configs[4]'s shape (4 x 16 GiB PAK-style files, ZStd 'ztd2') on data the codec can compress
             secondary = {}

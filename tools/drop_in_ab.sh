@@ -9,7 +9,7 @@ for lib in ${LIBS:-longtail_amd/liblongtail_hip.so}; do
 for leg in "random:--cpu-gib 8" "mixed:--kind mixed --cpu-gib 4" "zstd_mixed:--kind mixed --codec zstd --cpu-gib 4"; do
   name=${leg%%:*}; args=${leg#*:}
   out=gpurun_out/${tag}_dropin_$(basename $(dirname $lib))_$name
-  LTHIP_LIB_PATH=$(pwd)/$lib python bench.py --gib 8 --steps 1 --warmup 0 --no-secondary --no-live-traffic $args > $out.json 2> $out.err
+  LTHIP_LIB_PATH=$(pwd)/$lib python bench.py --full --gib 8 --steps 1 --warmup 0 --no-secondary --no-live-traffic $args > $out.json 2> $out.err
   python - "$(basename $(dirname $lib)) $name" $out.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
