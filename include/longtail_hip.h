@@ -53,6 +53,12 @@ LTHIP_EXPORT struct Longtail_HashAPI* Longtail_CreateHipBlake3HashAPI(void);
  * the GPU one by one (lthip_blake2s_one up to 64 KiB).  The chunker itself still computes BLAKE3 digests, unused here. */
 LTHIP_EXPORT struct Longtail_HashAPI* Longtail_CreateHipBlake2HashAPI(void);
 
+/* Replaces Longtail_CreateMeowHashAPI() (lib/meowhash/longtail_meowhash.h, implementation longtail_meowhash.c).  GetIdentifier ->
+ * 0x6d656f77 ('meow'); digests are the low 64 bits of Meow hash v0.5 with the default seed (MeowBegin / MeowAbsorb / MeowEnd,
+ * longtail_meowhash.c).  The entry points behave as the BLAKE2 object's, window digest table included: a chunker window filled by one
+ * object is filled again for the other, and each gets its own digests. */
+LTHIP_EXPORT struct Longtail_HashAPI* Longtail_CreateHipMeowHashAPI(void);
+
 /* WHEN TO CONSTRUCT THE CODEC OBJECTS.  One stored block per Compress call crosses the link twice: the HIP codec objects pay on data that
  * compresses -- WriteContent at 32 bikeshed workers: LZ4 31-47 GB/s against the reference codec's 22-25, ZStd 33-35 against 7-14 -- and
  * lose on incompressible bytes, where the CPU's LZ4 is a memcpy (25-29 against 56-105 GB/s): there bind the reference's own LZ4 beside
@@ -284,6 +290,28 @@ LTHIP_EXPORT int lthip_b2s_stream_batch(lthip_ctx* ctx, const void* d_data, uint
 LTHIP_EXPORT int lthip_b2s_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint64_t batch_count, void* d_state,
                                         uint64_t* d_out);
 
+/* ---- Meow hash v0.5, 64 bits: the 'meow' hash type (k_meow.hip) --------------------------------------------------------------
+ * Digest = the low 64 bits of MeowEnd after MeowBegin(MeowDefaultSeed) and MeowAbsorb of the bytes (longtail_meowhash.c:43-50).  The
+ * entry points have the contracts of the BLAKE2s ones above, name for name: _ranges[_dev], _one (at most 64 KiB, any alignment),
+ * _runs_u64[_bounded] (the bounds are ignored), and the stream pair.  Meow's absorb step takes whole 256-byte blocks, and a batch is
+ * 4096 of them; as for BLAKE2s, a batch is sent only when at least one byte follows it, and the final call takes the rest (1 .. one
+ * batch of bytes, or 0 bytes after 0 batches).  The state is {eight 128-bit registers, bytes so far}.  A stream is one serial chain on
+ * one quad of lanes. */
+#define LTHIP_MEOW_STREAM_BATCH LTHIP_B3_STREAM_BATCH
+#define LTHIP_MEOW_STREAM_STATE_BYTES 136u
+LTHIP_EXPORT int lthip_meow_ranges(lthip_ctx* ctx, const void* d_data, uint64_t range_count, const uint64_t* d_offsets,
+                                   const uint32_t* d_lens, uint32_t max_len, uint64_t* d_hashes);
+LTHIP_EXPORT int lthip_meow_ranges_dev(lthip_ctx* ctx, const void* d_data, uint64_t count_bound, const uint32_t* d_count,
+                                       const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t max_len, uint64_t* d_hashes);
+LTHIP_EXPORT int lthip_meow_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
+LTHIP_EXPORT int lthip_meow_runs_u64_bounded(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count,
+                                             uint64_t total_values_bound, uint64_t run_values_bound, uint64_t* d_out);
+LTHIP_EXPORT int lthip_meow_runs_u64(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count,
+                                     uint64_t* d_out);
+LTHIP_EXPORT int lthip_meow_stream_batch(lthip_ctx* ctx, const void* d_data, uint64_t batch_index, void* d_state);
+LTHIP_EXPORT int lthip_meow_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint64_t batch_count, void* d_state,
+                                         uint64_t* d_out);
+
 /* ---- phase 2: per-block compression ----------------------------------------------------------------
  * One call compresses a batch of stored blocks (the unit of CompressBlock, compressblockstore.c:67-141).
  * Block b = d_src[src_offsets[b] .. +src_sizes[b]) -> d_dst[dst_offsets[b] ..) with capacity dst_caps[b];
@@ -414,7 +442,8 @@ LTHIP_EXPORT int lthip_dedup_min_ordinal(lthip_ctx* ctx, uint64_t count, const u
  * asset a owning asset_chunk_counts[a] of them -- to the SERIALIZED VersionIndex (the bytes Longtail_WriteVersionIndexToBuffer
  * produces, :3415): first-seen unique chunk list + per-asset-chunk indexes, content hash per asset (hash of its chunk-hash
  * array), path hashes.  HASH TYPE: path, content and block hashes of this and the two builders below are BLAKE2s-64 when
- * hash_identifier is 'blk2' (0x626c6b32) and BLAKE3-64 for any other identifier ('blk3' and, as before, everything else); the
+ * hash_identifier is 'blk2' (0x626c6b32), Meow-64 when it is 'meow' (0x6d656f77), and BLAKE3-64 for any other identifier ('blk3' and,
+ * as before, everything else); the
  * chunk hashes are the caller's and must be of the same type.  The file list is a struct Longtail_FileInfos taken apart (src/longtail.h:1684-1692); directories are
  * assets with zero chunks.  Host arrays unless marked d_.  Returns ENOMEM with *out_size set when `out` is too small. */
 LTHIP_EXPORT size_t lthip_version_index_size(uint32_t asset_count, uint64_t unique_chunk_count, uint64_t asset_chunk_index_count,
@@ -493,8 +522,9 @@ typedef struct lthip_ingest lthip_ingest;
 typedef struct lthip_ingest_config
 {
     uint32_t target_chunk_size;    /* recorded in the VersionIndex */
-    uint32_t hash_identifier;      /* 0x626c6b33 'blk3', or 0x626c6b32 'blk2': path / content / block hashes with BLAKE2s (the caller's
-                                      chunk hashes then come from lthip_blake2s_ranges[_dev]) */
+    uint32_t hash_identifier;      /* 0x626c6b33 'blk3', 0x626c6b32 'blk2': path / content / block hashes with BLAKE2s (the caller's
+                                      chunk hashes then come from lthip_blake2s_ranges[_dev]), or 0x6d656f77 'meow': with Meow
+                                      (chunk hashes from lthip_meow_ranges[_dev]); any other value hashes with BLAKE3 */
     uint32_t max_block_size;       /* cmd/main.c:3006-3009 defaults: 8 MiB */
     uint32_t max_chunks_per_block; /*                                 1024  */
     uint32_t compression_type;     /* the tag stored with chunks and blocks: 'lz42', 'ztd1'..'ztd5' */

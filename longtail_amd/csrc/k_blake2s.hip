@@ -11,12 +11,14 @@
 //                    start at any byte: message words are rebuilt from aligned dwords with one v_alignbit each, and the next
 //                    block's loads are in flight while the current one is compressed.  Lanes take the ranges in an order sorted
 //                    by length class (k_b2s_class_*: a device-side counting sort of ceil(len / 64) into 4 classes per octave,
-//                    longest first), so the lanes of a wave run near-equal numbers of compressions.  Throughput path.
+//                    longest first), so the lanes of a wave run near-equal numbers of compressions.  Throughput path.  (The sort
+//                    is shared with Meow, k_meow.hip, which counts 256-byte blocks: lthip_len_class_order.)
 //   quad per message the four lanes of a quad hold the four columns (lane i: v[i], v[4+i], v[8+i], v[12+i]); the diagonal step
 //                    is a DPP quad rotation of rows 1..3 before and after.  A compression is ~1/4 of the dependent instructions of
 //                    the lane form.  Latency path: one input of up to 64 KiB (k_b2s_one), few long ranges (k_b2s_quads), the
 //                    streaming pair (k_b2s_stream).
 #include "lthip_internal.h"
+#include "k_hash_common.h"
 
 namespace
 {
@@ -89,20 +91,14 @@ __device__ __forceinline__ void b2_compress(uint32_t (&h)[8], const uint32_t (&m
     h[7] ^= s7 ^ s15;
 }
 
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ uint32_t range_count(uint64_t bound, const uint32_t* n_dev)
-{
-    return (uint32_t)(n_dev ? (*n_dev < bound ? *n_dev : bound) : bound);
-}
-
 // ---------------------------------------------------------------------------------------------------
-// length classes: cls = 4 * floor(log2(blocks)) + the next two bits of the block count (classes 1.25x apart at most), 0 .. 107
+// length classes: cls = 4 * floor(log2(blocks)) + the next two bits of the block count (classes 1.25x apart at most), 0 .. 127;
+// a block is 1 << unit_shift bytes (BLAKE2s: 64, Meow: 256)
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t B2_CLASSES = 128;
-__device__ __forceinline__ uint32_t b2_class(uint32_t len)
+__device__ __forceinline__ uint32_t b2_class(uint32_t len, uint32_t unit_shift)
 {
-    const uint32_t nb = len ? (len + 63u) >> 6 : 1u;
+    const uint32_t nb = len ? ((len - 1u) >> unit_shift) + 1u : 1u;
     const uint32_t e = 31u - (uint32_t)__builtin_clz(nb);
     const uint32_t mant = e >= 2u ? (nb >> (e - 2u)) & 3u : (nb << (2u - e)) & 3u;
     return e * 4u + mant;
@@ -110,7 +106,7 @@ __device__ __forceinline__ uint32_t b2_class(uint32_t len)
 
 // hist[cls] += ranges of that class (LDS histogram per workgroup, one global atomic per class)
 __global__ __launch_bounds__(256) void k_b2s_class_hist(const uint32_t* __restrict__ lens, uint64_t bound, const uint32_t* __restrict__ n_dev,
-                                                        uint32_t* __restrict__ hist)
+                                                        uint32_t unit_shift, uint32_t* __restrict__ hist)
 {
     __shared__ uint32_t s_h[B2_CLASSES];
     const uint32_t n = range_count(bound, n_dev);
@@ -119,7 +115,7 @@ __global__ __launch_bounds__(256) void k_b2s_class_hist(const uint32_t* __restri
     __syncthreads();
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
-        atomicAdd(&s_h[b2_class(lens[i])], 1u);
+        atomicAdd(&s_h[b2_class(lens[i], unit_shift)], 1u);
     __syncthreads();
     if (threadIdx.x < B2_CLASSES && s_h[threadIdx.x])
         atomicAdd(&hist[threadIdx.x], s_h[threadIdx.x]);
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(B2_CLASSES) void k_b2s_class_scan(const uint32_t* _
 
 // order[cursor[cls]++] = i  (the order inside a class is whatever the atomics give: every range still gets its own digest slot)
 __global__ __launch_bounds__(256) void k_b2s_class_scatter(const uint32_t* __restrict__ lens, uint64_t bound, const uint32_t* __restrict__ n_dev,
-                                                           uint32_t* __restrict__ cursor, uint32_t* __restrict__ order)
+                                                           uint32_t unit_shift, uint32_t* __restrict__ cursor, uint32_t* __restrict__ order)
 {
     __shared__ uint32_t s_h[B2_CLASSES], s_base[B2_CLASSES];
     const uint32_t n = range_count(bound, n_dev);
@@ -159,7 +155,7 @@ __global__ __launch_bounds__(256) void k_b2s_class_scatter(const uint32_t* __res
     uint32_t cls = 0, rank = 0;
     if (i < n)
     {
-        cls = b2_class(lens[i]);
+        cls = b2_class(lens[i], unit_shift);
         rank = atomicAdd(&s_h[cls], 1u);
     }
     __syncthreads();
@@ -268,15 +264,6 @@ __device__ __forceinline__ void b2_quad_idx(B2QuadIdx& q, uint32_t qi)
         q.ix[4 * r + 3] = B2_SIGMA[r][9u + 2u * qi];
     }
 }
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t quad_perm(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, false);
-}
-constexpr int QP_ROT1 = 0x39; // lane i <- lane (i + 1) & 3
-constexpr int QP_ROT2 = 0x4E; // lane i <- lane (i + 2) & 3
-constexpr int QP_ROT3 = 0x93; // lane i <- lane (i + 3) & 3
 
 // lane qi of the quad holds h[qi] (h0) and h[4 + qi] (h1); blk: the 16 message words in LDS.  All four lanes must be active.
 __device__ __forceinline__ void b2_quad_compress(uint32_t& h0, uint32_t& h1, const uint32_t* blk, const B2QuadIdx& q, uint32_t qi,
@@ -398,46 +385,7 @@ __global__ __launch_bounds__(64) void k_b2s_one(const uint8_t* __restrict__ in, 
     extern __shared__ __attribute__((aligned(16))) uint32_t s_in[]; // roundup(len, 64) bytes (at least one block), zero-padded
     const uint32_t lane = threadIdx.x;
     const uint32_t nblocks = len ? (len + 63u) >> 6 : 1u;
-    for (uint32_t i = lane; i < nblocks * 16u; i += 64u)
-        s_in[i] = 0u;
-    __syncthreads();
-    if (len)
-    {
-        const uint32_t head = (uint32_t)((uintptr_t)in & 15u);
-        const uint32_t nvec = (head + len + 15u) >> 4;
-        const uint4* in4 = reinterpret_cast<const uint4*>(in - head);
-        uint8_t* s8 = reinterpret_cast<uint8_t*>(s_in);
-        for (uint32_t v0 = 0; v0 < nvec; v0 += 64u * 8u)
-        {
-            uint4 qv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-            {
-                const uint32_t v = v0 + (uint32_t)u * 64u + lane;
-                qv[u] = v < nvec ? in4[v] : make_uint4(0, 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-            {
-                const uint32_t v = v0 + (uint32_t)u * 64u + lane;
-                if (v >= nvec)
-                    continue;
-                if (head == 0u && v * 16u + 16u <= len)
-                    reinterpret_cast<uint4*>(s_in)[v] = qv[u];
-                else
-                {
-                    const uint32_t w[4] = {qv[u].x, qv[u].y, qv[u].z, qv[u].w};
-                    for (uint32_t k = 0; k < 16u; ++k)
-                    {
-                        const int64_t j = (int64_t)v * 16 + k - head; // position in the input
-                        if (j >= 0 && j < (int64_t)len)
-                            s8[j] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
+    stage_input_lds(s_in, nblocks * 16u, in, len, lane);
     if (lane >= 4u)
         return;
     B2QuadIdx q;
@@ -497,6 +445,31 @@ __global__ __launch_bounds__(64) void k_b2s_stream(const uint8_t* __restrict__ d
 
 } // namespace
 
+// The length-class order of count ranges (count = min(count_bound, *d_count) when d_count != null), longest class first, in blocks of
+// 1 << unit_shift bytes: *order (count_bound entries) and *n_long = the device count of ranges of class long_class and above, which
+// lead the order.  S_B2_ORDER scratch; queued on the context's stream, nothing read back.
+int lthip_len_class_order(lthip_ctx* ctx, const uint32_t* d_lens, const uint32_t* d_count, uint64_t count_bound, uint32_t unit_shift,
+                          uint32_t long_class, const uint32_t** order, const uint32_t** n_long)
+{
+    void* sc;
+    int err;
+    if ((err = lthip_scratch(ctx, S_B2_ORDER, count_bound * 4u + 2u * B2_CLASSES * 4u, &sc)))
+        return err;
+    uint32_t* hist = (uint32_t*)sc;
+    uint32_t* cursor = hist + B2_CLASSES;
+    uint32_t* ord = cursor + B2_CLASSES;
+    const uint32_t grid = (uint32_t)div_up_u64(count_bound, 256);
+    LTHIP_CHECK(ctx, hipMemsetAsync(hist, 0, B2_CLASSES * 4u, ctx->stream));
+    hipLaunchKernelGGL(k_b2s_class_hist, dim3(grid), dim3(256), 0, ctx->stream, d_lens, count_bound, d_count, unit_shift, hist);
+    hipLaunchKernelGGL(k_b2s_class_scan, dim3(1), dim3(B2_CLASSES), 0, ctx->stream, (const uint32_t*)hist, cursor);
+    hipLaunchKernelGGL(k_b2s_class_scatter, dim3(grid), dim3(256), 0, ctx->stream, d_lens, count_bound, d_count, unit_shift, cursor, ord);
+    LTHIP_LAUNCH_CHECK(ctx);
+    // after the scatter cursor[c] = end of class c in the order, so cursor[long_class] = ranges of that class and above
+    *order = ord;
+    *n_long = cursor + long_class;
+    return 0;
+}
+
 // ranges up to this many go to the quad kernel (no sort): a call of few ranges is bound by its longest chain
 constexpr uint64_t B2_QUAD_RANGES = 256;
 // in larger calls, ranges of this length class and above (>= 1 MiB: 16384 blocks) also run on quads -- an asset's content hash over
@@ -519,24 +492,16 @@ int lthip_launch_blake2s(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* 
         LTHIP_LAUNCH_CHECK(ctx);
         return 0;
     }
-    void* sc;
+    const uint32_t* order;
+    const uint32_t* n_long;
     int err;
-    if ((err = lthip_scratch(ctx, S_B2_ORDER, count_bound * 4u + 2u * B2_CLASSES * 4u, &sc)))
+    if ((err = lthip_len_class_order(ctx, d_lens, d_count, count_bound, 6u, B2_LONG_CLASS, &order, &n_long)))
         return err;
-    uint32_t* hist = (uint32_t*)sc;
-    uint32_t* cursor = hist + B2_CLASSES;
-    uint32_t* order = cursor + B2_CLASSES;
     const uint32_t grid = (uint32_t)div_up_u64(count_bound, 256);
-    LTHIP_CHECK(ctx, hipMemsetAsync(hist, 0, B2_CLASSES * 4u, ctx->stream));
-    hipLaunchKernelGGL(k_b2s_class_hist, dim3(grid), dim3(256), 0, ctx->stream, d_lens, count_bound, d_count, hist);
-    hipLaunchKernelGGL(k_b2s_class_scan, dim3(1), dim3(B2_CLASSES), 0, ctx->stream, (const uint32_t*)hist, cursor);
-    hipLaunchKernelGGL(k_b2s_class_scatter, dim3(grid), dim3(256), 0, ctx->stream, d_lens, count_bound, d_count, cursor, order);
-    // after the scatter cursor[c] = end of class c in the order, so cursor[B2_LONG_CLASS] = ranges of that class and above
-    const uint32_t* n_long = cursor + B2_LONG_CLASS;
-    hipLaunchKernelGGL(k_b2s_quads, dim3(B2_LONG_GRID), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count,
-                       (const uint32_t*)order, n_long, d_hashes);
-    hipLaunchKernelGGL(k_b2s_lanes, dim3(grid), dim3(256), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count,
-                       (const uint32_t*)order, n_long, d_hashes);
+    hipLaunchKernelGGL(k_b2s_quads, dim3(B2_LONG_GRID), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count, order,
+                       n_long, d_hashes);
+    hipLaunchKernelGGL(k_b2s_lanes, dim3(grid), dim3(256), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count, order, n_long,
+                       d_hashes);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }

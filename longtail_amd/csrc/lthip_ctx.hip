@@ -1175,12 +1175,14 @@ int lthip_hash_ranges_known(lthip_ctx* ctx, const void* d_data, uint64_t range_c
 }
 
 // The hash of a longtail hash type over device ranges (lthip_internal.h): the one place the index builders and the ingest session
-// choose between BLAKE3 and BLAKE2s.
+// choose between BLAKE3, BLAKE2s and Meow.
 int lthip_hash_ranges_by_id(lthip_ctx* ctx, uint32_t hash_identifier, const void* d_data, uint64_t range_count, const uint64_t* d_offsets,
                             const uint32_t* d_lens, uint32_t max_len, uint64_t leaf_total, uint64_t* d_hashes)
 {
     if (hash_identifier == LTHIP_HASH_BLAKE2)
         return lthip_blake2s_ranges(ctx, d_data, range_count, d_offsets, d_lens, max_len, d_hashes);
+    if (hash_identifier == LTHIP_HASH_MEOW)
+        return lthip_meow_ranges(ctx, d_data, range_count, d_offsets, d_lens, max_len, d_hashes);
     if (leaf_total)
         return lthip_hash_ranges_known(ctx, d_data, range_count, d_offsets, d_lens, max_len, leaf_total, d_hashes);
     return lthip_hash_ranges(ctx, d_data, range_count, d_offsets, d_lens, max_len, d_hashes);
@@ -1253,4 +1255,72 @@ extern "C" int lthip_b2s_stream_final(lthip_ctx* ctx, const void* d_tail, uint32
         return EINVAL;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     return lthip_launch_blake2s_stream(ctx, d_tail, tail_len, (uint32_t*)d_state, batch_count == 0, 1, d_out);
+}
+
+// ---- Meow hash v0.5, low 64 bits ('meow', k_meow.hip): the contracts of the BLAKE2s calls ----
+extern "C" int lthip_meow_ranges_dev(lthip_ctx* ctx, const void* d_data, uint64_t count_bound, const uint32_t* d_count,
+                                     const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t max_len, uint64_t* d_hashes)
+{
+    (void)max_len; // a lane per range: the length bound does not change the launch
+    if (!ctx || (count_bound && (!d_offsets || !d_lens || !d_hashes)))
+        return EINVAL;
+    if (count_bound == 0)
+        return 0;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return lthip_launch_meow(ctx, (const uint8_t*)d_data, d_offsets, d_lens, d_count, count_bound, d_hashes);
+}
+
+extern "C" int lthip_meow_ranges(lthip_ctx* ctx, const void* d_data, uint64_t range_count, const uint64_t* d_offsets, const uint32_t* d_lens,
+                                 uint32_t max_len, uint64_t* d_hashes)
+{
+    return lthip_meow_ranges_dev(ctx, d_data, range_count, nullptr, d_offsets, d_lens, max_len, d_hashes);
+}
+
+extern "C" int lthip_meow_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out)
+{
+    if (!ctx || !out || (len && !in))
+        return EINVAL;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return lthip_launch_meow_one(ctx, in, len, out);
+}
+
+extern "C" int lthip_meow_runs_u64(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count, uint64_t* d_out)
+{
+    return lthip_meow_runs_u64_bounded(ctx, d_values, d_first, run_count, 0, 0, d_out);
+}
+
+extern "C" int lthip_meow_runs_u64_bounded(lthip_ctx* ctx, const uint64_t* d_values, const uint32_t* d_first, uint32_t run_count,
+                                           uint64_t total_values_bound, uint64_t run_values_bound, uint64_t* d_out)
+{
+    (void)total_values_bound;
+    (void)run_values_bound;
+    if (!ctx || !d_values || !d_first || !d_out)
+        return EINVAL;
+    if (run_count == 0)
+        return 0;
+    uint64_t* offs;
+    uint32_t* lens;
+    int err = runs_to_ranges(ctx, d_first, run_count, &offs, &lens);
+    if (err)
+        return err;
+    return lthip_launch_meow(ctx, (const uint8_t*)d_values, offs, lens, nullptr, run_count, d_out);
+}
+
+// Streaming Meow: batch `batch_index` (LTHIP_MEOW_STREAM_BATCH bytes = whole 256-byte blocks, not the end of the stream) advances the
+// state; the final call absorbs the rest and ends with the total length.  Batch 0 starts the state, so d_state needs no initialisation.
+extern "C" int lthip_meow_stream_batch(lthip_ctx* ctx, const void* d_data, uint64_t batch_index, void* d_state)
+{
+    if (!ctx || !d_data || !d_state)
+        return EINVAL;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return lthip_launch_meow_stream(ctx, d_data, LTHIP_MEOW_STREAM_BATCH, (uint32_t*)d_state, batch_index == 0, 0, nullptr);
+}
+
+extern "C" int lthip_meow_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_t tail_len, uint64_t batch_count, void* d_state,
+                                       uint64_t* d_out)
+{
+    if (!ctx || !d_out || (tail_len && !d_tail) || tail_len > LTHIP_MEOW_STREAM_BATCH || (batch_count && (!tail_len || !d_state)))
+        return EINVAL;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return lthip_launch_meow_stream(ctx, d_tail, tail_len, (uint32_t*)d_state, batch_count == 0, 1, d_out);
 }

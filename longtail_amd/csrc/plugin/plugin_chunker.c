@@ -190,7 +190,7 @@ static int chunker_refill(struct HipChunker* c, Longtail_Chunker_Feeder feeder, 
     c->pub.hashes = w->h_hash;
     c->pub.count = c->nfinal;
     c->pub.owner = w;
-    w->b2_ready = 0;
+    w->hash2_id = 0;
     ltp_window_publish(c->slot, &c->pub);
     ltp_window_set_current(c->slot);
     return 0;

@@ -86,8 +86,9 @@ struct ltp_chunk_window
     uint64_t* h_hash;
     lthip_plan* plan; /* one part of `cap` bytes, re-aimed per refill (lthip_plan_resize_single) */
     int d_resident;   /* d_win / d_off / d_len hold the published bytes and chunk lists (the direct path, not the batcher's arena) */
-    int b2_ready;     /* h_hash2 holds the BLAKE2 digests of the published chunks (reset at every publish) */
-    uint64_t* h_hash2; /* pinned, ccap entries, allocated by the first BLAKE2 look-up */
+    uint32_t hash2_id; /* the hash kind (its identifier) whose digests of the published chunks h_hash2 holds; 0: none (reset at every
+                          publish).  A look-up by another kind fills the table again. */
+    uint64_t* h_hash2; /* pinned, ccap entries, allocated by the first look-up of a kind without window digests (BLAKE2s, Meow) */
     int cls;          /* 0 small, 1 large, 2 private */
     struct ltp_chunk_window* next;
 };
@@ -110,7 +111,8 @@ int ltp_memo_get(const void* data, uint32_t length, uint64_t* out_hash);
 int ltp_codec_batch(int codec, int decompress, int quality, const void* d_in, uint32_t n, void* d_out, uint32_t cap, uint32_t* produced);
 void ltp_codec_batch_shutdown(void);
 
-/* ---- plugin_hash.c: the HashAPI object over a table of device calls (BLAKE3 there, BLAKE2s in plugin_blake2.c).  The streaming
+/* ---- plugin_hash.c: the HashAPI object over a table of device calls (BLAKE3 there, BLAKE2s in plugin_blake2.c, Meow in
+ * plugin_meow.c).  The streaming
  * context collects batches of LTHIP_B3_STREAM_BATCH bytes on the host for every kind; stream_state_bytes of device memory per stream.
  * use_windows: the chunk windows' digests and the batcher's memo are of this kind (BLAKE3 only) ---- */
 struct ltp_chunk_window;
@@ -126,9 +128,16 @@ struct ltp_hash_kind
     int use_windows;
     /* kinds without window digests (use_windows 0): the digest of a chunk of the calling thread's current window, computed for the
      * whole window on first use -- 1 + *out_hash, 0 (not such a chunk) or -errno; may be NULL */
-    int (*window_lookup)(const void* data, uint32_t len, uint64_t* out_hash);
+    int (*window_lookup)(const struct ltp_hash_kind* kind, const void* data, uint32_t len, uint64_t* out_hash);
 };
 struct Longtail_HashAPI* ltp_create_hash_api(const struct ltp_hash_kind* kind);
+/* window_lookup of the kinds without window digests: the window's table h_hash2, filled for `kind` by one kind->ranges call over
+ * all of the window's chunks -- from the window's device copy when the chunker left it resident (the direct path), else uploaded
+ * again from the pinned window (the batcher chunks small windows in an arena of its own) -- and read by later look-ups of the same
+ * kind.  Only the calling thread's current window is consulted (longtail's DynamicChunking calls NextChunk and HashBuffer
+ * alternately on one thread, src/longtail.c:2231-2296): the registry keeps it stable meanwhile, and no other thread reads or fills
+ * the table. */
+int ltp_window_table_lookup(const struct ltp_hash_kind* kind, const void* data, uint32_t len, uint64_t* out_hash);
 
 /* ---- error latch: void / value-returning entry points of the plugin structs (HashAPI.Hash, EndContext) cannot report failure;
  * the first errno of such a call on a thread is kept until read.  Exported as Longtail_Hip_GetLastError(). ---- */

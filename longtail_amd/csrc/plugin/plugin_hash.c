@@ -244,7 +244,7 @@ static int HipHash_HashBuffer(struct Longtail_HashAPI* hash_api, uint32_t length
     if (!kind->use_windows)
     {
         /* the window registry and the memo hold BLAKE3 digests: the kind's own table of the chunker's window, else the GPU */
-        const int hit = kind->window_lookup && length ? kind->window_lookup(data, length, out_hash) : 0;
+        const int hit = kind->window_lookup && length ? kind->window_lookup(kind, data, length, out_hash) : 0;
         if (hit < 0)
             return -hit;
         return hit ? 0 : gpu_hash(kind, data, length, out_hash);
@@ -254,6 +254,49 @@ static int HipHash_HashBuffer(struct Longtail_HashAPI* hash_api, uint32_t length
     if (ltp_memo_get(data, length, out_hash)) /* an asset's digest array the batcher has hashed on the GPU already */
         return 0;
     return gpu_hash(kind, data, length, out_hash);
+}
+
+struct window_table_arg
+{
+    const struct ltp_hash_kind* kind;
+    uint64_t* out_hash;
+};
+
+static int window_table_digest(const struct ltp_window* pub, uint32_t index, void* varg)
+{
+    const struct window_table_arg* arg = (const struct window_table_arg*)varg;
+    struct ltp_chunk_window* w = pub->owner;
+    if (w->hash2_id != arg->kind->id)
+    {
+        lthip_ctx* ctx = ltp_thread_ctx();
+        if (!ctx)
+            return -ENODEV;
+        int err = 0;
+        w->hash2_id = 0; /* a failure below leaves no kind's table */
+        if (!w->h_hash2)
+            err = lthip_malloc_pinned(ctx, (size_t)w->ccap * 8, (void**)&w->h_hash2);
+        if (!err && !w->d_resident)
+        {
+            err = lthip_copy_h2d(ctx, w->d_win, pub->base, (size_t)pub->size);
+            if (!err) err = lthip_copy_h2d(ctx, w->d_off, pub->offsets, (size_t)pub->count * 8);
+            if (!err) err = lthip_copy_h2d(ctx, w->d_len, pub->lens, (size_t)pub->count * 4);
+        }
+        if (!err) err = arg->kind->ranges(ctx, w->d_win, pub->count, w->d_off, w->d_len, w->max_chunk, w->d_hash);
+        if (!err) err = lthip_copy_d2h(ctx, w->h_hash2, w->d_hash, (size_t)pub->count * 8);
+        if (!err) err = lthip_ctx_sync(ctx);
+        if (err)
+            return -err;
+        w->hash2_id = arg->kind->id;
+    }
+    *arg->out_hash = w->h_hash2[index];
+    return 1;
+}
+
+int ltp_window_table_lookup(const struct ltp_hash_kind* kind, const void* data, uint32_t len, uint64_t* out_hash)
+{
+    struct window_table_arg arg = {kind, out_hash};
+    const int r = ltp_window_with_current(data, len, window_table_digest, &arg);
+    return r < 0 && r != -1 ? r : (r == 1);
 }
 
 static void HipHash_Dispose(struct Longtail_API* api) { ltp_free(api); }

@@ -34,6 +34,9 @@ HASH_BLAKE3 = 0x626C6B33  # 'blk3', lib/blake3/longtail_blake3.c
 HASH_BLAKE2 = 0x626C6B32  # 'blk2', lib/blake2/longtail_blake2.c
 B2S_STREAM_BATCH = 1 << 20  # include/longtail_hip.h LTHIP_B2S_STREAM_BATCH
 B2S_STREAM_STATE_BYTES = 64
+HASH_MEOW = 0x6D656F77  # 'meow', lib/meowhash/longtail_meowhash.c
+MEOW_STREAM_BATCH = 1 << 20  # include/longtail_hip.h LTHIP_MEOW_STREAM_BATCH
+MEOW_STREAM_STATE_BYTES = 136
 
 
 class LongtailHipError(RuntimeError):
@@ -85,6 +88,7 @@ class HipLib:
         sig("Longtail_CreateHipChunkerAPI", vp, [])
         sig("Longtail_CreateHipBlake3HashAPI", vp, [])
         sig("Longtail_CreateHipBlake2HashAPI", vp, [])
+        sig("Longtail_CreateHipMeowHashAPI", vp, [])
         sig("Longtail_CreateHipLZ4CompressionAPI", vp, [])
         sig("Longtail_CompressionRegistry_CreateForHipLZ4", vp, [u32, P(u32)])
         sig("Longtail_GetHipLZ4DefaultQuality", u32, [])
@@ -160,6 +164,13 @@ class HipLib:
         sig("lthip_blake2s_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
         sig("lthip_b2s_stream_batch", i32, [vp, vp, u64, vp])
         sig("lthip_b2s_stream_final", i32, [vp, vp, u32, u64, vp, vp])
+        sig("lthip_meow_ranges", i32, [vp, vp, u64, vp, vp, u32, vp])
+        sig("lthip_meow_ranges_dev", i32, [vp, vp, u64, vp, vp, vp, u32, vp])
+        sig("lthip_meow_one", i32, [vp, vp, u32, vp])
+        sig("lthip_meow_runs_u64", i32, [vp, vp, vp, u32, vp])
+        sig("lthip_meow_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
+        sig("lthip_meow_stream_batch", i32, [vp, vp, u64, vp])
+        sig("lthip_meow_stream_final", i32, [vp, vp, u32, u64, vp, vp])
         sig("lthip_dedup_first_seen_range", i32, [vp, u64, vp, u64, u64, vp, vp])
         sig("lthip_gather_ranges", i32, [vp, vp, u64, vp, vp, vp, vp])
         sig("lthip_pack_blocks", i32, [u64, vp, u32, u32, vp, u64, P(u64)])
@@ -372,6 +383,44 @@ class Context:
         tail = length - batches * B2S_STREAM_BATCH
         self._check(self.lib.dll.lthip_b2s_stream_final(self.h, base + batches * B2S_STREAM_BATCH if tail else None, tail, batches,
                                                         _ptr(state), _ptr(out)), "lthip_b2s_stream_final")
+        return int(out.cpu().numpy().view(np.uint64)[0])
+
+    # -- Meow hash v0.5, 64 bits ('meow') --
+    def meow_ranges(self, data, offsets, lens, max_len: int = 0, out=None, count_bound: Optional[int] = None, d_count=None):
+        """d_hashes[i] = meow-64 of the range; with d_count (device u32) the number of ranges is min(count_bound, *d_count)."""
+        torch = self.torch
+        n = int(offsets.numel()) if count_bound is None else int(count_bound)
+        if out is None:
+            out = torch.empty(max(1, n), dtype=torch.int64, device=self._dev())
+        if d_count is None:
+            err = self.lib.dll.lthip_meow_ranges(self.h, _ptr(data), n, _ptr(offsets), _ptr(lens), max_len, _ptr(out))
+        else:
+            err = self.lib.dll.lthip_meow_ranges_dev(self.h, _ptr(data), n, _ptr(d_count), _ptr(offsets), _ptr(lens), max_len, _ptr(out))
+        self._check(err, "lthip_meow_ranges")
+        return out[:n]
+
+    def meow_one(self, data, length: int, out) -> None:
+        """One input of at most 64 KiB (device or pinned memory); the digest lands in `out` (device or pinned) on the stream."""
+        self._check(self.lib.dll.lthip_meow_one(self.h, _ptr(data), length, _ptr(out)), "lthip_meow_one")
+
+    def meow_runs_u64(self, values, first, run_count: int, out=None):
+        if out is None:
+            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
+        self._check(self.lib.dll.lthip_meow_runs_u64(self.h, _ptr(values), _ptr(first), run_count, _ptr(out)), "lthip_meow_runs_u64")
+        return out[:run_count]
+
+    def meow_stream(self, data, length: int) -> int:
+        """Streaming meow-64 of the first `length` bytes of a device tensor, batch by batch (lthip_meow_stream_batch / _final)."""
+        torch = self.torch
+        state = torch.empty(MEOW_STREAM_STATE_BYTES, dtype=torch.uint8, device=self._dev())
+        out = torch.zeros(1, dtype=torch.int64, device=self._dev())
+        base = _ptr(data)
+        batches = max(0, (length - 1) // MEOW_STREAM_BATCH)
+        for b in range(batches):
+            self._check(self.lib.dll.lthip_meow_stream_batch(self.h, base + b * MEOW_STREAM_BATCH, b, _ptr(state)), "lthip_meow_stream_batch")
+        tail = length - batches * MEOW_STREAM_BATCH
+        self._check(self.lib.dll.lthip_meow_stream_final(self.h, base + batches * MEOW_STREAM_BATCH if tail else None, tail, batches,
+                                                         _ptr(state), _ptr(out)), "lthip_meow_stream_final")
         return int(out.cpu().numpy().view(np.uint64)[0])
 
     def timing_get_blake2s(self):
