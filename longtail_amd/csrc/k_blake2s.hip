@@ -10,7 +10,7 @@
 //                    the SIGMA schedule folded into register names, rotations are v_alignbit (as b3_g, k_blake3.hip).  Ranges
 //                    start at any byte: message words are rebuilt from aligned dwords with one v_alignbit each, and the next
 //                    block's loads are in flight while the current one is compressed.  Lanes take the ranges in an order sorted
-//                    by length class (k_b2s_class_*: a device-side counting sort of ceil(len / 64) into 4 classes per octave,
+//                    by length class (k_b2s_class_*, lthip_hash.hip: a device-side counting sort of ceil(len / 64) into 4 classes per octave,
 //                    longest first), so the lanes of a wave run near-equal numbers of compressions.  Throughput path.  (The sort
 //                    is shared with Meow, k_meow.hip, which counts 256-byte blocks: lthip_len_class_order.)
 //   quad per message the four lanes of a quad hold the four columns (lane i: v[i], v[4+i], v[8+i], v[12+i]); the diagonal step
@@ -89,81 +89,6 @@ __device__ __forceinline__ void b2_compress(uint32_t (&h)[8], const uint32_t (&m
     h[5] ^= s5 ^ s13;
     h[6] ^= s6 ^ s14;
     h[7] ^= s7 ^ s15;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// length classes: cls = 4 * floor(log2(blocks)) + the next two bits of the block count (classes 1.25x apart at most), 0 .. 127;
-// a block is 1 << unit_shift bytes (BLAKE2s: 64, Meow: 256)
-// ---------------------------------------------------------------------------------------------------
-constexpr uint32_t B2_CLASSES = 128;
-__device__ __forceinline__ uint32_t b2_class(uint32_t len, uint32_t unit_shift)
-{
-    const uint32_t nb = len ? ((len - 1u) >> unit_shift) + 1u : 1u;
-    const uint32_t e = 31u - (uint32_t)__builtin_clz(nb);
-    const uint32_t mant = e >= 2u ? (nb >> (e - 2u)) & 3u : (nb << (2u - e)) & 3u;
-    return e * 4u + mant;
-}
-
-// hist[cls] += ranges of that class (LDS histogram per workgroup, one global atomic per class)
-__global__ __launch_bounds__(256) void k_b2s_class_hist(const uint32_t* __restrict__ lens, uint64_t bound, const uint32_t* __restrict__ n_dev,
-                                                        uint32_t unit_shift, uint32_t* __restrict__ hist)
-{
-    __shared__ uint32_t s_h[B2_CLASSES];
-    const uint32_t n = range_count(bound, n_dev);
-    if (threadIdx.x < B2_CLASSES)
-        s_h[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        atomicAdd(&s_h[b2_class(lens[i], unit_shift)], 1u);
-    __syncthreads();
-    if (threadIdx.x < B2_CLASSES && s_h[threadIdx.x])
-        atomicAdd(&hist[threadIdx.x], s_h[threadIdx.x]);
-}
-
-// cursor[cls] = ranges of longer classes (longest first)
-__global__ __launch_bounds__(B2_CLASSES) void k_b2s_class_scan(const uint32_t* __restrict__ hist, uint32_t* __restrict__ cursor)
-{
-    __shared__ uint32_t s_h[B2_CLASSES];
-    const uint32_t t = threadIdx.x;
-    s_h[t] = hist[t];
-    __syncthreads();
-    if (t == 0)
-    {
-        uint32_t acc = 0;
-        for (int c = (int)B2_CLASSES - 1; c >= 0; --c)
-        {
-            const uint32_t v = s_h[c];
-            s_h[c] = acc;
-            acc += v;
-        }
-    }
-    __syncthreads();
-    cursor[t] = s_h[t];
-}
-
-// order[cursor[cls]++] = i  (the order inside a class is whatever the atomics give: every range still gets its own digest slot)
-__global__ __launch_bounds__(256) void k_b2s_class_scatter(const uint32_t* __restrict__ lens, uint64_t bound, const uint32_t* __restrict__ n_dev,
-                                                           uint32_t unit_shift, uint32_t* __restrict__ cursor, uint32_t* __restrict__ order)
-{
-    __shared__ uint32_t s_h[B2_CLASSES], s_base[B2_CLASSES];
-    const uint32_t n = range_count(bound, n_dev);
-    if (threadIdx.x < B2_CLASSES)
-        s_h[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t cls = 0, rank = 0;
-    if (i < n)
-    {
-        cls = b2_class(lens[i], unit_shift);
-        rank = atomicAdd(&s_h[cls], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < B2_CLASSES && s_h[threadIdx.x])
-        s_base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], s_h[threadIdx.x]);
-    __syncthreads();
-    if (i < n)
-        order[s_base[cls] + rank] = (uint32_t)i;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -443,96 +368,27 @@ __global__ __launch_bounds__(64) void k_b2s_stream(const uint8_t* __restrict__ d
     }
 }
 
+// the launch policy of k_hash_common.h over the four kernels
+struct B2Kind
+{
+    static constexpr auto lanes = &k_b2s_lanes, quads = &k_b2s_quads;
+    static constexpr auto one = &k_b2s_one;
+    static constexpr auto stream = &k_b2s_stream;
+    static constexpr int kid = LTHIP_K_BLAKE2S;
+    static constexpr const char* name = "blake2s";
+    static constexpr const char* name_one = "blake2s_one";
+    static constexpr uint32_t unit_shift = 6u;
+    // >= 1 MiB (16384 blocks): an asset's content hash over 10^5 .. 10^6 chunk hashes in a tree of many files; chunk hashing
+    // (<= 2 * target bytes) never gets there
+    static constexpr uint32_t long_class = 14u * 4u;
+    static size_t one_lds(uint32_t len) { return (size_t)(len ? (len + 63u) >> 6 : 1u) * 64u; }
+    static constexpr size_t one_lds_grant = 64u * 1024u - 1024u;
+};
+
 } // namespace
 
-// The length-class order of count ranges (count = min(count_bound, *d_count) when d_count != null), longest class first, in blocks of
-// 1 << unit_shift bytes: *order (count_bound entries) and *n_long = the device count of ranges of class long_class and above, which
-// lead the order.  S_B2_ORDER scratch; queued on the context's stream, nothing read back.
-int lthip_len_class_order(lthip_ctx* ctx, const uint32_t* d_lens, const uint32_t* d_count, uint64_t count_bound, uint32_t unit_shift,
-                          uint32_t long_class, const uint32_t** order, const uint32_t** n_long)
+const ChainHash* lthip_chain_blake2s()
 {
-    void* sc;
-    int err;
-    if ((err = lthip_scratch(ctx, S_B2_ORDER, count_bound * 4u + 2u * B2_CLASSES * 4u, &sc)))
-        return err;
-    uint32_t* hist = (uint32_t*)sc;
-    uint32_t* cursor = hist + B2_CLASSES;
-    uint32_t* ord = cursor + B2_CLASSES;
-    const uint32_t grid = (uint32_t)div_up_u64(count_bound, 256);
-    LTHIP_CHECK(ctx, hipMemsetAsync(hist, 0, B2_CLASSES * 4u, ctx->stream));
-    hipLaunchKernelGGL(k_b2s_class_hist, dim3(grid), dim3(256), 0, ctx->stream, d_lens, count_bound, d_count, unit_shift, hist);
-    hipLaunchKernelGGL(k_b2s_class_scan, dim3(1), dim3(B2_CLASSES), 0, ctx->stream, (const uint32_t*)hist, cursor);
-    hipLaunchKernelGGL(k_b2s_class_scatter, dim3(grid), dim3(256), 0, ctx->stream, d_lens, count_bound, d_count, unit_shift, cursor, ord);
-    LTHIP_LAUNCH_CHECK(ctx);
-    // after the scatter cursor[c] = end of class c in the order, so cursor[long_class] = ranges of that class and above
-    *order = ord;
-    *n_long = cursor + long_class;
-    return 0;
-}
-
-// ranges up to this many go to the quad kernel (no sort): a call of few ranges is bound by its longest chain
-constexpr uint64_t B2_QUAD_RANGES = 256;
-// in larger calls, ranges of this length class and above (>= 1 MiB: 16384 blocks) also run on quads -- an asset's content hash over
-// 10^5 .. 10^6 chunk hashes in a tree of many files; chunk hashing (<= 2 * target bytes) never gets there
-constexpr uint32_t B2_LONG_CLASS = 14u * 4u;
-constexpr uint32_t B2_LONG_GRID = 64; // workgroups of 16 quads that take the long ranges in turn
-
-int lthip_launch_blake2s(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
-                         uint64_t count_bound, uint64_t* d_hashes)
-{
-    if (count_bound == 0)
-        return 0;
-    if (count_bound > 0xFFFFFFF0ull)
-        return lthip_fail(ctx, EINVAL, "blake2s", "too many ranges in one call");
-    LaunchTimer t(ctx, LTHIP_K_BLAKE2S);
-    if (count_bound <= B2_QUAD_RANGES)
-    {
-        hipLaunchKernelGGL(k_b2s_quads, dim3((uint32_t)div_up_u64(count_bound, 16)), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens,
-                           count_bound, d_count, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_hashes);
-        LTHIP_LAUNCH_CHECK(ctx);
-        return 0;
-    }
-    const uint32_t* order;
-    const uint32_t* n_long;
-    int err;
-    if ((err = lthip_len_class_order(ctx, d_lens, d_count, count_bound, 6u, B2_LONG_CLASS, &order, &n_long)))
-        return err;
-    const uint32_t grid = (uint32_t)div_up_u64(count_bound, 256);
-    hipLaunchKernelGGL(k_b2s_quads, dim3(B2_LONG_GRID), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count, order,
-                       n_long, d_hashes);
-    hipLaunchKernelGGL(k_b2s_lanes, dim3(grid), dim3(256), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count, order, n_long,
-                       d_hashes);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int lthip_launch_blake2s_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out)
-{
-    if (len > 65536u)
-        return lthip_fail(ctx, EINVAL, "blake2s_one", "input above 64 KiB");
-    LaunchTimer t(ctx, LTHIP_K_BLAKE2S);
-    const size_t lds = (size_t)(len ? (len + 63u) >> 6 : 1u) * 64u;
-    if (lds > 64u * 1024u - 1024u)
-    {
-        // per device: more than 64 KiB of dynamic LDS has to be granted explicitly (plugin threads race here: the flag is atomic, and
-        // two threads that both set the attribute set the same value)
-        static std::atomic<bool> granted[64] = {};
-        if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device].load(std::memory_order_acquire))
-        {
-            LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_b2s_one), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            if (ctx->device >= 0 && ctx->device < 64)
-                granted[ctx->device].store(true, std::memory_order_release);
-        }
-    }
-    hipLaunchKernelGGL(k_b2s_one, dim3(1), dim3(64), lds, ctx->stream, (const uint8_t*)in, len, out);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int lthip_launch_blake2s_stream(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out)
-{
-    LaunchTimer t(ctx, LTHIP_K_BLAKE2S);
-    hipLaunchKernelGGL(k_b2s_stream, dim3(1), dim3(64), 0, ctx->stream, (const uint8_t*)d_data, len, d_state, first, final, d_out);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
+    static const ChainHash kind = {chain_launch_ranges<B2Kind>, chain_launch_one<B2Kind>, chain_launch_stream<B2Kind>, LTHIP_B2S_STREAM_BATCH};
+    return &kind;
 }

@@ -1,4 +1,5 @@
-// k_hash_common.h -- device helpers shared by the hash kernels that are one serial chain per message (k_blake2s.hip, k_meow.hip).
+// k_hash_common.h -- what the hashes that are one serial chain per message (k_blake2s.hip, k_meow.hip) share: device helpers of their
+// kernels, and the host-side launch policy as three templates over a kind's traits.
 #pragma once
 #include "lthip_internal.h"
 
@@ -68,6 +69,82 @@ __device__ __forceinline__ void stage_input_lds(uint32_t* s_in, uint32_t zero_wo
         }
     }
     __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// host side: the launch policy of a chain hash, once.  K is the kind's traits struct, defined next to its kernels:
+//   lanes, quads, one, stream   the four kernels (the same parameter lists for every kind)
+//   kid                         timing id of the launches
+//   name, name_one              what lthip_fail reports
+//   unit_shift                  log2 of the block that the length classes count
+//   long_class                  in calls of many ranges, those of this length class and above also run on quads
+//   one_lds(len)                dynamic LDS bytes of the `one` kernel
+//   one_lds_grant               above this many of them the kernel needs hipFuncAttributeMaxDynamicSharedMemorySize
+// ---------------------------------------------------------------------------------------------------
+// ranges up to this many go to the quad kernel (no sort): a call of few ranges is bound by its longest chain
+constexpr uint64_t CHAIN_QUAD_RANGES = 256;
+constexpr uint32_t CHAIN_LONG_GRID = 64; // workgroups of 16 quads that take the long ranges in turn
+
+template <class K>
+int chain_launch_ranges(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
+                        uint64_t count_bound, uint64_t* d_hashes)
+{
+    if (count_bound == 0)
+        return 0;
+    if (count_bound > 0xFFFFFFF0ull)
+        return lthip_fail(ctx, EINVAL, K::name, "too many ranges in one call");
+    LaunchTimer t(ctx, K::kid);
+    if (count_bound <= CHAIN_QUAD_RANGES)
+    {
+        hipLaunchKernelGGL(K::quads, dim3((uint32_t)div_up_u64(count_bound, 16)), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens,
+                           count_bound, d_count, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_hashes);
+        LTHIP_LAUNCH_CHECK(ctx);
+        return 0;
+    }
+    const uint32_t* order;
+    const uint32_t* n_long;
+    int err;
+    if ((err = lthip_len_class_order(ctx, d_lens, d_count, count_bound, K::unit_shift, K::long_class, &order, &n_long)))
+        return err;
+    hipLaunchKernelGGL(K::quads, dim3(CHAIN_LONG_GRID), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count, order,
+                       n_long, d_hashes);
+    hipLaunchKernelGGL(K::lanes, dim3((uint32_t)div_up_u64(count_bound, 256)), dim3(256), 0, ctx->stream, d_data, d_offsets, d_lens,
+                       count_bound, d_count, order, n_long, d_hashes);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+template <class K>
+int chain_launch_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out)
+{
+    if (len > 65536u)
+        return lthip_fail(ctx, EINVAL, K::name_one, "input above 64 KiB");
+    LaunchTimer t(ctx, K::kid);
+    const size_t lds = K::one_lds(len);
+    if (lds > K::one_lds_grant)
+    {
+        // per device and kind: more than 64 KiB of LDS has to be granted explicitly (plugin threads race here: the flag is atomic, and
+        // two threads that both set the attribute set the same value)
+        static std::atomic<bool> granted[64] = {};
+        if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device].load(std::memory_order_acquire))
+        {
+            LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(K::one), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+            if (ctx->device >= 0 && ctx->device < 64)
+                granted[ctx->device].store(true, std::memory_order_release);
+        }
+    }
+    hipLaunchKernelGGL(K::one, dim3(1), dim3(64), lds, ctx->stream, (const uint8_t*)in, len, out);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+template <class K>
+int chain_launch_stream(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out)
+{
+    LaunchTimer t(ctx, K::kid);
+    hipLaunchKernelGGL(K::stream, dim3(1), dim3(64), 0, ctx->stream, (const uint8_t*)d_data, len, d_state, first, final, d_out);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
 }
 
 } // namespace

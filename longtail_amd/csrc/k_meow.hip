@@ -23,7 +23,7 @@
 // Two formulations, as k_blake2s.hip:
 //   lane per range   k_meow_lanes: one lane holds the 32 state dwords of one range; half-block loads (128 bytes) are in flight while
 //                    the other half mixes.  Ranges start at any byte (lane dwords rebuilt with v_alignbit); lanes take the ranges in
-//                    the length-class order of k_b2s_class_* with 256-byte blocks (lthip_len_class_order).  Throughput path.
+//                    the length-class order of lthip_len_class_order (lthip_hash.hip) with 256-byte blocks.  Throughput path.
 //   quad per message lane i of a quad holds column i of every register; InvShiftRows becomes DPP quad rotations of the input
 //                    column, and paddq's carry from column 0 (2) to 1 (3) one more.  Blocks are staged through 64 LDS dwords of the
 //                    quad.  Latency path: one input of up to 64 KiB (k_meow_one), few or long ranges (k_meow_quads), the streaming
@@ -628,69 +628,25 @@ __global__ __launch_bounds__(64) void k_meow_stream(const uint8_t* __restrict__ 
     }
 }
 
+// the launch policy of k_hash_common.h over the four kernels
+struct MeowKind
+{
+    static constexpr auto lanes = &k_meow_lanes, quads = &k_meow_quads;
+    static constexpr auto one = &k_meow_one;
+    static constexpr auto stream = &k_meow_stream;
+    static constexpr int kid = LTHIP_K_OTHER;
+    static constexpr const char* name = "meow";
+    static constexpr const char* name_one = "meow_one";
+    static constexpr uint32_t unit_shift = 8u;
+    static constexpr uint32_t long_class = 12u * 4u; // >= 1 MiB: 4096 blocks of 256 bytes
+    static size_t one_lds(uint32_t len) { return (size_t)((len >> 8) + 1u) * 256u; }
+    static constexpr size_t one_lds_grant = 64u * 1024u - 8u * 1024u;
+};
+
 } // namespace
 
-// ranges up to this many go to the quad kernel (no sort): a call of few ranges is bound by its longest chain
-constexpr uint64_t MEOW_QUAD_RANGES = 256;
-// in larger calls, ranges of this length class and above (>= 1 MiB: 4096 blocks of 256 bytes) also run on quads
-constexpr uint32_t MEOW_LONG_CLASS = 12u * 4u;
-constexpr uint32_t MEOW_LONG_GRID = 64; // workgroups of 16 quads that take the long ranges in turn
-
-int lthip_launch_meow(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
-                      uint64_t count_bound, uint64_t* d_hashes)
+const ChainHash* lthip_chain_meow()
 {
-    if (count_bound == 0)
-        return 0;
-    if (count_bound > 0xFFFFFFF0ull)
-        return lthip_fail(ctx, EINVAL, "meow", "too many ranges in one call");
-    LaunchTimer t(ctx, LTHIP_K_OTHER);
-    if (count_bound <= MEOW_QUAD_RANGES)
-    {
-        hipLaunchKernelGGL(k_meow_quads, dim3((uint32_t)div_up_u64(count_bound, 16)), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens,
-                           count_bound, d_count, (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_hashes);
-        LTHIP_LAUNCH_CHECK(ctx);
-        return 0;
-    }
-    const uint32_t* order;
-    const uint32_t* n_long;
-    int err;
-    if ((err = lthip_len_class_order(ctx, d_lens, d_count, count_bound, 8u, MEOW_LONG_CLASS, &order, &n_long)))
-        return err;
-    hipLaunchKernelGGL(k_meow_quads, dim3(MEOW_LONG_GRID), dim3(64), 0, ctx->stream, d_data, d_offsets, d_lens, count_bound, d_count, order,
-                       n_long, d_hashes);
-    hipLaunchKernelGGL(k_meow_lanes, dim3((uint32_t)div_up_u64(count_bound, 256)), dim3(256), 0, ctx->stream, d_data, d_offsets, d_lens,
-                       count_bound, d_count, order, n_long, d_hashes);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int lthip_launch_meow_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out)
-{
-    if (len > 65536u)
-        return lthip_fail(ctx, EINVAL, "meow_one", "input above 64 KiB");
-    LaunchTimer t(ctx, LTHIP_K_OTHER);
-    const size_t lds = (size_t)((len >> 8) + 1u) * 256u;
-    if (lds > 64u * 1024u - 8u * 1024u)
-    {
-        // per device: more than 64 KiB of LDS has to be granted explicitly (plugin threads race here: the flag is atomic, and two threads
-        // that both set the attribute set the same value)
-        static std::atomic<bool> granted[64] = {};
-        if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device].load(std::memory_order_acquire))
-        {
-            LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_meow_one), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            if (ctx->device >= 0 && ctx->device < 64)
-                granted[ctx->device].store(true, std::memory_order_release);
-        }
-    }
-    hipLaunchKernelGGL(k_meow_one, dim3(1), dim3(64), lds, ctx->stream, (const uint8_t*)in, len, out);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int lthip_launch_meow_stream(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out)
-{
-    LaunchTimer t(ctx, LTHIP_K_OTHER);
-    hipLaunchKernelGGL(k_meow_stream, dim3(1), dim3(64), 0, ctx->stream, (const uint8_t*)d_data, len, d_state, first, final, d_out);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
+    static const ChainHash kind = {chain_launch_ranges<MeowKind>, chain_launch_one<MeowKind>, chain_launch_stream<MeowKind>, LTHIP_MEOW_STREAM_BATCH};
+    return &kind;
 }

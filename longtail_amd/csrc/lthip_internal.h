@@ -113,7 +113,7 @@ enum ScratchSlot
     S_SLICE_LENS,
     S_SLICE_HASH,
     S_SLICE_FIRST,
-    S_B2_ORDER,     // BLAKE2s and Meow ranges: class histogram, cursors and the length-class order of the ranges
+    S_LEN_CLASS_ORDER, // BLAKE2s and Meow ranges: class histogram, cursors and the length-class order of the ranges
     S_COUNT
 };
 
@@ -283,29 +283,31 @@ int lthip_launch_blake3_stream_final(lthip_ctx* ctx, const void* d_tail, uint32_
                                      uint32_t depth, uint64_t* d_out);
 int lthip_launch_blake3_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
 
-// BLAKE2s-64 (k_blake2s.hip) of count ranges (count = min(count_bound, *d_count) when d_count != null); never reads anything back
-int lthip_launch_blake2s(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
-                         uint64_t count_bound, uint64_t* d_hashes);
-int lthip_launch_blake2s_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
-int lthip_launch_blake2s_stream(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out);
-// The length-class order of ranges in blocks of 1 << unit_shift bytes, longest first (k_blake2s.hip, shared by BLAKE2s and Meow):
-// *order = count_bound slots, *n_long = device count of the leading ranges of class long_class and above.  S_B2_ORDER scratch.
+// A chain hash: one serial chain of compressions per message (BLAKE2s-64, k_blake2s.hip; Meow v0.5's low 64 bits, k_meow.hip).  The
+// launches of a kind (k_hash_common.h: one policy over the kind's kernels); none of them reads anything back.
+struct ChainHash
+{
+    // the digests of count ranges (count = min(count_bound, *d_count) when d_count != null)
+    int (*ranges)(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
+                  uint64_t count_bound, uint64_t* d_hashes);
+    int (*one)(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out); // ONE input of at most 64 KiB, read where it lies
+    int (*stream)(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out);
+    uint32_t stream_batch; // bytes of a stream batch (LTHIP_B2S_STREAM_BATCH / LTHIP_MEOW_STREAM_BATCH)
+};
+const ChainHash* lthip_chain_blake2s(); // k_blake2s.hip
+const ChainHash* lthip_chain_meow();    // k_meow.hip
+// The length-class order of ranges in blocks of 1 << unit_shift bytes, longest first (lthip_hash.hip, shared by the chain hashes):
+// *order = count_bound slots, *n_long = device count of the leading ranges of class long_class and above.  S_LEN_CLASS_ORDER scratch.
 int lthip_len_class_order(lthip_ctx* ctx, const uint32_t* d_lens, const uint32_t* d_count, uint64_t count_bound, uint32_t unit_shift,
                           uint32_t long_class, const uint32_t** order, const uint32_t** n_long);
 
-// Meow hash v0.5, low 64 bits (k_meow.hip): the same three launches as BLAKE2s
-int lthip_launch_meow(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
-                      uint64_t count_bound, uint64_t* d_hashes);
-int lthip_launch_meow_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
-int lthip_launch_meow_stream(lthip_ctx* ctx, const void* d_data, uint32_t len, uint32_t* d_state, int first, int final, uint64_t* d_out);
-
 // The hash of a longtail hash type over device ranges: what the index builders call for path hashes, asset content hashes and block
 // hashes.  'blk2' (LTHIP_HASH_BLAKE2) runs BLAKE2s, 'meow' (LTHIP_HASH_MEOW) Meow; every other identifier runs BLAKE3, exactly the
-// code path of lthip_hash_ranges /
-// lthip_hash_ranges_known (leaf_total 0 = unknown).
+// code path of lthip_hash_ranges / lthip_hash_ranges_known (leaf_total 0 = unknown).
 constexpr uint32_t LTHIP_HASH_BLAKE3 = 0x626c6b33u; // 'blk3', lib/blake3/longtail_blake3.c
 constexpr uint32_t LTHIP_HASH_BLAKE2 = 0x626c6b32u; // 'blk2', lib/blake2/longtail_blake2.c
 constexpr uint32_t LTHIP_HASH_MEOW = 0x6d656f77u;   // 'meow', lib/meowhash/longtail_meowhash.c
+const ChainHash* lthip_chain_hash(uint32_t hash_identifier); // the kind of 'blk2' and 'meow', null for every other identifier
 int lthip_hash_ranges_by_id(lthip_ctx* ctx, uint32_t hash_identifier, const void* d_data, uint64_t range_count, const uint64_t* d_offsets,
                             const uint32_t* d_lens, uint32_t max_len, uint64_t leaf_total, uint64_t* d_hashes);
 

@@ -157,20 +157,14 @@ class HipLib:
         sig("lthip_hash_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
         sig("lthip_b3_stream_batch", i32, [vp, vp, u64, vp])
         sig("lthip_b3_stream_final", i32, [vp, vp, u32, u64, vp, vp])
-        sig("lthip_blake2s_ranges", i32, [vp, vp, u64, vp, vp, u32, vp])
-        sig("lthip_blake2s_ranges_dev", i32, [vp, vp, u64, vp, vp, vp, u32, vp])
-        sig("lthip_blake2s_one", i32, [vp, vp, u32, vp])
-        sig("lthip_blake2s_runs_u64", i32, [vp, vp, vp, u32, vp])
-        sig("lthip_blake2s_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
-        sig("lthip_b2s_stream_batch", i32, [vp, vp, u64, vp])
-        sig("lthip_b2s_stream_final", i32, [vp, vp, u32, u64, vp, vp])
-        sig("lthip_meow_ranges", i32, [vp, vp, u64, vp, vp, u32, vp])
-        sig("lthip_meow_ranges_dev", i32, [vp, vp, u64, vp, vp, vp, u32, vp])
-        sig("lthip_meow_one", i32, [vp, vp, u32, vp])
-        sig("lthip_meow_runs_u64", i32, [vp, vp, vp, u32, vp])
-        sig("lthip_meow_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
-        sig("lthip_meow_stream_batch", i32, [vp, vp, u64, vp])
-        sig("lthip_meow_stream_final", i32, [vp, vp, u32, u64, vp, vp])
+        for name, stream in (("lthip_blake2s", "lthip_b2s_stream"), ("lthip_meow", "lthip_meow_stream")):  # the chain hashes
+            sig(name + "_ranges", i32, [vp, vp, u64, vp, vp, u32, vp])
+            sig(name + "_ranges_dev", i32, [vp, vp, u64, vp, vp, vp, u32, vp])
+            sig(name + "_one", i32, [vp, vp, u32, vp])
+            sig(name + "_runs_u64", i32, [vp, vp, vp, u32, vp])
+            sig(name + "_runs_u64_bounded", i32, [vp, vp, vp, u32, u64, u64, vp])
+            sig(stream + "_batch", i32, [vp, vp, u64, vp])
+            sig(stream + "_final", i32, [vp, vp, u32, u64, vp, vp])
         sig("lthip_dedup_first_seen_range", i32, [vp, u64, vp, u64, u64, vp, vp])
         sig("lthip_gather_ranges", i32, [vp, vp, u64, vp, vp, vp, vp])
         sig("lthip_pack_blocks", i32, [u64, vp, u32, u32, vp, u64, P(u64)])
@@ -347,81 +341,70 @@ class Context:
         )
         return out[:n]
 
-    # -- BLAKE2s-64 ('blk2') --
-    def blake2s_ranges(self, data, offsets, lens, max_len: int = 0, out=None, count_bound: Optional[int] = None, d_count=None):
-        """d_hashes[i] = blake2s-64 of the range; with d_count (device u32) the number of ranges is min(count_bound, *d_count)."""
+    # -- the chain hashes: BLAKE2s-64 ('blk2') and Meow hash v0.5, 64 bits ('meow'); `name` is the prefix of the kind's C calls --
+    def _chain_ranges(self, name, data, offsets, lens, max_len, out, count_bound, d_count):
         torch = self.torch
         n = int(offsets.numel()) if count_bound is None else int(count_bound)
         if out is None:
             out = torch.empty(max(1, n), dtype=torch.int64, device=self._dev())
         if d_count is None:
-            err = self.lib.dll.lthip_blake2s_ranges(self.h, _ptr(data), n, _ptr(offsets), _ptr(lens), max_len, _ptr(out))
+            err = getattr(self.lib.dll, name + "_ranges")(self.h, _ptr(data), n, _ptr(offsets), _ptr(lens), max_len, _ptr(out))
         else:
-            err = self.lib.dll.lthip_blake2s_ranges_dev(self.h, _ptr(data), n, _ptr(d_count), _ptr(offsets), _ptr(lens), max_len, _ptr(out))
-        self._check(err, "lthip_blake2s_ranges")
+            err = getattr(self.lib.dll, name + "_ranges_dev")(self.h, _ptr(data), n, _ptr(d_count), _ptr(offsets), _ptr(lens), max_len, _ptr(out))
+        self._check(err, name + "_ranges")
         return out[:n]
+
+    def _chain_one(self, name, data, length, out) -> None:
+        self._check(getattr(self.lib.dll, name + "_one")(self.h, _ptr(data), length, _ptr(out)), name + "_one")
+
+    def _chain_runs_u64(self, name, values, first, run_count, out):
+        if out is None:
+            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
+        self._check(getattr(self.lib.dll, name + "_runs_u64")(self.h, _ptr(values), _ptr(first), run_count, _ptr(out)), name + "_runs_u64")
+        return out[:run_count]
+
+    def _chain_stream(self, name, batch_bytes, state_bytes, data, length) -> int:
+        torch = self.torch
+        state = torch.empty(state_bytes, dtype=torch.uint8, device=self._dev())
+        out = torch.zeros(1, dtype=torch.int64, device=self._dev())
+        base = _ptr(data)
+        batches = max(0, (length - 1) // batch_bytes)
+        for b in range(batches):
+            self._check(getattr(self.lib.dll, name + "_batch")(self.h, base + b * batch_bytes, b, _ptr(state)), name + "_batch")
+        tail = length - batches * batch_bytes
+        self._check(getattr(self.lib.dll, name + "_final")(self.h, base + batches * batch_bytes if tail else None, tail, batches, _ptr(state),
+                                                           _ptr(out)), name + "_final")
+        return int(out.cpu().numpy().view(np.uint64)[0])
+
+    def blake2s_ranges(self, data, offsets, lens, max_len: int = 0, out=None, count_bound: Optional[int] = None, d_count=None):
+        """d_hashes[i] = blake2s-64 of the range; with d_count (device u32) the number of ranges is min(count_bound, *d_count)."""
+        return self._chain_ranges("lthip_blake2s", data, offsets, lens, max_len, out, count_bound, d_count)
 
     def blake2s_one(self, data, length: int, out) -> None:
         """One input of at most 64 KiB (device or pinned memory); the digest lands in `out` (device or pinned) on the stream."""
-        self._check(self.lib.dll.lthip_blake2s_one(self.h, _ptr(data), length, _ptr(out)), "lthip_blake2s_one")
+        self._chain_one("lthip_blake2s", data, length, out)
 
     def blake2s_runs_u64(self, values, first, run_count: int, out=None):
-        if out is None:
-            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
-        self._check(self.lib.dll.lthip_blake2s_runs_u64(self.h, _ptr(values), _ptr(first), run_count, _ptr(out)), "lthip_blake2s_runs_u64")
-        return out[:run_count]
+        return self._chain_runs_u64("lthip_blake2s", values, first, run_count, out)
 
     def b2s_stream(self, data, length: int) -> int:
         """Streaming BLAKE2s-64 of the first `length` bytes of a device tensor, batch by batch (lthip_b2s_stream_batch / _final)."""
-        torch = self.torch
-        state = torch.empty(B2S_STREAM_STATE_BYTES, dtype=torch.uint8, device=self._dev())
-        out = torch.zeros(1, dtype=torch.int64, device=self._dev())
-        base = _ptr(data)
-        batches = max(0, (length - 1) // B2S_STREAM_BATCH)
-        for b in range(batches):
-            self._check(self.lib.dll.lthip_b2s_stream_batch(self.h, base + b * B2S_STREAM_BATCH, b, _ptr(state)), "lthip_b2s_stream_batch")
-        tail = length - batches * B2S_STREAM_BATCH
-        self._check(self.lib.dll.lthip_b2s_stream_final(self.h, base + batches * B2S_STREAM_BATCH if tail else None, tail, batches,
-                                                        _ptr(state), _ptr(out)), "lthip_b2s_stream_final")
-        return int(out.cpu().numpy().view(np.uint64)[0])
+        return self._chain_stream("lthip_b2s_stream", B2S_STREAM_BATCH, B2S_STREAM_STATE_BYTES, data, length)
 
-    # -- Meow hash v0.5, 64 bits ('meow') --
     def meow_ranges(self, data, offsets, lens, max_len: int = 0, out=None, count_bound: Optional[int] = None, d_count=None):
         """d_hashes[i] = meow-64 of the range; with d_count (device u32) the number of ranges is min(count_bound, *d_count)."""
-        torch = self.torch
-        n = int(offsets.numel()) if count_bound is None else int(count_bound)
-        if out is None:
-            out = torch.empty(max(1, n), dtype=torch.int64, device=self._dev())
-        if d_count is None:
-            err = self.lib.dll.lthip_meow_ranges(self.h, _ptr(data), n, _ptr(offsets), _ptr(lens), max_len, _ptr(out))
-        else:
-            err = self.lib.dll.lthip_meow_ranges_dev(self.h, _ptr(data), n, _ptr(d_count), _ptr(offsets), _ptr(lens), max_len, _ptr(out))
-        self._check(err, "lthip_meow_ranges")
-        return out[:n]
+        return self._chain_ranges("lthip_meow", data, offsets, lens, max_len, out, count_bound, d_count)
 
     def meow_one(self, data, length: int, out) -> None:
         """One input of at most 64 KiB (device or pinned memory); the digest lands in `out` (device or pinned) on the stream."""
-        self._check(self.lib.dll.lthip_meow_one(self.h, _ptr(data), length, _ptr(out)), "lthip_meow_one")
+        self._chain_one("lthip_meow", data, length, out)
 
     def meow_runs_u64(self, values, first, run_count: int, out=None):
-        if out is None:
-            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
-        self._check(self.lib.dll.lthip_meow_runs_u64(self.h, _ptr(values), _ptr(first), run_count, _ptr(out)), "lthip_meow_runs_u64")
-        return out[:run_count]
+        return self._chain_runs_u64("lthip_meow", values, first, run_count, out)
 
     def meow_stream(self, data, length: int) -> int:
         """Streaming meow-64 of the first `length` bytes of a device tensor, batch by batch (lthip_meow_stream_batch / _final)."""
-        torch = self.torch
-        state = torch.empty(MEOW_STREAM_STATE_BYTES, dtype=torch.uint8, device=self._dev())
-        out = torch.zeros(1, dtype=torch.int64, device=self._dev())
-        base = _ptr(data)
-        batches = max(0, (length - 1) // MEOW_STREAM_BATCH)
-        for b in range(batches):
-            self._check(self.lib.dll.lthip_meow_stream_batch(self.h, base + b * MEOW_STREAM_BATCH, b, _ptr(state)), "lthip_meow_stream_batch")
-        tail = length - batches * MEOW_STREAM_BATCH
-        self._check(self.lib.dll.lthip_meow_stream_final(self.h, base + batches * MEOW_STREAM_BATCH if tail else None, tail, batches,
-                                                         _ptr(state), _ptr(out)), "lthip_meow_stream_final")
-        return int(out.cpu().numpy().view(np.uint64)[0])
+        return self._chain_stream("lthip_meow_stream", MEOW_STREAM_BATCH, MEOW_STREAM_STATE_BYTES, data, length)
 
     def timing_get_blake2s(self):
         """(total ms, launches) of the BLAKE2s kernels since the last timing_reset."""

@@ -29,6 +29,14 @@ def u32(t):
     return t.cpu().numpy().view(np.uint32)
 
 
+def dev_u64(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).cuda()
+
+
+def dev_u32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
+
+
 def gpu_chunk_hash(ctx, parts, mn, av, mx, hashes=True):
     """-> list per part of (offsets rel. to the part, lens, hashes)"""
     dev, offs = to_device(parts)

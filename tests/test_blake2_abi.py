@@ -57,4 +57,8 @@ def test_blake2_constructor_refuses_without_a_gpu(hiplib):
     # the bulk calls validate their arguments before they touch a device
     assert d.lthip_blake2s_one(None, None, 0, None) != 0
     assert d.lthip_blake2s_ranges(None, None, 1, None, None, 0, None) != 0
+    assert d.lthip_blake2s_ranges_dev(None, None, 1, None, None, None, 0, None) != 0
+    assert d.lthip_blake2s_runs_u64(None, None, None, 1, None) != 0
+    assert d.lthip_blake2s_runs_u64_bounded(None, None, None, 1, 0, 0, None) != 0
+    assert d.lthip_b2s_stream_batch(None, None, 0, None) != 0
     assert d.lthip_b2s_stream_final(None, None, 0, 0, None, None) != 0

@@ -18,9 +18,9 @@ import torch
 
 from longtail_amd.dist import JobPartition
 from longtail_amd.lib import HASH_BLAKE2, HASH_BLAKE3, Context, Ingest, chunker_params
-from tests.gpu_util import to_device, u32, u64
+from tests.gpu_util import dev_u32, dev_u64, to_device, u32, u64
 from tests.test_gpu_ingest import make_files, parse_store_index, ref_missing_content, version_unique_lists
-from tests.test_gpu_plugins import ChunkerAPIStruct, CompressionAPIStruct, HashAPIStruct
+from tests.test_gpu_plugins import ChunkerAPIStruct, CompressionAPIStruct, HashAPIStruct, PyHashAPI
 
 pytestmark = pytest.mark.gpu
 
@@ -34,14 +34,6 @@ def gpu():
     ctx = Context(0)
     yield ctx
     ctx.close()
-
-
-def dev_u64(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).cuda()
-
-
-def dev_u32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
 
 
 def check_ranges(gpu, host, offs, lens, max_len=0, **kw):
@@ -184,43 +176,9 @@ def test_hash_api_entry_points(hip_b2):
 
 
 # a hashlib-backed Longtail_HashAPI: the reference core with it builds the reference's BLAKE2 VersionIndex
-class PyBlake2HashAPI:
-    def __init__(self):
-        self.ctxs, self.next = {}, 1
-        CB = HashAPIStruct._fields_
-        f = dict(CB)
-        self._cbs = [
-            f["Dispose"](lambda api: None),
-            f["GetIdentifier"](lambda api: HASH_BLAKE2),
-            f["BeginContext"](self._begin),
-            f["Hash"](self._hash),
-            f["EndContext"](self._end),
-            f["HashBuffer"](self._buffer),
-        ]
-        self.struct = HashAPIStruct(*self._cbs)
-        self.ptr = C.addressof(self.struct)
-
-    def _begin(self, api, out):
-        k = self.next
-        self.next += 1
-        self.ctxs[k] = hashlib.blake2s(digest_size=8)
-        out[0] = k
-        return 0
-
-    def _hash(self, api, ctx, length, data):
-        self.ctxs[ctx].update(C.string_at(data, length))
-
-    def _end(self, api, ctx):
-        return int.from_bytes(self.ctxs.pop(ctx).digest(), "little")
-
-    def _buffer(self, api, length, data, out):
-        out[0] = b2(C.string_at(data, length) if length else b"")
-        return 0
-
-
 @pytest.fixture(scope="module")
 def py_b2():
-    return PyBlake2HashAPI()
+    return PyHashAPI(HASH_BLAKE2, b2)
 
 
 @pytest.mark.parametrize("workers", [0, 4])

@@ -20,10 +20,10 @@ import torch
 
 from longtail_amd.dist import JobPartition
 from longtail_amd.lib import HASH_BLAKE2, HASH_BLAKE3, HASH_MEOW, Context, Ingest, chunker_params
-from tests.gpu_util import to_device, u32, u64
+from tests.gpu_util import dev_u32, dev_u64, to_device, u32, u64
 from tests.meow_model import meow, meow_batch
 from tests.test_gpu_ingest import parse_store_index, ref_missing_content, version_unique_lists
-from tests.test_gpu_plugins import ChunkerAPIStruct, HashAPIStruct
+from tests.test_gpu_plugins import ChunkerAPIStruct, HashAPIStruct, PyHashAPI
 from tests.test_meow_abi import GOLDEN, golden_input
 
 pytestmark = pytest.mark.gpu
@@ -50,14 +50,6 @@ def gpu():
     ctx = Context(0)
     yield ctx
     ctx.close()
-
-
-def dev_u64(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).cuda()
-
-
-def dev_u32(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
 
 
 def check_ranges(gpu, host, offs, lens, max_len=0, expect=None):
@@ -219,38 +211,10 @@ def test_hash_api_entry_points(hip_meow):
     assert h.EndContext(hip_meow, ctx) == meow(b"")
 
 
-class PyMeowHashAPI:
-    """a Longtail_HashAPI backed by the CPU model: the reference core with it builds the reference's 'meow' VersionIndex"""
-
-    def __init__(self):
-        self.ctxs, self.next = {}, 1
-        f = dict(HashAPIStruct._fields_)
-        self._cbs = [f["Dispose"](lambda api: None), f["GetIdentifier"](lambda api: HASH_MEOW), f["BeginContext"](self._begin),
-                     f["Hash"](self._hash), f["EndContext"](self._end), f["HashBuffer"](self._buffer)]
-        self.struct = HashAPIStruct(*self._cbs)
-        self.ptr = C.addressof(self.struct)
-
-    def _begin(self, api, out):
-        k = self.next
-        self.next += 1
-        self.ctxs[k] = []
-        out[0] = k
-        return 0
-
-    def _hash(self, api, ctx, length, data):
-        self.ctxs[ctx].append(C.string_at(data, length))
-
-    def _end(self, api, ctx):
-        return meow(b"".join(self.ctxs.pop(ctx)))
-
-    def _buffer(self, api, length, data, out):
-        out[0] = meow(C.string_at(data, length) if length else b"")
-        return 0
-
-
+# a Longtail_HashAPI backed by the CPU model: the reference core with it builds the reference's 'meow' VersionIndex
 @pytest.fixture(scope="module")
 def py_meow():
-    return PyMeowHashAPI()
+    return PyHashAPI(HASH_MEOW, meow)
 
 
 def small_files(oracle):

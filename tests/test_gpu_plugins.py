@@ -25,6 +25,36 @@ class HashAPIStruct(C.Structure):
     ]
 
 
+class PyHashAPI:
+    """A Longtail_HashAPI over (identifier, digest function of the whole message) on the CPU: the reference core with it builds the
+    reference's index of that hash type.  A streaming context collects its pieces and digests them at the end."""
+
+    def __init__(self, identifier, digest):
+        self.digest, self.ctxs, self.next = digest, {}, 1
+        f = dict(HashAPIStruct._fields_)
+        self._cbs = [f["Dispose"](lambda api: None), f["GetIdentifier"](lambda api: identifier), f["BeginContext"](self._begin),
+                     f["Hash"](self._hash), f["EndContext"](self._end), f["HashBuffer"](self._buffer)]
+        self.struct = HashAPIStruct(*self._cbs)
+        self.ptr = C.addressof(self.struct)
+
+    def _begin(self, api, out):
+        k = self.next
+        self.next += 1
+        self.ctxs[k] = []
+        out[0] = k
+        return 0
+
+    def _hash(self, api, ctx, length, data):
+        self.ctxs[ctx].append(C.string_at(data, length))
+
+    def _end(self, api, ctx):
+        return self.digest(b"".join(self.ctxs.pop(ctx)))
+
+    def _buffer(self, api, length, data, out):
+        out[0] = self.digest(C.string_at(data, length) if length else b"")
+        return 0
+
+
 class CompressionAPIStruct(C.Structure):
     _fields_ = [
         ("Dispose", C.CFUNCTYPE(None, C.c_void_p)),

@@ -80,6 +80,7 @@ def test_meow_constructor_refuses_without_a_gpu(hiplib):
     assert d.lthip_meow_ranges(None, None, 1, None, None, 0, None) != 0
     assert d.lthip_meow_ranges_dev(None, None, 1, None, None, None, 0, None) != 0
     assert d.lthip_meow_runs_u64(None, None, None, 1, None) != 0
+    assert d.lthip_meow_runs_u64_bounded(None, None, None, 1, 0, 0, None) != 0
     assert d.lthip_meow_stream_batch(None, None, 0, None) != 0
     assert d.lthip_meow_stream_final(None, None, 0, 0, None, None) != 0
 
