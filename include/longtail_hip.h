@@ -203,6 +203,12 @@ LTHIP_EXPORT uint64_t lthip_plan_chunk_capacity(const lthip_plan* plan);
  * the product build, LTHIP_SLICES in the ablation build; 1 = the single pass.  Per-kernel timings (lthip_timing_get) of the scan and
  * the leaf hashing of a sliced call OVERLAP: their sum exceeds the wall time of the call. */
 LTHIP_EXPORT uint32_t lthip_plan_slices(const lthip_plan* plan);
+/* How many of those lthip_plan_slices scans are WALKING scans: a plan (or slice) of many more non-empty parts than the device holds
+ * scan waves, none of them long against a wave's share of the bytes, is scanned by waves that own whole parts and walk them chunk by
+ * chunk, skipping the bytes below every chunk's minimum length (candidate scan and cut selection in one launch, timed as
+ * LTHIP_K_BUZHASH; no LTHIP_K_SELECT launch).  Decided from the plan's shape at every aim; every other plan runs the tile scan.  The
+ * results are the same, bit for bit. */
+LTHIP_EXPORT uint32_t lthip_plan_walked_scans(const lthip_plan* plan);
 
 /* Runs buzhash scan -> cut selection -> compaction -> (if d_chunk_hashes) BLAKE3 on the stream.
  * Outputs (device pointers, capacity >= lthip_plan_chunk_capacity):
@@ -411,6 +417,9 @@ LTHIP_EXPORT void lthip_debug_reload_env(void);
  * WriteContent, nothing may leak, the same objects must work on the next call. */
 LTHIP_EXPORT int lthip_debug_fail_alloc(int64_t after, int64_t count);
 LTHIP_EXPORT int64_t lthip_debug_alloc_calls(int64_t* out_failed);
+/* Diagnostics, ABLATION build only (the product library answers ENOTSUP): the 4 KiB wave-tiles the walking scans of this process have
+ * hashed since the last call.  Waits for the device. */
+LTHIP_EXPORT int lthip_debug_walk_tiles(uint64_t* out_tiles);
 /* Diagnostics (parity tests): match-finder output of the last lthip_zstd_compress_blocks call (its last internal batch:
  * calls above LTHIP_BATCH_BYTES = 8 GiB of input are processed in several) on this context for the
  * 4 KiB units [first, first + count) -- 16 bytes of meta {nseq, nlit, tail, 0}, 4096 literal bytes and 1024 u64

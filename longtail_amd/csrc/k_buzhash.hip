@@ -351,6 +351,124 @@ __device__ __forceinline__ void prefix_table_init(uint32_t* tab, int tid, int nt
 // in front of that issue, so that the vmcnt(0) which retires the DMA never waits for a store just issued.
 constexpr int DMA_BUF_B = WROWS * 64; // 4160 bytes, linear
 
+// The LDS-DMA staging of one wave: its buffer, the lane's place in a DMA instruction and in the buffer, and the issue of a wave-tile.
+struct TileDma
+{
+    const uint8_t* data;
+    uint32_t* buf;
+    int lane;
+    uint32_t buf_byte; // LDS byte address of the buffer
+    uint32_t buf_mid;  // M0 (the LDS base of an LDS-DMA) points at the MIDDLE of the buffer for the whole kernel, the five pieces are told
+                       // apart by the instruction offset (13 bits, signed: -2048 .. +2048), which the hardware adds to the LDS address and
+                       // to the global address alike
+    uint32_t src_off;  // byte offset of the lane's source vector inside a 1 KiB piece
+    uint32_t own_row;  // own row r = lane + 1: data vector c sits at slot c ^ own_f, own_f = (r >> 2) & 3
+    uint32_t own_f;
+
+    __device__ __forceinline__ TileDma(const uint8_t* d, uint32_t* b, int ln) : data(d), buf(b), lane(ln)
+    {
+        buf_byte = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)buf);
+        buf_mid = buf_byte + 2048u;
+        // DMA instruction u moves vector V = 64 u + lane = slot (r = V >> 2, c' = V & 3); (r >> 2) & 3 = (lane >> 4) & 3 for every u
+        const uint32_t src_vec = 4u * ((uint32_t)lane >> 2) + (((uint32_t)lane & 3u) ^ (((uint32_t)lane >> 4) & 3u));
+        src_off = 16u * src_vec;
+        own_f = (((uint32_t)lane + 1u) >> 2) & 3u;
+        own_row = buf_byte + 64u * ((uint32_t)lane + 1u);
+    }
+
+    template <int MODE>
+    __device__ __forceinline__ PrefixConsts consts(const DivTest& dv) const
+    {
+        PrefixConsts pc;
+        pc.lane4 = (uint32_t)lane * 4u;
+        pc.hj = 63u - (uint32_t)lane;
+        pc.halo_byte = buf_byte + DMA_BUF_B;
+        pc.thr = MODE == 1 ? 0u : 0xFFFFFFFFu / (dv.d >> dv.k2);
+        pc.exact_add = dv.addc - dv.inv;
+        return pc;
+    }
+
+    template <int u>
+    __device__ __forceinline__ void piece(const uint8_t* mid_src) const
+    {
+        asm volatile("s_mov_b32 m0, %[l]\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %[v], %[b] offset:%[o]"
+                     :
+                     : [v] "v"(src_off), [l] "s"(buf_mid), [b] "s"(mid_src), [o] "i"(1024 * u - 2048)
+                     : "memory");
+    }
+
+    // a tile at an end of its part: vectors outside the part are not loaded (the slot keeps stale bytes; every position they could
+    // influence is masked by the caller), the vector that straddles the end is assembled from byte loads and stored by its lane
+    template <int u>
+    __device__ __forceinline__ void edge(const PartDev& p, uint64_t sp, const uint8_t* mid_src) const
+    {
+        const int64_t g = (int64_t)sp - 64 + 1024 * u + (int64_t)src_off;
+        const bool lane_on = u < 4 || lane < 4;
+        const bool whole = lane_on && g >= 0 && (uint64_t)g + 16 <= p.size;
+        const bool part = lane_on && g >= 0 && (uint64_t)g < p.size && (uint64_t)g + 16 > p.size;
+        if (whole)
+            piece<u>(mid_src);
+        if (part)
+        {
+            const uint8_t* src = data + p.off;
+            uint32_t w[4] = {0, 0, 0, 0};
+            const uint32_t n = (uint32_t)(p.size - (uint64_t)g);
+            for (uint32_t bb = 0; bb < n; ++bb)
+                w[bb >> 2] |= (uint32_t)src[g + bb] << (8 * (bb & 3));
+            uint32_t* d = buf + 256 * u + 4 * lane;
+            d[0] = w[0];
+            d[1] = w[1];
+            d[2] = w[2];
+            d[3] = w[3];
+        }
+    }
+
+    // issue the DMA of the wave-tile at part-relative `sp` (a multiple of 16) of part `p` into the wave's buffer
+    __device__ __forceinline__ void issue(const PartDev& p, uint64_t sp) const
+    {
+        const uint8_t* mid_src = data + p.off + sp - 64 + 2048; // the source of the buffer's middle (sp == 0: row 0 lies before the part and is not loaded)
+        if (sp >= 64 && sp + (uint64_t)WTILE <= p.size) // every vector inside the part: the common case
+        {
+            asm volatile("s_mov_b32 m0, %[l]\n\ts_nop 0\n\t"
+                         "global_load_lds_dwordx4 %[v], %[b] offset:-2048\n\t"
+                         "global_load_lds_dwordx4 %[v], %[b] offset:-1024\n\t"
+                         "global_load_lds_dwordx4 %[v], %[b] offset:0\n\t"
+                         "global_load_lds_dwordx4 %[v], %[b] offset:1024"
+                         :
+                         : [v] "v"(src_off), [l] "s"(buf_mid), [b] "s"(mid_src)
+                         : "memory");
+            if (lane < 4) // vectors 256..259: row 64 (src_off = 16 * lane for these lanes)
+                piece<4>(mid_src);
+        }
+        else
+        {
+            edge<0>(p, sp, mid_src);
+            edge<1>(p, sp, mid_src);
+            edge<2>(p, sp, mid_src);
+            edge<3>(p, sp, mid_src);
+            edge<4>(p, sp, mid_src);
+        }
+    }
+
+    // the landed tile into registers: win[] = the lane's 64-byte run, hb = its halo byte; the buffer is free on return
+    __device__ __forceinline__ void take(uint32_t (&win)[16], uint32_t& hb, const PrefixConsts& pc) const
+    {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the tile has landed (and the stores issued before it are done)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+        {
+            const uint4 q = lds_load_u128(own_row + 16u * ((uint32_t)c ^ own_f));
+            win[4 * c + 0] = q.x;
+            win[4 * c + 1] = q.y;
+            win[4 * c + 2] = q.z;
+            win[4 * c + 3] = q.w;
+        }
+        hb = lds_load_u8(buf_byte + pc.hj); // row 0 = the halo row, f(0) = 0
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+};
+
 template <int MODE, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint8_t* __restrict__ data,
                                                                        const PartDev* __restrict__ parts,
@@ -367,20 +485,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
     uint32_t* halo = buf + (DMA_BUF_B >> 2);
     prefix_table_init(smem, tid, 64 * WAVES);
 
-    const uint32_t buf_byte = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)buf);
-    PrefixConsts pc;
-    pc.lane4 = (uint32_t)lane * 4u;
-    pc.hj = 63u - (uint32_t)lane;
-    pc.halo_byte = buf_byte + DMA_BUF_B;
-    pc.thr = MODE == 1 ? 0u : 0xFFFFFFFFu / (dv.d >> dv.k2);
-    pc.exact_add = dv.addc - dv.inv;
-
-    // DMA instruction u moves vector V = 64 u + lane = slot (r = V >> 2, c' = V & 3); (r >> 2) & 3 = (lane >> 4) & 3 for every u
-    const uint32_t src_vec = 4u * ((uint32_t)lane >> 2) + (((uint32_t)lane & 3u) ^ (((uint32_t)lane >> 4) & 3u));
-    const uint32_t src_off = 16u * src_vec; // byte offset of the lane's source vector inside a 1 KiB piece
-    // own row r = lane + 1: data vector c sits at slot c ^ f, f = (r >> 2) & 3
-    const uint32_t own_f = (((uint32_t)lane + 1u) >> 2) & 3u;
-    const uint32_t own_row = buf_byte + 64u * ((uint32_t)lane + 1u);
+    const TileDma dma(data, buf, lane);
+    const PrefixConsts pc = dma.consts<MODE>(dv);
 
     const uint64_t nwt = (uint64_t)ntiles * 4u;
     const uint64_t wstride = (uint64_t)gridDim.x * (uint64_t)WAVES;
@@ -388,93 +494,16 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
     if (wt >= nwt)
         return;
 
-    // issue the DMA of the wave-tile at part-relative `sp` of part `p` into the wave's buffer.  M0 (the LDS base of an LDS-DMA)
-    // points at the MIDDLE of the buffer for the whole kernel, the five pieces are told apart by the instruction offset
-    // (13 bits, signed: -2048 .. +2048), which the hardware adds to the LDS address and to the global address alike.
-    const uint32_t buf_mid = buf_byte + 2048u;
-    auto piece = [&](auto U, const uint8_t* mid_src) __attribute__((always_inline))
-    {
-        constexpr int u = decltype(U)::value;
-        const uint32_t so = src_off, bm = buf_mid; // (named here: asm operands alone do not capture in a generic lambda)
-        asm volatile("s_mov_b32 m0, %[l]\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %[v], %[b] offset:%[o]"
-                     :
-                     : [v] "v"(so), [l] "s"(bm), [b] "s"(mid_src), [o] "i"(1024 * u - 2048)
-                     : "memory");
-    };
-    auto issue = [&](const PartDev& p, uint64_t sp) __attribute__((always_inline))
-    {
-        const uint8_t* mid_src = data + p.off + sp - 64 + 2048; // the source of the buffer's middle (sp == 0: row 0 lies before the part and is not loaded)
-        if (sp >= 64 && sp + (uint64_t)WTILE <= p.size) // every vector inside the part: the common case
-        {
-            asm volatile("s_mov_b32 m0, %[l]\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %[v], %[b] offset:-2048\n\t"
-                         "global_load_lds_dwordx4 %[v], %[b] offset:-1024\n\t"
-                         "global_load_lds_dwordx4 %[v], %[b] offset:0\n\t"
-                         "global_load_lds_dwordx4 %[v], %[b] offset:1024"
-                         :
-                         : [v] "v"(src_off), [l] "s"(buf_mid), [b] "s"(mid_src)
-                         : "memory");
-            if (lane < 4) // vectors 256..259: row 64 (src_off = 16 * lane for these lanes)
-                piece(std::integral_constant<int, 4>{}, mid_src);
-        }
-        else
-        {
-            // a tile at an end of its part: vectors outside the part are not loaded (the slot keeps stale bytes; every
-            // position they could influence is masked by prefix_legal), the vector that straddles the end is assembled
-            // from byte loads and stored by its lane
-            auto edge = [&](auto U) __attribute__((always_inline))
-            {
-                constexpr int u = decltype(U)::value;
-                const int64_t g = (int64_t)sp - 64 + 1024 * u + (int64_t)src_off;
-                const bool lane_on = u < 4 || lane < 4;
-                const bool whole = lane_on && g >= 0 && (uint64_t)g + 16 <= p.size;
-                const bool part = lane_on && g >= 0 && (uint64_t)g < p.size && (uint64_t)g + 16 > p.size;
-                if (whole)
-                    piece(U, mid_src);
-                if (part)
-                {
-                    const uint8_t* src = data + p.off;
-                    uint32_t w[4] = {0, 0, 0, 0};
-                    const uint32_t n = (uint32_t)(p.size - (uint64_t)g);
-                    for (uint32_t bb = 0; bb < n; ++bb)
-                        w[bb >> 2] |= (uint32_t)src[g + bb] << (8 * (bb & 3));
-                    uint32_t* d = buf + 256 * u + 4 * lane;
-                    d[0] = w[0];
-                    d[1] = w[1];
-                    d[2] = w[2];
-                    d[3] = w[3];
-                }
-            };
-            edge(std::integral_constant<int, 0>{});
-            edge(std::integral_constant<int, 1>{});
-            edge(std::integral_constant<int, 2>{});
-            edge(std::integral_constant<int, 3>{});
-            edge(std::integral_constant<int, 4>{});
-        }
-    };
-
     PartDev pd = parts[tile_part[wt >> 2]];
     uint64_t span = ((wt >> 2) - pd.tile_base) * (uint64_t)TILE + (wt & 3u) * (uint64_t)WTILE; // part-relative
-    issue(pd, span);
+    dma.issue(pd, span);
 
     uint64_t pend_m = 0, pend_summary = 0, pend_i0 = 0, pend_i1 = 0; // results of the tile before, stored one iteration late
     bool pend = false;
     for (;;)
     {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the tile has landed (and the stores of two tiles ago are done)
-        uint32_t win[16];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-        {
-            const uint4 q = lds_load_u128(own_row + 16u * ((uint32_t)c ^ own_f));
-            win[4 * c + 0] = q.x;
-            win[4 * c + 1] = q.y;
-            win[4 * c + 2] = q.z;
-            win[4 * c + 3] = q.w;
-        }
-        const uint32_t hb = lds_load_u8(buf_byte + pc.hj); // row 0 = the halo row, f(0) = 0
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the buffer is free
+        uint32_t win[16], hb;
+        dma.take(win, hb, pc); // (waits for the stores of two tiles ago as well)
 
         if (pend)
         {
@@ -491,7 +520,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
         {
             npd = parts[tile_part[next >> 2]];
             next_span = ((next >> 2) - npd.tile_base) * (uint64_t)TILE + (next & 3u) * (uint64_t)WTILE;
-            issue(npd, next_span);
+            dma.issue(npd, next_span);
         }
 
         pend_m = prefix_legal(prefix_tile<MODE>(win, hb, pc, dv, lane, halo), span + (uint64_t)lane * RUN, pd.size);
@@ -603,6 +632,179 @@ __global__ __launch_bounds__(64) void k_select_cuts(const PartDev* __restrict__ 
     }
     if (lane == 0)
         part_count[p] = n;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// K1 + K2 in one, the WALKING scan: a wave owns a whole part and walks it chunk by chunk.
+//
+// k_select_cuts reads only the candidate bits q in [s + min, s + end - 1] of a chunk that starts at s, and a candidate at q depends on
+// the bytes [q - 47, q] alone: the first min - 47 bytes of every chunk are hashed for nothing by a scan that does not know where the
+// chunks start.  A wave that walks its part serially knows: it jumps to the 64 bytes in front of s + min, hashes 4 KiB wave-tiles
+// (prefix_tile, the table, the DMA staging and the workgroup shape of k_buzhash_prefix_dma, unchanged) until the first legal
+// candidate, emits the chunk -- region[] and part_count[] exactly as k_select_cuts writes them -- and jumps again.  H is a pure
+// function of the 48 bytes before a position, so the de-rotated frame of prefix_tile is simply local to the tile and a tile may start
+// at any multiple of 16 (the DMA's source alignment).  Parts are drawn by ticket; everything the walk carries (s, the tile, the chunk
+// count) is wave-uniform.  GUESS: the next tile's DMA is issued before this tile is hashed, aimed at where the walk goes if this tile
+// holds no cut (the next 4 KiB, or the jump target behind a chunk that ends at `end`); a cut makes the guess wrong, and the tile is
+// issued again.  Without it a tile's DMA is issued when the walk knows where it goes (ablation build: the measured alternative).
+// Needs many more parts than resident waves (the host decides: plan_walk_rule, lthip_ctx.hip).
+// ---------------------------------------------------------------------------------------------------
+#ifdef LTHIP_ABLATIONS
+__device__ unsigned long long g_walk_tiles; // wave-tiles hashed by the walking scans of this process (lthip_debug_walk_tiles)
+#endif
+
+template <int MODE, int WAVES, bool GUESS>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts,
+                                                                 uint32_t nparts, DivTest dv, uint32_t min_chunk, uint32_t max_chunk,
+                                                                 uint2* __restrict__ region, uint32_t* __restrict__ part_count,
+                                                                 uint32_t* __restrict__ ticket)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t* buf = smem + 256 * TAB_REP + wave * ((DMA_BUF_B >> 2) + HALO_DW);
+    uint32_t* halo = buf + (DMA_BUF_B >> 2);
+    prefix_table_init(smem, tid, 64 * WAVES);
+
+    const TileDma dma(data, buf, lane);
+    const PrefixConsts pc = dma.consts<MODE>(dv);
+    const int lane_base = lane * RUN;
+
+    // the tile whose data starts at or below candidate q (>= 48) with the 64 bytes in front of it as the halo row
+    auto jump = [](uint64_t q) __attribute__((always_inline)) { return q >= 64 ? ((q - 64) & ~(uint64_t)15) + 64 : (uint64_t)0; };
+
+    bool inflight = false; // a guessed tile is on its way into the buffer
+    uint64_t inflight_tb = 0;
+#ifdef LTHIP_ABLATIONS
+    uint32_t tiles = 0;
+#endif
+    for (;;)
+    {
+        // Every lane takes part in the draw (lane 0 adds one, the others zero): no lane-dependent branch around the loop-carried
+        // ticket (the compiler hazard)
+        __builtin_amdgcn_wave_barrier();
+        uint32_t t = atomicAdd(ticket, lane == 0 ? 1u : 0u);
+        t = __builtin_amdgcn_readfirstlane(t);
+        if (t >= nparts)
+            break;
+        const PartDev pd = parts[t];
+        const uint64_t size = pd.size;
+        uint2* out = region + pd.region_base;
+        uint64_t s = 0, qlo = 0, qhi = 0;
+        uint32_t n = 0, end = 0;
+
+        // the chunks at s that need no scan (hpcdcchunker.c:257-264, and min == end); true: a scan over the candidates [qlo, qhi]
+        auto next_chunk = [&]() __attribute__((always_inline)) -> bool
+        {
+            for (;;)
+            {
+                if (s >= size)
+                    return false;
+                const uint64_t left = size - s;
+                const uint32_t len = left <= min_chunk ? (uint32_t)left : left > max_chunk ? max_chunk : (uint32_t)left; // :284
+                if (left > min_chunk && len > min_chunk)
+                {
+                    end = len;
+                    qlo = s + min_chunk; // a cut of length L needs candidate bit q = s + L - 1, L in [min + 1, end]
+                    qhi = s + end - 1;
+                    return true;
+                }
+                if (lane == 0)
+                    out[n] = make_uint2((uint32_t)s, len);
+                ++n;
+                s += len;
+            }
+        };
+
+        if (next_chunk())
+        {
+            uint64_t tb = jump(qlo); // part-relative start of the tile's data
+            for (bool walking = true; walking;)
+            {
+                if (!(inflight && inflight_tb == tb))
+                {
+                    if (inflight)
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the wrong guess has to land before the buffer is aimed at again
+                    dma.issue(pd, tb);
+                }
+                inflight = false;
+                uint32_t win[16], hb;
+                dma.take(win, hb, pc);
+                if (GUESS)
+                {
+                    uint64_t g = tb + (uint64_t)WTILE; // no cut in this tile: the chunk goes on ...
+                    bool aim = true;
+                    if (g > qhi) // ... or ends at `end`, and the walk jumps
+                    {
+                        const uint64_t s2 = s + end;
+                        aim = size - s2 > min_chunk && max_chunk > min_chunk;
+                        g = jump(s2 + min_chunk);
+                    }
+                    if (aim)
+                    {
+                        dma.issue(pd, g);
+                        inflight = true;
+                        inflight_tb = g;
+                    }
+                }
+                const uint64_t raw = prefix_tile<MODE>(win, hb, pc, dv, lane, halo); // bit k <=> candidate tb + lane_base + k
+#ifdef LTHIP_ABLATIONS
+                ++tiles;
+#endif
+                for (;;) // the chunks that end in this tile
+                {
+                    // the legal bits of the run: [qlo, qhi] relative to the tile, then to the run (beyond the part: qhi < size)
+                    const int lo = (int)(qlo > tb ? qlo - tb : 0) - lane_base;
+                    const int hi = (int)(qhi - tb < (uint64_t)WTILE ? qhi - tb : (uint64_t)WTILE - 1) - lane_base;
+                    uint64_t m = raw;
+                    if (lo > 0)
+                        m = lo > 63 ? 0ull : m & (~0ull << lo);
+                    if (hi < 63)
+                        m = hi < 0 ? 0ull : m & ((2ull << hi) - 1ull);
+                    const uint64_t any = __builtin_amdgcn_ballot_w64(m != 0ull);
+                    uint32_t len;
+                    if (any != 0ull)
+                    {
+                        const int f = __builtin_ctzll(any);
+                        const uint64_t q = tb + (uint64_t)(f * RUN + __builtin_ctzll(bcast64(m, f)));
+                        len = (uint32_t)(q - s) + 1u;
+                    }
+                    else if (qhi - tb < (uint64_t)WTILE)
+                        len = end; // no candidate up to the last legal one
+                    else
+                    {
+                        tb += (uint64_t)WTILE; // the chunk goes on in the next tile, whose halo row is this tile's last 64 bytes
+                        break;
+                    }
+                    if (lane == 0)
+                        out[n] = make_uint2((uint32_t)s, len);
+                    ++n;
+                    s += len;
+                    if (!next_chunk())
+                    {
+                        walking = false;
+                        break;
+                    }
+                    if (qlo >= tb && qlo - tb < (uint64_t)WTILE)
+                        continue; // (min < 4 KiB) the next chunk's first candidate lies in this tile as well
+                    tb = jump(qlo);
+                    break;
+                }
+            }
+        }
+        if (inflight)
+        {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // nothing may land in the buffer behind the next part's first tile
+            inflight = false;
+        }
+        if (lane == 0)
+            part_count[t] = n;
+    }
+#ifdef LTHIP_ABLATIONS
+    if (lane == 0 && tiles)
+        atomicAdd(&g_walk_tiles, (unsigned long long)tiles);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -916,6 +1118,88 @@ int lthip_launch_buzhash(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* 
         return launch_buzhash_roll(ctx, plan, d_data, bm0, bm1);
 #endif
     return launch_buzhash_prefix<16, true>(ctx, plan, d_data, bm0, bm1);
+}
+
+// waves of K1 that are resident on the device at a time: one 16-wave workgroup per CU
+uint32_t lthip_k1_resident_waves(int device)
+{
+    static std::atomic<uint32_t> cached[64] = {};
+    if (device >= 0 && device < 64 && cached[device].load(std::memory_order_relaxed))
+        return cached[device].load(std::memory_order_relaxed);
+    int ncu = 256;
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+    const uint32_t w = (uint32_t)(ncu > 0 ? ncu : 256) * 16u;
+    if (device >= 0 && device < 64)
+        cached[device].store(w, std::memory_order_relaxed);
+    return w;
+}
+
+#ifndef K1_WALK_GUESS
+#define K1_WALK_GUESS 1 // 1: the next tile's DMA in flight while this one is hashed, aimed again behind a cut; 0: decide first, then issue.
+                        // Measured on the headline tree, alternating (profiles/walk_scan_sweep.txt): 891-893 against 895-896 GB/s, K1 alone
+                        // 16.3 against 15.9 ms -- the plain form is 0.3-0.5 % ahead, inside the box's +-1 %.  The guess is the form the
+                        // whole test file ran on; the other is LTHIP_K1_WALK_GUESS=0 in the ablation build.
+#endif
+
+template <bool GUESS>
+static int launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count)
+{
+    constexpr int WAVES = 16;
+    const size_t lds = sizeof(uint32_t) * (256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW)); // (the budget of k_buzhash_prefix_dma)
+    auto k0 = &k_buzhash_walk<0, WAVES, GUESS>;
+    auto k1 = &k_buzhash_walk<1, WAVES, GUESS>;
+    static bool granted[64] = {}; // per device: more than 64 KiB of dynamic LDS has to be granted explicitly
+    if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device])
+    {
+        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (ctx->device >= 0 && ctx->device < 64)
+            granted[ctx->device] = true;
+    }
+    void* ticket;
+    int err = lthip_scratch(ctx, S_WALK_TICKET, 64, &ticket);
+    if (err)
+        return err;
+    uint32_t grid = lthip_k1_resident_waves(ctx->device) / WAVES;
+    if ((uint64_t)grid * WAVES > plan->nparts)
+        grid = (uint32_t)div_up_u64(plan->nparts, WAVES);
+    LaunchTimer t(ctx, LTHIP_K_BUZHASH);
+    LTHIP_CHECK(ctx, hipMemsetAsync(ticket, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(plan->div.pow2 ? k1 : k0, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts,
+                       plan->div, plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+// the walking scan: candidate scan and cut selection of every part in one launch (region / part_count as lthip_launch_select leaves them)
+int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count)
+{
+    if (plan->nparts == 0)
+        return 0;
+#ifdef LTHIP_ABLATIONS
+    LTHIP_ABLATION_ENV(env_guess, "LTHIP_K1_WALK_GUESS"); // 0 / 1: the other form of the prefetch
+    if (env_guess.get() >= 0 && (env_guess.get() != 0) != (K1_WALK_GUESS != 0))
+        return launch_buzhash_walk<!K1_WALK_GUESS>(ctx, plan, d_data, region, part_count);
+#endif
+    return launch_buzhash_walk<K1_WALK_GUESS != 0>(ctx, plan, d_data, region, part_count);
+}
+
+// (ablation build) wave-tiles the walking scans of this process have hashed since the last call; waits for the device
+extern "C" int lthip_debug_walk_tiles(uint64_t* out_tiles)
+{
+#ifdef LTHIP_ABLATIONS
+    if (!out_tiles)
+        return EINVAL;
+    unsigned long long v = 0, zero = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_walk_tiles), sizeof v) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(g_walk_tiles), &zero, sizeof zero) != hipSuccess)
+        return EIO;
+    *out_tiles = v;
+    return 0;
+#else
+    (void)out_tiles;
+    return ENOTSUP;
+#endif
 }
 
 int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* bm0, const uint64_t* bm1, uint2* region,

@@ -658,8 +658,18 @@ static int plan_layout(lthip_ctx* ctx, const char* what, uint32_t min_chunk, uin
         x.chunk_cap += cap;
         x.total_bytes += sz;
         x.leaf_cap += div_up_u64(sz, 1024) + cap;
+        x.nonempty_parts += sz != 0;
+        x.max_part_bytes = sz > x.max_part_bytes ? sz : x.max_part_bytes;
     }
     return 0;
+}
+
+// whether the parts a plan is aimed at suit the walking scan (lthip_internal.h: the rule and its two constants)
+static bool plan_walk_rule(const lthip_plan* plan)
+{
+    const uint64_t waves = lthip_k1_resident_waves(plan->device);
+    return plan->nonempty_parts >= LTHIP_WALK_MIN_PARTS_PER_WAVE * waves &&
+           plan->max_part_bytes * LTHIP_WALK_MAX_PART_DIV <= plan->total_bytes / waves;
 }
 
 static int plan_create_impl(lthip_ctx* ctx, uint32_t part_count, const uint64_t* part_offsets, const uint64_t* part_sizes,
@@ -696,6 +706,7 @@ static int plan_create_impl(lthip_ctx* ctx, uint32_t part_count, const uint64_t*
     plan->capacity_bytes = x.total_bytes;
     plan->cap_parts = part_count ? part_count : 1;
     plan->cap_tiles = x.ntiles ? x.ntiles : 1;
+    plan->walked = plan_walk_rule(plan);
 
     hipError_t e = lthip_hip_malloc((void**)&plan->d_parts, sizeof(PartDev) * plan->cap_parts);
     if (e == hipSuccess)
@@ -723,6 +734,7 @@ static int plan_create_impl(lthip_ctx* ctx, uint32_t part_count, const uint64_t*
 static int plan_aim(lthip_ctx* ctx, lthip_plan* plan, const PlanExtents& x, const PartDev* parts)
 {
     static_cast<PlanExtents&>(*plan) = x;
+    plan->walked = plan_walk_rule(plan);
     const int err = lthip_stage_upload(ctx, plan->d_parts, parts, sizeof(PartDev) * x.nparts, ctx->stream);
     return err ? err : lthip_launch_tile_table(ctx, plan);
 }
@@ -804,7 +816,7 @@ extern "C" int lthip_plan_resize_single(lthip_ctx* ctx, lthip_plan* plan, uint64
     const int err = plan_layout(ctx, "lthip_plan_resize_single", plan->min_chunk, 1, &off, &size, &pd, x);
     if (err)
         return err;
-    static_cast<PlanExtents&>(*plan) = x;
+    static_cast<PlanExtents&>(*plan) = x; // (one part: never walked)
     return lthip_stage_upload(ctx, plan->d_parts, &pd, sizeof pd, ctx->stream);
 }
 
@@ -860,34 +872,67 @@ extern "C" void lthip_plan_destroy(lthip_ctx* ctx, lthip_plan* plan)
 extern "C" uint64_t lthip_plan_chunk_capacity(const lthip_plan* plan) { return plan ? plan->chunk_cap : 0; }
 extern "C" uint32_t lthip_plan_slices(const lthip_plan* plan) { return plan && plan->sliced ? plan->nslices : 1u; }
 
+// whether the scan of (this slice of) a plan is the walking one
+static bool plan_walks(const lthip_plan* plan)
+{
+    LTHIP_ABLATION_ENV(env_walk, "LTHIP_K1_WALK"); // (ablation build: 0 / 1 force the tile scan / the walking scan for any plan)
+    if (env_walk.get() >= 0)
+        return env_walk.get() != 0 && plan->nparts != 0;
+    return plan->walked;
+}
+extern "C" uint32_t lthip_plan_walked_scans(const lthip_plan* plan)
+{
+    if (!plan)
+        return 0;
+    if (!plan->sliced)
+        return plan_walks(plan);
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < plan->nslices; ++k)
+        n += plan_walks(plan->slice[k]);
+    return n;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // phase 1
 // ---------------------------------------------------------------------------------------------------
-// the candidate bitmaps of a whole plan (the slices' lie back to back in them)
-static int chunk_bitmaps(lthip_ctx* ctx, const lthip_plan* plan, uint64_t** bm0, uint64_t** bm1)
+// What the scans of a whole plan leave for cut selection and compaction (the slices' lie back to back in them): the candidate bitmaps
+// of the tile scan -- a plan whose scans all walk needs none -- and the bounded chunk region with the per-part counts.
+struct ScanBuffers
 {
-    const int err = lthip_scratch(ctx, S_BM0, plan->bm0_words * 8, (void**)bm0);
-    return err ? err : lthip_scratch(ctx, S_BM1, plan->bm1_words * 8, (void**)bm1);
-}
-
-// The phase-1 sequence of a plan, in two halves that the sliced pass runs on two streams: the candidate scan into bm0 / bm1 ...
-static int chunk_scan(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, uint64_t* bm0, uint64_t* bm1)
+    uint64_t *bm0, *bm1;
+    uint2* region;
+    uint32_t* part_count;
+};
+static int chunk_scan_buffers(lthip_ctx* ctx, const lthip_plan* plan, bool bitmaps, ScanBuffers* b)
 {
-    return plan->nparts ? lthip_launch_buzhash(ctx, plan, (const uint8_t*)d_data, bm0, bm1) : 0;
-}
-
-// ... then cut selection, compaction and (with d_hashes) the BLAKE3 of the chunks, on ctx's stream behind the scan
-static int chunk_cut_hash(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, const uint64_t* bm0, const uint64_t* bm1,
-                          uint64_t* d_offsets, uint32_t* d_lens, uint64_t* d_hashes, uint32_t* d_part_first)
-{
-    void *region, *pcount;
+    b->bm0 = b->bm1 = nullptr;
     int err;
-    if ((err = lthip_scratch(ctx, S_REGION, plan->chunk_cap * sizeof(uint2), &region)) ||
-        (err = lthip_scratch(ctx, S_PART_COUNT, ((size_t)plan->nparts + 1) * 4, &pcount)))
+    if (bitmaps && ((err = lthip_scratch(ctx, S_BM0, plan->bm0_words * 8, (void**)&b->bm0)) ||
+                    (err = lthip_scratch(ctx, S_BM1, plan->bm1_words * 8, (void**)&b->bm1))))
         return err;
-    if (plan->nparts && (err = lthip_launch_select(ctx, plan, bm0, bm1, (uint2*)region, (uint32_t*)pcount)))
+    if ((err = lthip_scratch(ctx, S_REGION, plan->chunk_cap * sizeof(uint2), (void**)&b->region)))
         return err;
-    if ((err = lthip_launch_compact(ctx, plan, (const uint2*)region, (const uint32_t*)pcount, d_part_first, d_offsets, d_lens)))
+    return lthip_scratch(ctx, S_PART_COUNT, ((size_t)plan->nparts + 1) * 4, (void**)&b->part_count);
+}
+
+// The phase-1 sequence of a plan, in two halves that the sliced pass runs on two streams: the scan -- the tile scan into bm0 / bm1, or
+// the walking scan, which selects the cuts as well and leaves the chunk region and the per-part counts ...
+static int chunk_scan(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, const ScanBuffers& b)
+{
+    if (!plan->nparts)
+        return 0;
+    return plan_walks(plan) ? lthip_launch_buzhash_walk(ctx, plan, (const uint8_t*)d_data, b.region, b.part_count)
+                            : lthip_launch_buzhash(ctx, plan, (const uint8_t*)d_data, b.bm0, b.bm1);
+}
+
+// ... then cut selection (behind a tile scan), compaction and (with d_hashes) the BLAKE3 of the chunks, on ctx's stream behind the scan
+static int chunk_cut_hash(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data, const ScanBuffers& b, uint64_t* d_offsets,
+                          uint32_t* d_lens, uint64_t* d_hashes, uint32_t* d_part_first)
+{
+    int err;
+    if (plan->nparts && !plan_walks(plan) && (err = lthip_launch_select(ctx, plan, b.bm0, b.bm1, b.region, b.part_count)))
+        return err;
+    if ((err = lthip_launch_compact(ctx, plan, b.region, b.part_count, d_part_first, d_offsets, d_lens)))
         return err;
     return d_hashes ? lthip_launch_blake3(ctx, (const uint8_t*)d_data, d_offsets, d_lens, d_part_first + plan->nparts, plan->chunk_cap,
                                           plan->leaf_cap, plan->max_chunk, d_hashes)
@@ -939,10 +984,11 @@ static int chunk_hash_sliced(lthip_ctx* ctx, const lthip_plan* plan, const void*
         parts_rest += (uint64_t)plan->slice[k]->nparts + 1;
     }
     void *x_off, *x_len, *x_hash, *x_first;
-    uint64_t *bm0, *bm1;
+    ScanBuffers sb; // of the whole plan, on the context: scan k + 1 writes its share while the second stream still reads slice k's
+    const bool bitmaps = lthip_plan_walked_scans(plan) != S;
     if (lthip_scratch(ctx, S_SLICE_OFFS, cap_rest * 8, &x_off) || lthip_scratch(ctx, S_SLICE_LENS, cap_rest * 4, &x_len) ||
         lthip_scratch(ctx, S_SLICE_HASH, cap_rest * 8, &x_hash) || lthip_scratch(ctx, S_SLICE_FIRST, parts_rest * 4, &x_first) ||
-        chunk_bitmaps(ctx, plan, &bm0, &bm1))
+        chunk_scan_buffers(ctx, plan, bitmaps, &sb))
     {
         ctx->err[0] = 0;
         return 0;
@@ -963,7 +1009,7 @@ static int chunk_hash_sliced(lthip_ctx* ctx, const lthip_plan* plan, const void*
         first_k[k] = k ? (uint32_t*)x_first + po : d_part_first;
         co += k ? pk->chunk_cap + 1 : 0;
         po += k ? (uint64_t)pk->nparts + 1 : 0;
-        if ((err = chunk_scan(ctx, pk, d_data, bm0, bm1)))
+        if ((err = chunk_scan(ctx, pk, d_data, sb)))
             break;
         hipEvent_t scanned = lthip_sync_event(ctx);
         hipError_t e = hipEventRecord(scanned, ctx->stream);
@@ -971,10 +1017,15 @@ static int chunk_hash_sliced(lthip_ctx* ctx, const lthip_plan* plan, const void*
             e = hipStreamWaitEvent(c2->stream, scanned, 0);
         if (e != hipSuccess)
             err = lthip_fail(ctx, EIO, "lthip_chunk_hash (the wait of the second stream for a scan)", hipGetErrorString(e));
-        else if ((err = chunk_cut_hash(c2, pk, d_data, bm0, bm1, offs_k[k], lens_k[k], hash_k[k], first_k[k])))
+        else if ((err = chunk_cut_hash(c2, pk, d_data, sb, offs_k[k], lens_k[k], hash_k[k], first_k[k])))
             (void)lthip_fail(ctx, err, "lthip_chunk_hash (a slice on the second stream)", c2->err);
-        bm0 += pk->bm0_words;
-        bm1 += pk->bm1_words;
+        if (bitmaps)
+        {
+            sb.bm0 += pk->bm0_words;
+            sb.bm1 += pk->bm1_words;
+        }
+        sb.region += pk->chunk_cap;
+        sb.part_count += pk->nparts;
     }
     // the join (also after a failure: the context's stream never runs ahead of the second one)
     hipEvent_t hashed = lthip_sync_event(ctx);
@@ -1013,9 +1064,9 @@ extern "C" int lthip_chunk_hash(lthip_ctx* ctx, const lthip_plan* plan, const vo
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     bool sliced;
     int err = chunk_hash_sliced(ctx, plan, d_data, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first, &sliced);
-    uint64_t *bm0, *bm1;
-    if (!sliced && !(err = chunk_bitmaps(ctx, plan, &bm0, &bm1)) && !(err = chunk_scan(ctx, plan, d_data, bm0, bm1)))
-        err = chunk_cut_hash(ctx, plan, d_data, bm0, bm1, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first);
+    ScanBuffers sb;
+    if (!sliced && !(err = chunk_scan_buffers(ctx, plan, !plan_walks(plan), &sb)) && !(err = chunk_scan(ctx, plan, d_data, sb)))
+        err = chunk_cut_hash(ctx, plan, d_data, sb, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first);
     if (err)
         return err;
     if (out_total)

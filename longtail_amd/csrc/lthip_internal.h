@@ -50,6 +50,8 @@ struct PlanExtents
     uint64_t bm0_words;
     uint64_t bm1_words;
     uint64_t leaf_cap;
+    uint32_t nonempty_parts;
+    uint64_t max_part_bytes;
 };
 
 struct lthip_plan : PlanExtents
@@ -69,7 +71,16 @@ struct lthip_plan : PlanExtents
     uint32_t slice_first[9]; // slice i = parts [slice_first[i], slice_first[i + 1])
     uint32_t nslices;        // 0: the plan is run as one
     bool sliced;             // the slices are aimed at the plan's current parts
+    bool walked;             // the plan's shape suits the walking scan (plan_walk_rule, decided at every aim; a slice has its own)
 };
+// The walking scan (k_buzhash_walk) hands whole parts to waves.  It needs more non-empty parts than the device holds K1 waves, so that
+// the draw evens out what the parts cost, and no part so long that its wave works on alone at the end of the launch:
+//   non-empty parts >= LTHIP_WALK_MIN_PARTS_PER_WAVE x resident waves
+//   largest part x LTHIP_WALK_MAX_PART_DIV <= bytes / resident waves          (a part is at most that share of a wave's mean load)
+// Where the thresholds lie was measured (profiles/walk_scan_sweep.txt: 64 GiB per step in two slices of 4096 resident
+// waves each): 2 parts per wave (4 MiB files) still gain what 8 and 32 per wave gain, half a part per wave (16 MiB files) loses.
+constexpr uint32_t LTHIP_WALK_MIN_PARTS_PER_WAVE = 2;
+constexpr uint32_t LTHIP_WALK_MAX_PART_DIV = 2;
 constexpr uint64_t LTHIP_SLICE_MIN_BYTES = 1ull << 30;
 #ifndef LTHIP_SLICES
 #define LTHIP_SLICES 2 /* measured 2 .. 8 with the scans back to back (round 6): 2 is as good as any -- what the hashing gains is the issue slots the scans leave free while they run, whatever the granularity */
@@ -114,6 +125,7 @@ enum ScratchSlot
     S_SLICE_HASH,
     S_SLICE_FIRST,
     S_LEN_CLASS_ORDER, // BLAKE2s and Meow ranges: class histogram, cursors and the length-class order of the ranges
+    S_WALK_TICKET,     // the walking scan's part counter
     S_COUNT
 };
 
@@ -262,6 +274,9 @@ struct LaunchTimer
 // ---------------------------------------------------------------------------------------------------
 int lthip_launch_tile_table(lthip_ctx* ctx, lthip_plan* plan);
 int lthip_launch_buzhash(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint64_t* bm0, uint64_t* bm1);
+// K1 + K2 in one launch, a wave per part (k_buzhash.hip: the walking scan); needs neither bitmap
+int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count);
+uint32_t lthip_k1_resident_waves(int device); // waves of a K1 launch that the device holds at a time
 int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* bm0, const uint64_t* bm1, uint2* region,
                         uint32_t* part_count);
 int lthip_launch_compact(lthip_ctx* ctx, const lthip_plan* plan, const uint2* region, const uint32_t* part_count,

@@ -126,6 +126,7 @@ class HipLib:
         sig("lthip_plan_resize_single", i32, [vp, vp, u64])
         sig("lthip_plan_chunk_capacity", u64, [vp])
         sig("lthip_plan_slices", u32, [vp])
+        sig("lthip_plan_walked_scans", u32, [vp])
         sig("lthip_chunk_hash", i32, [vp, vp, vp, vp, vp, vp, vp, P(u64)])
         sig("lthip_chunk_from_buffer", i32, [vp, vp, u64, u32, u32, u32, P(u64)])
         sig("lthip_hash_ranges", i32, [vp, vp, u64, vp, vp, u32, vp])
@@ -142,6 +143,7 @@ class HipLib:
         sig("lthip_debug_reload_env", None, [])
         sig("lthip_debug_fail_alloc", i32, [C.c_int64, C.c_int64])
         sig("lthip_debug_alloc_calls", C.c_int64, [P(C.c_int64)])
+        sig("lthip_debug_walk_tiles", i32, [P(C.c_uint64)])
         sig("lthip_stored_block_header_size", sz, [u32])
         sig("lthip_write_stored_block_headers", i32, [vp, u32, vp, vp, vp, u32, u32, vp, vp, vp, vp])
         sig("lthip_create_missing_content", i32, [vp, u64, vp, u64, vp, vp, vp, u32, u32, u32, vp, sz, vp])
@@ -792,6 +794,11 @@ class Plan:
         """How many slices chunk_hash runs this plan in on two streams (1 = the single pass; 2 in the product build, LTHIP_SLICES in the
         ablation build): per-kernel timings of scan and leaf hashing of a sliced call overlap."""
         return int(self.ctx.lib.dll.lthip_plan_slices(self.h))
+
+    @property
+    def walked_scans(self) -> int:
+        """How many of the plan's `slices` scans are walking scans (a wave per part, chunk by chunk); 0 = the tile scan."""
+        return int(self.ctx.lib.dll.lthip_plan_walked_scans(self.h))
 
     def reaim(self, part_offsets, part_sizes):
         """The plan aimed at another set of parts (lthip_plan_reaim): no more parts / 16 KiB tiles than it was created with; the part
