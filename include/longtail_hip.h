@@ -199,8 +199,8 @@ LTHIP_EXPORT void lthip_plan_destroy(lthip_ctx* ctx, lthip_plan* plan);
 /* upper bound on the number of chunks the plan can produce (size the output arrays with it) */
 LTHIP_EXPORT uint64_t lthip_plan_chunk_capacity(const lthip_plan* plan);
 /* The number of slices the next lthip_chunk_hash with hashes runs this plan in, 1 .. 8: plans of >= 1 GiB in >= 2 parts run as slices
- * on two streams (the candidate scan of slice k + 1 beside the leaf hashing of slice k; results identical to the single pass), 2 in
- * the product build, LTHIP_SLICES in the ablation build; 1 = the single pass.  Per-kernel timings (lthip_timing_get) of the scan and
+ * on two streams (the candidate scan of slice k + 1 beside the leaf hashing of slice k; results identical to the single pass): 2 for
+ * plans that run the tile scan, 1 for plans whose scan walks; LTHIP_SLICES in the ablation build; 1 = the single pass.  Per-kernel timings (lthip_timing_get) of the scan and
  * the leaf hashing of a sliced call OVERLAP: their sum exceeds the wall time of the call. */
 LTHIP_EXPORT uint32_t lthip_plan_slices(const lthip_plan* plan);
 /* How many of those lthip_plan_slices scans are WALKING scans: a plan (or slice) of many more non-empty parts than the device holds

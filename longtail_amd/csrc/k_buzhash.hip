@@ -403,19 +403,27 @@ struct TileDma
     template <int u>
     __device__ __forceinline__ void edge(const PartDev& p, uint64_t sp, const uint8_t* mid_src) const
     {
-        const int64_t g = (int64_t)sp - 64 + 1024 * u + (int64_t)src_off;
-        const bool lane_on = u < 4 || lane < 4;
-        const bool whole = lane_on && g >= 0 && (uint64_t)g + 16 <= p.size;
-        const bool part = lane_on && g >= 0 && (uint64_t)g < p.size && (uint64_t)g + 16 > p.size;
+        // The lane's vector lies at part-relative base + src_off.  base (>= -64) is wave-uniform, so where the part begins and ends is
+        // two scalars relative to it and the lane's tests are 32-bit against its src_off (a multiple of 16, <= 1008): no lane holds a
+        // 64-bit position or address (held across the whole tile loop for all five pieces, they were 30 registers of the walking scan)
+        const int64_t base = (int64_t)sp - 64 + 1024 * u;
+        const int64_t left = (int64_t)p.size - base;                                      // bytes from base to the part's end: |left| < 2^33
+        const int32_t left_hi = (int32_t)(left >> 32);
+        const uint32_t before = base < 0 ? (uint32_t)-base : 0u;                          // bytes of the piece in front of the part
+        const uint32_t room = left_hi < 0 ? 0u : left_hi > 0 || (uint32_t)left > 1024u ? 1024u : (uint32_t)left;
+        const uint32_t room16 = room & ~15u;                                              // the vectors below it lie inside the part
+        const bool lane_on = (u < 4 || lane < 4) && src_off >= before;
+        const bool whole = lane_on && src_off < room16;
+        const bool part = lane_on && src_off == room16 && room != room16;                 // the vector that straddles the end
         if (whole)
             piece<u>(mid_src);
         if (part)
         {
-            const uint8_t* src = data + p.off;
+            const uint8_t* src = mid_src + (1024 * u - 2048); // the piece's first byte
             uint32_t w[4] = {0, 0, 0, 0};
-            const uint32_t n = (uint32_t)(p.size - (uint64_t)g);
+            const uint32_t n = room - src_off;
             for (uint32_t bb = 0; bb < n; ++bb)
-                w[bb >> 2] |= (uint32_t)src[g + bb] << (8 * (bb & 3));
+                w[bb >> 2] |= (uint32_t)src[src_off + bb] << (8 * (bb & 3));
             uint32_t* d = buf + 256 * u + 4 * lane;
             d[0] = w[0];
             d[1] = w[1];
@@ -469,6 +477,15 @@ struct TileDma
     }
 };
 
+// the level-0 words of a wave-tile as a SCALAR base, to be indexed by the lane's 32-bit number: left to itself the compiler keeps
+// bm0 + lane in a 64-bit register pair for the whole tile loop
+__device__ __forceinline__ uint64_t* run_words(uint64_t* __restrict__ bm0, uint64_t first)
+{
+    uint64_t* w = bm0 + first;
+    asm("" : "+s"(w));
+    return w;
+}
+
 template <int MODE, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint8_t* __restrict__ data,
                                                                        const PartDev* __restrict__ parts,
@@ -508,7 +525,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
         if (pend)
         {
             if (pend_m != 0ull)
-                bm0[pend_i0 + (uint64_t)lane] = pend_m; // one word per 64-byte run
+                run_words(bm0, pend_i0)[(uint32_t)lane] = pend_m; // one word per 64-byte run
             if (lane == 0)
                 bm1[pend_i1] = pend_summary;            // one word per 4 KiB
         }
@@ -516,7 +533,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
         const uint64_t next = wt + wstride;
         PartDev npd = pd;
         uint64_t next_span = 0;
-        if (next < nwt)
+        const bool more = (int64_t)(next - nwt) < 0; // (the sign of a scalar difference: no 64-bit constant in vector registers)
+        if (more)
         {
             npd = parts[tile_part[next >> 2]];
             next_span = ((next >> 2) - npd.tile_base) * (uint64_t)TILE + (next & 3u) * (uint64_t)WTILE;
@@ -529,14 +547,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
         pend_i1 = pd.bm1_base + (span >> 12);
         pend = true;
 
-        if (next >= nwt)
+        if (!more)
             break;
         wt = next;
         pd = npd;
         span = next_span;
     }
     if (pend_m != 0ull)
-        bm0[pend_i0 + (uint64_t)lane] = pend_m;
+        run_words(bm0, pend_i0)[(uint32_t)lane] = pend_m;
     if (lane == 0)
         bm1[pend_i1] = pend_summary;
 }
@@ -720,6 +738,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
         if (next_chunk())
         {
             uint64_t tb = jump(qlo); // part-relative start of the tile's data
+            // whether the chunk's last legal candidate lies in the tile at tb.  tb <= qlo <= qhi < size < 2^32 whenever a tile is hashed
+            // (tb = jump(qlo), or moved on by a tile because qhi lay behind it), so the distance is a 32-bit scalar
+            auto ends_here = [&]() __attribute__((always_inline)) { return (uint32_t)(qhi - tb) < (uint32_t)WTILE; };
             for (bool walking = true; walking;)
             {
                 if (!(inflight && inflight_tb == tb))
@@ -735,7 +756,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
                 {
                     uint64_t g = tb + (uint64_t)WTILE; // no cut in this tile: the chunk goes on ...
                     bool aim = true;
-                    if (g > qhi) // ... or ends at `end`, and the walk jumps
+                    if (ends_here()) // ... or ends at `end`, and the walk jumps
                     {
                         const uint64_t s2 = s + end;
                         aim = size - s2 > min_chunk && max_chunk > min_chunk;
@@ -756,7 +777,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
                 {
                     // the legal bits of the run: [qlo, qhi] relative to the tile, then to the run (beyond the part: qhi < size)
                     const int lo = (int)(qlo > tb ? qlo - tb : 0) - lane_base;
-                    const int hi = (int)(qhi - tb < (uint64_t)WTILE ? qhi - tb : (uint64_t)WTILE - 1) - lane_base;
+                    const int hi = (int)(ends_here() ? (uint32_t)(qhi - tb) : (uint32_t)WTILE - 1u) - lane_base;
                     uint64_t m = raw;
                     if (lo > 0)
                         m = lo > 63 ? 0ull : m & (~0ull << lo);
@@ -770,7 +791,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
                         const uint64_t q = tb + (uint64_t)(f * RUN + __builtin_ctzll(bcast64(m, f)));
                         len = (uint32_t)(q - s) + 1u;
                     }
-                    else if (qhi - tb < (uint64_t)WTILE)
+                    else if (ends_here())
                         len = end; // no candidate up to the last legal one
                     else
                     {
@@ -786,7 +807,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
                         walking = false;
                         break;
                     }
-                    if (qlo >= tb && qlo - tb < (uint64_t)WTILE)
+                    if ((uint32_t)(qlo - tb) < (uint32_t)WTILE) // (tb < s <= qlo < size: the chunk before ended in this tile)
                         continue; // (min < 4 KiB) the next chunk's first candidate lies in this tile as well
                     tb = jump(qlo);
                     break;

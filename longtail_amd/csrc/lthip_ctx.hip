@@ -639,6 +639,7 @@ static int plan_layout(lthip_ctx* ctx, const char* what, uint32_t min_chunk, uin
     for (uint32_t p = 0; p < part_count; ++p)
     {
         const uint64_t sz = part_sizes[p];
+        // (sizes below 4 GiB are load-bearing in K1: the walking scan holds part-relative distances in 32-bit scalars, k_buzhash.hip)
         if ((part_offsets[p] & 15u) != 0 || sz > 0xFFFFFFFFull)
             return lthip_fail(ctx, EINVAL, what, "part offsets must be 16-byte aligned, sizes < 4 GiB");
         PartDev& pd = parts[p];
@@ -743,9 +744,17 @@ static int plan_aim(lthip_ctx* ctx, lthip_plan* plan, const PlanExtents& x, cons
 // The first aim that slices creates them; a later aim re-aims them when the new parts fit them (they do when the layout is the one
 // the plan was created with: bench.py's steps), otherwise that aim runs as one.  Optional: a slice that cannot be made or aimed
 // leaves the plan unsliced and ctx->err clear, it is never an error of the call.
+// A plan whose own scan walks (plan_walks) runs as one unless LTHIP_SLICES of the ablation build names the count: with the walking scan
+// a single pass measured faster than any number of slices.  Its slices are still created with it, and kept, but not
+// aimed: a later aim at parts that are not walked finds them, as it did when every plan was sliced.
+static bool plan_walks(const lthip_plan* plan);
 static void plan_aim_slices(lthip_ctx* ctx, lthip_plan* plan, uint32_t want, const uint64_t* part_offsets, const uint64_t* part_sizes)
 {
     plan->sliced = false;
+    LTHIP_ABLATION_ENV(env_slices, "LTHIP_SLICES");
+    const bool as_one = plan_walks(plan) && env_slices.get() <= 0;
+    if (as_one && plan->nslices)
+        return;
     uint32_t first[9];
     const uint32_t S = plan_slice_points(plan->nparts, part_sizes, want, first);
     if (S == 0 || (plan->nslices && S != plan->nslices))
@@ -782,7 +791,7 @@ static void plan_aim_slices(lthip_ctx* ctx, lthip_plan* plan, uint32_t want, con
     }
     memcpy(plan->slice_first, first, sizeof(uint32_t) * (S + 1));
     plan->nslices = S;
-    plan->sliced = true;
+    plan->sliced = !as_one;
 }
 
 extern "C" int lthip_plan_create(lthip_ctx* ctx, uint32_t part_count, const uint64_t* part_offsets,

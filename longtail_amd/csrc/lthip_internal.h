@@ -83,7 +83,7 @@ constexpr uint32_t LTHIP_WALK_MIN_PARTS_PER_WAVE = 2;
 constexpr uint32_t LTHIP_WALK_MAX_PART_DIV = 2;
 constexpr uint64_t LTHIP_SLICE_MIN_BYTES = 1ull << 30;
 #ifndef LTHIP_SLICES
-#define LTHIP_SLICES 2 /* measured 2 .. 8 with the scans back to back (round 6): 2 is as good as any -- what the hashing gains is the issue slots the scans leave free while they run, whatever the granularity */
+#define LTHIP_SLICES 2 /* plans that run the tile scan; a plan whose scan walks runs as one (plan_aim_slices; DESIGN.md §3, profiles/walk_regs_ab.txt) */
 #endif
 
 // ---------------------------------------------------------------------------------------------------

@@ -924,8 +924,8 @@ class Plan:
 
     @property
     def slices(self) -> int:
-        """How many slices chunk_hash runs this plan in on two streams (1 = the single pass; 2 in the product build, LTHIP_SLICES in the
-        ablation build): per-kernel timings of scan and leaf hashing of a sliced call overlap."""
+        """How many slices chunk_hash runs this plan in on two streams (1 = the single pass, also what a walked plan runs as; 2 for tile-scan plans,
+        LTHIP_SLICES in the ablation build): per-kernel timings of scan and leaf hashing of a sliced call overlap."""
         return int(self.ctx.lib.dll.lthip_plan_slices(self.h))
 
     @property
