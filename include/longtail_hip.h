@@ -139,8 +139,10 @@ LTHIP_EXPORT const char* lthip_build_id(void);
  * moves, or an entry point changes its signature (new entry points alone do not bump it).  An embedder built against this header
  * checks  lthip_abi_version() == LTHIP_ABI_VERSION  once after loading the library.
  *   1  rounds 1-3      2  round 4: lthip_ingest_result.gathered_bytes appended, LTHIP_K_COUNT 9 -> 10
- *   3  round 5: lthip_ingest_result starts with struct_size (set by the caller; the library writes no more than that) */
-#define LTHIP_ABI_VERSION 3
+ *   3  round 5: lthip_ingest_result starts with struct_size (set by the caller; the library writes no more than that)
+ *   4  lthip_store and the sessions' set_store / store_stats: a session with a store attached writes what the store lacks, so
+ *      unique_local of the stream session's result may be below unique_all */
+#define LTHIP_ABI_VERSION 4
 LTHIP_EXPORT int lthip_abi_version(void);
 
 /* Memory helpers so that plain-C callers (the plugin layer) need no HIP headers.  Copies are
@@ -461,6 +463,39 @@ LTHIP_EXPORT int lthip_seen_add(lthip_seen* seen, uint64_t count, const uint64_t
 LTHIP_EXPORT uint64_t lthip_seen_total(const lthip_seen* seen); /* hashes added so far: host counter, no synchronisation */
 LTHIP_EXPORT uint64_t lthip_seen_grown(const lthip_seen* seen); /* how often the table has grown: host counter */
 
+/* ---- the set of chunk hashes a store already holds (k_dedup.hip) -----------------------------------------------------------------
+ * What an upload of version N + 1 into a store that holds versions 1 .. N consults: a device-resident set of 64-bit chunk hashes,
+ * built from the store's StoreIndex blobs (lthip_store_add_index) or from device arrays (lthip_store_add), asked with
+ * lthip_store_find, and attached to an ingest session with lthip_ingest_stream_set_store / lthip_ingest_set_store -- the session then
+ * writes only the chunks the store lacks (Longtail_CreateMissingContent(store, version), src/longtail.c:6882-6998).
+ * A key-only open-addressing table: 8 bytes per slot and no position word, so neither lthip_seen's uint32_t positions nor its
+ * 2^31 - 1 total apply.  Power-of-two slot count, at least two slots per hash added (duplicates counted: whether a call grows the
+ * table is decided on the host from the running total lthip_store_added), growth by re-inserting the keys into a table of at least
+ * twice the slots.  The table owns its memory; several stores, lthip_seen tables and one-shot dedup calls on one context do not
+ * disturb each other.  One store belongs to one context (and its thread); everything is asynchronous on the context's stream except
+ * where stated: a call that grows the table may wait for the stream, lthip_store_distinct does.
+ *   create     expected_hashes: the table is created for that many (0: the smallest table, 1024 slots)
+ *   add        count device hashes, duplicates (in the call, or of what the store holds) allowed; d_hashes must stay valid until the
+ *              call's work has run.  An allocation that fails while growing: ENOMEM, nothing changed, the old table stays live.
+ *   add_index  a serialized StoreIndex in HOST memory (the bytes Longtail_WriteStoreIndexToBuffer produces; read before the call
+ *              returns): adds its m_ChunkHashes.  EBADF for a blob shorter than its header, another version than 1.0.0 or a
+ *              truncated index; the set is unchanged then.
+ *   find       d_known[i] = 1 if the store holds d_hashes[i], else 0; *d_known_count (device, may be NULL) is SET to the number of
+ *              ones.  Answers what every add queued before it on the context's stream put in.
+ *   added      hashes passed to add / add_index so far, duplicates included: host counter, no synchronisation
+ *   distinct   distinct hashes in the store; waits for the context's stream
+ *   grown      how often the table has grown: host counter */
+typedef struct lthip_store lthip_store;
+LTHIP_EXPORT int lthip_store_create(lthip_ctx* ctx, uint64_t expected_hashes, lthip_store** out);
+LTHIP_EXPORT void lthip_store_destroy(lthip_store* store);
+LTHIP_EXPORT int lthip_store_add(lthip_store* store, uint64_t count, const uint64_t* d_hashes);
+LTHIP_EXPORT int lthip_store_add_index(lthip_store* store, const void* store_index, size_t store_index_size);
+LTHIP_EXPORT int lthip_store_find(const lthip_store* store, uint64_t count, const uint64_t* d_hashes, uint8_t* d_known,
+                                  uint64_t* d_known_count);
+LTHIP_EXPORT uint64_t lthip_store_added(const lthip_store* store);
+LTHIP_EXPORT int lthip_store_distinct(lthip_store* store, uint64_t* out);
+LTHIP_EXPORT uint64_t lthip_store_grown(const lthip_store* store);
+
 /* Hash-range-sharded form of the first-seen pass (multi-GPU): this rank holds an arbitrary subset of the tree's chunk hashes, each
  * with its global chunk position; d_first_ordinal[j] = smallest position among the subset's items with the hash of item j.  The
  * ranks route every chunk to the owner of its hash (longtail_amd/dist.py: sharded_first_seen), so a rank inserts 1/N of the tree's
@@ -609,6 +644,17 @@ LTHIP_EXPORT int lthip_ingest_images(const lthip_ingest* ingest, uint64_t* out_f
                                      const uint64_t** out_offsets, const uint32_t** out_sizes);
 /* per-block compressed sizes of the last lthip_ingest_write (host, valid after lthip_ingest_finish) */
 LTHIP_EXPORT const uint32_t* lthip_ingest_compressed_sizes(const lthip_ingest* ingest);
+/* Uploading into a store that already has content: with a store attached, the following lthip_ingest_index calls write only the
+ * chunks the store lacks -- a rank writes the chunks that are first-seen, lie in its own jobs AND are unknown to the store.  The
+ * VersionIndex is unchanged (the whole version's); the StoreIndex is Longtail_CreateMissingContent(store, version) for a single rank,
+ * and for R ranks that all hold the same store the reference's with existing = store + the chunks first seen in other ranks' jobs.
+ * When nothing is missing the StoreIndex is the 16-byte header of Longtail_CreateStoreIndexFromBlocks(0, 0) (hash identifier 0,
+ * src/longtail.c:6931-6943).  Result: unique_all = the version's distinct chunks, unique_local / blocks / raw_bytes / compressed_bytes
+ * what this rank wrote.  The store must be of the session's context and must not be added to or destroyed between lthip_ingest_index
+ * and lthip_ingest_finish; NULL detaches it.  lthip_ingest_store_stats (after lthip_ingest_index): the first-seen chunks of this
+ * rank's own jobs that the store held, and their bytes; 0 / 0 without a store. */
+LTHIP_EXPORT int lthip_ingest_set_store(lthip_ingest* ingest, const lthip_store* store);
+LTHIP_EXPORT int lthip_ingest_store_stats(const lthip_ingest* ingest, uint64_t* known_chunks, uint64_t* known_bytes);
 
 /* ---- the ingest session for a tree that arrives in slices (ingest_stream.hip) ----------------------------------------------------
  * lthip_ingest_index / _write / _finish need the whole tree's chunk lists and bytes on the device.  This session takes the tree as
@@ -616,7 +662,8 @@ LTHIP_EXPORT const uint32_t* lthip_ingest_compressed_sizes(const lthip_ingest* i
  * lthip_ingest_stream_finish
  *   the VersionIndex  is the bytes of Longtail_CreateVersionIndex + Longtail_WriteVersionIndexToBuffer for the tree,
  *   the StoreIndex    is the bytes of Longtail_CreateMissingContent against an empty store for the version's unique chunks: the
- *                     packing rule of src/longtail.c:6801-6860 applied to the unique list of the WHOLE tree, wherever the cuts fell,
+ *                     packing rule of src/longtail.c:6801-6860 applied to the unique list of the WHOLE tree, wherever the cuts fell
+ *                     (against the attached store, if there is one: lthip_ingest_stream_set_store below),
  *   the images        of all slice calls and of finish, in call order, are the blocks of that StoreIndex in its order (BlockIndex +
  *                     [raw][compressed] + payload, as lthip_ingest_images delivers them).
  * One first-seen table (lthip_seen) lives for the session: a chunk is written if it is new in its slice's lthip_seen_add, with its
@@ -667,6 +714,23 @@ LTHIP_EXPORT int lthip_ingest_stream_finish(lthip_ingest_stream* stream, void* d
                                             lthip_ingest_result* out_result);
 /* how often the session's first-seen table has grown so far (lthip_seen_grown of it) */
 LTHIP_EXPORT uint64_t lthip_ingest_stream_table_grown(const lthip_ingest_stream* stream);
+/* Uploading into a store that already has content.  set_store is allowed before the first slice call (EINVAL afterwards, the session
+ * stays usable); the store must be of the session's context; NULL detaches it.  With a store attached a slice asks it about the
+ * slice's hashes (lthip_store_find, queued beside the first-seen pass; one more byte per chunk comes to the host in the call's one
+ * wait) and a chunk is written only if it is new in the session's table AND unknown to the store.  After finish
+ *   the VersionIndex  is unchanged: the reference's bytes for the tree,
+ *   the StoreIndex    is the bytes of Longtail_CreateMissingContent(store, version) + Longtail_WriteStoreIndexToBuffer: the packing
+ *                     of :6801-6860 over the version-unique chunks the store lacks, in version order, with their assets' tags,
+ *                     wherever the cuts fell; when no chunk is missing, the 16-byte header with zero blocks and zero chunks
+ *                     (hash identifier 0, :6931-6943) and no images,
+ *   the images        of all calls, in call order, are that StoreIndex's blocks,
+ *   the result        unique_all = the version's distinct chunks, unique_local = the chunks written; raw_bytes, compressed_bytes and
+ *                     blocks count what was written (without a store unique_local == unique_all).
+ * lthip_ingest_stream_arena_bound stays an upper bound (fewer chunks are packed).  Adding to an attached store between the first
+ * slice and finish is not supported; the store must outlive the session's last slice call.
+ * lthip_ingest_stream_store_stats: the version-unique chunks (so far) that the store held, and their bytes; 0 / 0 without a store. */
+LTHIP_EXPORT int lthip_ingest_stream_set_store(lthip_ingest_stream* stream, const lthip_store* store);
+LTHIP_EXPORT int lthip_ingest_stream_store_stats(const lthip_ingest_stream* stream, uint64_t* known_chunks, uint64_t* known_bytes);
 
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets

@@ -17,6 +17,9 @@
 // Multi-GPU: the session is given ALL ranks' chunk hashes / lengths in job order (dist.exchange_chunks) plus
 // the list of its own jobs.  Every rank derives the same first-seen table; a rank writes the chunks that are first-seen AND
 // lie in its own jobs -- exactly Longtail_CreateMissingContent against a store that already holds the other ranks' chunks.
+//
+// A store that already has content (lthip_ingest_set_store): lthip_store_find over the rank's local chunks, and "this rank writes it"
+// becomes first-seen, in its own jobs AND unknown to the store.  Everything behind that flag is as without a store.
 #include "lthip_internal.h"
 #include "index_kernels.h"
 #include "ingest_buffers.h"
@@ -28,32 +31,74 @@
 namespace
 {
 
-// local chunk k of this rank -> its index in the job-ordered arrays of all ranks, and "this rank writes it":
-// owned[k] = first_index[g(k)] == g(k).  part_first = the rank's own chunk-list starts (lthip_chunk_hash), one part per own job,
-// job_gfirst[m] = index of own job m's first chunk in the global arrays.  With job_gfirst == null the arrays are the same.
+// local chunk k of this rank -> its index in the job-ordered arrays of all ranks.  part_first = the rank's own chunk-list starts
+// (lthip_chunk_hash), one part per own job, job_gfirst[m] = index of own job m's first chunk in the global arrays.  With
+// job_gfirst == null the arrays are the same.
+__device__ __forceinline__ uint32_t ing_global_index(uint32_t k, const uint32_t* __restrict__ part_first, uint32_t nparts,
+                                                     const uint32_t* __restrict__ job_gfirst)
+{
+    if (!job_gfirst)
+        return k;
+    uint32_t lo = 0, hi = nparts; // part m with part_first[m] <= k < part_first[m + 1] (empty parts: take the last such)
+    while (hi - lo > 1)
+    {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (part_first[mid] <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return job_gfirst[lo] + (k - part_first[lo]);
+}
+
+// "this rank writes it": owned[k] = first_index[g(k)] == g(k), and -- with a store attached, known != null: lthip_store_find's flags
+// of the local chunks -- the store does not hold it
 __global__ void k_ing_owned(const uint32_t* __restrict__ first_index, const uint32_t* __restrict__ part_first, uint32_t nparts,
                             const uint32_t* __restrict__ job_gfirst, uint32_t nlocal, uint32_t* __restrict__ owned,
-                            uint32_t* __restrict__ l2g)
+                            uint32_t* __restrict__ l2g, const uint8_t* __restrict__ known)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nlocal)
         return;
-    uint32_t g = k;
-    if (job_gfirst)
-    {
-        uint32_t lo = 0, hi = nparts; // part m with part_first[m] <= k < part_first[m + 1] (empty parts: take the last such)
-        while (hi - lo > 1)
-        {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (part_first[mid] <= k)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        g = job_gfirst[lo] + (k - part_first[lo]);
-    }
+    const uint32_t g = ing_global_index(k, part_first, nparts, job_gfirst);
     l2g[k] = g;
-    owned[k] = first_index[g] == g ? 1u : 0u;
+    owned[k] = first_index[g] == g && !(known && known[k]) ? 1u : 0u;
+}
+
+// the hashes of a rank's local chunks out of the arrays of all ranks: what lthip_store_find is asked (multi-GPU only: for a single
+// rank the arrays are the same)
+__global__ void k_ing_local_hashes(const uint32_t* __restrict__ part_first, uint32_t nparts, const uint32_t* __restrict__ job_gfirst,
+                                   uint32_t nlocal, const uint64_t* __restrict__ all_hashes, uint64_t* __restrict__ local_hashes)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < nlocal)
+        local_hashes[k] = all_hashes[ing_global_index(k, part_first, nparts, job_gfirst)];
+}
+
+// out[0] += first-seen local chunks the store holds, out[1] += their bytes (lthip_ingest_store_stats)
+__global__ void k_ing_known_stats(const uint32_t* __restrict__ first_index, const uint32_t* __restrict__ l2g, const uint8_t* __restrict__ known,
+                                  const uint32_t* __restrict__ all_lens, uint32_t nlocal, unsigned long long* __restrict__ out)
+{
+    unsigned long long chunks = 0, bytes = 0;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nlocal; k += gridDim.x * blockDim.x)
+    {
+        const uint32_t g = l2g[k];
+        if (first_index[g] == g && known[k])
+        {
+            ++chunks;
+            bytes += all_lens[g];
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1)
+    {
+        chunks += __shfl_down(chunks, o, 64);
+        bytes += __shfl_down(bytes, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0 && chunks)
+    {
+        atomicAdd(out, chunks);
+        atomicAdd(out + 1, bytes);
+    }
 }
 
 // compaction of the owned chunks: hash, length, byte offset in the rank's data and the tag of the chunk's asset
@@ -113,6 +158,11 @@ struct lthip_ingest
     // ---- index phase ----
     DBuf d_first, d_isfirst, d_rank, d_idx, d_uh, d_us, d_ut, d_starts, d_tags, d_counts, d_paths, d_aoff, d_alen, d_ph, d_ch;
     DBuf d_gfirst, d_owned, d_orank, d_l2g, d_mu_hash, d_mu_len, d_mu_off, d_mu_tag;
+    // what the target already holds (lthip_ingest_set_store; may be null): the flags of the local chunks, and for a rank of several
+    // their hashes
+    const lthip_store* store;
+    DBuf d_known, d_lhash;
+    uint64_t known_chunks, known_bytes;
     HBuf h_counts, h_mu_len, h_mu_off, h_mu_hash, h_mu_tag, h_bhash, h_comp, h_brk;
     DBuf d_brk;
     DBuf d_bhash, d_boff, d_blen, d_comp, d_sum;
@@ -225,6 +275,8 @@ extern "C" int lthip_ingest_create(lthip_ctx* ctx, const lthip_ingest_config* cf
     g->vi_pending = false;
     g->ev_counts = g->ev_lens = g->ev_index = g->ev_offs = g->ev_hashes = nullptr;
     g->blocks_done = false;
+    g->store = nullptr;
+    g->known_chunks = g->known_bytes = 0;
     if (hipEventCreateWithFlags(&g->ev_counts, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&g->ev_lens, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&g->ev_offs, hipEventDisableTiming) != hipSuccess ||
@@ -252,7 +304,8 @@ extern "C" void lthip_ingest_destroy(lthip_ingest* g)
     DBuf* dev[] = {&g->d_first, &g->d_isfirst, &g->d_rank, &g->d_idx, &g->d_uh, &g->d_us, &g->d_ut, &g->d_starts, &g->d_tags, &g->d_counts,
                    &g->d_paths, &g->d_aoff, &g->d_alen, &g->d_ph, &g->d_ch, &g->d_gfirst, &g->d_owned, &g->d_orank, &g->d_l2g, &g->d_mu_hash,
                    &g->d_mu_len, &g->d_mu_off, &g->d_mu_tag, &g->d_bhash, &g->d_boff, &g->d_blen, &g->d_comp, &g->d_sum, &g->d_gather,
-                   &g->d_gsrc, &g->d_glen, &g->d_gdst, &g->d_bfirst, &g->d_braw, &g->d_bimg, &g->d_btag, &g->d_tmpsz, &g->d_brk};
+                   &g->d_gsrc, &g->d_glen, &g->d_gdst, &g->d_bfirst, &g->d_braw, &g->d_bimg, &g->d_btag, &g->d_tmpsz, &g->d_brk, &g->d_known,
+                   &g->d_lhash};
     for (DBuf* b : dev)
         if (b->p)
             (void)hipFree(b->p);
@@ -285,6 +338,27 @@ extern "C" int lthip_ingest_set_first_seen(lthip_ingest* g, const uint32_t* d_fi
         return EINVAL;
     g->ext_first = d_first_index;
     g->ext_unique = unique_chunks;
+    return 0;
+}
+
+extern "C" int lthip_ingest_set_store(lthip_ingest* g, const lthip_store* store)
+{
+    if (!g)
+        return EINVAL;
+    if (store && lthip_store_ctx(store) != g->ctx)
+        return lthip_fail(g->ctx, EINVAL, "lthip_ingest_set_store", "the store belongs to another context");
+    g->store = store;
+    return 0;
+}
+
+extern "C" int lthip_ingest_store_stats(const lthip_ingest* g, uint64_t* known_chunks, uint64_t* known_bytes)
+{
+    if (!g)
+        return EINVAL;
+    if (known_chunks)
+        *known_chunks = g->store && g->indexed ? g->known_chunks : 0;
+    if (known_bytes)
+        *known_bytes = g->store && g->indexed ? g->known_bytes : 0;
     return 0;
 }
 
@@ -552,6 +626,8 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
         (err = reserve_dev(ctx, g->d_blen, (size_t)nl * 4)) || (err = reserve_dev(ctx, g->d_comp, (size_t)nl * 4)) ||
         (err = reserve_dev(ctx, g->d_sum, 8)))
         return err;
+    if (g->store && ((err = reserve_dev(ctx, g->d_known, (size_t)nl)) || (!all_mine && (err = reserve_dev(ctx, g->d_lhash, (size_t)nl * 8)))))
+        return err;
     tr.mark("reserve");
     uint64_t* d_counts = (uint64_t*)g->d_counts.p; // [0] distinct hashes of all ranks, [1] chunks this rank writes (u32 in the low half)
     volatile uint64_t* h_counts = (volatile uint64_t*)g->h_counts.p;
@@ -624,15 +700,39 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
                            (uint64_t*)g->d_uh.p, (uint32_t*)g->d_us.p, (uint32_t*)g->d_ut.p);
         LTHIP_LAUNCH_CHECK(ctx);
     }
-    // ---- the chunks this rank writes: first-seen and in one of its own jobs, in version order ----
-    h_counts[2] = h_counts[3] = 0;
+    // ---- the chunks this rank writes: first-seen, in one of its own jobs (and not in the store), in version order ----
+    h_counts[2] = h_counts[3] = h_counts[4] = h_counts[5] = 0;
+    const uint8_t* d_known = nullptr; // (no store: k_ing_owned gets a null flag pointer)
+    if (nl && g->store)
+    {
+        const uint32_t blocks = (uint32_t)div_up_u64(nl, 256);
+        const uint64_t* d_local_hashes = d_all_hashes; // (a single rank: the local arrays are the global ones)
+        if (!all_mine)
+        {
+            LaunchTimer tm(ctx, LTHIP_K_OTHER);
+            hipLaunchKernelGGL(k_ing_local_hashes, dim3(blocks), dim3(256), 0, s, d_local_part_first, (uint32_t)my_jobs,
+                               (const uint32_t*)g->d_gfirst.p, nl, d_all_hashes, (uint64_t*)g->d_lhash.p);
+            LTHIP_LAUNCH_CHECK(ctx);
+            d_local_hashes = (const uint64_t*)g->d_lhash.p;
+        }
+        if ((err = lthip_store_find(g->store, nl, d_local_hashes, (uint8_t*)g->d_known.p, nullptr)))
+            return err;
+        d_known = (const uint8_t*)g->d_known.p;
+    }
     if (nl)
     {
         const uint32_t blocks = (uint32_t)div_up_u64(nl, 256);
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_ing_owned, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_first.p, d_local_part_first, (uint32_t)my_jobs,
                            all_mine ? (const uint32_t*)nullptr : (const uint32_t*)g->d_gfirst.p, nl, (uint32_t*)g->d_owned.p,
-                           (uint32_t*)g->d_l2g.p);
+                           (uint32_t*)g->d_l2g.p, d_known);
+        if (d_known)
+        {
+            LTHIP_CHECK(ctx, hipMemsetAsync(d_counts + 4, 0, 16, s));
+            hipLaunchKernelGGL(k_ing_known_stats, dim3(std::min(blocks, 1024u)), dim3(256), 0, s, (const uint32_t*)g->d_first.p,
+                               (const uint32_t*)g->d_l2g.p, d_known, d_all_lens, nl, (unsigned long long*)(d_counts + 4));
+            LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 4), d_counts + 4, 16, hipMemcpyDeviceToHost, s));
+        }
         if ((err = lthip_exclusive_scan_u32(ctx, (const uint32_t*)g->d_owned.p, (uint32_t*)g->d_orank.p, nl, nullptr, LTHIP_K_OTHER)))
             return err;
         hipLaunchKernelGGL(k_ing_compact, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_owned.p, (const uint32_t*)g->d_orank.p,
@@ -653,6 +753,8 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
     const uint32_t nm = nl ? (uint32_t)(h_counts[2] & 0xFFFFFFFFu) + (uint32_t)(h_counts[3] & 0xFFFFFFFFu) : 0u;
     g->unique_all = unique;
     g->n_mine = nm;
+    g->known_chunks = h_counts[4];
+    g->known_bytes = h_counts[5];
 
     // ---- the host needs the owned chunks' lengths, offsets (and tags) for the packing and the codec calls.  Of the offsets the packing
     // loop reads only whether a chunk continues the range of the one before: a byte per chunk from k_ing_breaks.  The copies are 44 MB on
@@ -1040,7 +1142,9 @@ extern "C" int lthip_ingest_finish(lthip_ingest* g, void* h_store_index, size_t 
             LTHIP_CHECK(ctx, hipEventSynchronize(g->ev_index));  // block hashes ...
             LTHIP_CHECK(ctx, hipEventSynchronize(g->ev_hashes)); // ... and the owned chunks' hashes are on the host
             uint8_t* w = (uint8_t*)h_store_index;
-            const uint32_t head[4] = {(1u << 24) /* LONGTAIL_STORE_INDEX_VERSION_1_0_0, :19-23 */, g->cfg.hash_identifier, (uint32_t)nb, (uint32_t)m};
+            // (nothing to write: Longtail_CreateMissingContent returns Longtail_CreateStoreIndexFromBlocks(0, 0), hash identifier 0, :6931-6943)
+            const uint32_t head[4] = {(1u << 24) /* LONGTAIL_STORE_INDEX_VERSION_1_0_0, :19-23 */, m ? g->cfg.hash_identifier : 0u, (uint32_t)nb,
+                                      (uint32_t)m};
             memcpy(w, head, 16);
             w += 16;
             memcpy(w, g->h_bhash.p, nb * 8); // m_BlockHashes

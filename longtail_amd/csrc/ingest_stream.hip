@@ -3,6 +3,9 @@
 // tree at the end.
 //
 //   first-seen      one lthip_seen table for the session (k_dedup.hip): a chunk is written if it is new in its slice's lthip_seen_add
+//   the store       with an lthip_store attached (lthip_ingest_stream_set_store) a new chunk is written only if the store lacks it:
+//                   lthip_store_find over the slice's hashes beside the first-seen pass, a byte per chunk to the host with the lists.
+//                   Everything behind the unique list -- packing, carry, assembly, codec -- runs over the shorter list unchanged
 //   packing         Longtail_CreateStoreIndex's greedy rule (src/longtail.c:6801-6860) over the unique list of the whole tree, continued
 //                   from slice to slice: a block is closed only when the chunk that does not fit any more has been seen.  At the end of
 //                   a slice one block may be open; its chunk list stays on the host, its BYTES are gathered into d_carry
@@ -39,8 +42,11 @@ struct lthip_ingest_stream
     std::vector<uint32_t> asset_chunks; // chunks of every asset so far
     // ---- state ----
     lthip_seen* seen;
+    const lthip_store* store;                        // what the target already holds (may be null): its chunks are not written
+    uint64_t unique_all, known_chunks, known_bytes;  // the version's distinct chunks so far; those of them the store held
     uint64_t next_job;
-    bool closed; // finish has closed the open block: no more slices
+    bool started; // a slice call has begun work: the store can no longer be attached or detached
+    bool closed;  // finish has closed the open block: no more slices
     int sticky;  // a failure after work had started: what every later call returns
     // ---- every chunk of the tree so far: hash and length (pinned: the slices' lists are copied straight into them) ----
     HBuf h_all_hash, h_all_len;
@@ -59,7 +65,8 @@ struct lthip_ingest_stream
     std::vector<uint64_t> carry_off;
     uint64_t carry_bytes;
     // ---- per call ----
-    HBuf h_first, h_off, h_pf;
+    HBuf h_first, h_off, h_pf, h_known;
+    DBuf d_known;
     DBuf d_first, d_gather, d_gsrc, d_glen, d_gdst, d_uh, d_ul, d_boff, d_blen, d_bhash, d_comp, d_tmpsz, d_bfirst, d_braw, d_bimg, d_btag;
     DBuf d_vh, d_vl; // finish: the kept lists on the device
     std::vector<uint64_t> u_src; // byte offset in the slice's data of the chunks this slice added to the unique list
@@ -421,6 +428,8 @@ int stream_slice_work(Stream* s, uint64_t first_job, uint64_t job_count, uint64_
         (err = reserve_pinned(ctx, s->h_pf, (job_count + 1) * 4)) || (err = reserve_dev(ctx, s->d_first, chunks * 4)) ||
         (err = stream_grow_lists(s, chunks)))
         return err;
+    if (s->store && ((err = reserve_pinned(ctx, s->h_known, chunks)) || (err = reserve_dev(ctx, s->d_known, chunks))))
+        return err;
     // ---- first-seen over everything so far, then the slice's lists to the host: the call's one wait ----
     const uint64_t base = s->n_all;
     uint64_t* all_hash = (uint64_t*)s->h_all_hash.p + base;
@@ -429,6 +438,12 @@ int stream_slice_work(Stream* s, uint64_t first_job, uint64_t job_count, uint64_
     {
         if ((err = lthip_seen_add(s->seen, chunks, d_hashes, (uint32_t*)s->d_first.p, nullptr)))
             return err;
+        if (s->store)
+        {
+            if ((err = lthip_store_find(s->store, chunks, d_hashes, (uint8_t*)s->d_known.p, nullptr)))
+                return err;
+            LTHIP_CHECK(ctx, hipMemcpyAsync(s->h_known.p, s->d_known.p, chunks, hipMemcpyDeviceToHost, st));
+        }
         LTHIP_CHECK(ctx, hipMemcpyAsync(s->h_first.p, s->d_first.p, chunks * 4, hipMemcpyDeviceToHost, st));
         LTHIP_CHECK(ctx, hipMemcpyAsync(all_len, d_lens, chunks * 4, hipMemcpyDeviceToHost, st));
         LTHIP_CHECK(ctx, hipMemcpyAsync(all_hash, d_hashes, chunks * 8, hipMemcpyDeviceToHost, st));
@@ -442,6 +457,7 @@ int stream_slice_work(Stream* s, uint64_t first_job, uint64_t job_count, uint64_
     const uint32_t* first = (const uint32_t*)s->h_first.p;
     const uint64_t* offs = (const uint64_t*)s->h_off.p;
     const uint32_t* pf = (const uint32_t*)s->h_pf.p;
+    const uint8_t* known = s->store ? (const uint8_t*)s->h_known.p : nullptr;
     if (pf[0] != 0 || pf[job_count] != chunks)
         return lthip_fail(ctx, EINVAL, "lthip_ingest_stream_slice", "d_part_first does not span the slice's chunks");
     uint64_t sum = 0;
@@ -452,7 +468,7 @@ int stream_slice_work(Stream* s, uint64_t first_job, uint64_t job_count, uint64_
     for (uint64_t j = 0; j < chunks; ++j)
         if (all_len[j] > block_limit(&s->cfg)) // (lists of a chunker with a larger maximum than create assumed: d_carry and the arena bound hold a block)
             return lthip_fail(ctx, EINVAL, "lthip_ingest_stream_slice", "a chunk is larger than max_block_size * 1.1");
-    // ---- the chunks that are new: onto the unique list, with their asset's tag ----
+    // ---- the chunks that are new (and that the store lacks): onto the unique list, with their asset's tag ----
     const uint64_t fresh = s->u_len.size();
     s->u_src.clear();
     for (uint64_t m = 0; m < job_count; ++m)
@@ -464,6 +480,13 @@ int stream_slice_work(Stream* s, uint64_t first_job, uint64_t job_count, uint64_
         for (uint64_t j = pf[m]; j < pf[m + 1]; ++j)
             if (first[j] == (uint32_t)(base + j))
             {
+                ++s->unique_all;
+                if (known && known[j])
+                {
+                    ++s->known_chunks;
+                    s->known_bytes += all_len[j];
+                    continue;
+                }
                 s->u_hash.push_back(all_hash[j]);
                 s->u_len.push_back(all_len[j]);
                 s->u_tag.push_back(tag);
@@ -522,11 +545,11 @@ extern "C" void lthip_ingest_stream_destroy(lthip_ingest_stream* s)
     (void)hipStreamSynchronize(s->ctx->stream);
     lthip_seen_destroy(s->seen);
     DBuf* dev[] = {&s->d_carry, &s->d_first, &s->d_gather, &s->d_gsrc, &s->d_glen, &s->d_gdst, &s->d_uh, &s->d_ul, &s->d_boff, &s->d_blen, &s->d_bhash,
-                   &s->d_comp, &s->d_tmpsz, &s->d_bfirst, &s->d_braw, &s->d_bimg, &s->d_btag, &s->d_vh, &s->d_vl};
+                   &s->d_comp, &s->d_tmpsz, &s->d_bfirst, &s->d_braw, &s->d_bimg, &s->d_btag, &s->d_vh, &s->d_vl, &s->d_known};
     for (DBuf* b : dev)
         if (b->p)
             (void)hipFree(b->p);
-    HBuf* pin[] = {&s->h_all_hash, &s->h_all_len, &s->h_first, &s->h_off, &s->h_pf};
+    HBuf* pin[] = {&s->h_all_hash, &s->h_all_len, &s->h_first, &s->h_off, &s->h_pf, &s->h_known};
     for (HBuf* b : pin)
         if (b->p)
             (void)hipHostFree(b->p);
@@ -601,8 +624,10 @@ extern "C" int lthip_ingest_stream_create(lthip_ctx* ctx, const lthip_ingest_con
     s->job_size.swap(job_size);
     s->asset_chunks.assign(na, 0);
     s->seen = nullptr;
+    s->store = nullptr;
+    s->unique_all = s->known_chunks = s->known_bytes = 0;
     s->next_job = 0;
-    s->closed = false;
+    s->started = s->closed = false;
     s->sticky = 0;
     s->n_all = 0;
     s->b_first.push_back(0);
@@ -632,6 +657,32 @@ extern "C" int lthip_ingest_stream_create(lthip_ctx* ctx, const lthip_ingest_con
 
 extern "C" uint64_t lthip_ingest_stream_table_grown(const lthip_ingest_stream* s) { return s ? lthip_seen_grown(s->seen) : 0; }
 
+extern "C" int lthip_ingest_stream_set_store(lthip_ingest_stream* s, const lthip_store* store)
+{
+    if (!s)
+        return EINVAL;
+    if (s->sticky)
+        return s->sticky;
+    // (refused before any work: the session stays as it is)
+    if (s->started || s->closed)
+        return lthip_fail(s->ctx, EINVAL, "lthip_ingest_stream_set_store", "the store is attached before the first slice");
+    if (store && lthip_store_ctx(store) != s->ctx)
+        return lthip_fail(s->ctx, EINVAL, "lthip_ingest_stream_set_store", "the store belongs to another context");
+    s->store = store;
+    return 0;
+}
+
+extern "C" int lthip_ingest_stream_store_stats(const lthip_ingest_stream* s, uint64_t* known_chunks, uint64_t* known_bytes)
+{
+    if (!s)
+        return EINVAL;
+    if (known_chunks)
+        *known_chunks = s->known_chunks;
+    if (known_bytes)
+        *known_bytes = s->known_bytes;
+    return 0;
+}
+
 extern "C" int lthip_ingest_stream_slice(lthip_ingest_stream* s, uint64_t first_job, uint64_t job_count, const void* d_data,
                                          const uint64_t* d_chunk_offsets, const uint32_t* d_chunk_lens, const uint64_t* d_chunk_hashes,
                                          const uint32_t* d_part_first, uint64_t chunks, void* d_arena, uint64_t arena_bytes)
@@ -656,6 +707,7 @@ extern "C" int lthip_ingest_stream_slice(lthip_ingest_stream* s, uint64_t first_
     if (arena_bytes < lthip_ingest_stream_arena_bound(&s->cfg, bytes, chunks))
         return lthip_fail(ctx, ENOMEM, "lthip_ingest_stream_slice", "arena below lthip_ingest_stream_arena_bound of this slice");
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    s->started = true;
     return stream_fail(s, stream_slice_work(s, first_job, job_count, bytes, d_data, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first,
                                             chunks, d_arena, arena_bytes));
 }
@@ -708,11 +760,12 @@ extern "C" int lthip_ingest_stream_finish(lthip_ingest_stream* s, void* d_arena,
     lthip_ingest_result res;
     memset(&res, 0, sizeof res);
     res.chunks_all = res.chunks_local = s->n_all;
-    res.unique_all = res.unique_local = m;
+    res.unique_all = s->unique_all;
+    res.unique_local = m;
     res.blocks = nb;
     for (size_t c = 0; c < m; ++c)
         res.raw_bytes += s->u_len[c];
-    res.version_index_size = lthip_version_index_size(s->na, m, s->n_all, (uint32_t)s->path_data.size());
+    res.version_index_size = lthip_version_index_size(s->na, s->unique_all, s->n_all, (uint32_t)s->path_data.size());
     res.store_index_size = 16 + nb * 8 + m * 8 + nb * 12 + m * 4; // Longtail_GetStoreIndexDataSize
     auto deliver = [&]() {
         if (out)

@@ -425,3 +425,316 @@ extern "C" int lthip_seen_add(lthip_seen* t, uint64_t count, const uint64_t* d_h
     t->total += count;
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// lthip_store: the set of chunk hashes a store already holds (include/longtail_hip.h) -- what the ingest sessions ask "does the store
+// lack this chunk?".  Same slots, same probing and the same growth as lthip_seen, but a slot is the key alone: membership needs no
+// position, and a store can hold far more chunks than a version, so neither lthip_seen's uint32_t positions nor its 2^31 - 1 total
+// apply here.  The 0xFFFF...FFFF hash (the empty key) lives in a side flag.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace
+{
+
+__global__ void k_store_clear(uint64_t* __restrict__ keys, uint64_t slots)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * blockDim.x)
+        keys[i] = EMPTY_KEY;
+}
+
+__global__ void k_store_insert(const uint64_t* __restrict__ hashes, uint64_t n, uint64_t* __restrict__ keys, uint64_t mask, uint32_t* special,
+                               unsigned long long* distinct)
+{
+    const uint64_t pos = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool claimed = false;
+    if (pos < n)
+    {
+        const uint64_t h = hashes[pos];
+        if (h == EMPTY_KEY)
+            claimed = atomicCAS(special, 0u, 1u) == 0u;
+        else
+        {
+            uint64_t slot = mix64(h) & mask;
+            for (;;)
+            {
+                const unsigned long long prev =
+                    atomicCAS(reinterpret_cast<unsigned long long*>(&keys[slot]), (unsigned long long)EMPTY_KEY, (unsigned long long)h);
+                if (prev == EMPTY_KEY || prev == h)
+                {
+                    claimed = prev == EMPTY_KEY;
+                    break;
+                }
+                slot = (slot + 1) & mask;
+            }
+        }
+    }
+    const uint64_t b = __builtin_amdgcn_ballot_w64(claimed);
+    if (b && (threadIdx.x & 63) == 0)
+        atomicAdd(distinct, (unsigned long long)__builtin_popcountll(b));
+}
+
+// one thread per query; the probe ends at the key or at an empty slot, and there is one: at most half of the slots are taken
+__global__ void k_store_find(const uint64_t* __restrict__ hashes, uint64_t n, const uint64_t* __restrict__ keys, uint64_t mask,
+                             const uint32_t* special, uint8_t* __restrict__ known, unsigned long long* known_count)
+{
+    const uint64_t pos = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool hit = false;
+    if (pos < n)
+    {
+        const uint64_t h = hashes[pos];
+        if (h == EMPTY_KEY)
+            hit = *special != 0u;
+        else
+        {
+            uint64_t slot = mix64(h) & mask;
+            for (;;)
+            {
+                const uint64_t k = keys[slot];
+                if (k == h || k == EMPTY_KEY)
+                {
+                    hit = k == h;
+                    break;
+                }
+                slot = (slot + 1) & mask;
+            }
+        }
+        known[pos] = hit ? 1 : 0;
+    }
+    const uint64_t b = __builtin_amdgcn_ballot_w64(hit);
+    if (known_count && b && (threadIdx.x & 63) == 0)
+        atomicAdd(known_count, (unsigned long long)__builtin_popcountll(b));
+}
+
+// growth: every live key of the old table into the new one (the keys of a table are distinct: a slot is claimed by exactly one thread)
+__global__ void k_store_reinsert(const uint64_t* __restrict__ old_keys, uint64_t old_slots, uint64_t* __restrict__ keys, uint64_t mask)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= old_slots)
+        return;
+    const uint64_t h = old_keys[i];
+    if (h == EMPTY_KEY)
+        return;
+    uint64_t slot = mix64(h) & mask;
+    while (atomicCAS(reinterpret_cast<unsigned long long*>(&keys[slot]), (unsigned long long)EMPTY_KEY, (unsigned long long)h) !=
+           (unsigned long long)EMPTY_KEY)
+        slot = (slot + 1) & mask;
+}
+
+constexpr uint64_t STORE_LAUNCH_ITEMS = 1ull << 30; // items of one launch (a thread each): a larger call is several launches
+
+} // namespace
+
+struct lthip_store
+{
+    lthip_ctx* ctx;
+    uint64_t* keys;
+    void* misc;      // [0] u32: the store holds the 0xFFFF...FFFF hash (the table's empty key), [8] u64: distinct hashes
+    uint64_t* d_tmp; // lthip_store_add_index: the index's chunk hashes on the device
+    uint64_t tmp_cap;
+    uint64_t slots;
+    uint64_t added;
+    uint64_t grown;
+};
+
+static int store_alloc(lthip_ctx* ctx, size_t bytes, void** p, const char* what)
+{
+    *p = nullptr;
+    const hipError_t e = lthip_hip_malloc(p, bytes);
+    if (e != hipSuccess)
+        return lthip_fail(ctx, e == hipErrorOutOfMemory ? ENOMEM : EIO, what, hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int lthip_store_create(lthip_ctx* ctx, uint64_t expected_hashes, lthip_store** out)
+{
+    if (!ctx || !out)
+        return EINVAL;
+    *out = nullptr;
+    if (expected_hashes > (1ull << 56))
+        return lthip_fail(ctx, EINVAL, "lthip_store_create", "too many hashes");
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    lthip_store* t = new (std::nothrow) lthip_store();
+    if (!t)
+        return ENOMEM;
+    t->ctx = ctx;
+    t->slots = seen_slots_for(expected_hashes);
+    int err = store_alloc(ctx, t->slots * 8, (void**)&t->keys, "lthip_store_create");
+    if (!err)
+        err = store_alloc(ctx, 64, &t->misc, "lthip_store_create");
+    if (!err)
+    {
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_store_clear, dim3((uint32_t)std::min<uint64_t>(2048, div_up_u64(t->slots, 256))), dim3(256), 0, ctx->stream, t->keys,
+                           t->slots);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemsetAsync(t->misc, 0, 64, ctx->stream);
+        if (e != hipSuccess)
+            err = lthip_fail(ctx, EIO, "lthip_store_create", hipGetErrorString(e));
+    }
+    if (err)
+    {
+        lthip_store_destroy(t);
+        return err;
+    }
+    *out = t;
+    return 0;
+}
+
+extern "C" void lthip_store_destroy(lthip_store* t)
+{
+    if (!t)
+        return;
+    (void)hipSetDevice(t->ctx->device);
+    if (t->keys || t->misc || t->d_tmp)
+        (void)hipStreamSynchronize(t->ctx->stream);
+    if (t->keys)
+        (void)hipFree(t->keys);
+    if (t->misc)
+        (void)hipFree(t->misc);
+    if (t->d_tmp)
+        (void)hipFree(t->d_tmp);
+    delete t;
+}
+
+extern "C" uint64_t lthip_store_added(const lthip_store* t) { return t ? t->added : 0; }
+extern "C" uint64_t lthip_store_grown(const lthip_store* t) { return t ? t->grown : 0; }
+
+// room for `count` more hashes: two slots per hash of the new running total, at least twice the slots; the keys move, the side flag and
+// the counter stay.  A failure leaves the table as it was.
+static int store_make_room(lthip_store* t, uint64_t count)
+{
+    lthip_ctx* ctx = t->ctx;
+    if (count > (1ull << 56) || t->added + count > (1ull << 56))
+        return lthip_fail(ctx, EINVAL, "lthip_store_add", "too many hashes");
+    if ((t->added + count) * 2 <= t->slots)
+        return 0;
+    uint64_t slots = t->slots * 2;
+    while (slots < (t->added + count) * 2)
+        slots <<= 1;
+    uint64_t* keys;
+    int err;
+    if ((err = store_alloc(ctx, slots * 8, (void**)&keys, "lthip_store_add: table")))
+        return err; // (nothing queued, nothing changed)
+    {
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_store_clear, dim3((uint32_t)std::min<uint64_t>(2048, div_up_u64(slots, 256))), dim3(256), 0, ctx->stream, keys, slots);
+        hipLaunchKernelGGL(k_store_reinsert, dim3((uint32_t)div_up_u64(t->slots, 256)), dim3(256), 0, ctx->stream, (const uint64_t*)t->keys, t->slots,
+                           keys, slots - 1);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = lthip_stream_wait(ctx); // the old table is read until here
+    if (e != hipSuccess)
+    {
+        (void)hipFree(keys);
+        return lthip_fail(ctx, EIO, "lthip_store_add: growth", hipGetErrorString(e));
+    }
+    (void)hipFree(t->keys);
+    t->keys = keys;
+    t->slots = slots;
+    ++t->grown;
+    return 0;
+}
+
+static int store_insert(lthip_store* t, uint64_t count, const uint64_t* d_hashes)
+{
+    lthip_ctx* ctx = t->ctx;
+    LaunchTimer tm(ctx, LTHIP_K_OTHER);
+    for (uint64_t i = 0; i < count; i += STORE_LAUNCH_ITEMS)
+    {
+        const uint64_t k = std::min(STORE_LAUNCH_ITEMS, count - i);
+        hipLaunchKernelGGL(k_store_insert, dim3((uint32_t)div_up_u64(k, 256)), dim3(256), 0, ctx->stream, d_hashes + i, k, t->keys, t->slots - 1,
+                           (uint32_t*)t->misc, (unsigned long long*)((uint8_t*)t->misc + 8));
+    }
+    LTHIP_LAUNCH_CHECK(ctx);
+    t->added += count;
+    return 0;
+}
+
+extern "C" int lthip_store_add(lthip_store* t, uint64_t count, const uint64_t* d_hashes)
+{
+    if (!t || (count && !d_hashes))
+        return EINVAL;
+    lthip_ctx* ctx = t->ctx;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int err;
+    if ((err = store_make_room(t, count)))
+        return err;
+    return store_insert(t, count, d_hashes);
+}
+
+extern "C" int lthip_store_add_index(lthip_store* t, const void* store_index, size_t size)
+{
+    if (!t || !store_index)
+        return EINVAL;
+    lthip_ctx* ctx = t->ctx;
+    // the layout as lthip_get_existing_store_index reads it (src/longtail.c:8913-8931): [version, hash id, blocks, chunks], block hashes,
+    // chunk hashes, ...
+    if (size < 16)
+        return lthip_fail(ctx, EBADF, "lthip_store_add_index", "store index shorter than its header");
+    uint32_t head[4];
+    memcpy(head, store_index, 16);
+    const uint64_t nb = head[2], m = head[3];
+    if (head[0] != (1u << 24)) // LONGTAIL_STORE_INDEX_VERSION_1_0_0 (src/longtail.c:19-23)
+        return lthip_fail(ctx, EBADF, "lthip_store_add_index", "unsupported store index version");
+    if (size < 16 + nb * 8 + m * 8 + nb * 12 + m * 4)
+        return lthip_fail(ctx, EBADF, "lthip_store_add_index", "store index truncated");
+    if (!m)
+        return 0;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    int err;
+    if (t->tmp_cap < m)
+    {
+        // (the buffer of the call before may still be read by its inserts: hipFree waits for them)
+        uint64_t* p;
+        if ((err = store_alloc(ctx, m * 8, (void**)&p, "lthip_store_add_index")))
+            return err;
+        if (t->d_tmp)
+            (void)hipFree(t->d_tmp);
+        t->d_tmp = p;
+        t->tmp_cap = m;
+    }
+    if ((err = store_make_room(t, m)))
+        return err;
+    // through the staging ring in pieces, so that no staging slot grows to the size of a store's index
+    const uint8_t* src = (const uint8_t*)store_index + 16 + nb * 8;
+    constexpr uint64_t PIECE = 4u << 20;
+    for (uint64_t o = 0; o < m * 8; o += PIECE)
+        if ((err = lthip_stage_upload(ctx, (uint8_t*)t->d_tmp + o, src + o, (size_t)std::min(PIECE, m * 8 - o), ctx->stream)))
+            return err;
+    return store_insert(t, m, t->d_tmp);
+}
+
+extern "C" int lthip_store_find(const lthip_store* t, uint64_t count, const uint64_t* d_hashes, uint8_t* d_known, uint64_t* d_known_count)
+{
+    if (!t || (count && (!d_hashes || !d_known)))
+        return EINVAL;
+    lthip_ctx* ctx = t->ctx;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (d_known_count)
+        LTHIP_CHECK(ctx, hipMemsetAsync(d_known_count, 0, 8, ctx->stream)); // (set by the call, not accumulated)
+    if (!count)
+        return 0;
+    LaunchTimer tm(ctx, LTHIP_K_OTHER);
+    for (uint64_t i = 0; i < count; i += STORE_LAUNCH_ITEMS)
+    {
+        const uint64_t k = std::min(STORE_LAUNCH_ITEMS, count - i);
+        hipLaunchKernelGGL(k_store_find, dim3((uint32_t)div_up_u64(k, 256)), dim3(256), 0, ctx->stream, d_hashes + i, k, (const uint64_t*)t->keys,
+                           t->slots - 1, (const uint32_t*)t->misc, d_known + i, (unsigned long long*)d_known_count);
+    }
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int lthip_store_distinct(lthip_store* t, uint64_t* out)
+{
+    if (!t || !out)
+        return EINVAL;
+    lthip_ctx* ctx = t->ctx;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(out, (const uint8_t*)t->misc + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
+    LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
+    return 0;
+}
+
+lthip_ctx* lthip_store_ctx(const lthip_store* t) { return t->ctx; }

@@ -227,6 +227,7 @@ static inline hipError_t lthip_hip_malloc(void** p, size_t bytes) { return hipMa
 static inline hipError_t lthip_hip_host_malloc(void** p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
 #endif
 int lthip_scratch(lthip_ctx* ctx, int slot, size_t bytes, void** out);
+lthip_ctx* lthip_store_ctx(const lthip_store* store); // the context a store belongs to (k_dedup.hip)
 // A second in-order queue of the context for work that should overlap the main stream (callers order the two with
 // events from lthip_sync_event and must make the main stream wait for the side stream before they return).
 int lthip_second_stream(lthip_ctx* ctx, hipStream_t* out);

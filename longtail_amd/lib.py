@@ -53,7 +53,7 @@ def _u32arr(a: Sequence[int]) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint32))
 
 
-ABI_VERSION = 3  # include/longtail_hip.h LTHIP_ABI_VERSION
+ABI_VERSION = 4  # include/longtail_hip.h LTHIP_ABI_VERSION
 
 
 class HipLib:
@@ -157,7 +157,17 @@ class HipLib:
         sig("lthip_seen_add", i32, [vp, u64, vp, vp, vp])
         sig("lthip_seen_total", u64, [vp])
         sig("lthip_seen_grown", u64, [vp])
+        sig("lthip_store_create", i32, [vp, u64, P(vp)])
+        sig("lthip_store_destroy", None, [vp])
+        sig("lthip_store_add", i32, [vp, u64, vp])
+        sig("lthip_store_add_index", i32, [vp, vp, sz])
+        sig("lthip_store_find", i32, [vp, u64, vp, vp, vp])
+        sig("lthip_store_added", u64, [vp])
+        sig("lthip_store_distinct", i32, [vp, P(u64)])
+        sig("lthip_store_grown", u64, [vp])
         sig("lthip_ingest_set_first_seen", i32, [vp, vp, u64])
+        sig("lthip_ingest_set_store", i32, [vp, vp])
+        sig("lthip_ingest_store_stats", i32, [vp, P(u64), P(u64)])
         sig("lthip_plan_reaim", i32, [vp, vp, u32, vp, vp])
         sig("lthip_hash_one", i32, [vp, vp, u32, vp])
         sig("lthip_hash_runs_u64", i32, [vp, vp, vp, u32, vp])
@@ -192,6 +202,8 @@ class HipLib:
         sig("lthip_ingest_stream_images", i32, [vp, P(u64), P(u64), P(vp), P(vp)])
         sig("lthip_ingest_stream_finish", i32, [vp, vp, u64, vp, sz, vp, sz, vp])
         sig("lthip_ingest_stream_table_grown", u64, [vp])
+        sig("lthip_ingest_stream_set_store", i32, [vp, vp])
+        sig("lthip_ingest_stream_store_stats", i32, [vp, P(u64), P(u64)])
         sig("lthip_divtest_eval", i32, [u32, u32])
         sig("lthip_job_count", u64, [u32, vp, u32])
         sig("lthip_make_jobs", i32, [u32, vp, u32, u64, vp, vp, vp])
@@ -757,6 +769,17 @@ class Ingest:
         self.ctx._check(self.ctx.lib.dll.lthip_ingest_set_first_seen(self.h, _ptr(first_index), C.c_uint64(int(unique_chunks))),
                         "lthip_ingest_set_first_seen")
 
+    def set_store(self, store: "Optional[Store]"):
+        """The following index() calls write only what `store` lacks (None detaches it); the store must outlive them."""
+        self._store_keep = store
+        self.ctx._check(self.ctx.lib.dll.lthip_ingest_set_store(self.h, store.h if store is not None else None), "lthip_ingest_set_store")
+
+    def store_stats(self):
+        """(chunks, bytes) of the first-seen chunks of this rank's jobs that the attached store held; (0, 0) without a store."""
+        c, b = C.c_uint64(0), C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_ingest_store_stats(self.h, C.byref(c), C.byref(b)), "lthip_ingest_store_stats")
+        return int(c.value), int(b.value)
+
     def write(self, data, arena):
         self.ctx._check(self.ctx.lib.dll.lthip_ingest_write(self.h, _ptr(data), _ptr(arena), int(arena.numel())), "lthip_ingest_write")
 
@@ -840,6 +863,75 @@ class Seen:
         return int(self.ctx.lib.dll.lthip_seen_grown(self.h))
 
 
+class Store:
+    """lthip_store: the set of chunk hashes a store already holds, resident on the device -- built from StoreIndex blobs (add_index) or
+    device hashes (add), asked with find(), attached to a session with IngestStream.set_store / Ingest.set_store so that the session
+    writes only what the store lacks."""
+
+    def __init__(self, ctx: "Context", expected_hashes: int = 0):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(ctx.lib.dll.lthip_store_create(ctx.h, expected_hashes, C.byref(h)), "lthip_store_create")
+        self.h = h
+        self._keep = []
+
+    def close(self):
+        # (the C object reads its context when it is destroyed: a store that outlives its context is dropped, not touched again)
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.dll.lthip_store_destroy(self.h)
+        self.h = None
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, hashes):
+        """`hashes`: a device int64 / uint64 tensor, duplicates allowed.  Asynchronous on the context's stream."""
+        n = int(hashes.numel())
+        self.ctx._check(self.ctx.lib.dll.lthip_store_add(self.h, n, _ptr(hashes) if n else None), "lthip_store_add")
+        self._keep.append(hashes)  # read by the launch the call queued: kept until sync() or close()
+
+    def add_index(self, store_index: bytes):
+        """The chunk hashes of a serialized StoreIndex (host bytes); EBADF for a malformed one, which changes nothing."""
+        raw = np.frombuffer(store_index, np.uint8)
+        self.ctx._check(self.ctx.lib.dll.lthip_store_add_index(self.h, raw.ctypes.data if len(raw) else None, len(raw)), "lthip_store_add_index")
+
+    def find(self, hashes, count=None):
+        """-> (known: uint8 tensor, 1 where the store holds the hash; their number: a one-element int64 device tensor -- `count`, if
+        given: the call sets it, it does not add to it)"""
+        torch = self.ctx.torch
+        n = int(hashes.numel())
+        known = torch.empty(max(1, n), dtype=torch.uint8, device=self.ctx._dev())
+        if count is None:
+            count = torch.full((1,), -1, dtype=torch.int64, device=self.ctx._dev())
+        self.ctx._check(self.ctx.lib.dll.lthip_store_find(self.h, n, _ptr(hashes) if n else None, _ptr(known), _ptr(count)), "lthip_store_find")
+        self._keep.append(hashes)
+        return known[:n], count
+
+    def sync(self):
+        """Waits for the context's stream; the inputs of the add() / find() calls so far are let go."""
+        self.ctx.sync()
+        self._keep = []
+
+    @property
+    def added(self) -> int:
+        return int(self.ctx.lib.dll.lthip_store_added(self.h))
+
+    @property
+    def distinct(self) -> int:
+        out = C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_store_distinct(self.h, C.byref(out)), "lthip_store_distinct")
+        self._keep = []
+        return int(out.value)
+
+    @property
+    def grown(self) -> int:
+        return int(self.ctx.lib.dll.lthip_store_grown(self.h))
+
+
 class IngestStream:
     """lthip_ingest_stream: the ingest session for a tree that arrives in slices of jobs -- one first-seen table, one packing and one
     VersionIndex / StoreIndex pair for the whole tree, wherever the slices were cut (include/longtail_hip.h)."""
@@ -906,6 +998,18 @@ class IngestStream:
     @property
     def table_grown(self) -> int:
         return int(self.ctx.lib.dll.lthip_ingest_stream_table_grown(self.h))
+
+    def set_store(self, store: "Optional[Store]"):
+        """Before the first slice(): the session writes only what `store` lacks (None detaches it); the store must outlive it."""
+        self.ctx._check(self.ctx.lib.dll.lthip_ingest_stream_set_store(self.h, store.h if store is not None else None),
+                        "lthip_ingest_stream_set_store")
+        self._store_keep = store
+
+    def store_stats(self):
+        """(chunks, bytes) of the version-unique chunks so far that the attached store held; (0, 0) without a store."""
+        c, b = C.c_uint64(0), C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_ingest_stream_store_stats(self.h, C.byref(c), C.byref(b)), "lthip_ingest_stream_store_stats")
+        return int(c.value), int(b.value)
 
 
 class Plan:
