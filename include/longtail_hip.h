@@ -141,7 +141,9 @@ LTHIP_EXPORT const char* lthip_build_id(void);
  *   1  rounds 1-3      2  round 4: lthip_ingest_result.gathered_bytes appended, LTHIP_K_COUNT 9 -> 10
  *   3  round 5: lthip_ingest_result starts with struct_size (set by the caller; the library writes no more than that)
  *   4  lthip_store and the sessions' set_store / store_stats: a session with a store attached writes what the store lacks, so
- *      unique_local of the stream session's result may be below unique_all */
+ *      unique_local of the stream session's result may be below unique_all
+ *      (still 4 with LTHIP_CODEC_BY_TAG, lthip_block_index_size and lthip_write_raw_block_images: a new enum VALUE behind the existing
+ *      ones and new entry points -- no struct changes, no value moves, no signature changes) */
 #define LTHIP_ABI_VERSION 4
 LTHIP_EXPORT int lthip_abi_version(void);
 
@@ -534,6 +536,23 @@ LTHIP_EXPORT int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block
                                                   const uint64_t* d_chunk_hashes, const uint32_t* d_chunk_lens,
                                                   uint32_t hash_identifier, uint32_t tag, const uint32_t* raw_sizes,
                                                   const uint32_t* d_comp_sizes, void* d_arena, const uint64_t* image_offsets);
+/* A block with tag 0 is stored RAW: the reference's CompressBlock passes it through (lib/compressblockstore/
+ * longtail_compressblockstore.c:85-90), so its file is the BlockIndex followed by the chunks' bytes, without the [raw][compressed] words.
+ * lthip_block_index_size(n) = lthip_stored_block_header_size(n) - 8 = 20 + 12 n: the bytes of the BlockIndex; a raw image is that many
+ * bytes followed by the raw size of the block's chunks.
+ * lthip_write_raw_block_images writes, for every block, the COMPLETE tag-0 image: BlockIndex (block hash of hash_identifier's type, tag 0)
+ * + the block's chunks copied from d_src + d_chunk_src_offsets[c] back to back -- byte for byte Longtail_CreateStoredBlock(.., tag 0, ..)
+ * + Longtail_WriteStoredBlockToBuffer.  Table conventions as lthip_write_stored_block_headers: block b holds the chunks
+ * [block_first_chunk[b], block_first_chunk[b+1]) of the device arrays (hashes, lengths, and here the byte offset of every chunk in
+ * d_src); image offsets 8-byte aligned; host arrays unless marked d_ (they may be freed on return).  Asynchronous on the context's
+ * stream.  Writes nothing outside [image_offsets[b], + lthip_block_index_size(n_b) + raw_b); reads no 4-byte word of d_src that holds
+ * no byte of a chunk (a chunk may end at the last byte of an allocation).  d_src and the arena must not overlap.  Timed as
+ * LTHIP_K_GATHER. */
+LTHIP_EXPORT size_t lthip_block_index_size(uint32_t chunk_count);
+LTHIP_EXPORT int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_count, const uint64_t* block_first_chunk /*host, [n+1]*/,
+                                              const uint64_t* d_chunk_hashes, const uint32_t* d_chunk_lens,
+                                              const uint64_t* d_chunk_src_offsets, const void* d_src, uint32_t hash_identifier,
+                                              void* d_arena, const uint64_t* image_offsets /*host*/);
 
 /* ---- bulk Longtail_CreateMissingContent (src/longtail.c:6882-6998 with DiffHashes :6620-6743 and
  * Longtail_CreateStoreIndex :6745-6880) -------------------------------------------------------------------------------
@@ -577,12 +596,29 @@ LTHIP_EXPORT int lthip_get_existing_store_index(lthip_ctx* ctx, const void* stor
  * lthip_ingest_index has returned (the session keeps its own copy of what it reads later: round 4; round 3 read the caller's arrays from
  * a helper thread until lthip_ingest_finish).  The DEVICE arrays (d_all_hashes, d_all_lens, d_local_*) and the VersionIndex buffer must
  * stay valid, and the buffer unread, until lthip_ingest_finish has returned: the index is serialized by a helper thread next to
- * lthip_ingest_write, and the packing into blocks is finished there too (the result's block count comes from lthip_ingest_finish). */
+ * lthip_ingest_write, and the packing into blocks is finished there too (the result's block count comes from lthip_ingest_finish).
+ * TAGS AND CODECS (both sessions).  Blocks are packed by tag and every index records the tags; cfg.codec says what is written:
+ *   LTHIP_CODEC_BY_TAG  every block's codec follows its own tag, as in the reference (compressblockstore.c:85-97):
+ *                         0                  a raw image: BlockIndex + the chunks' bytes (lthip_block_index_size)
+ *                         'lz42'             LZ4
+ *                         'ztd1' .. 'ztd5'   zstd at lthip_zstd_quality_of_settings(tag)
+ *                       Any other tag (the 'btl?' ids included) is ENOTSUP.
+ *   LTHIP_CODEC_NONE    all blocks are written raw.  Valid only when every tag is 0: cfg.compression_type == 0, and asset_tags NULL
+ *                       or all zero; EINVAL otherwise.
+ *   LTHIP_CODEC_LZ4 / LTHIP_CODEC_ZSTD   ONE codec for all blocks whatever their tags (zstd at the quality of cfg.compression_type):
+ *                       the caller vouches that every tag names that codec -- a reader picks the decoder by the tag.
+ * The refusals come before any work is queued and leave the context and the session usable.  cfg.compression_type -- the single tag
+ * when asset_tags == NULL -- is checked by lthip_ingest_create and lthip_ingest_stream_create (always: with asset tags it must still be
+ * a tag the mode takes, 0 will do); the asset tags by lthip_ingest_index and lthip_ingest_stream_create.
+ * A raw block counts its raw size in compressed_bytes and in lthip_ingest_compressed_sizes; its image is lthip_block_index_size(n) + raw
+ * bytes long.  Raw blocks are copied straight from where their chunks lie: they never go through the block assembly and count 0 in
+ * gathered_blocks / gathered_bytes. */
 enum lthip_codec
 {
     LTHIP_CODEC_NONE = 0,
     LTHIP_CODEC_LZ4 = 1,
-    LTHIP_CODEC_ZSTD = 2
+    LTHIP_CODEC_ZSTD = 2,
+    LTHIP_CODEC_BY_TAG = 3
 };
 typedef struct lthip_ingest lthip_ingest;
 typedef struct lthip_ingest_config
@@ -593,7 +629,7 @@ typedef struct lthip_ingest_config
                                       (chunk hashes from lthip_meow_ranges[_dev]); any other value hashes with BLAKE3 */
     uint32_t max_block_size;       /* cmd/main.c:3006-3009 defaults: 8 MiB */
     uint32_t max_chunks_per_block; /*                                 1024  */
-    uint32_t compression_type;     /* the tag stored with chunks and blocks: 'lz42', 'ztd1'..'ztd5' */
+    uint32_t compression_type;     /* the tag stored with chunks and blocks: 0 (raw), 'lz42', 'ztd1'..'ztd5' */
     uint32_t codec;                /* enum lthip_codec */
     uint64_t batch_bytes;          /* raw bytes per codec batch, 0 = 8 GiB */
 } lthip_ingest_config;
@@ -636,7 +672,8 @@ LTHIP_EXPORT int lthip_ingest_finish(lthip_ingest* ingest, void* h_store_index, 
                                      lthip_ingest_result* out_result);
 /* The stored-block images of the LAST codec batch of lthip_ingest_write (host tables owned by the session, valid after
  * lthip_ingest_finish until the next lthip_ingest_index): blocks *out_first_block .. + *out_count of the session; image i lies at
- * d_arena + offsets[i] and is sizes[i] bytes long -- BlockIndex, [raw size][compressed size], payload: exactly what
+ * d_arena + offsets[i] and is sizes[i] bytes long -- BlockIndex, [raw size][compressed size], payload (a raw block: BlockIndex, the
+ * chunks' bytes): exactly what
  * Longtail_WriteStoredBlockToBuffer produces and PutStoredBlock receives (src/longtail.c:4111-4150, 4722-4757).  A session whose
  * write fit ONE batch (raw bytes <= cfg.batch_bytes, and the arena) has all of its images there: the host-fed loop of INTEGRATION.md
  * (pinned slice -> H2D -> lthip_chunk_hash -> session -> images D2H) downloads them through this table. */
@@ -672,7 +709,8 @@ LTHIP_EXPORT int lthip_ingest_store_stats(const lthip_ingest* ingest, uint64_t* 
  * the slice call queues; the next slice's call assembles the block from those bytes plus its own chunks.
  *
  *   create   tree: the assets (sizes, paths, permissions, tags or NULL) and the job table (job_count, job_asset) of lthip_make_jobs,
- *            deep-copied; job_first is ignored; my_jobs must be NULL (single GPU), EINVAL otherwise.  cfg.codec: LZ4 or ZStd.
+ *            deep-copied; job_first is ignored; my_jobs must be NULL (single GPU), EINVAL otherwise.  cfg.codec: any enum lthip_codec, with the tag rules
+ *            of TAGS AND CODECS above (ENOTSUP / EINVAL for tags the codec mode does not take).
  *            No chunk may be larger than a block, L = max_block_size * 1.1 (the open block's buffer and the arena bound hold L):
  *            EINVAL when the chunker's largest chunk, max(48, 2 * target_chunk_size), exceeds L; a slice whose lists hold a larger
  *            chunk all the same (another chunker) fails with EINVAL.
@@ -693,7 +731,8 @@ LTHIP_EXPORT int lthip_ingest_store_stats(const lthip_ingest* ingest, uint64_t* 
  * again.  The tree's host arrays may be freed when create has returned.
  * THE ARENA.  lthip_ingest_stream_arena_bound is host arithmetic only: an arena of that many bytes holds the images of ANY slice of
  * slice_bytes bytes in slice_chunks chunks, the block carried in from the slice before included (an image slot is
- * round64(lthip_stored_block_header_size(n) + codec bound(raw)), as in lthip_ingest_write).  A slice call with fewer arena_bytes
+ * round64(lthip_stored_block_header_size(n) + codec bound(raw)), as in lthip_ingest_write; with LTHIP_CODEC_NONE a slot is
+ * round64(lthip_block_index_size(n) + raw), with LTHIP_CODEC_BY_TAG a slot is the largest of the three codecs' slots, so the bound is no less than any one codec's).  A slice call with fewer arena_bytes
  * returns ENOMEM before it touches the session; finish needs lthip_ingest_stream_arena_bound(cfg, 0, 0).
  * ERRORS.  Refused before any work, the session stays usable: a slice that does not start at the next expected job (EINVAL), a call
  * after finish (EINVAL), finish before the last job (EINVAL), an arena below the bound (ENOMEM).  Any failure after work has started

@@ -245,22 +245,17 @@ struct IngTrace
     }
 };
 
-static size_t codec_bound(const lthip_ingest* g, size_t n)
-{
-    if (g->cfg.codec == LTHIP_CODEC_LZ4)
-        return lthip_lz4_bound(n);
-    if (g->cfg.codec == LTHIP_CODEC_ZSTD)
-        return lthip_zstd_bound(n);
-    return n;
-}
-
 extern "C" int lthip_ingest_create(lthip_ctx* ctx, const lthip_ingest_config* cfg, lthip_ingest** out)
 {
     if (!ctx || !cfg || !out)
         return EINVAL;
     *out = nullptr;
-    if (cfg->max_block_size == 0 || cfg->max_chunks_per_block == 0 || cfg->codec > LTHIP_CODEC_ZSTD)
+    if (cfg->max_block_size == 0 || cfg->max_chunks_per_block == 0 || cfg->codec > LTHIP_CODEC_BY_TAG)
         return lthip_fail(ctx, EINVAL, "lthip_ingest_create", "bad block / codec parameters");
+    // (the tag of every block when lthip_ingest_index gets no asset tags; the asset tags are checked there)
+    if (const int refused = tag_refusal(cfg->codec, cfg->compression_type))
+        return lthip_fail(ctx, refused, "lthip_ingest_create",
+                          refused == EINVAL ? "LTHIP_CODEC_NONE writes tag 0 only" : "LTHIP_CODEC_BY_TAG: compression_type names no codec of this library");
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     lthip_ingest* g = new (std::nothrow) lthip_ingest();
     if (!g)
@@ -588,6 +583,11 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
         return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "chunk counts out of range");
     if (t->job_count && t->job_first[t->job_count] != all_chunks)
         return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "job_first[job_count] must be the number of chunks");
+    if (t->asset_tags) // (before any work is queued: the session stays as it is)
+        for (uint32_t a = 0; a < t->asset_count; ++a)
+            if (const int refused = tag_refusal(g->cfg.codec, t->asset_tags[a]))
+                return lthip_fail(ctx, refused, "lthip_ingest_index",
+                                  refused == EINVAL ? "LTHIP_CODEC_NONE writes tag 0 only" : "LTHIP_CODEC_BY_TAG: an asset tag names no codec of this library");
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     g->vi_pending = false;
     (void)ingest_vi_join(g); // (an index that was never finished: its helper reads what this call is about to replace ...
@@ -883,6 +883,8 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
         return EINVAL;
     IngTrace tr("lthip_ingest_write");
     lthip_ctx* ctx = g->ctx;
+    // (tag 0 means a raw image only where the session writes by tag; LTHIP_CODEC_LZ4 / _ZSTD compress a tag-0 block like any other)
+    const uint32_t raw_mode = g->cfg.codec == LTHIP_CODEC_NONE || g->cfg.codec == LTHIP_CODEC_BY_TAG ? 1u : 0u;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint32_t* lens = (const uint32_t*)g->h_mu_len.p;
@@ -894,7 +896,9 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
     g->img_sizes.clear();
     g->img_hdr.clear();
     std::vector<uint64_t> src_off, dst_off, img_off, g_src, g_dst, bfirst;
-    std::vector<uint32_t> src_size, dst_cap, g_len, braw;
+    std::vector<uint32_t> src_size, dst_cap, g_len, braw, r_first, r_count;
+    std::vector<uint64_t> r_payload;
+    std::vector<BlockCodec> bcodec, keys;
     // more blocks, when the batch being put together has taken all there are and chunks are left
     auto more_blocks = [&](size_t have) -> int {
         while (g->b_size.size() == have && g->pack_next < g->n_mine)
@@ -921,7 +925,8 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
         while ((err = more_blocks(b1)) == 0 && b1 < g->b_size.size())
         {
             const uint32_t nchunks = (uint32_t)(g->b_first[b1 + 1] - g->b_first[b1]);
-            const uint64_t need = ((uint64_t)lthip_stored_block_header_size(nchunks) + codec_bound(g, g->b_size[b1]) + 63u) & ~(uint64_t)63u;
+            const uint32_t codec = block_codec(g->cfg, g->b_tag[b1]).codec; // (the arena need of a block: its own codec's bound)
+            const uint64_t need = ((uint64_t)block_header_bytes(codec, nchunks) + block_codec_bound(codec, g->b_size[b1]) + 63u) & ~(uint64_t)63u;
             if (b1 > b0 && (arena + need > arena_bytes || bytes + g->b_size[b1] > g->cfg.batch_bytes))
                 break;
             if (arena + need > arena_bytes)
@@ -929,7 +934,7 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             img_off.push_back(arena);
             arena += need;
             bytes += g->b_size[b1];
-            if (!g->b_is_range[b1])
+            if (!g->b_is_range[b1] && codec != LTHIP_CODEC_NONE) // (a raw block is copied from where its chunks lie)
                 gather_chunks += nchunks;
             ++b1;
         }
@@ -937,6 +942,17 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             return err;
         tr.mark("batch");
         const size_t cnt = b1 - b0;
+        // every block's codec, and the distinct (codec, zstd quality) keys of the batch in the order they appear: a codec call takes
+        // blocks of one key from one place.  One codec for the session (LTHIP_CODEC_LZ4 / _ZSTD): one key, the two calls of before
+        bcodec.resize(cnt);
+        keys.clear();
+        for (size_t b = b0; b < b1; ++b)
+        {
+            bcodec[b - b0] = block_codec(g->cfg, g->b_tag[b]);
+            if (bcodec[b - b0].codec != LTHIP_CODEC_NONE && std::find(keys.begin(), keys.end(), bcodec[b - b0]) == keys.end())
+                keys.push_back(bcodec[b - b0]);
+        }
+        auto staged = [&](size_t b) { return !g->b_is_range[b] && bcodec[b - b0].codec != LTHIP_CODEC_NONE; };
         // ---- block assembly (WriteContentBlockJob, :4640-4721) only for blocks that are not one byte range of the data ----
         if (gather_chunks)
         {
@@ -948,7 +964,7 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             g_dst.clear();
             uint64_t pos = 0;
             for (size_t b = b0; b < b1; ++b)
-                if (!g->b_is_range[b])
+                if (staged(b))
                 {
                     pos = (pos + 15u) & ~(uint64_t)15u;
                     for (uint64_t c = g->b_first[b]; c < g->b_first[b + 1]; ++c)
@@ -969,9 +985,30 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
                                            (const uint64_t*)g->d_gdst.p)))
                 return err;
         }
-        // ---- compress straight to image + header size; the blocks in place first, then the assembled ones ----
-        for (int pass = 0; pass < 2; ++pass)
+        // ---- raw blocks: the chunks' bytes straight from the data into the image, behind the BlockIndex ----
+        r_first.clear();
+        r_count.clear();
+        r_payload.clear();
+        uint64_t raw_bytes = 0;
+        for (size_t b = b0; b < b1; ++b)
+            if (bcodec[b - b0].codec == LTHIP_CODEC_NONE)
+            {
+                const uint32_t nchunks = (uint32_t)(g->b_first[b + 1] - g->b_first[b]);
+                r_first.push_back((uint32_t)g->b_first[b]);
+                r_count.push_back(nchunks);
+                r_payload.push_back(img_off[b - b0] + lthip_block_index_size(nchunks));
+                raw_bytes += g->b_size[b];
+            }
+        if (!r_first.empty() &&
+            (err = lthip_raw_copy_blocks(ctx, (uint32_t)r_first.size(), r_first.data(), r_count.data(), r_payload.data(), (uint32_t)g->b_first[b0],
+                                         (uint32_t)(g->b_first[b1] - g->b_first[b0]), (const uint32_t*)g->d_mu_len.p, (const uint64_t*)g->d_mu_off.p,
+                                         d_data, d_arena, raw_bytes + 1)))
+            return err;
+        // ---- compress straight to image + header size: per (codec, quality) the blocks in place first, then the assembled ones ----
+        for (size_t call = 0; call < keys.size() * 2; ++call)
         {
+            const size_t key = call / 2;
+            const int pass = (int)(call % 2);
             src_off.clear();
             src_size.clear();
             dst_off.clear();
@@ -980,16 +1017,18 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             uint64_t pos = 0;
             for (size_t b = b0; b < b1; ++b)
             {
+                if (bcodec[b - b0].codec == LTHIP_CODEC_NONE)
+                    continue;
                 const bool range = g->b_is_range[b] != 0;
                 if (!range)
                     pos = (pos + 15u) & ~(uint64_t)15u;
-                if (range == (pass == 0))
+                if (range == (pass == 0) && bcodec[b - b0] == keys[key])
                 {
                     const uint32_t nchunks = (uint32_t)(g->b_first[b + 1] - g->b_first[b]);
                     src_off.push_back(range ? offs[g->b_first[b]] : pos);
                     src_size.push_back((uint32_t)g->b_size[b]);
                     dst_off.push_back(img_off[b - b0] + lthip_stored_block_header_size(nchunks));
-                    dst_cap.push_back((uint32_t)codec_bound(g, g->b_size[b]));
+                    dst_cap.push_back((uint32_t)block_codec_bound(keys[key].codec, g->b_size[b]));
                     which.push_back((uint32_t)b);
                 }
                 if (!range)
@@ -997,8 +1036,8 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             }
             if (src_off.empty())
                 continue;
-            // the codec entry points write one size per block of the call: the two passes are contiguous runs only when the
-            // batch is all-range or all-gathered, so sizes go through a per-call list and are scattered by `which`
+            // the codec entry points write one size per block of the call: a call's blocks are a contiguous run only when the
+            // batch is of one key and all-range or all-gathered, so sizes go through a per-call list and are scattered by `which`
             const void* src = pass == 0 ? d_data : g->d_gather.p;
             const uint32_t k = (uint32_t)src_off.size();
             bool contiguous = true;
@@ -1011,13 +1050,11 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
                     return err;
                 d_sizes = (uint32_t*)g->d_tmpsz.p;
             }
-            if (g->cfg.codec == LTHIP_CODEC_LZ4)
+            if (keys[key].codec == LTHIP_CODEC_LZ4)
                 err = lthip_lz4_compress_blocks(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes, 0);
-            else if (g->cfg.codec == LTHIP_CODEC_ZSTD)
-                err = lthip_zstd_compress_blocks_q(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes,
-                                                   lthip_zstd_quality_of_settings(g->cfg.compression_type)); // ('ztd4': high, 'ztd3' / 'ztd5': max)
             else
-                err = lthip_fail(ctx, EINVAL, "lthip_ingest_write", "codec 0 (store raw) is not implemented");
+                err = lthip_zstd_compress_blocks_q(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes,
+                                                   keys[key].quality);
             if (err)
                 return err;
             if (!contiguous)
@@ -1053,7 +1090,8 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
         if ((err = ingest_vi_start(g)) || (err = ingest_blocks_done(g)))
             return err;
         tr.mark("blocks");
-        // ---- BlockIndex + [raw][compressed] around the payloads (:4111-4150; compressblockstore.c:103-139) ----
+        // ---- BlockIndex + [raw][compressed] around the payloads (:4111-4150; compressblockstore.c:103-139); a raw block gets the BlockIndex
+        // alone, and its entry of d_comp is filled in with its raw size ----
         if ((err = reserve_dev(ctx, g->d_bfirst, (cnt + 1) * 4)) || (err = reserve_dev(ctx, g->d_braw, cnt * 4)) ||
             (err = reserve_dev(ctx, g->d_bimg, cnt * 8)) || (err = reserve_dev(ctx, g->d_btag, cnt * 4)))
             return err;
@@ -1079,14 +1117,14 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             hipLaunchKernelGGL(k_stored_block_headers, dim3((uint32_t)cnt), dim3(64), 0, s, (const uint32_t*)g->d_bfirst.p, (uint32_t)cnt,
                                (const uint64_t*)g->d_mu_hash.p, (const uint32_t*)g->d_mu_len.p, (const uint64_t*)g->d_bhash.p + b0,
                                g->cfg.hash_identifier, g->cfg.compression_type, d_tags, (const uint32_t*)g->d_braw.p,
-                               (const uint32_t*)g->d_comp.p + b0, (const uint64_t*)g->d_bimg.p, (uint8_t*)d_arena);
+                               (uint32_t*)g->d_comp.p + b0, (const uint64_t*)g->d_bimg.p, (uint8_t*)d_arena, raw_mode);
             LTHIP_LAUNCH_CHECK(ctx);
         }
         g->img_first = b0;
         g->img_offsets.assign(img_off.begin(), img_off.end());
         g->img_hdr.resize(cnt);
         for (size_t b = b0; b < b1; ++b)
-            g->img_hdr[b - b0] = (uint32_t)lthip_stored_block_header_size((uint32_t)(g->b_first[b + 1] - g->b_first[b]));
+            g->img_hdr[b - b0] = (uint32_t)block_header_bytes(bcodec[b - b0].codec, (uint32_t)(g->b_first[b + 1] - g->b_first[b]));
         g->img_sizes = g->img_hdr; // (headers only until lthip_ingest_finish knows the payload sizes)
         b0 = b1;
     }

@@ -67,6 +67,7 @@ struct lthip_ingest_stream
     // ---- per call ----
     HBuf h_first, h_off, h_pf, h_known;
     DBuf d_known;
+    DBuf d_usrc; // raw blocks: the address of every chunk of the call (d_carry or the slice's data)
     DBuf d_first, d_gather, d_gsrc, d_glen, d_gdst, d_uh, d_ul, d_boff, d_blen, d_bhash, d_comp, d_tmpsz, d_bfirst, d_braw, d_bimg, d_btag;
     DBuf d_vh, d_vl; // finish: the kept lists on the device
     std::vector<uint64_t> u_src; // byte offset in the slice's data of the chunks this slice added to the unique list
@@ -90,15 +91,13 @@ namespace
 
 typedef lthip_ingest_stream Stream;
 
-size_t stream_codec_bound(uint32_t codec, size_t n) { return codec == LTHIP_CODEC_ZSTD ? lthip_zstd_bound(n) : lthip_lz4_bound(n); }
-
 uint64_t block_limit(const lthip_ingest_config* cfg) { return (uint64_t)cfg->max_block_size + cfg->max_block_size / 10; }
 
 bool config_ok(const lthip_ingest_config* cfg)
 {
     // (a block is one codec call's source: below the codecs' 2^31 - 2^25 bytes)
     return cfg && cfg->max_block_size != 0 && cfg->max_block_size <= 0x70000000u && cfg->max_chunks_per_block != 0 &&
-           (cfg->codec == LTHIP_CODEC_LZ4 || cfg->codec == LTHIP_CODEC_ZSTD);
+           cfg->codec <= LTHIP_CODEC_BY_TAG;
 }
 
 int stream_fail(Stream* s, int err)
@@ -197,7 +196,8 @@ int stream_gather(Stream* s, const void* d_src, const Ranges& r, void* d_dst)
 
 // The images of blocks [b0, b1) into the arena: assembly, codec, block hashes, BlockIndex + [raw][compressed] around the payloads
 // (:4111-4150; compressblockstore.c:103-139).  Chunks below `fresh` (an index into the unique list) lie in d_carry at carry_off, the others
-// in d_data at u_src.
+// in d_data at u_src.  A block's codec follows cfg.codec and its tag (block_codec): a raw block is copied from where its chunks lie, the
+// others are compressed with one call per (codec, quality, place).
 int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fresh, void* d_arena, uint64_t arena_bytes)
 {
     lthip_ctx* ctx = s->ctx;
@@ -211,17 +211,35 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
         return 0;
     const uint64_t c0 = s->b_first[b0], c1 = s->b_first[b1], nc = c1 - c0, open0 = fresh - s->carry_off.size();
     int err;
-    // ---- where the images go, and where every block's bytes are: 0 in d_data, 1 to be gathered, 2 in d_carry ----
+    // ---- where the images go, and where every block's bytes are: 0 in d_data, 1 to be gathered, 2 in d_carry; 3: a raw block, copied
+    // chunk run by chunk run from wherever they are ----
     std::vector<uint64_t> img_off(cnt), gpos(cnt, 0);
     std::vector<uint8_t> kind(cnt);
+    std::vector<BlockCodec> bcodec(cnt), keys;
+    std::vector<uint32_t> r_first, r_count;
+    std::vector<uint64_t> r_payload;
+    uint64_t raw_bytes = 0;
     Ranges from_carry, from_data;
     uint64_t arena = 0, pos = 0;
     for (size_t b = b0; b < b1; ++b)
     {
         const uint64_t first = s->b_first[b], last = s->b_first[b + 1];
-        const uint64_t need = ((uint64_t)lthip_stored_block_header_size((uint32_t)(last - first)) + stream_codec_bound(s->cfg.codec, s->b_size[b]) + 63u) & ~(uint64_t)63u;
+        const BlockCodec bc = block_codec(s->cfg, s->b_tag[b]);
+        bcodec[b - b0] = bc;
+        const uint64_t need = ((uint64_t)block_header_bytes(bc.codec, (uint32_t)(last - first)) + block_codec_bound(bc.codec, s->b_size[b]) + 63u) & ~(uint64_t)63u;
         img_off[b - b0] = arena;
         arena += need;
+        if (bc.codec == LTHIP_CODEC_NONE)
+        {
+            kind[b - b0] = 3;
+            r_first.push_back((uint32_t)(first - c0));
+            r_count.push_back((uint32_t)(last - first));
+            r_payload.push_back(img_off[b - b0] + lthip_block_index_size((uint32_t)(last - first)));
+            raw_bytes += s->b_size[b];
+            continue;
+        }
+        if (std::find(keys.begin(), keys.end(), bc) == keys.end())
+            keys.push_back(bc);
         uint8_t k = 1;
         if (last <= fresh)
             k = 2; // (carried chunks lie back to back)
@@ -263,24 +281,41 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
             (err = stream_gather(s, d_data, from_data, s->d_gather.p)))
             return err;
     }
-    // ---- the codec, straight to image + header size: a call per place the sources lie in ----
+    // ---- the chunk lengths of the call's blocks (the raw copy and the BlockIndex kernel read them) ----
+    if ((err = lthip_stage_upload(ctx, s->d_ul.p, s->u_len.data() + c0, nc * 4, st)))
+        return err;
+    // ---- raw blocks: straight from d_carry / the slice's data into the image, behind the BlockIndex ----
+    if (!r_first.empty())
+    {
+        std::vector<uint64_t> addr(nc, 0); // (the two places are two allocations: the copy takes addresses, relative to a null base)
+        for (size_t i = 0; i < r_first.size(); ++i)
+            for (uint64_t c = c0 + r_first[i]; c < c0 + r_first[i] + r_count[i]; ++c)
+                addr[c - c0] = c < fresh ? (uint64_t)(uintptr_t)s->d_carry.p + s->carry_off[c - open0] : (uint64_t)(uintptr_t)d_data + s->u_src[c - fresh];
+        if ((err = reserve_dev(ctx, s->d_usrc, nc * 8)) || (err = lthip_stage_upload(ctx, s->d_usrc.p, addr.data(), nc * 8, st)) ||
+            (err = lthip_raw_copy_blocks(ctx, (uint32_t)r_first.size(), r_first.data(), r_count.data(), r_payload.data(), 0u, (uint32_t)nc,
+                                         (const uint32_t*)s->d_ul.p, (const uint64_t*)s->d_usrc.p, nullptr, d_arena, raw_bytes + 1)))
+            return err;
+    }
+    // ---- the codec, straight to image + header size: a call per (codec, quality) and place the sources lie in ----
     std::vector<uint64_t> src_off, dst_off;
     std::vector<uint32_t> src_size, dst_cap, which;
-    for (uint8_t pass = 0; pass < 3; ++pass)
+    for (size_t call = 0; call < keys.size() * 3; ++call)
     {
+        const size_t key = call / 3;
+        const uint8_t pass = (uint8_t)(call % 3);
         src_off.clear();
         src_size.clear();
         dst_off.clear();
         dst_cap.clear();
         which.clear();
         for (size_t b = b0; b < b1; ++b)
-            if (kind[b - b0] == pass)
+            if (kind[b - b0] == pass && bcodec[b - b0] == keys[key])
             {
                 const uint64_t first = s->b_first[b];
                 src_off.push_back(pass == 0 ? s->u_src[first - fresh] : pass == 1 ? gpos[b - b0] : s->carry_off[first - open0]);
                 src_size.push_back((uint32_t)s->b_size[b]);
                 dst_off.push_back(img_off[b - b0] + lthip_stored_block_header_size((uint32_t)(s->b_first[b + 1] - first)));
-                dst_cap.push_back((uint32_t)stream_codec_bound(s->cfg.codec, s->b_size[b]));
+                dst_cap.push_back((uint32_t)block_codec_bound(keys[key].codec, s->b_size[b]));
                 which.push_back((uint32_t)(b - b0));
             }
         if (src_off.empty())
@@ -299,11 +334,11 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
                 return err;
             d_sizes = (uint32_t*)s->d_tmpsz.p;
         }
-        if (s->cfg.codec == LTHIP_CODEC_LZ4)
+        if (keys[key].codec == LTHIP_CODEC_LZ4)
             err = lthip_lz4_compress_blocks(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes, 0);
         else
             err = lthip_zstd_compress_blocks_q(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes,
-                                               lthip_zstd_quality_of_settings(s->cfg.compression_type));
+                                               keys[key].quality);
         if (err)
             return err;
         if (!contiguous)
@@ -336,7 +371,6 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
     }
     first32[cnt] = (uint32_t)nc;
     if ((err = lthip_stage_upload(ctx, s->d_uh.p, s->u_hash.data() + c0, nc * 8, st)) ||
-        (err = lthip_stage_upload(ctx, s->d_ul.p, s->u_len.data() + c0, nc * 4, st)) ||
         (err = lthip_stage_upload(ctx, s->d_boff.p, boff.data(), cnt * 8, st)) || (err = lthip_stage_upload(ctx, s->d_blen.p, blen.data(), cnt * 4, st)) ||
         (err = lthip_stage_upload(ctx, s->d_bfirst.p, first32.data(), (cnt + 1) * 4, st)) ||
         (err = lthip_stage_upload(ctx, s->d_braw.p, braw.data(), cnt * 4, st)) || (err = lthip_stage_upload(ctx, s->d_bimg.p, img_off.data(), cnt * 8, st)) ||
@@ -349,8 +383,10 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_stored_block_headers, dim3((uint32_t)cnt), dim3(64), 0, st, (const uint32_t*)s->d_bfirst.p, (uint32_t)cnt,
                            (const uint64_t*)s->d_uh.p, (const uint32_t*)s->d_ul.p, (const uint64_t*)s->d_bhash.p, s->cfg.hash_identifier,
-                           s->cfg.compression_type, (const uint32_t*)s->d_btag.p, (const uint32_t*)s->d_braw.p, (const uint32_t*)s->d_comp.p,
-                           (const uint64_t*)s->d_bimg.p, (uint8_t*)d_arena);
+                           s->cfg.compression_type, (const uint32_t*)s->d_btag.p, (const uint32_t*)s->d_braw.p, (uint32_t*)s->d_comp.p,
+                           (const uint64_t*)s->d_bimg.p, (uint8_t*)d_arena,
+                           // (tag 0 means a raw image only where the session writes by tag: its entry of d_comp receives its raw size)
+                           s->cfg.codec == LTHIP_CODEC_NONE || s->cfg.codec == LTHIP_CODEC_BY_TAG ? 1u : 0u);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     // ---- block hashes and compressed sizes on their way to the host ----
@@ -379,7 +415,7 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
     s->img_offsets = img_off;
     s->img_hdr.resize(cnt);
     for (size_t b = b0; b < b1; ++b)
-        s->img_hdr[b - b0] = (uint32_t)lthip_stored_block_header_size((uint32_t)(s->b_first[b + 1] - s->b_first[b]));
+        s->img_hdr[b - b0] = (uint32_t)block_header_bytes(bcodec[b - b0].codec, (uint32_t)(s->b_first[b + 1] - s->b_first[b]));
     s->img_sizes = s->img_hdr; // (headers only until the compressed sizes are collected)
     return 0;
 }
@@ -531,10 +567,22 @@ extern "C" size_t lthip_ingest_stream_arena_bound(const lthip_ingest_config* cfg
     // block carried in).  With bound(a) + bound(b) <= bound(a + b) + bound(0) for both codecs -- their bounds are n + floor(n / k) + c(n),
     // c(n) <= c(0) -- and at most N blocks of sum(n_b) <= N chunks:
     //   sum round64(header(n_b) + bound(raw_b)) <= bound(R) + N * (header(0) + bound(0) + 63) + 12 * N
+    // LTHIP_CODEC_NONE: a slot is round64(lthip_block_index_size(n_b) + raw_b), the same sum with bound(n) = n and the BlockIndex for the
+    // header.  LTHIP_CODEC_BY_TAG: a block takes one of the three, so a slot is at most the largest of the three,
+    // round64(header(n_b) + m(raw_b)) with m(n) = n + floor(n / 255) + 64 >= each codec's bound (zstd's is n + (n >> 8) + at most 64, LZ4's
+    // n + floor(n / 255) + 16), and m(a) + m(b) <= m(a + b) + m(0) again: the same sum with m for the bound.  That is no less than the
+    // bound of any one codec.
     const uint64_t R = slice_bytes + block_limit(cfg), N = slice_chunks + cfg->max_chunks_per_block;
-    const size_t per_chunk = lthip_stored_block_header_size(1) + stream_codec_bound(cfg->codec, 0) + 63u;
-    const size_t whole = cfg->codec == LTHIP_CODEC_ZSTD ? lthip_zstd_bound((size_t)R) : (size_t)(R + R / 255 + 16); // (lthip_lz4_bound stops at 2^31)
-    return whole + (size_t)N * per_chunk;
+    auto of = [&](uint32_t codec) -> size_t {
+        const size_t per_chunk = block_header_bytes(codec, 1) + block_codec_bound(codec, 0) + 63u;
+        const size_t whole = codec == LTHIP_CODEC_ZSTD   ? lthip_zstd_bound((size_t)R)
+                             : codec == LTHIP_CODEC_LZ4  ? (size_t)(R + R / 255 + 16) // (lthip_lz4_bound stops at 2^31)
+                                                         : (size_t)R;
+        return whole + (size_t)N * per_chunk;
+    };
+    if (cfg->codec != LTHIP_CODEC_BY_TAG)
+        return of(cfg->codec);
+    return (size_t)(R + R / 255 + 64) + (size_t)N * (lthip_stored_block_header_size(1) + 64u + 63u);
 }
 
 extern "C" void lthip_ingest_stream_destroy(lthip_ingest_stream* s)
@@ -545,7 +593,7 @@ extern "C" void lthip_ingest_stream_destroy(lthip_ingest_stream* s)
     (void)hipStreamSynchronize(s->ctx->stream);
     lthip_seen_destroy(s->seen);
     DBuf* dev[] = {&s->d_carry, &s->d_first, &s->d_gather, &s->d_gsrc, &s->d_glen, &s->d_gdst, &s->d_uh, &s->d_ul, &s->d_boff, &s->d_blen, &s->d_bhash,
-                   &s->d_comp, &s->d_tmpsz, &s->d_bfirst, &s->d_braw, &s->d_bimg, &s->d_btag, &s->d_vh, &s->d_vl, &s->d_known};
+                   &s->d_comp, &s->d_tmpsz, &s->d_bfirst, &s->d_braw, &s->d_bimg, &s->d_btag, &s->d_vh, &s->d_vl, &s->d_known, &s->d_usrc};
     for (DBuf* b : dev)
         if (b->p)
             (void)hipFree(b->p);
@@ -584,6 +632,12 @@ extern "C" int lthip_ingest_stream_create(lthip_ctx* ctx, const lthip_ingest_con
         return lthip_fail(ctx, EINVAL, "lthip_ingest_stream_create", "2 * target_chunk_size must not exceed max_block_size * 1.1");
     if ((t->job_count && !t->job_asset) || (t->asset_count && (!t->asset_sizes || !t->path_start_offsets || !t->permissions || !t->path_data)))
         return EINVAL;
+    // every tag the tree carries must be one the codec mode writes (include/longtail_hip.h, TAGS AND CODECS)
+    // (cfg.compression_type too, as lthip_ingest_create checks it: it is the tag of every asset when there are no asset tags)
+    for (uint32_t a = 0; a < (t->asset_tags ? t->asset_count + 1u : 1u); ++a)
+        if (const int refused = tag_refusal(cfg->codec, a ? t->asset_tags[a - 1] : cfg->compression_type))
+            return lthip_fail(ctx, refused, "lthip_ingest_stream_create",
+                              refused == EINVAL ? "LTHIP_CODEC_NONE writes tag 0 only" : "LTHIP_CODEC_BY_TAG: a tag names no codec of this library");
     // the jobs of lthip_make_jobs: asset after asset, 1 + size / part jobs each (src/longtail.c:2399-2404, 2432-2457)
     const uint32_t na = t->asset_count;
     const uint64_t part = (uint64_t)cfg->target_chunk_size * 1024u;

@@ -4,6 +4,10 @@
 // v_alignbit.  Only needed when a block is not already one contiguous range of the asset buffer (dedup holes,
 // assets whose sizes are not multiples of 16).
 #include "lthip_internal.h"
+#include "index_kernels.h"
+
+#include <algorithm>
+#include <vector>
 
 namespace
 {
@@ -95,6 +99,188 @@ __global__ void k_job_ordinals(const uint32_t* __restrict__ part_first, uint32_t
     out[k] = job_gfirst[lo] + (k - part_first[lo]);
 }
 
+// ---- raw block images: the payload of a block with tag 0 is its chunks' bytes as they are (CompressBlock, compressblockstore.c:85-90) ----
+// A pure copy of N bytes to where the images lie: the payload starts 20 + 12 n bytes into an 8-aligned image, the chunks follow each other
+// at any byte position.  The unit of work is a bounded PIECE of a RUN -- a maximal stretch of a block's chunks that is contiguous in the
+// source (a block that is one byte range of the data is one run) -- and a unit belongs to a wave, so a run of 48 bytes costs a wave
+// a few instructions and not a workgroup, and an 8 MiB run spreads over 256 waves.
+//
+//   k_raw_runs   a wave per block walks its chunk list 64 chunks at a time: destination of every chunk (prefix sum of the lengths), run
+//                starts (a chunk that does not continue the one before), and per run {source, destination, length} in the slot of its
+//                first chunk; every other slot of the block gets 0 pieces
+//   scan         pieces of the slots -> first piece of every slot (lthip_exclusive_scan_u32)
+//   k_raw_copy   a fixed grid of waves strides over the pieces; a piece finds its slot by bisection of the scan (scalar loads)
+constexpr uint32_t RAW_PIECE_VEC = 2048; // 16-byte vectors of a piece: 32 KiB, eight rounds of four requests per lane
+
+__device__ __forceinline__ uint32_t raw_pieces(uint64_t dst, uint64_t len)
+{
+    if (len == 0)
+        return 0u;
+    uint64_t head = (16u - (dst & 15u)) & 15u;
+    if (head > len)
+        head = len;
+    const uint64_t nvec = (len - head) >> 4;
+    return nvec ? (uint32_t)((nvec + RAW_PIECE_VEC - 1) / RAW_PIECE_VEC) : 1u;
+}
+
+__global__ __launch_bounds__(64) void k_raw_runs(const uint64_t* __restrict__ blk_payload, const uint32_t* __restrict__ blk_first,
+                                                 const uint32_t* __restrict__ blk_count, uint32_t nblocks, uint32_t chunk_base,
+                                                 const uint32_t* __restrict__ lens, const uint64_t* __restrict__ src_offsets,
+                                                 uint64_t* __restrict__ run_src, uint64_t* __restrict__ run_dst, uint64_t* __restrict__ run_len,
+                                                 uint32_t* __restrict__ pieces)
+{
+    const uint32_t b = blockIdx.x;
+    if (b >= nblocks)
+        return;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t c0 = blk_first[b], n = blk_count[b];
+    uint64_t pos = blk_payload[b]; // destination of the group's first chunk
+    uint64_t prev_end = 0;          // source end of the chunk before the group
+    bool open = false;              // a run that began in an earlier group and has not ended
+    uint32_t open_slot = 0;
+    uint64_t open_dst = 0;
+    for (uint32_t g = 0; g < n; g += 64)
+    {
+        const uint32_t i = g + lane;
+        const bool valid = i < n;
+        const uint32_t len = valid ? lens[c0 + i] : 0u;
+        const uint64_t so = valid ? src_offsets[c0 + i] : 0ull;
+        uint64_t incl = len; // inclusive prefix sum over the wave
+        for (int o = 1; o < 64; o <<= 1)
+        {
+            const uint64_t up = __shfl_up(incl, o, 64);
+            if ((int)lane >= o)
+                incl += up;
+        }
+        const uint64_t dst = pos + incl - len, end = so + len;
+        uint64_t before = __shfl_up(end, 1, 64);
+        if (lane == 0)
+            before = prev_end;
+        const bool start = valid && (i == 0 || so != before);
+        const uint64_t mask = __ballot(start);
+        // every start finds the next one in the group: that is where its run ends; the last start of the group stays open
+        const uint64_t above = lane < 63 ? mask & ~((2ull << lane) - 1ull) : 0ull;
+        const uint32_t next = start && above ? (uint32_t)__ffsll((unsigned long long)above) - 1u : lane;
+        const uint64_t next_dst = __shfl(dst, (int)next, 64);
+        if (mask)
+        {
+            const uint32_t f = (uint32_t)__ffsll((unsigned long long)mask) - 1u, l = 63u - (uint32_t)__clzll((long long)mask);
+            const uint64_t first_dst = __shfl(dst, (int)f, 64), last_dst = __shfl(dst, (int)l, 64);
+            if (open && lane == 0) // the run carried in ends at the group's first start
+            {
+                run_len[open_slot] = first_dst - open_dst;
+                pieces[open_slot] = raw_pieces(open_dst, first_dst - open_dst);
+            }
+            open = true;
+            open_slot = c0 + g + l - chunk_base;
+            open_dst = last_dst;
+        }
+        if (valid)
+        {
+            const uint32_t slot = c0 + i - chunk_base;
+            uint32_t np = 0;
+            if (start)
+            {
+                run_src[slot] = so;
+                run_dst[slot] = dst;
+                if (above)
+                {
+                    run_len[slot] = next_dst - dst;
+                    np = raw_pieces(dst, next_dst - dst);
+                }
+            }
+            if (!start || above) // (the open run's slot is written when it ends)
+                pieces[slot] = np;
+        }
+        const uint32_t last_valid = n - g < 64u ? n - g - 1u : 63u;
+        pos += __shfl(incl, 63, 64);
+        prev_end = __shfl(end, (int)last_valid, 64);
+    }
+    if (open && lane == 0)
+    {
+        run_len[open_slot] = pos - open_dst;
+        pieces[open_slot] = raw_pieces(open_dst, pos - open_dst);
+    }
+}
+
+// four dwords at a 4-byte aligned address (and the fifth, when the source is not: it holds the last bytes of the vector) -> 16 bytes of
+// the source.  No dword is touched that holds no byte of the vector.
+struct RawVec
+{
+    u32x4_a4 a;
+    uint32_t e;
+};
+__device__ __forceinline__ RawVec raw_load(const uint32_t* __restrict__ q, uint32_t mis)
+{
+    RawVec r;
+    r.a = *reinterpret_cast<const u32x4_a4*>(q);
+    r.e = mis ? q[4] : 0u;
+    return r;
+}
+__device__ __forceinline__ uint4 raw_align(const RawVec& r, uint32_t sh)
+{
+    uint4 o;
+    o.x = __builtin_amdgcn_alignbit(r.a.y, r.a.x, sh);
+    o.y = __builtin_amdgcn_alignbit(r.a.z, r.a.y, sh);
+    o.z = __builtin_amdgcn_alignbit(r.a.w, r.a.z, sh);
+    o.w = __builtin_amdgcn_alignbit(r.e, r.a.w, sh);
+    return o;
+}
+
+__global__ __launch_bounds__(GT) void k_raw_copy(const uint32_t* __restrict__ first_piece /* [slots + 1] */, uint32_t slots,
+                                                 const uint64_t* __restrict__ run_src, const uint64_t* __restrict__ run_dst,
+                                                 const uint64_t* __restrict__ run_len, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t waves = gridDim.x * (GT / 64u);
+    const uint32_t total = first_piece[slots];
+    for (uint32_t u = blockIdx.x * (GT / 64u) + wave; u < total; u += waves)
+    {
+        uint32_t lo = 0, hi = slots; // first_piece[lo] <= u < first_piece[hi]: the slot that owns piece u (empty slots: the last such)
+        while (hi - lo > 1)
+        {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (first_piece[mid] <= u)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint32_t p = u - first_piece[lo], np = first_piece[lo + 1] - first_piece[lo];
+        const uint8_t* s = src + run_src[lo];
+        uint8_t* d = dst + run_dst[lo];
+        uint64_t n = run_len[lo];
+        uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
+        if (head > n)
+            head = (uint32_t)n;
+        if (p == 0 && lane < head)
+            d[lane] = s[lane];
+        d += head;
+        s += head;
+        n -= head;
+        const uint64_t nvec = n >> 4;
+        const uint32_t tail = (uint32_t)(n & 15u);
+        if (p == np - 1 && lane < tail)
+            d[(nvec << 4) + lane] = s[(nvec << 4) + lane];
+        // the piece's share of the run's vectors: equal parts
+        const uint64_t v0 = nvec * p / np, v1 = nvec * (p + 1u) / np;
+        const uint32_t mis = (uint32_t)((uintptr_t)s & 3u), sh = mis * 8u;
+        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s - mis);
+        uint64_t v = v0 + lane;
+        for (; v + 192u < v1; v += 256u) // four 16-byte requests of every lane in flight (1 KiB per wave and request)
+        {
+            const RawVec a = raw_load(s4 + v * 4u, mis), b = raw_load(s4 + (v + 64u) * 4u, mis), c = raw_load(s4 + (v + 128u) * 4u, mis),
+                         e = raw_load(s4 + (v + 192u) * 4u, mis);
+            *reinterpret_cast<uint4*>(d + v * 16u) = raw_align(a, sh);
+            *reinterpret_cast<uint4*>(d + (v + 64u) * 16u) = raw_align(b, sh);
+            *reinterpret_cast<uint4*>(d + (v + 128u) * 16u) = raw_align(c, sh);
+            *reinterpret_cast<uint4*>(d + (v + 192u) * 16u) = raw_align(e, sh);
+        }
+        for (; v < v1; v += 64u)
+            *reinterpret_cast<uint4*>(d + v * 16u) = raw_align(raw_load(s4 + v * 4u, mis), sh);
+    }
+}
+
 // element ranges -> byte ranges of k_gather_ranges
 __global__ void k_scale_ranges(const uint64_t* __restrict__ src, const uint64_t* __restrict__ dst, const uint32_t* __restrict__ cnt,
                                uint64_t count, uint32_t elem_bytes, uint64_t* __restrict__ src_b, uint64_t* __restrict__ dst_b,
@@ -147,6 +333,114 @@ extern "C" int lthip_exchange_reorder(lthip_ctx* ctx, const void* d_gathered, vo
                        d_src_b, d_dst_b, d_len_b);
     hipLaunchKernelGGL(k_gather_ranges, dim3((uint32_t)n), dim3(GT), 0, s, (const uint8_t*)d_gathered, d_src_b, d_len_b, d_dst_b,
                        (uint64_t)n, (uint8_t*)d_out);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int lthip_raw_copy_blocks(lthip_ctx* ctx, uint32_t count, const uint32_t* h_first, const uint32_t* h_count, const uint64_t* h_payload,
+                          uint32_t chunk_base, uint32_t chunk_span, const uint32_t* d_lens, const uint64_t* d_src_offsets, const void* d_src,
+                          void* d_arena, uint64_t bytes_bound)
+{
+    if (count == 0 || chunk_span == 0)
+        return 0;
+    hipStream_t s = ctx->stream;
+    // block tables: [count u64 payload][count u32 first][count u32 chunks], one upload
+    const size_t k = count, span = chunk_span, span2 = (span + 2) & ~(size_t)1;
+    std::vector<uint64_t> tab(k * 2);
+    memcpy(tab.data(), h_payload, k * 8);
+    memcpy((uint32_t*)(tab.data() + k), h_first, k * 4);
+    memcpy((uint32_t*)(tab.data() + k) + k, h_count, k * 4);
+    void *blocks = nullptr, *runs = nullptr;
+    int err;
+    if ((err = lthip_scratch(ctx, S_RAW_BLOCKS, k * 16, &blocks)) || (err = lthip_scratch(ctx, S_RAW_RUNS, span2 * 32, &runs)) ||
+        (err = lthip_stage_upload(ctx, blocks, tab.data(), k * 16, s)))
+        return err;
+    const uint64_t* d_payload = (const uint64_t*)blocks;
+    const uint32_t* d_first = (const uint32_t*)(d_payload + k);
+    const uint32_t* d_count = d_first + k;
+    uint64_t* run_src = (uint64_t*)runs; // one slot per chunk of the span
+    uint64_t* run_dst = run_src + span2;
+    uint64_t* run_len = run_dst + span2;
+    uint32_t* pieces = (uint32_t*)(run_len + span2);
+    uint32_t* first_piece = pieces + span2; // [span + 1]
+    LTHIP_CHECK(ctx, hipMemsetAsync(pieces, 0, span * 4, s)); // (chunks of the span that are in none of these blocks)
+    {
+        LaunchTimer t(ctx, LTHIP_K_GATHER);
+        hipLaunchKernelGGL(k_raw_runs, dim3(count), dim3(64), 0, s, d_payload, d_first, d_count, count, chunk_base, d_lens, d_src_offsets,
+                           run_src, run_dst, run_len, pieces);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    if ((err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, span, nullptr, LTHIP_K_GATHER)))
+        return err;
+    // a fixed grid strides over the pieces (their number is on the device): eight workgroups per CU at most, fewer when the bytes are few
+    uint64_t grid = 2048;
+    if (bytes_bound)
+        grid = std::min<uint64_t>(grid, div_up_u64(bytes_bound / (RAW_PIECE_VEC * 16u) + span + k, GT / 64u));
+    LaunchTimer t(ctx, LTHIP_K_GATHER);
+    hipLaunchKernelGGL(k_raw_copy, dim3((uint32_t)grid), dim3(GT), 0, s, (const uint32_t*)first_piece, chunk_span, (const uint64_t*)run_src,
+                       (const uint64_t*)run_dst, (const uint64_t*)run_len, (const uint8_t*)d_src, (uint8_t*)d_arena);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_count, const uint64_t* block_first_chunk, const uint64_t* d_chunk_hashes,
+                                            const uint32_t* d_chunk_lens, const uint64_t* d_chunk_src_offsets, const void* d_src,
+                                            uint32_t hash_identifier, void* d_arena, const uint64_t* image_offsets)
+{
+    if (!ctx || (block_count && (!block_first_chunk || !d_chunk_hashes || !d_chunk_lens || !d_chunk_src_offsets || !d_src || !d_arena || !image_offsets)))
+        return EINVAL;
+    if (block_count == 0)
+        return 0;
+    const size_t nb = block_count;
+    std::vector<uint32_t> first(nb + 1), hlen(nb), cnt(nb);
+    std::vector<uint64_t> hoff(nb), payload(nb);
+    uint32_t max_len = 0;
+    uint64_t leaves = 0;
+    for (size_t b = 0; b <= nb; ++b)
+    {
+        if (block_first_chunk[b] > 0x7FFFFFF0ull || (b && block_first_chunk[b] < block_first_chunk[b - 1]))
+            return lthip_fail(ctx, EINVAL, "raw block images", "block_first_chunk must be non-decreasing and below 2^31");
+        first[b] = (uint32_t)block_first_chunk[b];
+    }
+    for (size_t b = 0; b < nb; ++b)
+    {
+        if (image_offsets[b] & 7u)
+            return lthip_fail(ctx, EINVAL, "raw block images", "image offsets must be 8-byte aligned");
+        cnt[b] = first[b + 1] - first[b];
+        if ((uint64_t)cnt[b] * 8u > 0xFFFFFFFFull)
+            return lthip_fail(ctx, EINVAL, "raw block images", "a block of more than 2^29 chunks");
+        hoff[b] = (uint64_t)first[b] * 8u;
+        hlen[b] = cnt[b] * 8u;
+        max_len = std::max(max_len, hlen[b]);
+        leaves += hlen[b] ? (hlen[b] + 1023u) >> 10 : 1u;
+        payload[b] = image_offsets[b] + lthip_block_index_size(cnt[b]);
+    }
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // ---- the payloads first: the copy is the long part, the BlockIndex kernel runs behind it ----
+    int err;
+    if ((err = lthip_raw_copy_blocks(ctx, block_count, first.data(), cnt.data(), payload.data(), first[0], first[nb] - first[0], d_chunk_lens,
+                                     d_chunk_src_offsets, d_src, d_arena, 0)))
+        return err;
+    // ---- block hashes = hash of each block's chunk-hash array (:3753-3757), then the BlockIndex in front of every payload ----
+    const size_t nb2 = (nb + 2) & ~(size_t)1;
+    void* tabs = nullptr;
+    if ((err = lthip_scratch(ctx, S_RAW_TABLES, nb2 * 32, &tabs)))
+        return err;
+    uint64_t* d_off = (uint64_t*)tabs;
+    uint64_t* d_img = d_off + nb2;
+    uint64_t* d_bh = d_img + nb2;
+    uint32_t* d_len = (uint32_t*)(d_bh + nb2);
+    uint32_t* d_firstc = d_len + nb2; // [nb + 1]
+    if ((err = lthip_stage_upload(ctx, d_off, hoff.data(), nb * 8, s)) || (err = lthip_stage_upload(ctx, d_img, image_offsets, nb * 8, s)) ||
+        (err = lthip_stage_upload(ctx, d_len, hlen.data(), nb * 4, s)) || (err = lthip_stage_upload(ctx, d_firstc, first.data(), (nb + 1) * 4, s)))
+        return err;
+    if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes, nb, d_off, d_len, max_len, leaves, d_bh)))
+        return err;
+    LaunchTimer t(ctx, LTHIP_K_GATHER);
+    hipLaunchKernelGGL(k_stored_block_headers, dim3(block_count), dim3(64), 0, s, (const uint32_t*)d_firstc, block_count, d_chunk_hashes,
+                       d_chunk_lens, (const uint64_t*)d_bh, hash_identifier, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+                       (uint32_t*)nullptr, (const uint64_t*)d_img, (uint8_t*)d_arena, 1u);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }

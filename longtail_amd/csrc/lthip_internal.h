@@ -126,6 +126,9 @@ enum ScratchSlot
     S_SLICE_FIRST,
     S_LEN_CLASS_ORDER, // BLAKE2s and Meow ranges: class histogram, cursors and the length-class order of the ranges
     S_WALK_TICKET,     // the walking scan's part counter
+    S_RAW_BLOCKS,      // raw block images: per-block tables of lthip_raw_copy_blocks {payload offset, first chunk, chunk count}
+    S_RAW_RUNS,        // ... its runs (one slot per chunk: source, destination, length), their piece counts and the scan of those
+    S_RAW_TABLES,      // ... and the hash / BlockIndex tables of lthip_write_raw_block_images
     S_COUNT
 };
 
@@ -280,6 +283,13 @@ int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint
 uint32_t lthip_k1_resident_waves(int device); // waves of a K1 launch that the device holds at a time
 int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* bm0, const uint64_t* bm1, uint2* region,
                         uint32_t* part_count);
+// The payloads of raw (tag 0) block images (k_gather.hip): for each of `count` blocks the chunks [h_first[i], h_first[i] + h_count[i]) of the
+// device lists, copied back to back from d_src + d_src_offsets[c] to d_arena + h_payload[i].  The chunk indices lie in
+// [chunk_base, chunk_base + chunk_span); bytes_bound: an upper bound of the bytes copied (0 = unknown).  Host tables may be freed on
+// return; nothing is waited for.
+int lthip_raw_copy_blocks(lthip_ctx* ctx, uint32_t count, const uint32_t* h_first, const uint32_t* h_count, const uint64_t* h_payload,
+                          uint32_t chunk_base, uint32_t chunk_span, const uint32_t* d_lens, const uint64_t* d_src_offsets, const void* d_src,
+                          void* d_arena, uint64_t bytes_bound);
 int lthip_launch_compact(lthip_ctx* ctx, const lthip_plan* plan, const uint2* region, const uint32_t* part_count,
                          uint32_t* d_part_first, uint64_t* d_chunk_offsets, uint32_t* d_chunk_lens);
 int lthip_exclusive_scan_u32(lthip_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint64_t n_bound, const uint32_t* d_n,

@@ -187,6 +187,10 @@ extern "C" size_t lthip_stored_block_header_size(uint32_t chunk_count)
     return 8 + 4 + 4 + 4 + (size_t)chunk_count * 12 /* Longtail_GetBlockIndexDataSize */ + 8 /* raw + compressed size */;
 }
 
+// the BlockIndex alone: all there is in front of the chunks' bytes in the image of a block with tag 0 (CompressBlock stores it as it is,
+// compressblockstore.c:85-90)
+extern "C" size_t lthip_block_index_size(uint32_t chunk_count) { return lthip_stored_block_header_size(chunk_count) - 8; }
+
 extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_count, const uint64_t* block_first_chunk,
                                                 const uint64_t* d_chunk_hashes, const uint32_t* d_chunk_lens,
                                                 uint32_t hash_identifier, uint32_t tag, const uint32_t* raw_sizes,
@@ -232,8 +236,8 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
         return err;
     LaunchTimer t(ctx, LTHIP_K_OTHER);
     hipLaunchKernelGGL(k_stored_block_headers, dim3(block_count), dim3(64), 0, ctx->stream, (const uint32_t*)d_first.p, block_count,
-                       d_chunk_hashes, d_chunk_lens, (const uint64_t*)d_bh.p, hash_identifier, tag, (const uint32_t*)nullptr, (const uint32_t*)d_raw.p, d_comp_sizes,
-                       (const uint64_t*)d_img.p, (uint8_t*)d_arena);
+                       d_chunk_hashes, d_chunk_lens, (const uint64_t*)d_bh.p, hash_identifier, tag, (const uint32_t*)nullptr, (const uint32_t*)d_raw.p,
+                       const_cast<uint32_t*>(d_comp_sizes) /* only read: raw_mode 0 */, (const uint64_t*)d_img.p, (uint8_t*)d_arena, 0u);
     LTHIP_LAUNCH_CHECK(ctx);
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // the DevBufs are freed on return
     return 0;

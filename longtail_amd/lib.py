@@ -146,6 +146,8 @@ class HipLib:
         sig("lthip_debug_walk_tiles", i32, [P(C.c_uint64)])
         sig("lthip_stored_block_header_size", sz, [u32])
         sig("lthip_write_stored_block_headers", i32, [vp, u32, vp, vp, vp, u32, u32, vp, vp, vp, vp])
+        sig("lthip_block_index_size", sz, [u32])
+        sig("lthip_write_raw_block_images", i32, [vp, u32, vp, vp, vp, vp, vp, u32, vp, vp])
         sig("lthip_create_missing_content", i32, [vp, u64, vp, u64, vp, vp, vp, u32, u32, u32, vp, sz, vp])
         sig("lthip_get_existing_store_index", i32, [vp, vp, sz, u64, vp, u32, vp, sz, vp])
         sig("lthip_version_index_size", sz, [u32, u64, u64, u32])
@@ -519,6 +521,19 @@ class Context:
                                                                   hash_identifier, tag, rs.ctypes.data, _ptr(comp_sizes), _ptr(arena),
                                                                   io.ctypes.data), "lthip_write_stored_block_headers")
 
+    def block_index_size(self, chunk_count: int) -> int:
+        """bytes of a BlockIndex of that many chunks: what lies in front of the chunks' bytes in a raw (tag 0) block image"""
+        return int(self.lib.dll.lthip_block_index_size(chunk_count))
+
+    def write_raw_block_images(self, block_first_chunk, chunk_hashes, chunk_lens, chunk_src_offsets, src, arena, image_offsets,
+                               hash_identifier: int = 0x626C6B33):
+        """The complete tag-0 images -- BlockIndex + the chunks' bytes copied from src + chunk_src_offsets[c] -- at `image_offsets` of
+        `arena`; asynchronous on the context's stream (see longtail_hip.h)."""
+        bf, io = _u64arr(block_first_chunk), _u64arr(image_offsets)
+        self._check(self.lib.dll.lthip_write_raw_block_images(self.h, len(io), bf.ctypes.data, _ptr(chunk_hashes), _ptr(chunk_lens),
+                                                              _ptr(chunk_src_offsets), _ptr(src), hash_identifier, _ptr(arena),
+                                                              io.ctypes.data), "lthip_write_raw_block_images")
+
     def create_missing_content(self, existing_hashes, chunk_hashes, chunk_lens, chunk_tags, max_block_size: int,
                                max_chunks_per_block: int, hash_identifier: int = 0x626C6B33) -> bytes:
         """Serialized StoreIndex of the version chunks a store with `existing_hashes` lacks (see longtail_hip.h)."""
@@ -708,9 +723,21 @@ class IngestResult(C.Structure):
                                           "compressed_bytes", "gathered_blocks", "version_index_size", "store_index_size", "gathered_bytes")]
 
 
-CODECS = {"none": 0, "lz4": 1, "zstd": 2}
+CODECS = {"none": 0, "lz4": 1, "zstd": 2, "by-tag": 3}  # enum lthip_codec; "by-tag": every block's codec follows its own tag
 LZ4_TYPE = 0x6C7A3432    # 'lz42', lib/lz4/longtail_lz4.c:10
 ZSTD_DEFAULT = 0x7A746432  # 'ztd2', lib/zstd/longtail_zstd.c:12-22 (ZSTD default quality)
+
+
+def _default_tag(codec: str, compression_type: Optional[int], has_tags: bool) -> int:
+    """cfg.compression_type where the caller gave none: the codec's own tag; 0 for "none" (the only tag it writes).  "by-tag" has no
+    default: the caller passes compression_type or asset tags (cfg.compression_type is then 0, a tag the mode takes)."""
+    if compression_type is not None:
+        return compression_type
+    if codec == "by-tag":
+        if not has_tags:
+            raise ValueError('codec "by-tag" needs compression_type or asset tags')
+        return 0
+    return {"none": 0, "lz4": LZ4_TYPE, "zstd": ZSTD_DEFAULT}[codec]
 
 
 class Ingest:
@@ -719,8 +746,9 @@ class Ingest:
     def __init__(self, ctx: "Context", target_chunk_size: int, max_block_size: int, max_chunks_per_block: int, codec: str,
                  compression_type: Optional[int] = None, batch_bytes: int = 0, hash_identifier: int = 0x626C6B33):
         self.ctx = ctx
-        if compression_type is None:
-            compression_type = LZ4_TYPE if codec == "lz4" else ZSTD_DEFAULT
+        # ("by-tag" without compression_type: the tags come with the tree, index() insists on them)
+        self._needs_tags = codec == "by-tag" and compression_type is None
+        compression_type = _default_tag(codec, compression_type, True)
         self.cfg = IngestConfig(target_chunk_size, hash_identifier, max_block_size, max_chunks_per_block, compression_type,
                                 CODECS[codec], batch_bytes)
         h = C.c_void_p()
@@ -757,6 +785,8 @@ class Ingest:
     def index(self, tree: IngestTree, all_hashes, all_lens, all_chunks: int, local_offsets, local_part_first, local_chunks: int,
               version_index_out=None):
         """version_index_out: a (pinned) uint8 torch tensor or numpy array, or None."""
+        if getattr(self, "_needs_tags", False) and not tree.asset_tags:
+            raise ValueError('codec "by-tag" needs compression_type or asset tags')
         cap = 0 if version_index_out is None else (version_index_out.numel() if hasattr(version_index_out, "numel") else len(version_index_out))
         err = self.ctx.lib.dll.lthip_ingest_index(self.h, C.byref(tree), _ptr(all_hashes), _ptr(all_lens), all_chunks, _ptr(local_offsets),
                                                   _ptr(local_part_first), local_chunks, _ptr(version_index_out) or None, cap)
@@ -939,8 +969,7 @@ class IngestStream:
     def __init__(self, ctx: "Context", tree: IngestTree, target_chunk_size: int, max_block_size: int, max_chunks_per_block: int, codec: str,
                  compression_type: Optional[int] = None, hash_identifier: int = 0x626C6B33):
         self.ctx = ctx
-        if compression_type is None:
-            compression_type = LZ4_TYPE if codec == "lz4" else ZSTD_DEFAULT
+        compression_type = _default_tag(codec, compression_type, bool(tree.asset_tags))
         self.cfg = IngestConfig(target_chunk_size, hash_identifier, max_block_size, max_chunks_per_block, compression_type, CODECS[codec], 0)
         h = C.c_void_p()
         ctx._check(ctx.lib.dll.lthip_ingest_stream_create(ctx.h, C.byref(self.cfg), C.byref(tree), C.byref(h)), "lthip_ingest_stream_create")
