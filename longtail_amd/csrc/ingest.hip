@@ -166,7 +166,8 @@ struct lthip_ingest
     HBuf h_counts, h_mu_len, h_mu_off, h_mu_hash, h_mu_tag, h_bhash, h_comp, h_brk;
     DBuf d_brk;
     DBuf d_bhash, d_boff, d_blen, d_comp, d_sum;
-    DBuf d_gather, d_gsrc, d_glen, d_gdst, d_bfirst, d_braw, d_bimg, d_btag, d_tmpsz;
+    DBuf d_gather;
+    BlockImageBufs wbufs; // the block writer's tables (block_images.hip)
     hipEvent_t ev_counts, ev_lens, ev_offs, ev_index;
     // the first-seen index of every chunk computed elsewhere (the sharded table of the multi-GPU path): consumed by the next
     // lthip_ingest_index instead of its own table pass
@@ -206,12 +207,11 @@ struct lthip_ingest
     std::vector<uint32_t> vi_starts, vi_counts;
     const uint64_t* vi_hashes;
     void* vi_out;
-    // the stored-block images of the last codec batch (lthip_ingest_images): first block, offsets in the arena, header sizes; the image
+    // the codec batch being written (kept for its vectors), and the stored-block images of the last one (lthip_ingest_images): their
     // sizes are completed by lthip_ingest_finish (they need the compressed sizes)
-    uint64_t img_first;
-    std::vector<uint64_t> img_offsets;
-    std::vector<uint32_t> img_sizes; // header + payload per image: computed by every lthip_ingest_finish from img_hdr (calling it twice adds nothing twice)
-    std::vector<uint32_t> img_hdr;   // BlockIndex + [raw][compressed] of the last batch's images
+    BlockBatch batch;
+    Ranges gather;
+    BlockImages img;
 };
 
 // LTHIP_INGEST_TRACE=1: host time between the marks of lthip_ingest_index / _write, to stderr
@@ -254,8 +254,7 @@ extern "C" int lthip_ingest_create(lthip_ctx* ctx, const lthip_ingest_config* cf
         return lthip_fail(ctx, EINVAL, "lthip_ingest_create", "bad block / codec parameters");
     // (the tag of every block when lthip_ingest_index gets no asset tags; the asset tags are checked there)
     if (const int refused = tag_refusal(cfg->codec, cfg->compression_type))
-        return lthip_fail(ctx, refused, "lthip_ingest_create",
-                          refused == EINVAL ? "LTHIP_CODEC_NONE writes tag 0 only" : "LTHIP_CODEC_BY_TAG: compression_type names no codec of this library");
+        return lthip_fail(ctx, refused, "lthip_ingest_create", tag_refusal_text(refused));
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     lthip_ingest* g = new (std::nothrow) lthip_ingest();
     if (!g)
@@ -299,8 +298,8 @@ extern "C" void lthip_ingest_destroy(lthip_ingest* g)
     DBuf* dev[] = {&g->d_first, &g->d_isfirst, &g->d_rank, &g->d_idx, &g->d_uh, &g->d_us, &g->d_ut, &g->d_starts, &g->d_tags, &g->d_counts,
                    &g->d_paths, &g->d_aoff, &g->d_alen, &g->d_ph, &g->d_ch, &g->d_gfirst, &g->d_owned, &g->d_orank, &g->d_l2g, &g->d_mu_hash,
                    &g->d_mu_len, &g->d_mu_off, &g->d_mu_tag, &g->d_bhash, &g->d_boff, &g->d_blen, &g->d_comp, &g->d_sum, &g->d_gather,
-                   &g->d_gsrc, &g->d_glen, &g->d_gdst, &g->d_bfirst, &g->d_braw, &g->d_bimg, &g->d_btag, &g->d_tmpsz, &g->d_brk, &g->d_known,
-                   &g->d_lhash};
+                   &g->d_brk, &g->d_known, &g->d_lhash, &g->wbufs.d_tmpsz, &g->wbufs.d_gsrc, &g->wbufs.d_glen, &g->wbufs.d_gdst, &g->wbufs.d_bfirst,
+                   &g->wbufs.d_braw, &g->wbufs.d_bimg, &g->wbufs.d_btag};
     for (DBuf* b : dev)
         if (b->p)
             (void)hipFree(b->p);
@@ -366,28 +365,20 @@ static void ingest_pack(lthip_ingest* g, uint64_t raw_budget)
     const uint32_t* lens = (const uint32_t*)g->h_mu_len.p;
     const uint8_t* brk = (const uint8_t*)g->h_brk.p;
     const uint32_t* tags = g->has_tags ? (const uint32_t*)g->h_mu_tag.p : nullptr;
-    const uint64_t limit = (uint64_t)g->cfg.max_block_size + g->cfg.max_block_size / 10;
+    const uint64_t limit = block_limit(g->cfg.max_block_size);
     const uint32_t max_chunks = g->cfg.max_chunks_per_block;
     uint64_t added = 0;
     uint32_t i = g->pack_next;
     while (i < avail && added < raw_budget)
     {
-        uint64_t size = lens[i];
-        uint32_t j = i + 1;
-        bool range = true;
-        const uint32_t tag = tags ? tags[i] : g->cfg.compression_type;
-        while (j < avail && j - i < max_chunks && (!tags || tags[j] == tag) && size + lens[j] <= limit)
-        {
-            range &= brk[j] == 0;
-            size += lens[j];
-            ++j;
-        }
+        uint64_t size;
+        const uint32_t j = next_block_end(lens, tags, i, avail, max_chunks, limit, &size);
         if (j == avail && avail < nm && j - i < max_chunks)
             break; // the next chunk may still belong to this block
         g->b_size.push_back(size);
         g->b_first.push_back(j); // (b_first[b + 1]: where block b ends)
-        g->b_is_range.push_back(range ? 1 : 0);
-        g->b_tag.push_back(tag);
+        g->b_is_range.push_back(memchr(brk + i + 1, 1, j - i - 1) ? 0 : 1); // (no chunk behind the first breaks the byte range)
+        g->b_tag.push_back(tags ? tags[i] : g->cfg.compression_type);
         added += size;
         i = j;
     }
@@ -418,22 +409,13 @@ static int ingest_blocks_done(lthip_ingest* g)
         return err;
     if (nb)
     {
-        std::vector<uint64_t> o(nb);
-        std::vector<uint32_t> l(nb);
-        uint32_t max_len = 0;
-        uint64_t leaves = 0; // (1 KiB leaves of the hash arrays: known here, so the hash launcher reads nothing back -- the stream holds
-                             // the first codec batch by now)
-        for (size_t b = 0; b < nb; ++b)
-        {
-            o[b] = g->b_first[b] * 8u;
-            l[b] = (uint32_t)(g->b_first[b + 1] - g->b_first[b]) * 8u;
-            max_len = std::max(max_len, l[b]);
-            leaves += l[b] ? (l[b] + 1023u) >> 10 : 1u;
-        }
-        if ((err = lthip_stage_upload(ctx, g->d_boff.p, o.data(), nb * 8, s)) || (err = lthip_stage_upload(ctx, g->d_blen.p, l.data(), nb * 4, s)))
+        BlockHashRanges r; // (with the leaves of the hash arrays, so the hash launcher reads nothing back -- the stream holds the first
+                           // codec batch by now)
+        r.fill(g->b_first.data(), nb, 0);
+        if ((err = lthip_stage_upload(ctx, g->d_boff.p, r.off.data(), nb * 8, s)) || (err = lthip_stage_upload(ctx, g->d_blen.p, r.len.data(), nb * 4, s)))
             return err;
-        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, g->d_mu_hash.p, nb, (const uint64_t*)g->d_boff.p, (const uint32_t*)g->d_blen.p, max_len, leaves,
-                                           (uint64_t*)g->d_bhash.p)))
+        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, g->d_mu_hash.p, nb, (const uint64_t*)g->d_boff.p, (const uint32_t*)g->d_blen.p, r.max_len,
+                                           r.leaves, (uint64_t*)g->d_bhash.p)))
             return err;
         LTHIP_CHECK(ctx, hipMemcpyAsync(g->h_bhash.p, g->d_bhash.p, nb * 8, hipMemcpyDeviceToHost, s));
     }
@@ -586,8 +568,7 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
     if (t->asset_tags) // (before any work is queued: the session stays as it is)
         for (uint32_t a = 0; a < t->asset_count; ++a)
             if (const int refused = tag_refusal(g->cfg.codec, t->asset_tags[a]))
-                return lthip_fail(ctx, refused, "lthip_ingest_index",
-                                  refused == EINVAL ? "LTHIP_CODEC_NONE writes tag 0 only" : "LTHIP_CODEC_BY_TAG: an asset tag names no codec of this library");
+                return lthip_fail(ctx, refused, "lthip_ingest_index", tag_refusal_text(refused));
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     g->vi_pending = false;
     (void)ingest_vi_join(g); // (an index that was never finished: its helper reads what this call is about to replace ...
@@ -883,22 +864,15 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
         return EINVAL;
     IngTrace tr("lthip_ingest_write");
     lthip_ctx* ctx = g->ctx;
-    // (tag 0 means a raw image only where the session writes by tag; LTHIP_CODEC_LZ4 / _ZSTD compress a tag-0 block like any other)
-    const uint32_t raw_mode = g->cfg.codec == LTHIP_CODEC_NONE || g->cfg.codec == LTHIP_CODEC_BY_TAG ? 1u : 0u;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint32_t* lens = (const uint32_t*)g->h_mu_len.p;
     const uint64_t* offs = (const uint64_t*)g->h_mu_off.p;
     int err;
     uint64_t gathered_blocks = 0, gathered_bytes = 0;
-    g->img_first = 0;
-    g->img_offsets.clear();
-    g->img_sizes.clear();
-    g->img_hdr.clear();
-    std::vector<uint64_t> src_off, dst_off, img_off, g_src, g_dst, bfirst;
-    std::vector<uint32_t> src_size, dst_cap, g_len, braw, r_first, r_count;
-    std::vector<uint64_t> r_payload;
-    std::vector<BlockCodec> bcodec, keys;
+    BlockBatch& bt = g->batch;
+    bt.clear();
+    g->img.set(0, bt);
     // more blocks, when the batch being put together has taken all there are and chunks are left
     auto more_blocks = [&](size_t have) -> int {
         while (g->b_size.size() == have && g->pack_next < g->n_mine)
@@ -918,214 +892,57 @@ extern "C" int lthip_ingest_write(lthip_ingest* g, const void* d_data, void* d_a
             return err;
         if (b0 == g->b_size.size())
             break;
-        // ---- one batch: as many blocks as the arena and the codec's batch size hold (always at least one) ----
+        // ---- one batch: as many blocks as the arena and the codec's batch size hold (always at least one).  A block that is one byte
+        // range of the data is compressed where it lies (place 0), every other one is assembled in d_gather first (place 1;
+        // WriteContentBlockJob, :4640-4721), a range per chunk; a raw block is copied from where its chunks lie ----
         size_t b1 = b0;
-        uint64_t arena = 0, bytes = 0, gather_chunks = 0;
-        img_off.clear();
+        uint64_t bytes = 0, pos = 0;
+        bt.clear();
+        g->gather.clear();
         while ((err = more_blocks(b1)) == 0 && b1 < g->b_size.size())
         {
             const uint32_t nchunks = (uint32_t)(g->b_first[b1 + 1] - g->b_first[b1]);
-            const uint32_t codec = block_codec(g->cfg, g->b_tag[b1]).codec; // (the arena need of a block: its own codec's bound)
-            const uint64_t need = ((uint64_t)block_header_bytes(codec, nchunks) + block_codec_bound(codec, g->b_size[b1]) + 63u) & ~(uint64_t)63u;
-            if (b1 > b0 && (arena + need > arena_bytes || bytes + g->b_size[b1] > g->cfg.batch_bytes))
+            const BlockCodec bc = block_codec(g->cfg, g->b_tag[b1]);
+            const uint64_t need = BlockBatch::slot(bc.codec, nchunks, g->b_size[b1]);
+            if (b1 > b0 && (bt.arena + need > arena_bytes || bytes + g->b_size[b1] > g->cfg.batch_bytes))
                 break;
-            if (arena + need > arena_bytes)
+            if (bt.arena + need > arena_bytes)
                 return lthip_fail(ctx, ENOMEM, "lthip_ingest_write", "the arena does not hold a single stored block");
-            img_off.push_back(arena);
-            arena += need;
+            const uint32_t place = bc.codec == LTHIP_CODEC_NONE ? PLACE_RAW : g->b_is_range[b1] ? 0u : 1u;
+            uint64_t off = place == 0 ? offs[g->b_first[b1]] : 0;
+            if (place == 1)
+            {
+                off = pos = (pos + 15u) & ~(uint64_t)15u;
+                for (uint64_t c = g->b_first[b1]; c < g->b_first[b1 + 1]; ++c)
+                {
+                    g->gather.add(offs[c], lens[c], pos, 0);
+                    pos += lens[c];
+                }
+                ++gathered_blocks;
+                gathered_bytes += g->b_size[b1];
+            }
+            bt.add(nchunks, g->b_size[b1], g->b_tag[b1], bc, place, off);
             bytes += g->b_size[b1];
-            if (!g->b_is_range[b1] && codec != LTHIP_CODEC_NONE) // (a raw block is copied from where its chunks lie)
-                gather_chunks += nchunks;
             ++b1;
         }
         if (err)
             return err;
         tr.mark("batch");
-        const size_t cnt = b1 - b0;
-        // every block's codec, and the distinct (codec, zstd quality) keys of the batch in the order they appear: a codec call takes
-        // blocks of one key from one place.  One codec for the session (LTHIP_CODEC_LZ4 / _ZSTD): one key, the two calls of before
-        bcodec.resize(cnt);
-        keys.clear();
-        for (size_t b = b0; b < b1; ++b)
-        {
-            bcodec[b - b0] = block_codec(g->cfg, g->b_tag[b]);
-            if (bcodec[b - b0].codec != LTHIP_CODEC_NONE && std::find(keys.begin(), keys.end(), bcodec[b - b0]) == keys.end())
-                keys.push_back(bcodec[b - b0]);
-        }
-        auto staged = [&](size_t b) { return !g->b_is_range[b] && bcodec[b - b0].codec != LTHIP_CODEC_NONE; };
-        // ---- block assembly (WriteContentBlockJob, :4640-4721) only for blocks that are not one byte range of the data ----
-        if (gather_chunks)
-        {
-            if ((err = reserve_dev(ctx, g->d_gsrc, gather_chunks * 8)) ||
-                (err = reserve_dev(ctx, g->d_glen, gather_chunks * 4)) || (err = reserve_dev(ctx, g->d_gdst, gather_chunks * 8)))
-                return err;
-            g_src.clear();
-            g_len.clear();
-            g_dst.clear();
-            uint64_t pos = 0;
-            for (size_t b = b0; b < b1; ++b)
-                if (staged(b))
-                {
-                    pos = (pos + 15u) & ~(uint64_t)15u;
-                    for (uint64_t c = g->b_first[b]; c < g->b_first[b + 1]; ++c)
-                    {
-                        g_src.push_back(offs[c]);
-                        g_len.push_back(lens[c]);
-                        g_dst.push_back(pos);
-                        pos += lens[c];
-                    }
-                }
-            if ((err = reserve_dev(ctx, g->d_gather, pos + 256)))
-                return err;
-            if ((err = lthip_stage_upload(ctx, g->d_gsrc.p, g_src.data(), g_src.size() * 8, s)) ||
-                (err = lthip_stage_upload(ctx, g->d_glen.p, g_len.data(), g_len.size() * 4, s)) ||
-                (err = lthip_stage_upload(ctx, g->d_gdst.p, g_dst.data(), g_dst.size() * 8, s)))
-                return err;
-            if ((err = lthip_gather_ranges(ctx, d_data, g_src.size(), (const uint64_t*)g->d_gsrc.p, (const uint32_t*)g->d_glen.p, g->d_gather.p,
-                                           (const uint64_t*)g->d_gdst.p)))
-                return err;
-        }
-        // ---- raw blocks: the chunks' bytes straight from the data into the image, behind the BlockIndex ----
-        r_first.clear();
-        r_count.clear();
-        r_payload.clear();
-        uint64_t raw_bytes = 0;
-        for (size_t b = b0; b < b1; ++b)
-            if (bcodec[b - b0].codec == LTHIP_CODEC_NONE)
-            {
-                const uint32_t nchunks = (uint32_t)(g->b_first[b + 1] - g->b_first[b]);
-                r_first.push_back((uint32_t)g->b_first[b]);
-                r_count.push_back(nchunks);
-                r_payload.push_back(img_off[b - b0] + lthip_block_index_size(nchunks));
-                raw_bytes += g->b_size[b];
-            }
-        if (!r_first.empty() &&
-            (err = lthip_raw_copy_blocks(ctx, (uint32_t)r_first.size(), r_first.data(), r_count.data(), r_payload.data(), (uint32_t)g->b_first[b0],
-                                         (uint32_t)(g->b_first[b1] - g->b_first[b0]), (const uint32_t*)g->d_mu_len.p, (const uint64_t*)g->d_mu_off.p,
-                                         d_data, d_arena, raw_bytes + 1)))
+        if (pos && ((err = reserve_dev(ctx, g->d_gather, pos + 256)) || (err = lthip_gather_upload(ctx, g->wbufs, d_data, g->gather, g->d_gather.p))))
             return err;
-        // ---- compress straight to image + header size: per (codec, quality) the blocks in place first, then the assembled ones ----
-        for (size_t call = 0; call < keys.size() * 2; ++call)
-        {
-            const size_t key = call / 2;
-            const int pass = (int)(call % 2);
-            src_off.clear();
-            src_size.clear();
-            dst_off.clear();
-            dst_cap.clear();
-            std::vector<uint32_t> which;
-            uint64_t pos = 0;
-            for (size_t b = b0; b < b1; ++b)
-            {
-                if (bcodec[b - b0].codec == LTHIP_CODEC_NONE)
-                    continue;
-                const bool range = g->b_is_range[b] != 0;
-                if (!range)
-                    pos = (pos + 15u) & ~(uint64_t)15u;
-                if (range == (pass == 0) && bcodec[b - b0] == keys[key])
-                {
-                    const uint32_t nchunks = (uint32_t)(g->b_first[b + 1] - g->b_first[b]);
-                    src_off.push_back(range ? offs[g->b_first[b]] : pos);
-                    src_size.push_back((uint32_t)g->b_size[b]);
-                    dst_off.push_back(img_off[b - b0] + lthip_stored_block_header_size(nchunks));
-                    dst_cap.push_back((uint32_t)block_codec_bound(keys[key].codec, g->b_size[b]));
-                    which.push_back((uint32_t)b);
-                }
-                if (!range)
-                    pos += g->b_size[b];
-            }
-            if (src_off.empty())
-                continue;
-            // the codec entry points write one size per block of the call: a call's blocks are a contiguous run only when the
-            // batch is of one key and all-range or all-gathered, so sizes go through a per-call list and are scattered by `which`
-            const void* src = pass == 0 ? d_data : g->d_gather.p;
-            const uint32_t k = (uint32_t)src_off.size();
-            bool contiguous = true;
-            for (uint32_t i = 1; i < k; ++i)
-                contiguous &= which[i] == which[i - 1] + 1;
-            uint32_t* d_sizes = (uint32_t*)g->d_comp.p + which[0];
-            if (!contiguous)
-            {
-                if ((err = reserve_dev(ctx, g->d_tmpsz, (size_t)k * 4)))
-                    return err;
-                d_sizes = (uint32_t*)g->d_tmpsz.p;
-            }
-            if (keys[key].codec == LTHIP_CODEC_LZ4)
-                err = lthip_lz4_compress_blocks(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes, 0);
-            else
-                err = lthip_zstd_compress_blocks_q(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes,
-                                                   keys[key].quality);
-            if (err)
-                return err;
-            if (!contiguous)
-            {
-                // scatter: comp[which[i]] = sizes[i]  (gather kernel on 4-byte ranges)
-                std::vector<uint64_t> so(k), dof(k);
-                std::vector<uint32_t> four(k, 4u);
-                for (uint32_t i = 0; i < k; ++i)
-                {
-                    so[i] = (uint64_t)i * 4u;
-                    dof[i] = (uint64_t)which[i] * 4u;
-                }
-                if ((err = reserve_dev(ctx, g->d_gsrc, (size_t)k * 8)) || (err = reserve_dev(ctx, g->d_glen, (size_t)k * 4)) ||
-                    (err = reserve_dev(ctx, g->d_gdst, (size_t)k * 8)))
-                    return err;
-                if ((err = lthip_stage_upload(ctx, g->d_gsrc.p, so.data(), (size_t)k * 8, s)) ||
-                    (err = lthip_stage_upload(ctx, g->d_glen.p, four.data(), (size_t)k * 4, s)) ||
-                    (err = lthip_stage_upload(ctx, g->d_gdst.p, dof.data(), (size_t)k * 8, s)))
-                    return err;
-                if ((err = lthip_gather_ranges(ctx, g->d_tmpsz.p, k, (const uint64_t*)g->d_gsrc.p, (const uint32_t*)g->d_glen.p, g->d_comp.p,
-                                               (const uint64_t*)g->d_gdst.p)))
-                    return err;
-            }
-            if (pass == 1)
-            {
-                gathered_blocks += k;
-                for (uint32_t i = 0; i < k; ++i)
-                    gathered_bytes += src_size[i];
-            }
-        }
+        const BlockBatchDev dev = {{d_data, g->d_gather.p}, 2, (const uint64_t*)g->d_mu_hash.p, (const uint32_t*)g->d_mu_len.p, (uint32_t)g->b_first[b0],
+                                   (const uint64_t*)g->d_mu_off.p, d_data, (const uint64_t*)g->d_bhash.p + b0, (uint32_t*)g->d_comp.p + b0, d_arena};
+        if ((err = lthip_block_payloads(ctx, g->wbufs, bt, dev)))
+            return err;
         tr.mark("codec");
         // ---- (first batch: the codec has work now; the rest of the packing and all block hashes) ----
         if ((err = ingest_vi_start(g)) || (err = ingest_blocks_done(g)))
             return err;
         tr.mark("blocks");
-        // ---- BlockIndex + [raw][compressed] around the payloads (:4111-4150; compressblockstore.c:103-139); a raw block gets the BlockIndex
-        // alone, and its entry of d_comp is filled in with its raw size ----
-        if ((err = reserve_dev(ctx, g->d_bfirst, (cnt + 1) * 4)) || (err = reserve_dev(ctx, g->d_braw, cnt * 4)) ||
-            (err = reserve_dev(ctx, g->d_bimg, cnt * 8)) || (err = reserve_dev(ctx, g->d_btag, cnt * 4)))
+        // (a tree without asset tags: every block carries cfg.compression_type, and no tags are uploaded)
+        if ((err = lthip_block_headers_upload(ctx, g->wbufs, bt, g->has_tags)) || (err = lthip_block_headers(ctx, g->wbufs, bt, dev, g->cfg, g->has_tags)))
             return err;
-        std::vector<uint32_t> first32(cnt + 1);
-        braw.resize(cnt);
-        for (size_t b = b0; b <= b1; ++b)
-            first32[b - b0] = (uint32_t)g->b_first[b];
-        for (size_t b = b0; b < b1; ++b)
-            braw[b - b0] = (uint32_t)g->b_size[b];
-        if ((err = lthip_stage_upload(ctx, g->d_bfirst.p, first32.data(), (cnt + 1) * 4, s)) ||
-            (err = lthip_stage_upload(ctx, g->d_braw.p, braw.data(), cnt * 4, s)) ||
-            (err = lthip_stage_upload(ctx, g->d_bimg.p, img_off.data(), cnt * 8, s)))
-            return err;
-        const uint32_t* d_tags = nullptr;
-        if (g->has_tags)
-        {
-            if ((err = lthip_stage_upload(ctx, g->d_btag.p, g->b_tag.data() + b0, cnt * 4, s)))
-                return err;
-            d_tags = (const uint32_t*)g->d_btag.p;
-        }
-        {
-            LaunchTimer tm(ctx, LTHIP_K_OTHER);
-            hipLaunchKernelGGL(k_stored_block_headers, dim3((uint32_t)cnt), dim3(64), 0, s, (const uint32_t*)g->d_bfirst.p, (uint32_t)cnt,
-                               (const uint64_t*)g->d_mu_hash.p, (const uint32_t*)g->d_mu_len.p, (const uint64_t*)g->d_bhash.p + b0,
-                               g->cfg.hash_identifier, g->cfg.compression_type, d_tags, (const uint32_t*)g->d_braw.p,
-                               (uint32_t*)g->d_comp.p + b0, (const uint64_t*)g->d_bimg.p, (uint8_t*)d_arena, raw_mode);
-            LTHIP_LAUNCH_CHECK(ctx);
-        }
-        g->img_first = b0;
-        g->img_offsets.assign(img_off.begin(), img_off.end());
-        g->img_hdr.resize(cnt);
-        for (size_t b = b0; b < b1; ++b)
-            g->img_hdr[b - b0] = (uint32_t)block_header_bytes(bcodec[b - b0].codec, (uint32_t)(g->b_first[b + 1] - g->b_first[b]));
-        g->img_sizes = g->img_hdr; // (headers only until lthip_ingest_finish knows the payload sizes)
+        g->img.set(b0, bt);
         b0 = b1;
     }
     if ((err = ingest_vi_start(g)) || (err = ingest_blocks_done(g))) // (nothing to write)
@@ -1155,10 +972,9 @@ extern "C" int lthip_ingest_finish(lthip_ingest* g, void* h_store_index, size_t 
     if (!g || !g->indexed)
         return EINVAL;
     lthip_ctx* ctx = g->ctx;
-    // (the caller says how large ITS struct is: a header older or newer than this library's never gets written past its end.  Checked
-    // before any work: a call that is going to be refused changes nothing)
-    if (out && (out->struct_size < 16 || out->struct_size > 4096))
-        return lthip_fail(ctx, EINVAL, "lthip_ingest_finish", "out_result->struct_size must be set to sizeof(lthip_ingest_result)");
+    // (checked before any work: a call that is going to be refused changes nothing)
+    if (!result_struct_ok(out))
+        return lthip_fail(ctx, EINVAL, "lthip_ingest_finish", RESULT_STRUCT_TEXT);
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     {
         int err = ingest_blocks_done(g); // (an index without lthip_ingest_write)
@@ -1168,7 +984,7 @@ extern "C" int lthip_ingest_finish(lthip_ingest* g, void* h_store_index, size_t 
             return err;
     }
     const size_t nb = g->b_size.size(), m = (size_t)g->n_mine;
-    const size_t size = 16 + nb * 8 + m * 8 + nb * 12 + m * 4; // Longtail_GetStoreIndexDataSize
+    const size_t size = store_index_size(nb, m);
     g->res.store_index_size = size;
     int rc = 0;
     if (h_store_index)
@@ -1179,25 +995,7 @@ extern "C" int lthip_ingest_finish(lthip_ingest* g, void* h_store_index, size_t 
         {
             LTHIP_CHECK(ctx, hipEventSynchronize(g->ev_index));  // block hashes ...
             LTHIP_CHECK(ctx, hipEventSynchronize(g->ev_hashes)); // ... and the owned chunks' hashes are on the host
-            uint8_t* w = (uint8_t*)h_store_index;
-            // (nothing to write: Longtail_CreateMissingContent returns Longtail_CreateStoreIndexFromBlocks(0, 0), hash identifier 0, :6931-6943)
-            const uint32_t head[4] = {(1u << 24) /* LONGTAIL_STORE_INDEX_VERSION_1_0_0, :19-23 */, m ? g->cfg.hash_identifier : 0u, (uint32_t)nb,
-                                      (uint32_t)m};
-            memcpy(w, head, 16);
-            w += 16;
-            memcpy(w, g->h_bhash.p, nb * 8); // m_BlockHashes
-            w += nb * 8;
-            memcpy(w, g->h_mu_hash.p, m * 8); // m_ChunkHashes
-            w += m * 8;
-            uint32_t* bo = (uint32_t*)w; // m_BlockChunksOffsets, m_BlockChunkCounts, m_BlockTags
-            for (size_t b = 0; b < nb; ++b)
-            {
-                bo[b] = (uint32_t)g->b_first[b];
-                bo[nb + b] = (uint32_t)(g->b_first[b + 1] - g->b_first[b]);
-                bo[2 * nb + b] = g->b_tag[b];
-            }
-            w += nb * 12;
-            memcpy(w, g->h_mu_len.p, m * 4); // m_ChunkSizes
+            write_store_index(h_store_index, g->cfg.hash_identifier, nb, m, g->h_bhash.p, g->h_mu_hash.p, g->b_first.data(), g->b_tag.data(), g->h_mu_len.p);
         }
     }
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
@@ -1209,17 +1007,8 @@ extern "C" int lthip_ingest_finish(lthip_ingest* g, void* h_store_index, size_t 
     }
     g->res.compressed_bytes = g->written ? *(const uint64_t*)g->h_comp.p : 0;
     if (g->written)
-    {
-        const uint32_t* comp = (const uint32_t*)((const uint8_t*)g->h_comp.p + 8);
-        for (size_t i = 0; i < g->img_hdr.size(); ++i)
-            g->img_sizes[i] = g->img_hdr[i] + comp[g->img_first + i]; // header (BlockIndex + [raw][compressed]) + payload
-    }
-    if (out)
-    {
-        const uint64_t have = out->struct_size;
-        g->res.struct_size = have < sizeof g->res ? have : sizeof g->res;
-        memcpy(out, &g->res, (size_t)g->res.struct_size);
-    }
+        g->img.complete(lthip_ingest_compressed_sizes(g));
+    deliver_result(out, &g->res);
     return rc;
 }
 
@@ -1228,14 +1017,7 @@ extern "C" int lthip_ingest_images(const lthip_ingest* g, uint64_t* out_first_bl
 {
     if (!g || !g->written)
         return EINVAL;
-    if (out_first_block)
-        *out_first_block = g->img_first;
-    if (out_count)
-        *out_count = g->img_offsets.size();
-    if (out_offsets)
-        *out_offsets = g->img_offsets.data();
-    if (out_sizes)
-        *out_sizes = g->img_sizes.data();
+    g->img.get(out_first_block, out_count, out_offsets, out_sizes);
     return 0;
 }
 

@@ -20,7 +20,6 @@
 // a pinned batch record and is collected by lthip_ingest_stream_images, by finish, or by a later call once its event has fired.
 // The passes of different slices are NOT overlapped here: everything is queued on the context's one stream.
 #include "lthip_internal.h"
-#include "index_kernels.h"
 #include "ingest_buffers.h"
 
 #include <algorithm>
@@ -68,7 +67,8 @@ struct lthip_ingest_stream
     HBuf h_first, h_off, h_pf, h_known;
     DBuf d_known;
     DBuf d_usrc; // raw blocks: the address of every chunk of the call (d_carry or the slice's data)
-    DBuf d_first, d_gather, d_gsrc, d_glen, d_gdst, d_uh, d_ul, d_boff, d_blen, d_bhash, d_comp, d_tmpsz, d_bfirst, d_braw, d_bimg, d_btag;
+    DBuf d_first, d_gather, d_uh, d_ul, d_boff, d_blen, d_bhash, d_comp;
+    BlockImageBufs wbufs; // the block writer's tables (block_images.hip)
     DBuf d_vh, d_vl; // finish: the kept lists on the device
     std::vector<uint64_t> u_src; // byte offset in the slice's data of the chunks this slice added to the unique list
     hipEvent_t ev_lists, ev_call;
@@ -80,10 +80,9 @@ struct lthip_ingest_stream
         hipEvent_t ev;
     };
     std::vector<Batch> pending, spare;
-    // ---- the images of the last call ----
-    uint64_t img_first;
-    std::vector<uint64_t> img_offsets;
-    std::vector<uint32_t> img_sizes, img_hdr;
+    // ---- the blocks of the call being written (kept for its vectors), and the images of the last call ----
+    BlockBatch batch;
+    BlockImages img;
 };
 
 namespace
@@ -91,7 +90,7 @@ namespace
 
 typedef lthip_ingest_stream Stream;
 
-uint64_t block_limit(const lthip_ingest_config* cfg) { return (uint64_t)cfg->max_block_size + cfg->max_block_size / 10; }
+uint64_t block_limit(const lthip_ingest_config* cfg) { return block_limit(cfg->max_block_size); }
 
 bool config_ok(const lthip_ingest_config* cfg)
 {
@@ -142,57 +141,20 @@ void stream_pack(Stream* s, bool final)
     uint64_t i = s->b_first.back();
     while (i < nu)
     {
-        uint64_t size = s->u_len[i], j = i + 1;
-        const uint32_t tag = s->u_tag[i];
-        while (j < nu && j - i < max_chunks && s->u_tag[j] == tag && size + s->u_len[j] <= limit)
-            size += s->u_len[j++];
+        uint64_t size;
+        const uint64_t j = next_block_end(s->u_len.data(), s->u_tag.data(), i, nu, max_chunks, limit, &size);
         if (j == nu && !final && j - i < max_chunks)
             break; // the next chunk may still belong to this block
         s->b_size.push_back(size);
         s->b_first.push_back(j);
-        s->b_tag.push_back(tag);
+        s->b_tag.push_back(s->u_tag[i]);
         i = j;
     }
 }
 
-// host tables of one lthip_gather_ranges call.  Neighbours that continue each other on both sides become one range, up to MERGE_BYTES:
-// the gather kernel copies a range per workgroup, so small chunks share a workgroup and a long run (the open block is usually one
-// byte range of the slice, up to max_block_size * 1.1) still spreads over the device instead of being copied by one CU.
+// gathers merge neighbours up to this many bytes (Ranges::add): the open block is usually one byte range of the slice, up to
+// max_block_size * 1.1, and still spreads over the device
 constexpr uint64_t MERGE_BYTES = 128u << 10;
-struct Ranges
-{
-    std::vector<uint64_t> src, dst;
-    std::vector<uint32_t> len;
-    void add(uint64_t s, uint32_t l, uint64_t d)
-    {
-        if (l == 0)
-            return;
-        if (!src.empty() && src.back() + len.back() == s && dst.back() + len.back() == d && (uint64_t)len.back() + l <= MERGE_BYTES)
-            len.back() += l;
-        else
-        {
-            src.push_back(s);
-            len.push_back(l);
-            dst.push_back(d);
-        }
-    }
-};
-
-int stream_gather(Stream* s, const void* d_src, const Ranges& r, void* d_dst)
-{
-    lthip_ctx* ctx = s->ctx;
-    const size_t k = r.src.size();
-    if (!k)
-        return 0;
-    int err;
-    // (the tables of the call before this one were read by a kernel queued before these uploads: the stream orders them)
-    if ((err = reserve_dev(ctx, s->d_gsrc, k * 8)) || (err = reserve_dev(ctx, s->d_glen, k * 4)) || (err = reserve_dev(ctx, s->d_gdst, k * 8)) ||
-        (err = lthip_stage_upload(ctx, s->d_gsrc.p, r.src.data(), k * 8, ctx->stream)) ||
-        (err = lthip_stage_upload(ctx, s->d_glen.p, r.len.data(), k * 4, ctx->stream)) ||
-        (err = lthip_stage_upload(ctx, s->d_gdst.p, r.dst.data(), k * 8, ctx->stream)))
-        return err;
-    return lthip_gather_ranges(ctx, d_src, k, (const uint64_t*)s->d_gsrc.p, (const uint32_t*)s->d_glen.p, d_dst, (const uint64_t*)s->d_gdst.p);
-}
 
 // The images of blocks [b0, b1) into the arena: assembly, codec, block hashes, BlockIndex + [raw][compressed] around the payloads
 // (:4111-4150; compressblockstore.c:103-139).  Chunks below `fresh` (an index into the unique list) lie in d_carry at carry_off, the others
@@ -202,193 +164,89 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
 {
     lthip_ctx* ctx = s->ctx;
     hipStream_t st = ctx->stream;
-    s->img_first = b0;
-    s->img_offsets.clear();
-    s->img_hdr.clear();
-    s->img_sizes.clear();
+    BlockBatch& bt = s->batch;
+    bt.clear();
+    s->img.set(b0, bt);
     const size_t cnt = b1 - b0;
     if (!cnt)
         return 0;
     const uint64_t c0 = s->b_first[b0], c1 = s->b_first[b1], nc = c1 - c0, open0 = fresh - s->carry_off.size();
     int err;
-    // ---- where the images go, and where every block's bytes are: 0 in d_data, 1 to be gathered, 2 in d_carry; 3: a raw block, copied
-    // chunk run by chunk run from wherever they are ----
-    std::vector<uint64_t> img_off(cnt), gpos(cnt, 0);
-    std::vector<uint8_t> kind(cnt);
-    std::vector<BlockCodec> bcodec(cnt), keys;
-    std::vector<uint32_t> r_first, r_count;
-    std::vector<uint64_t> r_payload;
-    uint64_t raw_bytes = 0;
+    // ---- where every block's bytes are: place 0 in d_data, 1 to be gathered, 2 in d_carry; a raw block is copied chunk run by chunk
+    // run from wherever they are: its chunks' addresses (the two places are two allocations: the copy takes them relative to a null base) ----
+    std::vector<uint64_t> addr;
     Ranges from_carry, from_data;
-    uint64_t arena = 0, pos = 0;
+    uint64_t pos = 0;
     for (size_t b = b0; b < b1; ++b)
     {
         const uint64_t first = s->b_first[b], last = s->b_first[b + 1];
         const BlockCodec bc = block_codec(s->cfg, s->b_tag[b]);
-        bcodec[b - b0] = bc;
-        const uint64_t need = ((uint64_t)block_header_bytes(bc.codec, (uint32_t)(last - first)) + block_codec_bound(bc.codec, s->b_size[b]) + 63u) & ~(uint64_t)63u;
-        img_off[b - b0] = arena;
-        arena += need;
+        uint32_t place = 1;
+        uint64_t off = 0;
         if (bc.codec == LTHIP_CODEC_NONE)
         {
-            kind[b - b0] = 3;
-            r_first.push_back((uint32_t)(first - c0));
-            r_count.push_back((uint32_t)(last - first));
-            r_payload.push_back(img_off[b - b0] + lthip_block_index_size((uint32_t)(last - first)));
-            raw_bytes += s->b_size[b];
-            continue;
+            place = PLACE_RAW;
+            addr.resize(nc, 0);
+            for (uint64_t c = first; c < last; ++c)
+                addr[c - c0] = c < fresh ? (uint64_t)(uintptr_t)s->d_carry.p + s->carry_off[c - open0] : (uint64_t)(uintptr_t)d_data + s->u_src[c - fresh];
         }
-        if (std::find(keys.begin(), keys.end(), bc) == keys.end())
-            keys.push_back(bc);
-        uint8_t k = 1;
-        if (last <= fresh)
-            k = 2; // (carried chunks lie back to back)
+        else if (last <= fresh) // (carried chunks lie back to back)
+        {
+            place = 2;
+            off = s->carry_off[first - open0];
+        }
         else if (first >= fresh)
         {
-            k = 0;
-            for (uint64_t c = first + 1; c < last && k == 0; ++c)
+            place = 0;
+            off = s->u_src[first - fresh];
+            for (uint64_t c = first + 1; c < last && place == 0; ++c)
                 if (s->u_src[c - fresh] != s->u_src[c - 1 - fresh] + s->u_len[c - 1])
-                    k = 1;
+                    place = 1;
         }
-        kind[b - b0] = k;
-        if (k == 1)
+        if (place == 1)
         {
-            pos = (pos + 15u) & ~(uint64_t)15u;
-            gpos[b - b0] = pos;
+            off = pos = (pos + 15u) & ~(uint64_t)15u;
             for (uint64_t c = first; c < last; ++c)
             {
                 if (c < fresh)
-                    from_carry.add(s->carry_off[c - open0], s->u_len[c], pos);
+                    from_carry.add(s->carry_off[c - open0], s->u_len[c], pos, MERGE_BYTES);
                 else
-                    from_data.add(s->u_src[c - fresh], s->u_len[c], pos);
+                    from_data.add(s->u_src[c - fresh], s->u_len[c], pos, MERGE_BYTES);
                 pos += s->u_len[c];
             }
             ++s->gathered_blocks;
             s->gathered_bytes += s->b_size[b];
         }
+        bt.add((uint32_t)(last - first), s->b_size[b], s->b_tag[b], bc, place, off);
     }
-    if (arena > arena_bytes) // (lthip_ingest_stream_arena_bound is a bound of this sum: tests/test_ingest_stream_abi.py)
+    if (bt.arena > arena_bytes) // (lthip_ingest_stream_arena_bound is a bound of this sum: tests/test_ingest_stream_abi.py)
         return lthip_fail(ctx, ENOMEM, "lthip_ingest_stream", "the arena does not hold the call's images");
     if ((err = reserve_dev(ctx, s->d_comp, cnt * 4)) || (err = reserve_dev(ctx, s->d_bhash, cnt * 8)) || (err = reserve_dev(ctx, s->d_boff, cnt * 8)) ||
-        (err = reserve_dev(ctx, s->d_blen, cnt * 4)) || (err = reserve_dev(ctx, s->d_bfirst, (cnt + 1) * 4)) || (err = reserve_dev(ctx, s->d_braw, cnt * 4)) ||
-        (err = reserve_dev(ctx, s->d_bimg, cnt * 8)) || (err = reserve_dev(ctx, s->d_btag, cnt * 4)) || (err = reserve_dev(ctx, s->d_uh, nc * 8)) ||
-        (err = reserve_dev(ctx, s->d_ul, nc * 4)))
+        (err = reserve_dev(ctx, s->d_blen, cnt * 4)) || (err = reserve_dev(ctx, s->d_uh, nc * 8)) || (err = reserve_dev(ctx, s->d_ul, nc * 4)))
         return err;
     // ---- block assembly (WriteContentBlockJob, :4640-4721) for the blocks that are not one byte range ----
-    if (pos)
-    {
-        if ((err = reserve_dev(ctx, s->d_gather, pos + 256)) || (err = stream_gather(s, s->d_carry.p, from_carry, s->d_gather.p)) ||
-            (err = stream_gather(s, d_data, from_data, s->d_gather.p)))
-            return err;
-    }
-    // ---- the chunk lengths of the call's blocks (the raw copy and the BlockIndex kernel read them) ----
+    if (pos && ((err = reserve_dev(ctx, s->d_gather, pos + 256)) || (err = lthip_gather_upload(ctx, s->wbufs, s->d_carry.p, from_carry, s->d_gather.p)) ||
+                (err = lthip_gather_upload(ctx, s->wbufs, d_data, from_data, s->d_gather.p))))
+        return err;
+    // ---- the chunk lengths of the call's blocks (the raw copy and the BlockIndex kernel read them), the raw blocks' addresses ----
     if ((err = lthip_stage_upload(ctx, s->d_ul.p, s->u_len.data() + c0, nc * 4, st)))
         return err;
-    // ---- raw blocks: straight from d_carry / the slice's data into the image, behind the BlockIndex ----
-    if (!r_first.empty())
-    {
-        std::vector<uint64_t> addr(nc, 0); // (the two places are two allocations: the copy takes addresses, relative to a null base)
-        for (size_t i = 0; i < r_first.size(); ++i)
-            for (uint64_t c = c0 + r_first[i]; c < c0 + r_first[i] + r_count[i]; ++c)
-                addr[c - c0] = c < fresh ? (uint64_t)(uintptr_t)s->d_carry.p + s->carry_off[c - open0] : (uint64_t)(uintptr_t)d_data + s->u_src[c - fresh];
-        if ((err = reserve_dev(ctx, s->d_usrc, nc * 8)) || (err = lthip_stage_upload(ctx, s->d_usrc.p, addr.data(), nc * 8, st)) ||
-            (err = lthip_raw_copy_blocks(ctx, (uint32_t)r_first.size(), r_first.data(), r_count.data(), r_payload.data(), 0u, (uint32_t)nc,
-                                         (const uint32_t*)s->d_ul.p, (const uint64_t*)s->d_usrc.p, nullptr, d_arena, raw_bytes + 1)))
-            return err;
-    }
-    // ---- the codec, straight to image + header size: a call per (codec, quality) and place the sources lie in ----
-    std::vector<uint64_t> src_off, dst_off;
-    std::vector<uint32_t> src_size, dst_cap, which;
-    for (size_t call = 0; call < keys.size() * 3; ++call)
-    {
-        const size_t key = call / 3;
-        const uint8_t pass = (uint8_t)(call % 3);
-        src_off.clear();
-        src_size.clear();
-        dst_off.clear();
-        dst_cap.clear();
-        which.clear();
-        for (size_t b = b0; b < b1; ++b)
-            if (kind[b - b0] == pass && bcodec[b - b0] == keys[key])
-            {
-                const uint64_t first = s->b_first[b];
-                src_off.push_back(pass == 0 ? s->u_src[first - fresh] : pass == 1 ? gpos[b - b0] : s->carry_off[first - open0]);
-                src_size.push_back((uint32_t)s->b_size[b]);
-                dst_off.push_back(img_off[b - b0] + lthip_stored_block_header_size((uint32_t)(s->b_first[b + 1] - first)));
-                dst_cap.push_back((uint32_t)block_codec_bound(keys[key].codec, s->b_size[b]));
-                which.push_back((uint32_t)(b - b0));
-            }
-        if (src_off.empty())
-            continue;
-        const void* src = pass == 0 ? d_data : pass == 1 ? s->d_gather.p : s->d_carry.p;
-        const uint32_t k = (uint32_t)src_off.size();
-        // the codec writes one size per block of the call: a run of neighbours writes them in place, anything else goes through a list
-        // of the call's own and is scattered (gather kernel on 4-byte ranges), as in lthip_ingest_write
-        bool contiguous = true;
-        for (uint32_t i = 1; i < k; ++i)
-            contiguous &= which[i] == which[i - 1] + 1;
-        uint32_t* d_sizes = (uint32_t*)s->d_comp.p + which[0];
-        if (!contiguous)
-        {
-            if ((err = reserve_dev(ctx, s->d_tmpsz, (size_t)k * 4)))
-                return err;
-            d_sizes = (uint32_t*)s->d_tmpsz.p;
-        }
-        if (keys[key].codec == LTHIP_CODEC_LZ4)
-            err = lthip_lz4_compress_blocks(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes, 0);
-        else
-            err = lthip_zstd_compress_blocks_q(ctx, src, k, src_off.data(), src_size.data(), d_arena, dst_off.data(), dst_cap.data(), d_sizes,
-                                               keys[key].quality);
-        if (err)
-            return err;
-        if (!contiguous)
-        {
-            Ranges sc;
-            for (uint32_t i = 0; i < k; ++i)
-            {
-                sc.src.push_back((uint64_t)i * 4u);
-                sc.len.push_back(4u);
-                sc.dst.push_back((uint64_t)which[i] * 4u);
-            }
-            if ((err = stream_gather(s, s->d_tmpsz.p, sc, s->d_comp.p)))
-                return err;
-        }
-    }
-    // ---- block hashes = hash of each block's chunk-hash array (:3753-3757), then the bytes around the payloads ----
-    std::vector<uint64_t> boff(cnt);
-    std::vector<uint32_t> blen(cnt), first32(cnt + 1), braw(cnt);
-    uint32_t max_len = 0;
-    uint64_t leaves = 0;
-    for (size_t b = b0; b < b1; ++b)
-    {
-        const size_t i = b - b0;
-        boff[i] = (s->b_first[b] - c0) * 8u;
-        blen[i] = (uint32_t)(s->b_first[b + 1] - s->b_first[b]) * 8u;
-        first32[i] = (uint32_t)(s->b_first[b] - c0);
-        braw[i] = (uint32_t)s->b_size[b];
-        max_len = std::max(max_len, blen[i]);
-        leaves += blen[i] ? (blen[i] + 1023u) >> 10 : 1u;
-    }
-    first32[cnt] = (uint32_t)nc;
+    if (!addr.empty() && ((err = reserve_dev(ctx, s->d_usrc, nc * 8)) || (err = lthip_stage_upload(ctx, s->d_usrc.p, addr.data(), nc * 8, st))))
+        return err;
+    const BlockBatchDev dev = {{d_data, s->d_gather.p, s->d_carry.p}, 3, (const uint64_t*)s->d_uh.p, (const uint32_t*)s->d_ul.p, 0u,
+                               (const uint64_t*)s->d_usrc.p, nullptr, (const uint64_t*)s->d_bhash.p, (uint32_t*)s->d_comp.p, d_arena};
+    if ((err = lthip_block_payloads(ctx, s->wbufs, bt, dev)))
+        return err;
+    // ---- block hashes = hash of each block's chunk-hash array (:3753-3757), then the bytes around the payloads (always with the blocks' tags) ----
+    BlockHashRanges r;
+    r.fill(bt.first.data(), cnt, 0);
     if ((err = lthip_stage_upload(ctx, s->d_uh.p, s->u_hash.data() + c0, nc * 8, st)) ||
-        (err = lthip_stage_upload(ctx, s->d_boff.p, boff.data(), cnt * 8, st)) || (err = lthip_stage_upload(ctx, s->d_blen.p, blen.data(), cnt * 4, st)) ||
-        (err = lthip_stage_upload(ctx, s->d_bfirst.p, first32.data(), (cnt + 1) * 4, st)) ||
-        (err = lthip_stage_upload(ctx, s->d_braw.p, braw.data(), cnt * 4, st)) || (err = lthip_stage_upload(ctx, s->d_bimg.p, img_off.data(), cnt * 8, st)) ||
-        (err = lthip_stage_upload(ctx, s->d_btag.p, s->b_tag.data() + b0, cnt * 4, st)))
+        (err = lthip_stage_upload(ctx, s->d_boff.p, r.off.data(), cnt * 8, st)) || (err = lthip_stage_upload(ctx, s->d_blen.p, r.len.data(), cnt * 4, st)) ||
+        (err = lthip_block_headers_upload(ctx, s->wbufs, bt, true)) ||
+        (err = lthip_hash_ranges_by_id(ctx, s->cfg.hash_identifier, s->d_uh.p, cnt, (const uint64_t*)s->d_boff.p, (const uint32_t*)s->d_blen.p, r.max_len,
+                                       r.leaves, (uint64_t*)s->d_bhash.p)) ||
+        (err = lthip_block_headers(ctx, s->wbufs, bt, dev, s->cfg, true)))
         return err;
-    if ((err = lthip_hash_ranges_by_id(ctx, s->cfg.hash_identifier, s->d_uh.p, cnt, (const uint64_t*)s->d_boff.p, (const uint32_t*)s->d_blen.p, max_len,
-                                       leaves, (uint64_t*)s->d_bhash.p)))
-        return err;
-    {
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_stored_block_headers, dim3((uint32_t)cnt), dim3(64), 0, st, (const uint32_t*)s->d_bfirst.p, (uint32_t)cnt,
-                           (const uint64_t*)s->d_uh.p, (const uint32_t*)s->d_ul.p, (const uint64_t*)s->d_bhash.p, s->cfg.hash_identifier,
-                           s->cfg.compression_type, (const uint32_t*)s->d_btag.p, (const uint32_t*)s->d_braw.p, (uint32_t*)s->d_comp.p,
-                           (const uint64_t*)s->d_bimg.p, (uint8_t*)d_arena,
-                           // (tag 0 means a raw image only where the session writes by tag: its entry of d_comp receives its raw size)
-                           s->cfg.codec == LTHIP_CODEC_NONE || s->cfg.codec == LTHIP_CODEC_BY_TAG ? 1u : 0u);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
     // ---- block hashes and compressed sizes on their way to the host ----
     Stream::Batch rec;
     if (!s->spare.empty())
@@ -412,11 +270,7 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
     LTHIP_CHECK(ctx, hipMemcpyAsync(rec.h.p, s->d_bhash.p, cnt * 8, hipMemcpyDeviceToHost, st));
     LTHIP_CHECK(ctx, hipMemcpyAsync((uint8_t*)rec.h.p + cnt * 8, s->d_comp.p, cnt * 4, hipMemcpyDeviceToHost, st));
     LTHIP_CHECK(ctx, hipEventRecord(rec.ev, st));
-    s->img_offsets = img_off;
-    s->img_hdr.resize(cnt);
-    for (size_t b = b0; b < b1; ++b)
-        s->img_hdr[b - b0] = (uint32_t)block_header_bytes(bcodec[b - b0].codec, (uint32_t)(s->b_first[b + 1] - s->b_first[b]));
-    s->img_sizes = s->img_hdr; // (headers only until the compressed sizes are collected)
+    s->img.set(b0, bt);
     return 0;
 }
 
@@ -545,13 +399,13 @@ int stream_slice_work(Stream* s, uint64_t first_job, uint64_t job_count, uint64_
     Ranges keep;
     for (uint64_t c = std::max<uint64_t>(s->b_first.back(), fresh); c < s->u_len.size(); ++c)
     {
-        keep.add(s->u_src[c - fresh], s->u_len[c], s->carry_bytes);
+        keep.add(s->u_src[c - fresh], s->u_len[c], s->carry_bytes, MERGE_BYTES);
         s->carry_off.push_back(s->carry_bytes);
         s->carry_bytes += s->u_len[c];
     }
     if (s->carry_bytes > block_limit(&s->cfg))
         return lthip_fail(ctx, EIO, "lthip_ingest_stream_slice", "the open block outgrew a block");
-    if ((err = stream_gather(s, d_data, keep, s->d_carry.p)))
+    if ((err = lthip_gather_upload(ctx, s->wbufs, d_data, keep, s->d_carry.p)))
         return err;
     LTHIP_CHECK(ctx, hipEventRecord(s->ev_call, st));
     return 0;
@@ -592,8 +446,9 @@ extern "C" void lthip_ingest_stream_destroy(lthip_ingest_stream* s)
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     lthip_seen_destroy(s->seen);
-    DBuf* dev[] = {&s->d_carry, &s->d_first, &s->d_gather, &s->d_gsrc, &s->d_glen, &s->d_gdst, &s->d_uh, &s->d_ul, &s->d_boff, &s->d_blen, &s->d_bhash,
-                   &s->d_comp, &s->d_tmpsz, &s->d_bfirst, &s->d_braw, &s->d_bimg, &s->d_btag, &s->d_vh, &s->d_vl, &s->d_known, &s->d_usrc};
+    DBuf* dev[] = {&s->d_carry, &s->d_first, &s->d_gather, &s->d_uh, &s->d_ul, &s->d_boff, &s->d_blen, &s->d_bhash, &s->d_comp, &s->d_vh, &s->d_vl,
+                   &s->d_known, &s->d_usrc, &s->wbufs.d_tmpsz, &s->wbufs.d_gsrc, &s->wbufs.d_glen, &s->wbufs.d_gdst, &s->wbufs.d_bfirst, &s->wbufs.d_braw,
+                   &s->wbufs.d_bimg, &s->wbufs.d_btag};
     for (DBuf* b : dev)
         if (b->p)
             (void)hipFree(b->p);
@@ -636,8 +491,7 @@ extern "C" int lthip_ingest_stream_create(lthip_ctx* ctx, const lthip_ingest_con
     // (cfg.compression_type too, as lthip_ingest_create checks it: it is the tag of every asset when there are no asset tags)
     for (uint32_t a = 0; a < (t->asset_tags ? t->asset_count + 1u : 1u); ++a)
         if (const int refused = tag_refusal(cfg->codec, a ? t->asset_tags[a - 1] : cfg->compression_type))
-            return lthip_fail(ctx, refused, "lthip_ingest_stream_create",
-                              refused == EINVAL ? "LTHIP_CODEC_NONE writes tag 0 only" : "LTHIP_CODEC_BY_TAG: a tag names no codec of this library");
+            return lthip_fail(ctx, refused, "lthip_ingest_stream_create", tag_refusal_text(refused));
     // the jobs of lthip_make_jobs: asset after asset, 1 + size / part jobs each (src/longtail.c:2399-2404, 2432-2457)
     const uint32_t na = t->asset_count;
     const uint64_t part = (uint64_t)cfg->target_chunk_size * 1024u;
@@ -688,7 +542,6 @@ extern "C" int lthip_ingest_stream_create(lthip_ctx* ctx, const lthip_ingest_con
     s->gathered_blocks = s->gathered_bytes = 0;
     s->carry_bytes = 0;
     s->ev_lists = s->ev_call = nullptr;
-    s->img_first = 0;
     // the lists and the table for the chunks the tree is expected to come to (chunks average the target size or more); both grow
     const uint64_t expect = std::min<uint64_t>(cfg->target_chunk_size ? tree_bytes / cfg->target_chunk_size + t->job_count : t->job_count, 1ull << 28);
     int err = 0;
@@ -780,16 +633,8 @@ extern "C" int lthip_ingest_stream_images(lthip_ingest_stream* s, uint64_t* out_
         err = lthip_fail(ctx, EIO, "lthip_ingest_stream_images", "hipEventSynchronize");
     if (err)
         return stream_fail(s, err);
-    for (size_t i = 0; i < s->img_hdr.size(); ++i)
-        s->img_sizes[i] = s->img_hdr[i] + s->b_comp[s->img_first + i]; // header (BlockIndex + [raw][compressed]) + payload
-    if (out_first_block)
-        *out_first_block = s->img_first;
-    if (out_count)
-        *out_count = s->img_offsets.size();
-    if (out_offsets)
-        *out_offsets = s->img_offsets.data();
-    if (out_sizes)
-        *out_sizes = s->img_sizes.data();
+    s->img.complete(s->b_comp.data());
+    s->img.get(out_first_block, out_count, out_offsets, out_sizes);
     return 0;
 }
 
@@ -803,8 +648,8 @@ extern "C" int lthip_ingest_stream_finish(lthip_ingest_stream* s, void* d_arena,
     if (s->sticky)
         return s->sticky;
     // ---- refused before any work ----
-    if (out && (out->struct_size < 16 || out->struct_size > 4096))
-        return lthip_fail(ctx, EINVAL, "lthip_ingest_stream_finish", "out_result->struct_size must be set to sizeof(lthip_ingest_result)");
+    if (!result_struct_ok(out))
+        return lthip_fail(ctx, EINVAL, "lthip_ingest_stream_finish", RESULT_STRUCT_TEXT);
     if (s->next_job != s->njobs)
         return lthip_fail(ctx, EINVAL, "lthip_ingest_stream_finish", "not every job of the tree has been delivered");
     const bool open = s->b_first.back() < s->u_len.size();
@@ -820,18 +665,10 @@ extern "C" int lthip_ingest_stream_finish(lthip_ingest_stream* s, void* d_arena,
     for (size_t c = 0; c < m; ++c)
         res.raw_bytes += s->u_len[c];
     res.version_index_size = lthip_version_index_size(s->na, s->unique_all, s->n_all, (uint32_t)s->path_data.size());
-    res.store_index_size = 16 + nb * 8 + m * 8 + nb * 12 + m * 4; // Longtail_GetStoreIndexDataSize
-    auto deliver = [&]() {
-        if (out)
-        {
-            const uint64_t have = out->struct_size;
-            res.struct_size = have < sizeof res ? have : sizeof res;
-            memcpy(out, &res, (size_t)res.struct_size);
-        }
-    };
+    res.store_index_size = store_index_size(nb, m);
     if ((h_version_index && version_index_capacity < res.version_index_size) || (h_store_index && store_index_capacity < res.store_index_size))
     {
-        deliver(); // (both sizes; nothing done: the call may be repeated)
+        deliver_result(out, &res); // (both sizes; nothing done: the call may be repeated)
         return lthip_fail(ctx, ENOMEM, "lthip_ingest_stream_finish", "index buffer too small");
     }
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -878,27 +715,7 @@ extern "C" int lthip_ingest_stream_finish(lthip_ingest_stream* s, void* d_arena,
     }
     // ---- the StoreIndex from the session's block table (Longtail_CreateStoreIndexFromBlocks :9060-9125, layout :8913-8931) ----
     if (h_store_index)
-    {
-        uint8_t* w = (uint8_t*)h_store_index;
-        // (a tree without chunks: Longtail_CreateMissingContent returns Longtail_CreateStoreIndexFromBlocks(0, 0), hash identifier 0, :6931-6943)
-        const uint32_t head[4] = {(1u << 24) /* LONGTAIL_STORE_INDEX_VERSION_1_0_0, :19-23 */, m ? s->cfg.hash_identifier : 0u, (uint32_t)nb,
-                                  (uint32_t)m};
-        memcpy(w, head, 16);
-        w += 16;
-        memcpy(w, s->b_hash.data(), nb * 8); // m_BlockHashes
-        w += nb * 8;
-        memcpy(w, s->u_hash.data(), m * 8); // m_ChunkHashes
-        w += m * 8;
-        uint32_t* bo = (uint32_t*)w; // m_BlockChunksOffsets, m_BlockChunkCounts, m_BlockTags
-        for (size_t b = 0; b < nb; ++b)
-        {
-            bo[b] = (uint32_t)s->b_first[b];
-            bo[nb + b] = (uint32_t)(s->b_first[b + 1] - s->b_first[b]);
-            bo[2 * nb + b] = s->b_tag[b];
-        }
-        w += nb * 12;
-        memcpy(w, s->u_len.data(), m * 4); // m_ChunkSizes
-    }
-    deliver();
+        write_store_index(h_store_index, s->cfg.hash_identifier, nb, m, s->b_hash.data(), s->u_hash.data(), s->b_first.data(), s->b_tag.data(), s->u_len.data());
+    deliver_result(out, &res);
     return 0;
 }

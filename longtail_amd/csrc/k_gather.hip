@@ -4,7 +4,7 @@
 // v_alignbit.  Only needed when a block is not already one contiguous range of the asset buffer (dedup holes,
 // assets whose sizes are not multiples of 16).
 #include "lthip_internal.h"
-#include "index_kernels.h"
+#include "store_layout.h"
 
 #include <algorithm>
 #include <vector>
@@ -392,10 +392,8 @@ extern "C" int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_count
     if (block_count == 0)
         return 0;
     const size_t nb = block_count;
-    std::vector<uint32_t> first(nb + 1), hlen(nb), cnt(nb);
-    std::vector<uint64_t> hoff(nb), payload(nb);
-    uint32_t max_len = 0;
-    uint64_t leaves = 0;
+    std::vector<uint32_t> first(nb + 1), cnt(nb);
+    std::vector<uint64_t> payload(nb);
     for (size_t b = 0; b <= nb; ++b)
     {
         if (block_first_chunk[b] > 0x7FFFFFF0ull || (b && block_first_chunk[b] < block_first_chunk[b - 1]))
@@ -409,12 +407,10 @@ extern "C" int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_count
         cnt[b] = first[b + 1] - first[b];
         if ((uint64_t)cnt[b] * 8u > 0xFFFFFFFFull)
             return lthip_fail(ctx, EINVAL, "raw block images", "a block of more than 2^29 chunks");
-        hoff[b] = (uint64_t)first[b] * 8u;
-        hlen[b] = cnt[b] * 8u;
-        max_len = std::max(max_len, hlen[b]);
-        leaves += hlen[b] ? (hlen[b] + 1023u) >> 10 : 1u;
         payload[b] = image_offsets[b] + lthip_block_index_size(cnt[b]);
     }
+    BlockHashRanges r;
+    r.fill(first.data(), nb, 0);
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // ---- the payloads first: the copy is the long part, the BlockIndex kernel runs behind it ----
@@ -432,17 +428,13 @@ extern "C" int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_count
     uint64_t* d_bh = d_img + nb2;
     uint32_t* d_len = (uint32_t*)(d_bh + nb2);
     uint32_t* d_firstc = d_len + nb2; // [nb + 1]
-    if ((err = lthip_stage_upload(ctx, d_off, hoff.data(), nb * 8, s)) || (err = lthip_stage_upload(ctx, d_img, image_offsets, nb * 8, s)) ||
-        (err = lthip_stage_upload(ctx, d_len, hlen.data(), nb * 4, s)) || (err = lthip_stage_upload(ctx, d_firstc, first.data(), (nb + 1) * 4, s)))
+    if ((err = lthip_stage_upload(ctx, d_off, r.off.data(), nb * 8, s)) || (err = lthip_stage_upload(ctx, d_img, image_offsets, nb * 8, s)) ||
+        (err = lthip_stage_upload(ctx, d_len, r.len.data(), nb * 4, s)) || (err = lthip_stage_upload(ctx, d_firstc, first.data(), (nb + 1) * 4, s)))
         return err;
-    if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes, nb, d_off, d_len, max_len, leaves, d_bh)))
+    if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes, nb, d_off, d_len, r.max_len, r.leaves, d_bh)))
         return err;
-    LaunchTimer t(ctx, LTHIP_K_GATHER);
-    hipLaunchKernelGGL(k_stored_block_headers, dim3(block_count), dim3(64), 0, s, (const uint32_t*)d_firstc, block_count, d_chunk_hashes,
-                       d_chunk_lens, (const uint64_t*)d_bh, hash_identifier, 0u, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                       (uint32_t*)nullptr, (const uint64_t*)d_img, (uint8_t*)d_arena, 1u);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
+    return lthip_launch_block_headers(ctx, LTHIP_K_GATHER, d_firstc, block_count, d_chunk_hashes, d_chunk_lens, d_bh, hash_identifier, 0u, nullptr, nullptr,
+                                      nullptr, d_img, d_arena, 1u);
 }
 
 extern "C" int lthip_job_ordinals(lthip_ctx* ctx, uint64_t my_job_count, const uint32_t* local_first, const uint32_t* global_first,

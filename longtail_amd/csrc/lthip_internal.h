@@ -290,6 +290,38 @@ int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* 
 int lthip_raw_copy_blocks(lthip_ctx* ctx, uint32_t count, const uint32_t* h_first, const uint32_t* h_count, const uint64_t* h_payload,
                           uint32_t chunk_base, uint32_t chunk_span, const uint32_t* d_lens, const uint64_t* d_src_offsets, const void* d_src,
                           void* d_arena, uint64_t bytes_bound);
+// The block writer of the ingest sessions (block_images.hip; the host side of a batch -- BlockBatch, Ranges -- and the tables the writer
+// keeps -- BlockImageBufs -- are in ingest_buffers.h).  What a session says about the device side of a batch:
+struct BlockBatchDev
+{
+    const void* places[3];         // the base pointers BlockBatch::place indexes, in the order the codec calls go
+    uint32_t nplaces;
+    const uint64_t* d_hashes;      // the chunk lists the batch's chunk ranges index ...
+    const uint32_t* d_lens;
+    uint32_t chunk_base;           // ... and the batch's first chunk in them
+    const uint64_t* d_raw_offsets; // raw blocks: chunk c of the lists lies at d_raw_src + d_raw_offsets[c] (lthip_raw_copy_blocks)
+    const void* d_raw_src;
+    const uint64_t* d_bhash;       // the batch's entries of the block hashes and of the compressed sizes
+    uint32_t* d_comp;
+    void* d_arena;
+};
+struct BlockBatch;
+struct BlockImageBufs;
+struct Ranges;
+// uploads the tables of `r` and copies its ranges from d_src to d_dst (lthip_gather_ranges)
+int lthip_gather_upload(lthip_ctx* ctx, BlockImageBufs& w, const void* d_src, const Ranges& r, void* d_dst);
+// the payloads of the batch's images: the raw copy, then the codec calls
+int lthip_block_payloads(lthip_ctx* ctx, BlockImageBufs& w, BlockBatch& bt, const BlockBatchDev& dev);
+// the bytes around them: the tables of k_stored_block_headers (with_tags: the blocks' tags too; without, every block carries
+// cfg.compression_type), and its launch -- behind the launch that writes dev.d_bhash
+int lthip_block_headers_upload(lthip_ctx* ctx, BlockImageBufs& w, const BlockBatch& bt, bool with_tags);
+int lthip_block_headers(lthip_ctx* ctx, const BlockImageBufs& w, const BlockBatch& bt, const BlockBatchDev& dev, const lthip_ingest_config& cfg,
+                        bool with_tags);
+// k_stored_block_headers on the context's stream, for the bulk calls that bring tables of their own (kid: the timing class)
+int lthip_launch_block_headers(lthip_ctx* ctx, int kid, const uint32_t* d_block_first_chunk, uint32_t nblocks, const uint64_t* d_chunk_hashes,
+                               const uint32_t* d_chunk_lens, const uint64_t* d_block_hashes, uint32_t hash_identifier, uint32_t tag,
+                               const uint32_t* d_block_tags, const uint32_t* d_raw_sizes, uint32_t* d_comp_sizes, const uint64_t* d_image_offsets,
+                               void* d_arena, uint32_t raw_mode);
 int lthip_launch_compact(lthip_ctx* ctx, const lthip_plan* plan, const uint2* region, const uint32_t* part_count,
                          uint32_t* d_part_first, uint64_t* d_chunk_offsets, uint32_t* d_chunk_lens);
 int lthip_exclusive_scan_u32(lthip_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint64_t n_bound, const uint32_t* d_n,

@@ -10,6 +10,7 @@
 // layout, byte for byte what Longtail_WriteVersionIndexToBuffer (:3415) would write.
 #include "lthip_internal.h"
 #include "index_kernels.h"
+#include "store_layout.h"
 
 #include <algorithm>
 #include <unordered_set>
@@ -202,9 +203,7 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
     if (block_count == 0)
         return 0;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::vector<uint32_t> first((size_t)block_count + 1), lens(block_count);
-    std::vector<uint64_t> offs(block_count);
-    uint32_t max_len = 0;
+    std::vector<uint32_t> first((size_t)block_count + 1);
     for (uint32_t b = 0; b <= block_count; ++b)
     {
         if (block_first_chunk[b] > 0x7FFFFFF0ull || (b && block_first_chunk[b] < block_first_chunk[b - 1]))
@@ -212,13 +211,10 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
         first[b] = (uint32_t)block_first_chunk[b];
     }
     for (uint32_t b = 0; b < block_count; ++b)
-    {
         if (image_offsets[b] & 7u)
             return lthip_fail(ctx, EINVAL, "stored blocks", "image offsets must be 8-byte aligned");
-        offs[b] = (uint64_t)first[b] * 8u;
-        lens[b] = (first[b + 1] - first[b]) * 8u;
-        max_len = lens[b] > max_len ? lens[b] : max_len;
-    }
+    BlockHashRanges r;
+    r.fill(first.data(), block_count, 0);
     DevBuf d_first, d_off, d_len, d_bh, d_raw, d_img;
     int err;
     if ((err = d_first.alloc(ctx, ((size_t)block_count + 1) * 4)) || (err = d_off.alloc(ctx, (size_t)block_count * 8)) ||
@@ -226,19 +222,17 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
         (err = d_raw.alloc(ctx, (size_t)block_count * 4)) || (err = d_img.alloc(ctx, (size_t)block_count * 8)))
         return err;
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_first.p, first.data(), ((size_t)block_count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, offs.data(), (size_t)block_count * 8, hipMemcpyHostToDevice, ctx->stream));
-    LTHIP_CHECK(ctx, hipMemcpyAsync(d_len.p, lens.data(), (size_t)block_count * 4, hipMemcpyHostToDevice, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, r.off.data(), (size_t)block_count * 8, hipMemcpyHostToDevice, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(d_len.p, r.len.data(), (size_t)block_count * 4, hipMemcpyHostToDevice, ctx->stream));
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_raw.p, raw_sizes, (size_t)block_count * 4, hipMemcpyHostToDevice, ctx->stream));
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_img.p, image_offsets, (size_t)block_count * 8, hipMemcpyHostToDevice, ctx->stream));
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // host vectors go out of scope
-    if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes, block_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, max_len, 0u,
-                                 (uint64_t*)d_bh.p)))
+    if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes, block_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, r.max_len, 0u,
+                                 (uint64_t*)d_bh.p)) ||
+        (err = lthip_launch_block_headers(ctx, LTHIP_K_OTHER, (const uint32_t*)d_first.p, block_count, d_chunk_hashes, d_chunk_lens, (const uint64_t*)d_bh.p,
+                                          hash_identifier, tag, nullptr, (const uint32_t*)d_raw.p, const_cast<uint32_t*>(d_comp_sizes) /* only read: raw_mode 0 */,
+                                          (const uint64_t*)d_img.p, d_arena, 0u)))
         return err;
-    LaunchTimer t(ctx, LTHIP_K_OTHER);
-    hipLaunchKernelGGL(k_stored_block_headers, dim3(block_count), dim3(64), 0, ctx->stream, (const uint32_t*)d_first.p, block_count,
-                       d_chunk_hashes, d_chunk_lens, (const uint64_t*)d_bh.p, hash_identifier, tag, (const uint32_t*)nullptr, (const uint32_t*)d_raw.p,
-                       const_cast<uint32_t*>(d_comp_sizes) /* only read: raw_mode 0 */, (const uint64_t*)d_img.p, (uint8_t*)d_arena, 0u);
-    LTHIP_LAUNCH_CHECK(ctx);
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // the DevBufs are freed on return
     return 0;
 }
@@ -295,66 +289,38 @@ extern "C" int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_co
         }
     const size_t m = m_hash.size();
     // greedy packing, :6801-6860
-    std::vector<uint32_t> b_off, b_cnt, b_tag;
-    const uint64_t limit = (uint64_t)max_block_size + max_block_size / 10;
-    for (size_t i = 0; i < m;)
+    std::vector<uint32_t> b_first(1, 0u), b_tag; // block b = chunks [b_first[b], b_first[b + 1])
+    for (size_t i = 0; i < m; i = b_first.back())
     {
-        uint64_t size = m_size[i];
-        size_t j = i + 1;
-        while (j < m && m_tag[j] == m_tag[i] && j - i < max_chunks_per_block && size + m_size[j] <= limit)
-            size += m_size[j++];
-        b_off.push_back((uint32_t)i);
-        b_cnt.push_back((uint32_t)(j - i));
+        uint64_t size;
+        b_first.push_back((uint32_t)next_block_end(m_size.data(), m_tag.data(), i, m, max_chunks_per_block, block_limit(max_block_size), &size));
         b_tag.push_back(m_tag[i]);
-        i = j;
     }
-    const size_t nb = b_off.size();
+    const size_t nb = b_tag.size();
     // block hashes = BLAKE3 of each block's chunk-hash array (:3753-3757)
     std::vector<uint64_t> b_hash(nb);
     if (nb)
     {
         DevBuf d_mh, d_o, d_l, d_bh;
-        std::vector<uint64_t> o(nb);
-        std::vector<uint32_t> l(nb);
-        uint32_t max_len = 0;
-        for (size_t b = 0; b < nb; ++b)
-        {
-            o[b] = (uint64_t)b_off[b] * 8u;
-            l[b] = b_cnt[b] * 8u;
-            max_len = l[b] > max_len ? l[b] : max_len;
-        }
+        BlockHashRanges r;
+        r.fill(b_first.data(), nb, 0);
         if ((err = d_mh.alloc(ctx, m * 8)) || (err = d_o.alloc(ctx, nb * 8)) || (err = d_l.alloc(ctx, nb * 4)) ||
             (err = d_bh.alloc(ctx, nb * 8)))
             return err;
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_mh.p, m_hash.data(), m * 8, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_o.p, o.data(), nb * 8, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_l.p, l.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(d_o.p, r.off.data(), nb * 8, hipMemcpyHostToDevice, ctx->stream));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(d_l.p, r.len.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_mh.p, nb, (const uint64_t*)d_o.p, (const uint32_t*)d_l.p, max_len, 0u, (uint64_t*)d_bh.p)))
+        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_mh.p, nb, (const uint64_t*)d_o.p, (const uint32_t*)d_l.p, r.max_len, 0u, (uint64_t*)d_bh.p)))
             return err;
         LTHIP_CHECK(ctx, hipMemcpyAsync(b_hash.data(), d_bh.p, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
     }
-    // Longtail_GetStoreIndexDataSize, :8913-8931
-    const size_t size = 16 + nb * 8 + m * 8 + nb * 12 + m * 4;
+    const size_t size = store_index_size(nb, m);
     *out_size = size;
     if (!out || out_capacity < size)
         return ENOMEM;
-    uint8_t* w = (uint8_t*)out;
-    const uint32_t head[4] = {(1u << 24) /* LONGTAIL_STORE_INDEX_VERSION_1_0_0, :19-23 */, hash_identifier, (uint32_t)nb, (uint32_t)m};
-    memcpy(w, head, 16);
-    w += 16;
-    memcpy(w, b_hash.data(), nb * 8);  // m_BlockHashes
-    w += nb * 8;
-    memcpy(w, m_hash.data(), m * 8);   // m_ChunkHashes
-    w += m * 8;
-    memcpy(w, b_off.data(), nb * 4);   // m_BlockChunksOffsets
-    w += nb * 4;
-    memcpy(w, b_cnt.data(), nb * 4);   // m_BlockChunkCounts
-    w += nb * 4;
-    memcpy(w, b_tag.data(), nb * 4);   // m_BlockTags
-    w += nb * 4;
-    memcpy(w, m_size.data(), m * 4);   // m_ChunkSizes
+    write_store_index(out, hash_identifier, nb, m, b_hash.data(), m_hash.data(), b_first.data(), b_tag.data(), m_size.data());
     return 0;
 }
 

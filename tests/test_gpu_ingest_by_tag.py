@@ -11,6 +11,7 @@ on the trees of tests/test_gpu_ingest_stream.py, against the reference (oracle/_
   * refusals: "by-tag" with a tag that names no codec here is ENOTSUP, "none" with a tag other than 0 EINVAL, from stream create and
     from the one-shot index (create, for cfg.compression_type); context and session work afterwards
   * codec "lz4" with tag 'lz42' and codec "by-tag" with the same tag give the same indexes and the same image bytes
+  * the one-shot session by tag in several codec batches: indexes, compressed sizes and the last batch's images are the one-batch session's
 
 The expected VersionIndex for per-asset tags is the reference's for ONE tag with its chunk-tag column replaced: a unique chunk carries
 the tag of the asset it is first seen in (src/longtail.c:2951-2970); the harness of oracle/ passes one tag to Longtail_CreateVersionIndex.
@@ -78,13 +79,13 @@ def expected_version_index(oracle, ref, target, asset_tags, max_block, max_chunk
     return bytes(vi)
 
 
-def run_one_shot(gpu, tree, target, codec, max_block, max_chunks, tag, asset_tags=None, store=None, ing=None):
+def run_one_shot(gpu, tree, target, codec, max_block, max_chunks, tag, asset_tags=None, store=None, ing=None, batch_bytes=0):
     """lthip_ingest_index / _write / _finish over the whole tree.  -> both indexes, the result, the images, the slice's host copies (in
     the shape of run_stream's result: one call, one slice)."""
     njobs, part = tree["part"].job_count, tree["part"]
     sl = chunk_jobs(gpu, tree, target, 0, njobs)
     if ing is None:
-        ing = keep(Ingest(gpu, target, max_block, max_chunks, codec, compression_type=tag))
+        ing = keep(Ingest(gpu, target, max_block, max_chunks, codec, compression_type=tag, batch_bytes=batch_bytes))
     if store is not None:
         ing.set_store(store)
     job_first = sl["d_first"].cpu().numpy().view(np.uint32).astype(np.uint64)
@@ -195,6 +196,67 @@ def test_every_block_is_written_as_its_tag_says(gpu, oracle, ref, target, max_bl
         assert len(met) >= 3 and 0 in met, met
         assert r["res"].compressed_bytes == stored
     assert (run["res"].blocks, run["res"].raw_bytes, run["res"].unique_local) == (one["res"].blocks, one["res"].raw_bytes, one["res"].unique_local)
+
+
+# ---- the one-shot session, by tag, in more than one codec batch ----
+
+SMALL_BATCH = 1 << 20
+
+
+def last_batch_start(raw_sizes, batch_bytes):
+    """Where lthip_ingest_write's last batch begins when the arena is no limit: a batch takes blocks until the next one would bring its
+    raw bytes above batch_bytes, and always at least one."""
+    b0 = acc = 0
+    for b, raw in enumerate(raw_sizes):
+        if b > b0 and acc + raw > batch_bytes:
+            b0, acc = b, 0
+        acc += raw
+    return b0
+
+
+@pytest.mark.parametrize("rotate_by", ["directory", "asset"])
+def test_by_tag_in_several_batches_writes_what_one_batch_writes(gpu, oracle, ref, rotate_by):
+    """A one-shot session that writes by tag in more than one batch: the block hashes, the compressed sizes, the tags and the scatter of
+    the codec calls' sizes of a batch all start at a block above 0.  Same indexes (the reference's), same compressed sizes of all blocks,
+    and the last batch's images are byte for byte those of the same blocks written in one batch.
+
+    The tags rotate over (0, 'lz42', 'ztd2', 'ztd4') by top-level directory, as in the tests above, and by asset.  By directory the tree's
+    blocks are four runs of one tag each, the tag-0 run first, and a last batch is a tail of the blocks no larger than the batches
+    before it: whatever the batch size it holds no tag-0 block and no codec's blocks with another's in between.  By asset it does, at
+    the 1 MiB of tests/test_gpu_ingest.py's packing-in-slices test: the conditions on the last batch are asserted for that case."""
+    target, max_block, max_chunks = CONFIGS[0]
+    tree = tree_of(oracle, ref, target)
+    over = (0, LZ4, ZTD2, ZTD4)
+    tags = rotating_tags(tree, over) if rotate_by == "directory" else np.array([over[a % len(over)] for a in range(len(tree["paths"]))], np.uint32)
+    expect_vi = expected_version_index(oracle, ref, target, tags, max_block, max_chunks)
+    uh, us, ut = version_unique_lists(expect_vi)
+    expect_si = ref_missing_content(ref, np.zeros(0, np.uint64), uh, us, ut, max_block, max_chunks)
+    once = run_one_shot(gpu, tree, target, "by-tag", max_block, max_chunks, None, asset_tags=tags)
+    small = run_one_shot(gpu, tree, target, "by-tag", max_block, max_chunks, None, asset_tags=tags, batch_bytes=SMALL_BATCH)
+    # ---- about this test's own input, read off the one-batch run's StoreIndex: the small run's last batch starts above block 0 and holds
+    # blocks of two codecs (a tag is a codec key here); by asset also a raw block, and one codec's blocks with another block in between ----
+    si = parse_store_index(once["si"])
+    raw = [int(si["chunk_sizes"][int(o) : int(o) + int(n)].astype(np.int64).sum()) for o, n in zip(si["block_offsets"], si["block_counts"])]
+    b0 = last_batch_start(raw, SMALL_BATCH)
+    last = [int(t) for t in si["block_tags"][b0:]]
+    assert 0 < b0 < len(raw)
+    assert len(set(last) - {0}) >= 2, [hex(t) for t in last]
+    if rotate_by == "asset":
+        assert 0 in last, [hex(t) for t in last]
+        assert any(np.diff(np.flatnonzero(np.array(last) == t)).max(initial=1) > 1 for t in set(last) - {0}), "every codec's blocks are one run"
+    assert once["res"].gathered_blocks > 0
+    # ---- what the issue is about ----
+    for name, r in (("one batch", once), ("small batches", small)):
+        assert r["vi"] == expect_vi, f"{name}: VersionIndex differs from the reference's for these tags"
+        assert r["si"] == expect_si, f"{name}: StoreIndex differs from Longtail_CreateMissingContent over the VersionIndex's unique lists"
+    assert small["res"].blocks == once["res"].blocks == len(raw) and (small["comp"] == once["comp"]).all()
+    assert (small["res"].compressed_bytes, small["res"].gathered_blocks, small["res"].gathered_bytes) == \
+        (once["res"].compressed_bytes, once["res"].gathered_blocks, once["res"].gathered_bytes)
+    (first_once, all_images), (first, images) = once["calls"][0], small["calls"][0]
+    assert first_once == 0 and len(all_images) == len(raw), "the default batch size takes the tree in one batch"
+    assert first == b0 and len(images) == len(raw) - b0, "the last batch is not the one this test reckoned with"
+    for b, image in enumerate(images, b0):
+        assert len(image) == len(all_images[b]) and (image == all_images[b]).all(), b
 
 
 # ---- with a store attached ----
