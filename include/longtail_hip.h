@@ -464,6 +464,10 @@ LTHIP_EXPORT int lthip_seen_add(lthip_seen* seen, uint64_t count, const uint64_t
                                 uint64_t* d_distinct);
 LTHIP_EXPORT uint64_t lthip_seen_total(const lthip_seen* seen); /* hashes added so far: host counter, no synchronisation */
 LTHIP_EXPORT uint64_t lthip_seen_grown(const lthip_seen* seen); /* how often the table has grown: host counter */
+/* The table as a hash -> position map: d_position[i] = position of the first occurrence of d_hashes[i] among everything added, or
+ * 0xFFFFFFFF when the table does not hold it.  Answers what every lthip_seen_add queued before it on the context's stream put in;
+ * asynchronous, never waits, changes nothing. */
+LTHIP_EXPORT int lthip_seen_find(const lthip_seen* seen, uint64_t count, const uint64_t* d_hashes, uint32_t* d_position);
 
 /* ---- the set of chunk hashes a store already holds (k_dedup.hip) -----------------------------------------------------------------
  * What an upload of version N + 1 into a store that holds versions 1 .. N consults: a device-resident set of 64-bit chunk hashes,
@@ -770,6 +774,98 @@ LTHIP_EXPORT uint64_t lthip_ingest_stream_table_grown(const lthip_ingest_stream*
  * lthip_ingest_stream_store_stats: the version-unique chunks (so far) that the store held, and their bytes; 0 / 0 without a store. */
 LTHIP_EXPORT int lthip_ingest_stream_set_store(lthip_ingest_stream* stream, const lthip_store* store);
 LTHIP_EXPORT int lthip_ingest_stream_store_stats(const lthip_ingest_stream* stream, uint64_t* known_chunks, uint64_t* known_bytes);
+
+/* ---- the restore session: stored blocks back into a version's assets (restore.hip) --------------------------------------------------
+ * The device side of Longtail_WriteVersion (src/longtail.c:6471-6573 with BuildAssetWriteList :6021 and WriteAssetsFromBlock :5700) and
+ * of DecompressBlock (compressblockstore.c:271-338) for a caller that holds a serialized VersionIndex, a serialized StoreIndex and the
+ * stored-block images the ingest sessions (or the reference) wrote, the images already in HBM: the assets' bytes are written into ONE
+ * device buffer, asset a at asset_offsets[a].  Single GPU; files are not written.
+ *   layout         host only.  The dense layout of a serialized VersionIndex's assets: asset_offsets[a] (may be NULL) = the end of asset
+ *                  a - 1 rounded up to `align` (a power of two, >= 1; EINVAL otherwise), *total_bytes = the end of the last asset,
+ *                  *asset_count = the version's assets.  EBADF for a blob that is short, of another version than 0.0.2, or inconsistent
+ *                  (a chunk index that names no chunk, an asset whose chunk sizes do not sum to its size, a path that does not end
+ *                  inside the blob, a hash identifier other than 'blk2' / 'blk3' / 'meow', a target chunk size of 2^31 or more).
+ *   create         reads both blobs (host memory, any alignment; they may be freed on return) and asset_offsets[asset_count] (host): any
+ *                  byte offsets into the output, no alignment required, LTHIP_RESTORE_SKIP leaves the asset out.  Builds the write plan
+ *                  on the device -- per selected asset and chunk one OCCURRENCE (chunk hash, destination, length), resolved against
+ *                  the StoreIndex's chunk hashes in an lthip_seen of the session's own and sorted block-major -- and waits for the
+ *                  stream once, for the plan's per-block counts.  EBADF: a malformed blob.  EINVAL: the blobs' hash identifiers differ
+ *                  (a StoreIndex without chunks has none), or a selected asset's window leaves [0, out_bytes).  ENOENT: a selected asset
+ *                  needs a chunk the StoreIndex does not hold (src/longtail.c:6081, :6094) or holds with another size.  ENOMEM.  On any
+ *                  error nothing stays allocated and the context stays usable.  Directories and empty files plan nothing; content and
+ *                  path hashes are not consulted.  cfg->verify: 1 = every chunk of a delivered block is hashed and compared.
+ *   needed_blocks  host only.  The blocks that hold a chunk of a selected asset, in StoreIndex order; block_hashes NULL or capacity too
+ *                  small: the count only.
+ *   scratch_bound  host arithmetic: the scratch a blocks call with these blocks needs -- round64(raw size) per needed block with a
+ *                  codec's tag, 0 for raw (tag 0) blocks, unneeded blocks and hashes the StoreIndex does not hold.
+ *   blocks         delivers block_count images: image i lies at d_images + image_offsets[i] (8-byte aligned, EINVAL otherwise) and is
+ *                  image_sizes[i] bytes long.  Refused before any work is queued, the session unchanged and usable: ENOENT a block hash
+ *                  the StoreIndex does not hold, EEXIST a block delivered before or twice in the call, ENOTSUP a needed block whose tag
+ *                  names no codec here ('btl?' ...), ENOMEM scratch below the bound.  A block no selected asset needs is accepted,
+ *                  counted and not touched.  Everything else is queued on the context's stream: the call never waits for the device
+ *                  (but where a scratch pool of the context has to grow, as in every bulk call, and for a BLAKE3 verify of chunks
+ *                  above 256 KiB, whose launcher reads a count back) and reads nothing back -- every decoder table comes from the
+ *                  StoreIndex and image_sizes: raw size = the sum of the block's chunk sizes, compressed size = image size -
+ *                  lthip_stored_block_header_size(n).  Queued per call:
+ *                    check    a wave per image compares block hash, hash identifier, chunk count, tag, every chunk hash and size, and
+ *                             for a tagged block the [raw][compressed] words, against the session's device copy of the StoreIndex; it
+ *                             reads nothing beyond image_sizes[i]; an image shorter than its header is bad
+ *                    decode   tagged blocks through lthip_lz4_decompress_blocks / lthip_zstd_decompress_blocks, one call per codec, into
+ *                             64-byte slots of d_scratch.  Both decoders take a payload at ANY byte position (they load the source by
+ *                             dwords around it, k_lz4_decode.hip / zd_execute.inc), so the payload -- 28 + 12 n bytes into an 8-byte
+ *                             aligned image, i.e. 4-byte aligned -- is decoded where it lies: the session does not realign it.  A raw
+ *                             block is not copied: its chunks lie at image + lthip_block_index_size(n)
+ *                    verify   (cfg.verify) the chunks of the good blocks hashed with the StoreIndex's hash type and compared
+ *                    scatter  every planned occurrence of the call's good blocks copied to its destination: 16-byte stores, source and
+ *                             destination at any, independent byte positions; no 4-byte word is read that holds no byte of the chunk (a
+ *                             chunk may end at the last byte of d_scratch or of an image).  Timed as LTHIP_K_GATHER (the decoders and
+ *                             the hashes as they always are, everything else as LTHIP_K_OTHER)
+ *                  d_images and d_scratch may be reused once the call's work has run.  The scatter, and a decoder's second pass, cost
+ *                  one more read and write of the output than a decoder writing into place would (first figures: README.md, "Restore
+ *                  session"; tools/restore_rate.py).
+ *   finish         the session's one full synchronisation.  0: every needed block was delivered and good.  ENOENT: needed blocks are
+ *                  outstanding (result.blocks_needed - the needed ones delivered); deliver more and call again.  EBADF: a delivered
+ *                  block was bad -- it takes precedence.  The result is filled either way (struct_size honoured).
+ *   block_status   after finish: per block hash 0 or flag bits; ENOENT for a hash the StoreIndex does not hold.
+ * THE GUARANTEE: no byte of a bad block reaches d_out, and nothing is written outside the selected assets' windows.  A block is bad
+ * when its header differs from the StoreIndex (LTHIP_RESTORE_BAD_HEADER), when its decoder does not return exactly the raw size -- a
+ * raw image that is not lthip_block_index_size(n) + raw size bytes long counts as that -- (LTHIP_RESTORE_BAD_PAYLOAD), or, with verify,
+ * when one of its chunks does not hash to its recorded hash (LTHIP_RESTORE_BAD_CHUNK).  The payload behind a wrong header is not
+ * judged: such a block carries LTHIP_RESTORE_BAD_HEADER alone.  The occurrences a bad block feeds keep what d_out held.  One session belongs to one context (and its thread) and must be destroyed before it. */
+#define LTHIP_RESTORE_SKIP 0xFFFFFFFFFFFFFFFFull
+#define LTHIP_RESTORE_NOT_DELIVERED 1u
+#define LTHIP_RESTORE_BAD_HEADER 2u
+#define LTHIP_RESTORE_BAD_PAYLOAD 4u
+#define LTHIP_RESTORE_BAD_CHUNK 8u
+typedef struct lthip_restore lthip_restore;
+typedef struct lthip_restore_config
+{
+    uint64_t struct_size; /* IN: sizeof(lthip_restore_config) of the caller's header; the library reads at most that */
+    uint32_t verify;      /* 0 or 1 */
+} lthip_restore_config;
+typedef struct lthip_restore_result
+{
+    uint64_t struct_size;       /* IN: sizeof(lthip_restore_result) of the caller's header; the library fills at most that */
+    uint64_t assets_selected;   /* assets with an offset other than LTHIP_RESTORE_SKIP */
+    uint64_t occurrences;       /* planned chunk writes */
+    uint64_t occurrences_written, bytes_written; /* those fed by delivered, good blocks */
+    uint64_t blocks_needed, blocks_delivered /* all accepted blocks, unneeded ones included */, blocks_unneeded, blocks_bad;
+    uint64_t chunks_mismatched; /* verify: chunks whose hash differed */
+    uint64_t decoded_bytes;     /* raw bytes of the tagged blocks whose decoder returned the raw size */
+} lthip_restore_result;
+LTHIP_EXPORT int lthip_restore_layout(const void* version_index, size_t version_index_size, uint64_t align, uint64_t* asset_offsets,
+                                      uint32_t* asset_count, uint64_t* total_bytes);
+LTHIP_EXPORT int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* config, const void* version_index,
+                                      size_t version_index_size, const void* store_index, size_t store_index_size,
+                                      const uint64_t* asset_offsets /*host, [asset_count]*/, uint64_t out_bytes, lthip_restore** out);
+LTHIP_EXPORT void lthip_restore_destroy(lthip_restore* restore);
+LTHIP_EXPORT int lthip_restore_needed_blocks(const lthip_restore* restore, uint64_t* block_hashes, uint64_t capacity, uint64_t* out_count);
+LTHIP_EXPORT size_t lthip_restore_scratch_bound(const lthip_restore* restore, uint32_t block_count, const uint64_t* block_hashes);
+LTHIP_EXPORT int lthip_restore_blocks(lthip_restore* restore, uint32_t block_count, const uint64_t* block_hashes /*host*/,
+                                      const void* d_images, const uint64_t* image_offsets /*host, 8-byte aligned*/,
+                                      const uint32_t* image_sizes /*host*/, void* d_scratch, uint64_t scratch_bytes, void* d_out);
+LTHIP_EXPORT int lthip_restore_finish(lthip_restore* restore, lthip_restore_result* out_result);
+LTHIP_EXPORT int lthip_restore_block_status(const lthip_restore* restore, uint32_t count, const uint64_t* block_hashes, uint32_t* status);
 
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets

@@ -167,6 +167,34 @@ __global__ void k_seen_lookup(const uint64_t* __restrict__ hashes, uint64_t n, c
     first_index[i] = f;
 }
 
+// k_seen_lookup for hashes that may be ABSENT (lthip_seen_find): the probe ends at the key or at an empty slot, and there is one -- at
+// most half of the slots are taken.  The position word of a key's slot is final once the inserts queued before this launch have run.
+__global__ void k_seen_find(const uint64_t* __restrict__ hashes, uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                            uint64_t mask, const uint32_t* special, uint32_t* __restrict__ position)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint64_t h = hashes[i];
+    uint32_t f = 0xFFFFFFFFu;
+    if (h == EMPTY_KEY)
+        f = *special; // (0xFFFFFFFF while that hash was never added)
+    else
+    {
+        uint64_t slot = mix64(h) & mask;
+        for (;;)
+        {
+            const uint64_t k = keys[slot];
+            if (k == h)
+                f = idx[slot];
+            if (k == h || k == EMPTY_KEY)
+                break;
+            slot = (slot + 1) & mask;
+        }
+    }
+    position[i] = f;
+}
+
 // growth: every live (key, position) pair of the old table into the new one.  The keys of a table are distinct, so a slot of the new
 // table is claimed by exactly one thread, which then owns its position word.
 __global__ void k_seen_reinsert(const uint64_t* __restrict__ old_keys, const uint32_t* __restrict__ old_idx, uint64_t old_slots,
@@ -423,6 +451,23 @@ extern "C" int lthip_seen_add(lthip_seen* t, uint64_t count, const uint64_t* d_h
     if (d_distinct)
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_distinct, distinct, 8, hipMemcpyDeviceToDevice, s));
     t->total += count;
+    return 0;
+}
+
+extern "C" int lthip_seen_find(const lthip_seen* t, uint64_t count, const uint64_t* d_hashes, uint32_t* d_position)
+{
+    if (!t || (count && (!d_hashes || !d_position)))
+        return EINVAL;
+    lthip_ctx* ctx = t->ctx;
+    if (count > 0x7FFFFFFFull * 256u)
+        return lthip_fail(ctx, EINVAL, "lthip_seen_find", "too many hashes in one call");
+    if (!count)
+        return 0;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    LaunchTimer tm(ctx, LTHIP_K_OTHER);
+    hipLaunchKernelGGL(k_seen_find, dim3((uint32_t)div_up_u64(count, 256)), dim3(256), 0, ctx->stream, d_hashes, count, (const uint64_t*)t->keys,
+                       (const uint32_t*)t->idx, t->slots - 1, (const uint32_t*)t->misc, d_position);
+    LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }
 

@@ -1,0 +1,784 @@
+// restore.hip -- the restore session (include/longtail_hip.h, "the restore session"): stored-block images in HBM back into the assets of
+// a version, the device side of Longtail_WriteVersion (src/longtail.c:6471-6573; BuildAssetWriteList :6021, WriteAssetsFromBlock :5700)
+// and DecompressBlock (compressblockstore.c:271-338).
+//
+//   create   the host expands the VersionIndex into OCCURRENCES (chunk hash, destination, length) -- prefix arithmetic over
+//            m_AssetChunkIndexes and m_ChunkSizes -- and the StoreIndex into per-chunk (block, offset in block).  The device resolves:
+//            the StoreIndex's chunk hashes go into an lthip_seen, lthip_seen_find gives every occurrence the position of its chunk,
+//            k_restore_resolve checks the size and counts occurrences per block, an exclusive scan gives every block its first entry,
+//            k_restore_fill places (offset in block, length, destination) block-major.  The block_count + 1 firsts come back once.
+//   blocks   k_restore_check_images (a wave per image, against the device copy of the StoreIndex) -> the decoders into 64-byte slots of
+//            the caller's scratch -> k_restore_ranges (the decoders' verdict into the block's status word; with verify the (offset,
+//            length) of every chunk) -> lthip_hash_ranges_by_id -> k_restore_compare -> k_restore_scatter over the call's entries.
+//            Nothing is allocated and nothing is waited for: the session's tables were sized by create.
+// The scatter and a decoder's second pass cost one more read and write of the output than decoding into place would: about a tenth on top
+// of the bare decoder calls (profiles/restore_rate.json).
+#include "lthip_internal.h"
+#include "restore_parse.h"
+#include "store_layout.h"
+
+#include <new>
+#include <unordered_map>
+
+namespace
+{
+
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int RT = 256;
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+
+// one delivered, needed block of a lthip_restore_blocks call
+struct RItem
+{
+    uint64_t image;  // where its image starts in d_images
+    uint64_t src;    // device address of its chunks' bytes: the image's payload (raw block) or its scratch slot
+    uint32_t size;   // bytes of the image
+    uint32_t block;  // its index in the StoreIndex
+    uint32_t raw;    // the sum of its chunk sizes
+    uint32_t efirst; // its first entry among the call's entries ...
+    uint32_t ebase;  // ... and in the plan
+    uint32_t vfirst; // its first chunk among the call's verify ranges
+};
+
+// ---- plan ----
+__global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint32_t* __restrict__ csize,
+                                  const uint32_t* __restrict__ cblock, uint32_t* __restrict__ hist, unsigned long long* __restrict__ bbytes,
+                                  unsigned long long* unresolved)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool miss = false;
+    if (i < n)
+    {
+        const uint32_t p = pos[i];
+        const uint32_t b = p == NONE ? NONE : cblock[p];
+        if (b == NONE || csize[p] != olen[i])
+            miss = true;
+        else
+        {
+            atomicAdd(&hist[b], 1u);
+            atomicAdd(&bbytes[b], (unsigned long long)olen[i]);
+        }
+    }
+    const uint64_t m = __builtin_amdgcn_ballot_w64(miss);
+    if (m && (threadIdx.x & 63) == 0)
+        atomicAdd(unresolved, (unsigned long long)__builtin_popcountll(m));
+}
+
+// the order of a block's entries is whatever the atomics give; the output does not depend on it
+__global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint64_t* __restrict__ odst,
+                               const uint32_t* __restrict__ csize, const uint32_t* __restrict__ cblock, const uint32_t* __restrict__ coff,
+                               const uint32_t* __restrict__ firsts, uint32_t* __restrict__ cursor, uint4* __restrict__ entries)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint32_t p = pos[i];
+    const uint32_t b = p == NONE ? NONE : cblock[p];
+    if (b == NONE || csize[p] != olen[i])
+        return;
+    const uint32_t slot = firsts[b] + atomicAdd(&cursor[b], 1u);
+    const uint64_t d = odst[i];
+    entries[slot] = make_uint4(coff[p], olen[i], (uint32_t)d, (uint32_t)(d >> 32));
+}
+
+// ---- a delivered image against the StoreIndex: one wave per image ----
+__global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __restrict__ items, uint32_t k, const uint8_t* __restrict__ images,
+                                                             const uint64_t* __restrict__ bhash, const uint32_t* __restrict__ bcoff,
+                                                             const uint32_t* __restrict__ bcnt, const uint32_t* __restrict__ btag,
+                                                             const uint32_t* __restrict__ braw, uint32_t hash_identifier,
+                                                             const uint64_t* __restrict__ chash, const uint32_t* __restrict__ csize,
+                                                             uint32_t* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x;
+    if (i >= k)
+        return;
+    const uint32_t lane = threadIdx.x;
+    const RItem it = items[i];
+    const uint32_t b = it.block, n = bcnt[b], tag = btag[b], c0 = bcoff[b], raw = braw[b];
+    const uint64_t hdr = 20ull + 12ull * n + (tag ? 8u : 0u);
+    uint32_t st = 0;
+    if ((uint64_t)it.size < hdr) // (nothing of it is read)
+        st = LTHIP_RESTORE_BAD_HEADER;
+    else
+    {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(images + it.image); // 8-byte aligned by contract
+        bool bad = false;
+        if (lane == 0)
+        {
+            const uint64_t h = bhash[b];
+            bad = w[0] != (uint32_t)h || w[1] != (uint32_t)(h >> 32) || w[2] != hash_identifier || w[3] != n || w[4] != tag;
+            if (tag) // [raw size][compressed size] behind the BlockIndex
+                bad = bad || w[5ull + 3ull * n] != raw || (uint64_t)w[6ull + 3ull * n] != (uint64_t)it.size - hdr;
+        }
+        for (uint32_t j = lane; j < n; j += 64)
+        {
+            const uint64_t h = chash[c0 + j];
+            bad = bad || w[5ull + 2ull * j] != (uint32_t)h || w[6ull + 2ull * j] != (uint32_t)(h >> 32) || w[5ull + 2ull * n + j] != csize[c0 + j];
+        }
+        if (__builtin_amdgcn_ballot_w64(bad))
+            st = LTHIP_RESTORE_BAD_HEADER;
+        else if (!tag && (uint64_t)it.size != hdr + raw) // a raw image is its BlockIndex and its chunks, no more and no less
+            st = LTHIP_RESTORE_BAD_PAYLOAD;
+    }
+    if (lane == 0)
+        status[b] = st;
+}
+
+// ---- behind the decoders: their verdict into the status word; with verify, the byte range of every chunk of the good blocks (a bad
+// block's chunks become empty ranges at offset 0: nothing of it is read) ----
+__global__ __launch_bounds__(64) void k_restore_ranges(const RItem* __restrict__ items, uint32_t k, const uint32_t* __restrict__ outsz,
+                                                       const uint32_t* __restrict__ bcoff, const uint32_t* __restrict__ bcnt,
+                                                       const uint32_t* __restrict__ csize, const uint32_t* __restrict__ coff,
+                                                       uint32_t* __restrict__ status, uint32_t verify, uint64_t base, uint64_t* __restrict__ voff,
+                                                       uint32_t* __restrict__ vlen, uint32_t* __restrict__ vblock, uint32_t* __restrict__ vchunk)
+{
+    const uint32_t i = blockIdx.x;
+    if (i >= k)
+        return;
+    const uint32_t lane = threadIdx.x;
+    const RItem it = items[i];
+    const uint32_t b = it.block;
+    uint32_t st = status[b];
+    if (!(st & LTHIP_RESTORE_BAD_HEADER) && outsz[i] != it.raw) // (the payload behind a wrong header is not judged)
+        st |= LTHIP_RESTORE_BAD_PAYLOAD;
+    if (lane == 0)
+        status[b] = st;
+    if (!verify)
+        return;
+    const uint32_t c0 = bcoff[b], n = bcnt[b];
+    for (uint32_t j = lane; j < n; j += 64)
+    {
+        const uint32_t r = it.vfirst + j, c = c0 + j;
+        voff[r] = st ? 0ull : it.src - base + coff[c];
+        vlen[r] = st ? 0u : csize[c];
+        vblock[r] = b;
+        vchunk[r] = c;
+    }
+}
+
+__global__ void k_restore_compare(uint32_t n, const uint64_t* __restrict__ vhash, const uint32_t* __restrict__ vblock,
+                                  const uint32_t* __restrict__ vchunk, const uint64_t* __restrict__ chash, uint32_t* status,
+                                  unsigned long long* mismatched)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n)
+        return;
+    const uint32_t b = vblock[r];
+    // (the header and payload bits were final before this launch; only the chunk bit is set beside these reads)
+    if (__hip_atomic_load(&status[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (LTHIP_RESTORE_BAD_HEADER | LTHIP_RESTORE_BAD_PAYLOAD))
+        return;
+    if (vhash[r] != chash[vchunk[r]])
+    {
+        atomicOr(&status[b], LTHIP_RESTORE_BAD_CHUNK);
+        atomicAdd(mismatched, 1ull);
+    }
+}
+
+// ---- the scatter: a workgroup per entry of the call's blocks, block-major.  The copy is k_gather_ranges' (k_gather.hip): the head up to
+// the destination's 16-byte boundary and the tail by bytes, in between 16-byte stores of a source realigned from dwords with v_alignbit.
+// The dwords loaded are those that hold a byte of the vector: q[0..3] always do (the source lies mis < 4 bytes into q[0]), q[4] is
+// loaded only when mis != 0, and then it holds the vector's last mis bytes.  Source and destination sit at any byte positions. ----
+__global__ __launch_bounds__(RT) void k_restore_scatter(const RItem* __restrict__ items, uint32_t k, const uint4* __restrict__ entries,
+                                                        const uint32_t* __restrict__ status, const uint32_t* __restrict__ outsz,
+                                                        uint32_t entry0, uint8_t* __restrict__ out)
+{
+    const uint32_t e = entry0 + blockIdx.x;
+    uint32_t lo = 0, hi = k; // items[lo].efirst <= e < items[hi].efirst: the block that owns entry e (every item has entries)
+    while (hi - lo > 1)
+    {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (items[mid].efirst <= e)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const RItem it = items[lo];
+    if (status[it.block] != 0u || outsz[lo] != it.raw) // no byte of a bad block reaches the output
+        return;
+    const uint4 en = entries[it.ebase + (e - it.efirst)];
+    const int tid = threadIdx.x;
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(it.src) + en.x;
+    uint8_t* d = out + ((uint64_t)en.z | ((uint64_t)en.w << 32));
+    uint32_t n = en.y;
+    uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
+    if (head > n)
+        head = n;
+    if ((uint32_t)tid < head)
+        d[tid] = s[tid];
+    d += head;
+    s += head;
+    n -= head;
+    const uint32_t nvec = n >> 4;
+    const uint32_t mis = (uint32_t)((uintptr_t)s & 3u);
+    const uint32_t sh = mis * 8u;
+    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s - mis);
+    for (uint32_t v = tid; v < nvec; v += RT)
+    {
+        const uint32_t* q = s4 + (size_t)v * 4u;
+        const u32x4_a4 a = *reinterpret_cast<const u32x4_a4*>(q);
+        const uint32_t x = mis ? q[4] : 0u;
+        uint4 o;
+        o.x = __builtin_amdgcn_alignbit(a.y, a.x, sh);
+        o.y = __builtin_amdgcn_alignbit(a.z, a.y, sh);
+        o.z = __builtin_amdgcn_alignbit(a.w, a.z, sh);
+        o.w = __builtin_amdgcn_alignbit(x, a.w, sh);
+        *reinterpret_cast<uint4*>(d + (size_t)v * 16u) = o;
+    }
+    const uint32_t done = nvec << 4;
+    if ((uint32_t)tid < n - done)
+        d[done + tid] = s[done + tid];
+}
+
+// host table -> device through the staging ring, in pieces, so that no staging slot grows to the size of an index
+int upload(lthip_ctx* ctx, void* d_dst, const void* h_src, size_t bytes)
+{
+    constexpr size_t PIECE = 4u << 20;
+    for (size_t o = 0; o < bytes; o += PIECE)
+    {
+        const int err = lthip_stage_upload(ctx, (uint8_t*)d_dst + o, (const uint8_t*)h_src + o, std::min(PIECE, bytes - o), ctx->stream);
+        if (err)
+            return err;
+    }
+    return 0;
+}
+
+// sub-allocation of one device allocation: sizes first (p == null), then the same calls again hand out the pieces
+struct Carver
+{
+    uint8_t* p = nullptr;
+    size_t at = 0;
+    template <class T> void take(T** out, size_t count)
+    {
+        if (p)
+            *out = reinterpret_cast<T*>(p + at);
+        at += (count * sizeof(T) + 255u) & ~(size_t)255u;
+    }
+};
+
+uint64_t round64(uint64_t x) { return (x + 63u) & ~(uint64_t)63u; }
+
+} // namespace
+
+struct lthip_restore
+{
+    lthip_ctx* ctx = nullptr;
+    uint32_t verify = 0, hash_identifier = 0;
+    uint32_t nb = 0, m = 0, nocc = 0, max_chunk = 0;
+    uint64_t block_chunks = 0; // the blocks' chunk counts summed: m for an index whose blocks share no chunk position
+    uint64_t assets_selected = 0, needed = 0, needed_delivered = 0, delivered_all = 0, unneeded = 0;
+    bool finished = false;
+    // the StoreIndex and the plan on the host
+    std::vector<uint64_t> bhash, bbytes, bleaves;
+    std::vector<uint32_t> bcnt, btag, braw, firsts, status;
+    std::vector<uint8_t> delivered, in_call;
+    std::unordered_map<uint64_t, uint32_t> block_of_hash;
+    // the device side: one allocation for what lives as long as the session, one for what only the plan needs
+    lthip_seen* seen = nullptr;
+    void *d_mem = nullptr, *d_tmp = nullptr;
+    uint64_t *d_chash = nullptr, *d_bhash = nullptr, *d_voff = nullptr, *d_vhash = nullptr;
+    uint32_t *d_csize = nullptr, *d_cblock = nullptr, *d_coff = nullptr, *d_bcoff = nullptr, *d_bcnt = nullptr, *d_btag = nullptr, *d_braw = nullptr,
+             *d_status = nullptr, *d_firsts = nullptr, *d_outsz = nullptr, *d_vlen = nullptr, *d_vblock = nullptr, *d_vchunk = nullptr;
+    uint4* d_entries = nullptr;
+    RItem* d_items = nullptr;
+    unsigned long long* d_counters = nullptr; // [0] occurrences the StoreIndex does not resolve, [1] chunks whose hash differed
+    // host tables of a lthip_restore_blocks call, kept for their capacity
+    std::vector<RItem> items;
+    std::vector<uint32_t> outsz, group[3], c_size, c_cap;
+    std::vector<uint64_t> c_src, c_dst;
+
+    bool is_needed(uint32_t b) const { return firsts[b + 1] != firsts[b]; }
+    void carve(Carver& c, size_t items_cap)
+    {
+        c.take(&d_chash, m), c.take(&d_csize, m), c.take(&d_cblock, m), c.take(&d_coff, m);
+        c.take(&d_bhash, nb), c.take(&d_bcoff, nb), c.take(&d_bcnt, nb), c.take(&d_btag, nb), c.take(&d_braw, nb), c.take(&d_status, nb);
+        c.take(&d_firsts, (size_t)nb + 1), c.take(&d_entries, nocc), c.take(&d_items, items_cap), c.take(&d_outsz, items_cap), c.take(&d_counters, 8);
+        if (verify)
+            c.take(&d_voff, block_chunks), c.take(&d_vhash, block_chunks), c.take(&d_vlen, block_chunks), c.take(&d_vblock, block_chunks),
+                c.take(&d_vchunk, block_chunks);
+    }
+};
+
+extern "C" int lthip_restore_layout(const void* version_index, size_t size, uint64_t align, uint64_t* asset_offsets, uint32_t* asset_count,
+                                    uint64_t* total_bytes)
+{
+    if (!version_index)
+        return EINVAL;
+    restore_parse::VersionIndex v;
+    int err = restore_parse::parse_version_index(version_index, size, &v);
+    if (!err)
+        err = restore_parse::layout(v, align, asset_offsets, total_bytes);
+    if (!err && asset_count)
+        *asset_count = v.asset_count;
+    return err;
+}
+
+extern "C" void lthip_restore_destroy(lthip_restore* r)
+{
+    if (!r)
+        return;
+    (void)hipSetDevice(r->ctx->device);
+    if (r->d_mem || r->d_tmp)
+        (void)hipStreamSynchronize(r->ctx->stream);
+    lthip_seen_destroy(r->seen);
+    if (r->d_mem)
+        (void)hipFree(r->d_mem);
+    if (r->d_tmp)
+        (void)hipFree(r->d_tmp);
+    delete r;
+}
+
+static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, const void* version_index, size_t vi_size, const void* store_index,
+                         size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes)
+{
+    lthip_ctx* ctx = r->ctx;
+    restore_parse::VersionIndex vi;
+    restore_parse::StoreIndex si;
+    if (restore_parse::parse_version_index(version_index, vi_size, &vi))
+        return lthip_fail(ctx, EBADF, "lthip_restore_create", "malformed version index");
+    if (restore_parse::parse_store_index(store_index, si_size, &si))
+        return lthip_fail(ctx, EBADF, "lthip_restore_create", "malformed store index");
+    if (si.chunk_count && si.hash_identifier != vi.hash_identifier)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_create", "the version index and the store index carry different hash identifiers");
+    if (vi.asset_count && !asset_offsets)
+        return EINVAL;
+    if (cfg)
+    {
+        if (cfg->struct_size < 8 || cfg->struct_size > 4096)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_create", "config->struct_size must be set to sizeof(lthip_restore_config)");
+        r->verify = cfg->struct_size >= 12 && cfg->verify ? 1u : 0u;
+    }
+    r->hash_identifier = vi.hash_identifier;
+    // ---- occurrences of the selected assets: destination = the asset's offset + the sizes of its chunks so far ----
+    std::vector<uint64_t> ohash, odst;
+    std::vector<uint32_t> olen;
+    for (uint64_t a = 0; a < vi.asset_count; ++a)
+    {
+        const uint64_t off = asset_offsets[a], size = vi.asset_sizes[a];
+        if (off == restore_parse::SKIP)
+            continue;
+        ++r->assets_selected;
+        if (!size)
+            continue; // directories and empty files plan nothing
+        if (off > out_bytes || size > out_bytes - off)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_create", "a selected asset's window leaves the output");
+        const uint64_t start = vi.asset_chunk_index_starts[a], count = vi.asset_chunk_counts[a];
+        if (ohash.size() + count > 0x7FFFFFF0ull)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_create", "more than 2^31 chunk writes in one session");
+        uint64_t at = off;
+        for (uint64_t k = 0; k < count; ++k)
+        {
+            const uint32_t c = vi.asset_chunk_indexes[start + k];
+            const uint32_t len = vi.chunk_sizes[c];
+            ohash.push_back(vi.chunk_hashes[c]);
+            odst.push_back(at);
+            olen.push_back(len);
+            at += len;
+        }
+    }
+    // ---- the StoreIndex: per block its tables, per chunk position the block that holds it and where ----
+    const uint32_t nb = r->nb = si.block_count, m = r->m = si.chunk_count;
+    const uint32_t nocc = r->nocc = (uint32_t)ohash.size();
+    if (m > 0x7FFFFFFFu)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_create", "more than 2^31 - 1 chunks in the store index");
+    std::vector<uint64_t> chash(m);
+    std::vector<uint32_t> csize(m), cblock(m, NONE), coff(m, 0u), bcoff(nb);
+    for (uint32_t c = 0; c < m; ++c)
+    {
+        chash[c] = si.chunk_hashes[c];
+        csize[c] = si.chunk_sizes[c];
+        r->max_chunk = std::max(r->max_chunk, csize[c]);
+    }
+    r->bhash.resize(nb), r->bcnt.resize(nb), r->btag.resize(nb), r->braw.resize(nb), r->bleaves.resize(nb);
+    for (uint32_t b = 0; b < nb; ++b)
+    {
+        r->bhash[b] = si.block_hashes[b];
+        bcoff[b] = si.block_chunk_offsets[b];
+        r->bcnt[b] = si.block_chunk_counts[b];
+        r->btag[b] = si.block_tags[b];
+        uint64_t off = 0, leaves = 0;
+        for (uint32_t k = 0; k < r->bcnt[b]; ++k)
+        {
+            const uint32_t c = bcoff[b] + k;
+            if (cblock[c] == NONE) // (blocks that share a chunk position: no writer produces them; the first block keeps it)
+            {
+                cblock[c] = b;
+                coff[c] = (uint32_t)off;
+            }
+            off += csize[c];
+            leaves += csize[c] ? ((uint64_t)csize[c] + 1023u) >> 10 : 1u;
+        }
+        r->braw[b] = (uint32_t)off; // (below 4 GiB: parse_store_index)
+        r->block_chunks += r->bcnt[b];
+        r->bleaves[b] = leaves;
+        r->block_of_hash.emplace(r->bhash[b], b);
+    }
+    if (r->block_chunks > 0x7FFFFFFFull)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_create", "the store index's blocks list more than 2^31 - 1 chunks");
+    r->delivered.assign(nb, 0), r->in_call.assign(nb, 0), r->status.assign(nb, 0u);
+    r->firsts.assign((size_t)nb + 1, 0u), r->bbytes.assign(nb, 0ull);
+    // ---- device memory: the session's, and the plan's temporaries ----
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    Carver size_of;
+    r->carve(size_of, nb);
+    LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_mem, size_of.at + 256));
+    Carver place;
+    place.p = (uint8_t*)r->d_mem;
+    r->carve(place, nb);
+    uint64_t *t_ohash = nullptr, *t_odst = nullptr;
+    unsigned long long* t_bbytes = nullptr;
+    uint32_t *t_olen = nullptr, *t_pos = nullptr, *t_hist = nullptr, *t_cursor = nullptr, *t_first = nullptr;
+    for (int pass = 0; pass < 2; ++pass)
+    {
+        Carver c;
+        c.p = (uint8_t*)r->d_tmp;
+        c.take(&t_ohash, nocc), c.take(&t_odst, nocc), c.take(&t_bbytes, nb), c.take(&t_olen, nocc), c.take(&t_pos, nocc), c.take(&t_hist, nb),
+            c.take(&t_cursor, nb), c.take(&t_first, m);
+        if (pass == 0)
+            LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_tmp, c.at + 256));
+    }
+    hipStream_t s = ctx->stream;
+    int err;
+    if ((err = upload(ctx, r->d_chash, chash.data(), (size_t)m * 8)) || (err = upload(ctx, r->d_csize, csize.data(), (size_t)m * 4)) ||
+        (err = upload(ctx, r->d_cblock, cblock.data(), (size_t)m * 4)) || (err = upload(ctx, r->d_coff, coff.data(), (size_t)m * 4)) ||
+        (err = upload(ctx, r->d_bhash, r->bhash.data(), (size_t)nb * 8)) || (err = upload(ctx, r->d_bcoff, bcoff.data(), (size_t)nb * 4)) ||
+        (err = upload(ctx, r->d_bcnt, r->bcnt.data(), (size_t)nb * 4)) || (err = upload(ctx, r->d_btag, r->btag.data(), (size_t)nb * 4)) ||
+        (err = upload(ctx, r->d_braw, r->braw.data(), (size_t)nb * 4)) || (err = upload(ctx, t_ohash, ohash.data(), (size_t)nocc * 8)) ||
+        (err = upload(ctx, t_odst, odst.data(), (size_t)nocc * 8)) || (err = upload(ctx, t_olen, olen.data(), (size_t)nocc * 4)))
+        return err;
+    LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, 64, s));
+    if (nb)
+    {
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->d_status, 0, (size_t)nb * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t_hist, 0, (size_t)nb * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t_cursor, 0, (size_t)nb * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t_bbytes, 0, (size_t)nb * 8, s));
+    }
+    // ---- the plan: hash -> position in the StoreIndex's chunk list, occurrences per block, firsts, entries block-major ----
+    if ((err = lthip_seen_create(ctx, m, &r->seen)) || (err = lthip_seen_add(r->seen, m, r->d_chash, t_first, nullptr)))
+        return err;
+    if (nocc)
+    {
+        if ((err = lthip_seen_find(r->seen, nocc, t_ohash, t_pos)))
+            return err;
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
+                           (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, t_hist, t_bbytes, r->d_counters);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    if ((err = lthip_exclusive_scan_u32(ctx, t_hist, r->d_firsts, nb, nullptr, LTHIP_K_OTHER)))
+        return err;
+    if (nocc)
+    {
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
+                           (const uint64_t*)t_odst, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, (const uint32_t*)r->d_coff,
+                           (const uint32_t*)r->d_firsts, t_cursor, r->d_entries);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    // ---- the one read-back: the firsts (and the bytes per block, for the statistics) and what did not resolve ----
+    unsigned long long unresolved = 0;
+    LTHIP_CHECK(ctx, hipMemcpyAsync(r->firsts.data(), r->d_firsts, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (nb)
+        LTHIP_CHECK(ctx, hipMemcpyAsync(r->bbytes.data(), t_bbytes, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(&unresolved, r->d_counters, 8, hipMemcpyDeviceToHost, s));
+    LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
+    if (unresolved)
+        return lthip_fail(ctx, ENOENT, "lthip_restore_create", "a selected asset needs a chunk the store index does not hold (or holds with another size)");
+    LTHIP_CHECK(ctx, hipFree(r->d_tmp));
+    r->d_tmp = nullptr;
+    for (uint32_t b = 0; b < nb; ++b)
+        r->needed += r->is_needed(b);
+    return 0;
+}
+
+extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const void* version_index, size_t vi_size,
+                                    const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes, lthip_restore** out)
+{
+    if (!ctx || !out || !version_index || !store_index)
+        return EINVAL;
+    *out = nullptr;
+    lthip_restore* r = new (std::nothrow) lthip_restore();
+    if (!r)
+        return ENOMEM;
+    r->ctx = ctx;
+    int err;
+    try
+    {
+        err = restore_build(r, cfg, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes);
+    }
+    catch (const std::bad_alloc&)
+    {
+        err = lthip_fail(ctx, ENOMEM, "lthip_restore_create", "host tables");
+    }
+    if (err)
+    {
+        lthip_restore_destroy(r); // (waits for what was queued; nothing stays allocated)
+        return err;
+    }
+    *out = r;
+    return 0;
+}
+
+extern "C" int lthip_restore_needed_blocks(const lthip_restore* r, uint64_t* block_hashes, uint64_t capacity, uint64_t* out_count)
+{
+    if (!r || !out_count)
+        return EINVAL;
+    *out_count = r->needed;
+    if (!block_hashes || capacity < r->needed)
+        return 0;
+    uint64_t k = 0;
+    for (uint32_t b = 0; b < r->nb; ++b)
+        if (r->is_needed(b))
+            block_hashes[k++] = r->bhash[b];
+    return 0;
+}
+
+extern "C" size_t lthip_restore_scratch_bound(const lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes)
+{
+    if (!r || (block_count && !block_hashes))
+        return 0;
+    uint64_t bytes = 0;
+    for (uint32_t i = 0; i < block_count; ++i)
+    {
+        const auto it = r->block_of_hash.find(block_hashes[i]);
+        if (it != r->block_of_hash.end() && r->is_needed(it->second) && r->btag[it->second] != 0u)
+            bytes += round64(r->braw[it->second]);
+    }
+    return (size_t)bytes;
+}
+
+static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images, const uint64_t* image_offsets,
+                         const uint32_t* image_sizes, void* d_scratch, void* d_out)
+{
+    lthip_ctx* ctx = r->ctx;
+    // ---- the call's needed blocks in three groups: not decoded (raw blocks; an image too short to hold a payload), LZ4, zstd ----
+    for (auto& g : r->group)
+        g.clear();
+    for (uint32_t i = 0; i < block_count; ++i)
+    {
+        const uint32_t b = r->block_of_hash.find(block_hashes[i])->second;
+        r->delivered[b] = 1;
+        ++r->delivered_all;
+        if (!r->is_needed(b))
+        {
+            ++r->unneeded;
+            continue;
+        }
+        ++r->needed_delivered;
+        const int codec = codec_of_tag(r->btag[b]);
+        const bool payload = (uint64_t)image_sizes[i] > lthip_stored_block_header_size(r->bcnt[b]);
+        r->group[codec == LTHIP_CODEC_NONE || !payload ? 0 : codec == LTHIP_CODEC_LZ4 ? 1 : 2].push_back(i);
+    }
+    r->finished = false;
+    const size_t k = r->group[0].size() + r->group[1].size() + r->group[2].size();
+    if (!k)
+        return 0;
+    r->items.clear(), r->outsz.clear();
+    uint64_t slot = 0, entries = 0, ranges = 0, leaves = 0;
+    for (int g = 0; g < 3; ++g)
+        for (const uint32_t i : r->group[g])
+        {
+            const uint32_t b = r->block_of_hash.find(block_hashes[i])->second;
+            const bool tagged = r->btag[b] != 0u;
+            RItem it;
+            it.image = image_offsets[i];
+            it.src = tagged ? (uint64_t)(uintptr_t)d_scratch + slot : (uint64_t)(uintptr_t)d_images + image_offsets[i] + lthip_block_index_size(r->bcnt[b]);
+            it.size = image_sizes[i];
+            it.block = b;
+            it.raw = r->braw[b];
+            it.efirst = (uint32_t)entries;
+            it.ebase = r->firsts[b];
+            it.vfirst = (uint32_t)ranges;
+            r->items.push_back(it);
+            r->outsz.push_back(tagged ? NONE : it.raw); // (a decoder overwrites its blocks' words; a raw block has nothing to decode)
+            if (tagged)
+                slot += round64(it.raw);
+            entries += r->firsts[b + 1] - r->firsts[b];
+            ranges += r->bcnt[b];
+            leaves += r->bleaves[b];
+        }
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int err;
+    if ((err = upload(ctx, r->d_items, r->items.data(), k * sizeof(RItem))) || (err = upload(ctx, r->d_outsz, r->outsz.data(), k * 4)))
+        return err;
+    {
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_check_images, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint8_t*)d_images,
+                           (const uint64_t*)r->d_bhash, (const uint32_t*)r->d_bcoff, (const uint32_t*)r->d_bcnt, (const uint32_t*)r->d_btag,
+                           (const uint32_t*)r->d_braw, r->hash_identifier, (const uint64_t*)r->d_chash, (const uint32_t*)r->d_csize, r->d_status);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    // ---- decode: one call per codec; sizes and places from the StoreIndex and image_sizes alone ----
+    size_t at = r->group[0].size();
+    for (int g = 1; g < 3; ++g)
+    {
+        const size_t cnt = r->group[g].size();
+        if (!cnt)
+            continue;
+        r->c_src.clear(), r->c_size.clear(), r->c_dst.clear(), r->c_cap.clear();
+        for (size_t j = 0; j < cnt; ++j)
+        {
+            const RItem& it = r->items[at + j];
+            const uint64_t hdr = lthip_stored_block_header_size(r->bcnt[it.block]);
+            r->c_src.push_back(it.image + hdr);
+            r->c_size.push_back((uint32_t)(it.size - hdr));
+            r->c_dst.push_back(it.src - (uint64_t)(uintptr_t)d_scratch);
+            r->c_cap.push_back(it.raw);
+        }
+        err = g == 1 ? lthip_lz4_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_scratch, r->c_dst.data(),
+                                                   r->c_cap.data(), r->d_outsz + at)
+                     : lthip_zstd_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_scratch, r->c_dst.data(),
+                                                    r->c_cap.data(), r->d_outsz + at);
+        if (err)
+            return err;
+        at += cnt;
+    }
+    // ---- the decoders' verdict, then verify, both before the scatter ----
+    const uint64_t base = slot ? std::min((uint64_t)(uintptr_t)d_images, (uint64_t)(uintptr_t)d_scratch) : (uint64_t)(uintptr_t)d_images;
+    {
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_ranges, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint32_t*)r->d_outsz,
+                           (const uint32_t*)r->d_bcoff, (const uint32_t*)r->d_bcnt, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_coff, r->d_status,
+                           r->verify, base, r->d_voff, r->d_vlen, r->d_vblock, r->d_vchunk);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    if (r->verify && ranges)
+    {
+        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, (const void*)(uintptr_t)base, ranges, r->d_voff, r->d_vlen, r->max_chunk, leaves,
+                                           r->d_vhash)))
+            return err;
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_compare, dim3((uint32_t)((ranges + 255u) / 256u)), dim3(256), 0, s, (uint32_t)ranges, (const uint64_t*)r->d_vhash,
+                           (const uint32_t*)r->d_vblock, (const uint32_t*)r->d_vchunk, (const uint64_t*)r->d_chash, r->d_status, r->d_counters + 1);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    LaunchTimer tm(ctx, LTHIP_K_GATHER);
+    constexpr uint64_t LAUNCH_ENTRIES = 1u << 23; // (a launch holds fewer than 2^32 threads)
+    for (uint64_t e0 = 0; e0 < entries; e0 += LAUNCH_ENTRIES)
+        hipLaunchKernelGGL(k_restore_scatter, dim3((uint32_t)std::min(LAUNCH_ENTRIES, entries - e0)), dim3(RT), 0, s, (const RItem*)r->d_items,
+                           (uint32_t)k, (const uint4*)r->d_entries, (const uint32_t*)r->d_status, (const uint32_t*)r->d_outsz, (uint32_t)e0,
+                           (uint8_t*)d_out);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images,
+                                    const uint64_t* image_offsets, const uint32_t* image_sizes, void* d_scratch, uint64_t scratch_bytes, void* d_out)
+{
+    if (!r || (block_count && (!block_hashes || !d_images || !image_offsets || !image_sizes)))
+        return EINVAL;
+    lthip_ctx* ctx = r->ctx;
+    // ---- the refusals, before anything is queued or changed ----
+    int refused = 0;
+    const char* why = "";
+    uint64_t scratch = 0;
+    bool any_needed = false;
+    uint32_t marked = 0;
+    for (; marked < block_count && !refused; ++marked)
+    {
+        const auto it = r->block_of_hash.find(block_hashes[marked]);
+        if (it == r->block_of_hash.end())
+        {
+            refused = ENOENT, why = "a block hash the store index does not hold";
+            break;
+        }
+        const uint32_t b = it->second;
+        if (r->delivered[b] || r->in_call[b])
+        {
+            refused = EEXIST, why = "a block was delivered before, or twice in this call";
+            break;
+        }
+        r->in_call[b] = 1;
+        if (image_offsets[marked] & 7u)
+            refused = EINVAL, why = "image offsets must be 8-byte aligned";
+        else if (r->is_needed(b))
+        {
+            any_needed = true;
+            if (codec_of_tag(r->btag[b]) < 0)
+                refused = ENOTSUP, why = "a needed block's tag names no codec of this library";
+            else if (r->btag[b] != 0u)
+                scratch += round64(r->braw[b]);
+        }
+    }
+    for (uint32_t i = 0; i < block_count && i <= marked; ++i) // (the marks of this call, the refused block's included)
+    {
+        const auto it = r->block_of_hash.find(block_hashes[i]);
+        if (it != r->block_of_hash.end() && !r->delivered[it->second])
+            r->in_call[it->second] = 0;
+    }
+    if (!refused && scratch > scratch_bytes)
+        refused = ENOMEM, why = "scratch below lthip_restore_scratch_bound";
+    if (!refused && ((scratch && !d_scratch) || (any_needed && !d_out)))
+        refused = EINVAL, why = "null scratch or output";
+    if (refused)
+        return lthip_fail(ctx, refused, "lthip_restore_blocks", why);
+    try
+    {
+        return restore_queue(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, d_out);
+    }
+    catch (const std::bad_alloc&)
+    {
+        return lthip_fail(ctx, ENOMEM, "lthip_restore_blocks", "host tables");
+    }
+}
+
+extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
+{
+    if (!r || (out && (out->struct_size < 16 || out->struct_size > 4096)))
+        return EINVAL;
+    lthip_ctx* ctx = r->ctx;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    unsigned long long mismatched = 0;
+    if (r->nb)
+        LTHIP_CHECK(ctx, hipMemcpyAsync(r->status.data(), r->d_status, (size_t)r->nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(&mismatched, r->d_counters + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+    LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
+    r->finished = true;
+    lthip_restore_result res;
+    memset(&res, 0, sizeof res);
+    res.assets_selected = r->assets_selected;
+    res.occurrences = r->nocc;
+    res.blocks_needed = r->needed;
+    res.blocks_delivered = r->delivered_all;
+    res.blocks_unneeded = r->unneeded;
+    res.chunks_mismatched = mismatched;
+    for (uint32_t b = 0; b < r->nb; ++b)
+    {
+        if (!r->delivered[b] || !r->is_needed(b))
+            continue;
+        if (r->status[b])
+            ++res.blocks_bad;
+        else
+        {
+            res.occurrences_written += r->firsts[b + 1] - r->firsts[b];
+            res.bytes_written += r->bbytes[b];
+        }
+        if (r->btag[b] != 0u && !(r->status[b] & (LTHIP_RESTORE_BAD_HEADER | LTHIP_RESTORE_BAD_PAYLOAD)))
+            res.decoded_bytes += r->braw[b];
+    }
+    if (out)
+    {
+        const uint64_t have = out->struct_size;
+        res.struct_size = have < sizeof res ? have : sizeof res;
+        memcpy(out, &res, (size_t)res.struct_size);
+    }
+    return res.blocks_bad ? EBADF : r->needed_delivered < r->needed ? ENOENT : 0;
+}
+
+extern "C" int lthip_restore_block_status(const lthip_restore* r, uint32_t count, const uint64_t* block_hashes, uint32_t* status)
+{
+    if (!r || (count && (!block_hashes || !status)))
+        return EINVAL;
+    if (!r->finished)
+        return lthip_fail(r->ctx, EINVAL, "lthip_restore_block_status", "valid after lthip_restore_finish");
+    for (uint32_t i = 0; i < count; ++i)
+    {
+        const auto it = r->block_of_hash.find(block_hashes[i]);
+        if (it == r->block_of_hash.end())
+            return lthip_fail(r->ctx, ENOENT, "lthip_restore_block_status", "a block hash the store index does not hold");
+        const uint32_t b = it->second;
+        status[i] = !r->is_needed(b) ? 0u : !r->delivered[b] ? LTHIP_RESTORE_NOT_DELIVERED : r->status[b];
+    }
+    return 0;
+}

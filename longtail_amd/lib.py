@@ -159,6 +159,15 @@ class HipLib:
         sig("lthip_seen_add", i32, [vp, u64, vp, vp, vp])
         sig("lthip_seen_total", u64, [vp])
         sig("lthip_seen_grown", u64, [vp])
+        sig("lthip_seen_find", i32, [vp, u64, vp, vp])
+        sig("lthip_restore_layout", i32, [vp, sz, u64, vp, P(u32), P(u64)])
+        sig("lthip_restore_create", i32, [vp, vp, vp, sz, vp, sz, vp, u64, P(vp)])
+        sig("lthip_restore_destroy", None, [vp])
+        sig("lthip_restore_needed_blocks", i32, [vp, vp, u64, P(u64)])
+        sig("lthip_restore_scratch_bound", sz, [vp, u32, vp])
+        sig("lthip_restore_blocks", i32, [vp, u32, vp, vp, vp, vp, vp, u64, vp])
+        sig("lthip_restore_finish", i32, [vp, vp])
+        sig("lthip_restore_block_status", i32, [vp, u32, vp, vp])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -879,6 +888,16 @@ class Seen:
         self._keep.append(hashes)  # read by the launches the call queued: kept until sync() or close()
         return first[:n], distinct
 
+    def find(self, hashes):
+        """-> int32 tensor: the position of the first occurrence of every hash among everything added so far, -1 (0xFFFFFFFF) where
+        the table does not hold it.  Answers what the add() calls before it put in; asynchronous on the context's stream."""
+        torch = self.ctx.torch
+        n = int(hashes.numel())
+        position = torch.empty(max(1, n), dtype=torch.int32, device=self.ctx._dev())
+        self.ctx._check(self.ctx.lib.dll.lthip_seen_find(self.h, n, _ptr(hashes) if n else None, _ptr(position)), "lthip_seen_find")
+        self._keep.append(hashes)
+        return position[:n]
+
     def sync(self):
         """Waits for the context's stream; the inputs of the add() calls so far are let go."""
         self.ctx.sync()
@@ -1039,6 +1058,111 @@ class IngestStream:
         c, b = C.c_uint64(0), C.c_uint64(0)
         self.ctx._check(self.ctx.lib.dll.lthip_ingest_stream_store_stats(self.h, C.byref(c), C.byref(b)), "lthip_ingest_stream_store_stats")
         return int(c.value), int(b.value)
+
+
+class RestoreConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64), ("verify", C.c_uint32)]
+
+
+class RestoreResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_uint64) for n in (
+        "assets_selected", "occurrences", "occurrences_written", "bytes_written", "blocks_needed", "blocks_delivered", "blocks_unneeded",
+        "blocks_bad", "chunks_mismatched", "decoded_bytes")]
+
+
+RESTORE_SKIP = 0xFFFFFFFFFFFFFFFF  # include/longtail_hip.h LTHIP_RESTORE_SKIP
+RESTORE_NOT_DELIVERED, RESTORE_BAD_HEADER, RESTORE_BAD_PAYLOAD, RESTORE_BAD_CHUNK = 1, 2, 4, 8
+
+
+class Restore:
+    """lthip_restore: stored-block images in HBM back into a version's assets, asset a at asset_offsets[a] of one device buffer
+    (include/longtail_hip.h, "the restore session").  layout() -> offsets; needed_blocks() -> which blocks to fetch; blocks() per batch of
+    images; finish() -> (0 / ENOENT: blocks outstanding / EBADF: a bad block, the result)."""
+
+    SKIP = RESTORE_SKIP
+
+    @staticmethod
+    def layout(version_index: bytes, align: int = 1, lib: Optional[HipLib] = None):
+        """-> (asset offsets: uint64 array, total bytes) of the dense layout at `align`-byte boundaries; host only."""
+        dll = (lib or load()).dll
+        raw = np.frombuffer(version_index, np.uint8)
+        n, total = C.c_uint32(0), C.c_uint64(0)
+        err = dll.lthip_restore_layout(raw.ctypes.data if len(raw) else None, len(raw), align, None, C.byref(n), C.byref(total))
+        if err:
+            raise LongtailHipError(err, "lthip_restore_layout")
+        offsets = np.zeros(n.value, np.uint64)
+        err = dll.lthip_restore_layout(raw.ctypes.data, len(raw), align, offsets.ctypes.data, C.byref(n), C.byref(total))
+        if err:
+            raise LongtailHipError(err, "lthip_restore_layout")
+        return offsets, int(total.value)
+
+    def __init__(self, ctx: "Context", version_index: bytes, store_index: bytes, asset_offsets, out_bytes: int, verify: bool = True):
+        self.ctx = ctx
+        self.h = None
+        vi, si = np.frombuffer(version_index, np.uint8), np.frombuffer(store_index, np.uint8)
+        offs = _u64arr(asset_offsets)
+        cfg = RestoreConfig(C.sizeof(RestoreConfig), 1 if verify else 0)
+        h = C.c_void_p()
+        ctx._check(ctx.lib.dll.lthip_restore_create(ctx.h, C.byref(cfg), vi.ctypes.data if len(vi) else None, len(vi),
+                                                    si.ctypes.data if len(si) else None, len(si), offs.ctypes.data if len(offs) else None,
+                                                    out_bytes, C.byref(h)), "lthip_restore_create")
+        self.h = h
+        self._keep = []
+
+    def close(self):
+        # (the C object reads its context when it is destroyed: a session that outlives its context is dropped, not touched again)
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.dll.lthip_restore_destroy(self.h)
+        self.h = None
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def needed_blocks(self) -> np.ndarray:
+        """The hashes of the blocks that hold a chunk of a selected asset, in StoreIndex order."""
+        n = C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_needed_blocks(self.h, None, 0, C.byref(n)), "lthip_restore_needed_blocks")
+        out = np.zeros(n.value, np.uint64)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_needed_blocks(self.h, out.ctypes.data, len(out), C.byref(n)), "lthip_restore_needed_blocks")
+        return out
+
+    def scratch_bound(self, block_hashes) -> int:
+        h = _u64arr(block_hashes)
+        return int(self.ctx.lib.dll.lthip_restore_scratch_bound(self.h, len(h), h.ctypes.data if len(h) else None))
+
+    def blocks(self, block_hashes, images, image_offsets, image_sizes, scratch, out):
+        """Delivers the images (a device uint8 tensor; image i at image_offsets[i], image_sizes[i] bytes) of these blocks; `scratch`: a
+        device uint8 tensor of at least scratch_bound(block_hashes) bytes, or None.  Asynchronous on the context's stream: the tensors
+        are kept until finish() or close()."""
+        h, o, z = _u64arr(block_hashes), _u64arr(image_offsets), _u32arr(image_sizes)
+        assert len(h) == len(o) == len(z)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_blocks(self.h, len(h), h.ctypes.data if len(h) else None, _ptr(images),
+                                                              o.ctypes.data if len(o) else None, z.ctypes.data if len(z) else None,
+                                                              _ptr(scratch), _numel(scratch), _ptr(out)), "lthip_restore_blocks")
+        self._keep.append((images, scratch, out))
+
+    def finish(self):
+        """-> (code, RestoreResult): 0, errno.ENOENT (needed blocks are outstanding: deliver them and call again) or errno.EBADF (a
+        delivered block was bad).  The session's one full synchronisation."""
+        res = RestoreResult()
+        res.struct_size = C.sizeof(RestoreResult)
+        code = self.ctx.lib.dll.lthip_restore_finish(self.h, C.byref(res))
+        if code not in (0, errno.ENOENT, errno.EBADF):
+            self.ctx._check(code, "lthip_restore_finish")
+        self._keep = []
+        return code, res
+
+    def block_status(self, block_hashes) -> np.ndarray:
+        """After finish(): per block 0 or RESTORE_* flag bits."""
+        h = _u64arr(block_hashes)
+        out = np.zeros(len(h), np.uint32)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_block_status(self.h, len(h), h.ctypes.data if len(h) else None,
+                                                                    out.ctypes.data if len(h) else None), "lthip_restore_block_status")
+        return out
 
 
 class Plan:
