@@ -848,10 +848,12 @@ typedef struct lthip_restore_result
     uint64_t struct_size;       /* IN: sizeof(lthip_restore_result) of the caller's header; the library fills at most that */
     uint64_t assets_selected;   /* assets with an offset other than LTHIP_RESTORE_SKIP */
     uint64_t occurrences;       /* planned chunk writes */
-    uint64_t occurrences_written, bytes_written; /* those fed by delivered, good blocks */
+    uint64_t occurrences_written, bytes_written; /* those fed by delivered, good blocks and, once carried, by good chunks of the base */
     uint64_t blocks_needed, blocks_delivered /* all accepted blocks, unneeded ones included */, blocks_unneeded, blocks_bad;
     uint64_t chunks_mismatched; /* verify: chunks whose hash differed */
     uint64_t decoded_bytes;     /* raw bytes of the tagged blocks whose decoder returned the raw size */
+    uint64_t base_occurrences, base_bytes; /* of the planned writes, those the base feeds (0 without a base) */
+    uint64_t base_chunks_mismatched;       /* verify: distinct base chunks whose hash differed */
 } lthip_restore_result;
 LTHIP_EXPORT int lthip_restore_layout(const void* version_index, size_t version_index_size, uint64_t align, uint64_t* asset_offsets,
                                       uint32_t* asset_count, uint64_t* total_bytes);
@@ -866,6 +868,68 @@ LTHIP_EXPORT int lthip_restore_blocks(lthip_restore* restore, uint32_t block_cou
                                       const uint32_t* image_sizes /*host*/, void* d_scratch, uint64_t scratch_bytes, void* d_out);
 LTHIP_EXPORT int lthip_restore_finish(lthip_restore* restore, lthip_restore_result* out_result);
 LTHIP_EXPORT int lthip_restore_block_status(const lthip_restore* restore, uint32_t count, const uint64_t* block_hashes, uint32_t* status);
+
+/* ---- updating a resident version: a base for the restore session (restore.hip) ------------------------------------------------------
+ * The device side of the reference's down-sync -- Longtail_GetRequiredChunkHashes (src/longtail.c:4349-4418) and the copying half of
+ * Longtail_ChangeVersion (:8013) -- for a caller in whose HBM version N lies restored while version N + 1 is wanted: the chunks the two
+ * share are copied from where they lie, and only the rest has to come out of delivered blocks.  The StoreIndex may then be the small
+ * one an incremental ingest returns (lthip_ingest*_set_store: the blocks N + 1 added), which lthip_restore_create refuses with ENOENT.
+ *   create_from_base  lthip_restore_create with a second source.  base->version_index: the serialized VersionIndex of the resident
+ *                  version (host, any alignment, may be freed on return); base->asset_offsets[a]: asset a of the base lies at
+ *                  d_base + asset_offsets[a], LTHIP_RESTORE_SKIP = not resident; every resident asset's window lies in
+ *                  [0, base->base_bytes).  An occurrence of the target is FED BY THE BASE when the base holds its chunk hash with the
+ *                  same size in a resident asset (the first such place, in asset and chunk order); otherwise it is resolved against the
+ *                  StoreIndex exactly as lthip_restore_create does; ENOENT when neither holds it.  The base wins when both hold a chunk:
+ *                  needed_blocks shrinks to the blocks that hold a chunk no resident asset has, and needed_blocks, scratch_bound,
+ *                  blocks and block_status work unchanged over that shorter list.  Still one read-back and one wait.  EINVAL: base or
+ *                  base->version_index is NULL, base->struct_size is not sizeof(lthip_restore_base), the hash identifiers of base and
+ *                  target differ, a resident base asset's window leaves [0, base_bytes).  EBADF: the base blob is malformed.  Every
+ *                  other refusal as lthip_restore_create; on any error nothing stays allocated and the context stays usable.
+ *   carry          queues the copy of every base-fed occurrence from d_base to d_out on the context's stream: never waits, reads nothing
+ *                  back, allocates nothing (but where a scratch pool of the context has to grow, and for a BLAKE3 verify of chunks
+ *                  above 256 KiB, as blocks).  The base-fed occurrences are kept in occurrence order (asset by asset, chunk by chunk);
+ *                  an entry that continues the one before it in source AND destination joins its run, and maximal runs are copied by
+ *                  the raw-block copy (k_raw_copy) in pieces of 32 KiB: an unchanged asset, and an unchanged stretch of a modified one,
+ *                  is one run.  Source and destination at any byte positions; no 4-byte word is read that holds no byte of a chunk.
+ *                  cfg.verify: before the copy the base chunks that feed something are hashed where they lie in d_base, with the
+ *                  VersionIndex's hash type, and compared with the base VersionIndex's hashes; a chunk that differs is counted and every
+ *                  occurrence it would have fed is left out and keeps what d_out held -- THE GUARANTEE extended to the base.  WITHOUT
+ *                  verify THE BASE IS TRUSTED and copied as it is.  EINVAL: the session has no base; d_base or d_out is NULL while
+ *                  there are base-fed occurrences; [d_base, d_base + base_bytes) and [d_out, d_out + out_bytes) overlap (the update is
+ *                  out of place).  EEXIST: carry was called before.  A refused call changes nothing.  carry and the blocks calls write
+ *                  disjoint destinations and may come in any order; d_base must stay valid and unchanged until the work has run.
+ *   finish         additionally ENOENT while base-fed occurrences exist and carry has not been called, EBADF (it keeps precedence)
+ *                  for a mismatched base chunk.  result.occurrences stays every planned write; base_occurrences / base_bytes are those
+ *                  planned from the base; occurrences_written / bytes_written count both sources and exclude what a mismatched base
+ *                  chunk would have fed. */
+typedef struct lthip_restore_base
+{
+    uint64_t struct_size;          /* IN: sizeof(lthip_restore_base) */
+    const void* version_index;     /* the serialized VersionIndex of the version that is resident (host, any alignment) */
+    uint64_t version_index_size;
+    const uint64_t* asset_offsets; /* host, [its asset count]: asset a of the base lies at d_base + asset_offsets[a];
+                                      LTHIP_RESTORE_SKIP = not resident */
+    uint64_t base_bytes;           /* every resident asset's window lies in [0, base_bytes) */
+} lthip_restore_base;
+LTHIP_EXPORT int lthip_restore_create_from_base(lthip_ctx* ctx, const lthip_restore_config* config, const lthip_restore_base* base,
+                                                const void* version_index, size_t version_index_size, const void* store_index,
+                                                size_t store_index_size, const uint64_t* asset_offsets /*host, [asset_count]*/,
+                                                uint64_t out_bytes, lthip_restore** out);
+LTHIP_EXPORT int lthip_restore_carry(lthip_restore* restore, const void* d_base, void* d_out);
+/* What changed between two serialized VersionIndexes, host only (version_diff.h): the lists of Longtail_CreateVersionDiff
+ * (src/longtail.c:7493-7756).  Assets are matched by path hash.  source_removed[source assets] / target_added[target assets]: asset
+ * indices only one version has; the content-modified and permissions-modified pairs [min of both asset counts]: an asset both have
+ * whose content hashes / permissions differ (it may be in both pairs), source and target index at the same position, in ascending
+ * path-hash order, identical with the reference's.  Removed assets are ordered by path length, longest first, added ones shortest first;
+ * the reference leaves assets of equal path length to its qsort, here they stay in ascending path-hash order.  Any list pointer may be
+ * NULL; counts[4] = {removed, added, modified content, modified permissions} is always filled.  EBADF: a malformed blob, or two assets
+ * of one version with the same path hash.  EINVAL: a NULL blob or counts, or the hash identifiers differ.  The restore session does not
+ * call it: it is what lets a caller restore only what changed (LTHIP_RESTORE_SKIP for every target asset outside target_added and
+ * target_content_modified) and tells it which files to delete or re-permission. */
+LTHIP_EXPORT int lthip_version_diff(const void* source_version_index, size_t source_size, const void* target_version_index, size_t target_size,
+                                    uint32_t* source_removed, uint32_t* target_added, uint32_t* source_content_modified,
+                                    uint32_t* target_content_modified, uint32_t* source_permissions_modified,
+                                    uint32_t* target_permissions_modified, uint32_t counts[4]);
 
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets

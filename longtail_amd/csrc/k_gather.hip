@@ -110,19 +110,8 @@ __global__ void k_job_ordinals(const uint32_t* __restrict__ part_first, uint32_t
 //                first chunk; every other slot of the block gets 0 pieces
 //   scan         pieces of the slots -> first piece of every slot (lthip_exclusive_scan_u32)
 //   k_raw_copy   a fixed grid of waves strides over the pieces; a piece finds its slot by bisection of the scan (scalar loads)
-constexpr uint32_t RAW_PIECE_VEC = 2048; // 16-byte vectors of a piece: 32 KiB, eight rounds of four requests per lane
-
-__device__ __forceinline__ uint32_t raw_pieces(uint64_t dst, uint64_t len)
-{
-    if (len == 0)
-        return 0u;
-    uint64_t head = (16u - (dst & 15u)) & 15u;
-    if (head > len)
-        head = len;
-    const uint64_t nvec = (len - head) >> 4;
-    return nvec ? (uint32_t)((nvec + RAW_PIECE_VEC - 1) / RAW_PIECE_VEC) : 1u;
-}
-
+// (the size of a piece, LTHIP_RAW_PIECE_VEC, and the pieces of a run, lthip_raw_pieces: lthip_internal.h -- the restore session's carry
+// forms runs of its own)
 __global__ __launch_bounds__(64) void k_raw_runs(const uint64_t* __restrict__ blk_payload, const uint32_t* __restrict__ blk_first,
                                                  const uint32_t* __restrict__ blk_count, uint32_t nblocks, uint32_t chunk_base,
                                                  const uint32_t* __restrict__ lens, const uint64_t* __restrict__ src_offsets,
@@ -169,7 +158,7 @@ __global__ __launch_bounds__(64) void k_raw_runs(const uint64_t* __restrict__ bl
             if (open && lane == 0) // the run carried in ends at the group's first start
             {
                 run_len[open_slot] = first_dst - open_dst;
-                pieces[open_slot] = raw_pieces(open_dst, first_dst - open_dst);
+                pieces[open_slot] = lthip_raw_pieces(open_dst, first_dst - open_dst);
             }
             open = true;
             open_slot = c0 + g + l - chunk_base;
@@ -186,7 +175,7 @@ __global__ __launch_bounds__(64) void k_raw_runs(const uint64_t* __restrict__ bl
                 if (above)
                 {
                     run_len[slot] = next_dst - dst;
-                    np = raw_pieces(dst, next_dst - dst);
+                    np = lthip_raw_pieces(dst, next_dst - dst);
                 }
             }
             if (!start || above) // (the open run's slot is written when it ends)
@@ -199,7 +188,7 @@ __global__ __launch_bounds__(64) void k_raw_runs(const uint64_t* __restrict__ bl
     if (open && lane == 0)
     {
         run_len[open_slot] = pos - open_dst;
-        pieces[open_slot] = raw_pieces(open_dst, pos - open_dst);
+        pieces[open_slot] = lthip_raw_pieces(open_dst, pos - open_dst);
     }
 }
 
@@ -337,6 +326,22 @@ extern "C" int lthip_exchange_reorder(lthip_ctx* ctx, const void* d_gathered, vo
     return 0;
 }
 
+int lthip_raw_copy_runs(lthip_ctx* ctx, const uint32_t* d_first_piece, uint32_t slots, const uint64_t* d_run_src, const uint64_t* d_run_dst,
+                        const uint64_t* d_run_len, const void* d_src, void* d_dst, uint64_t pieces_bound)
+{
+    if (slots == 0)
+        return 0;
+    // a fixed grid strides over the pieces (their number is on the device): eight workgroups per CU at most, fewer when the pieces are few
+    uint64_t grid = 2048;
+    if (pieces_bound)
+        grid = std::min<uint64_t>(grid, div_up_u64(pieces_bound, GT / 64u));
+    LaunchTimer t(ctx, LTHIP_K_GATHER);
+    hipLaunchKernelGGL(k_raw_copy, dim3((uint32_t)grid), dim3(GT), 0, ctx->stream, d_first_piece, slots, d_run_src, d_run_dst, d_run_len,
+                       (const uint8_t*)d_src, (uint8_t*)d_dst);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
 int lthip_raw_copy_blocks(lthip_ctx* ctx, uint32_t count, const uint32_t* h_first, const uint32_t* h_count, const uint64_t* h_payload,
                           uint32_t chunk_base, uint32_t chunk_span, const uint32_t* d_lens, const uint64_t* d_src_offsets, const void* d_src,
                           void* d_arena, uint64_t bytes_bound)
@@ -372,15 +377,8 @@ int lthip_raw_copy_blocks(lthip_ctx* ctx, uint32_t count, const uint32_t* h_firs
     }
     if ((err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, span, nullptr, LTHIP_K_GATHER)))
         return err;
-    // a fixed grid strides over the pieces (their number is on the device): eight workgroups per CU at most, fewer when the bytes are few
-    uint64_t grid = 2048;
-    if (bytes_bound)
-        grid = std::min<uint64_t>(grid, div_up_u64(bytes_bound / (RAW_PIECE_VEC * 16u) + span + k, GT / 64u));
-    LaunchTimer t(ctx, LTHIP_K_GATHER);
-    hipLaunchKernelGGL(k_raw_copy, dim3((uint32_t)grid), dim3(GT), 0, s, (const uint32_t*)first_piece, chunk_span, (const uint64_t*)run_src,
-                       (const uint64_t*)run_dst, (const uint64_t*)run_len, (const uint8_t*)d_src, (uint8_t*)d_arena);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
+    return lthip_raw_copy_runs(ctx, first_piece, chunk_span, run_src, run_dst, run_len, d_src, d_arena,
+                               bytes_bound ? bytes_bound / (LTHIP_RAW_PIECE_VEC * 16u) + span + k : 0);
 }
 
 extern "C" int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_count, const uint64_t* block_first_chunk, const uint64_t* d_chunk_hashes,

@@ -129,6 +129,7 @@ enum ScratchSlot
     S_RAW_BLOCKS,      // raw block images: per-block tables of lthip_raw_copy_blocks {payload offset, first chunk, chunk count}
     S_RAW_RUNS,        // ... its runs (one slot per chunk: source, destination, length), their piece counts and the scan of those
     S_RAW_TABLES,      // ... and the hash / BlockIndex tables of lthip_write_raw_block_images
+    S_CARRY_RUNS,      // restore session, lthip_restore_carry: boundary flags and their scan, the runs, their piece counts and the scan of those
     S_COUNT
 };
 
@@ -290,6 +291,24 @@ int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* 
 int lthip_raw_copy_blocks(lthip_ctx* ctx, uint32_t count, const uint32_t* h_first, const uint32_t* h_count, const uint64_t* h_payload,
                           uint32_t chunk_base, uint32_t chunk_span, const uint32_t* d_lens, const uint64_t* d_src_offsets, const void* d_src,
                           void* d_arena, uint64_t bytes_bound);
+// The copy under it, for a caller that brings a run table of its own (the restore session's carry): run i = d_run_len[i] bytes from
+// d_src + d_run_src[i] to d_dst + d_run_dst[i], any byte positions, cut into d_first_piece[i + 1] - d_first_piece[i] pieces
+// (lthip_raw_pieces of the run's destination and length; 0 for a slot that holds no run; d_first_piece: slots + 1 entries, the
+// exclusive scan of the piece counts).  pieces_bound: an upper bound of the pieces in all (0 = unknown).  Source and destination must not
+// overlap.  Nothing is waited for.
+int lthip_raw_copy_runs(lthip_ctx* ctx, const uint32_t* d_first_piece, uint32_t slots, const uint64_t* d_run_src, const uint64_t* d_run_dst,
+                        const uint64_t* d_run_len, const void* d_src, void* d_dst, uint64_t pieces_bound);
+constexpr uint32_t LTHIP_RAW_PIECE_VEC = 2048; // 16-byte vectors of a piece: 32 KiB, eight rounds of four requests per lane
+__device__ __forceinline__ uint32_t lthip_raw_pieces(uint64_t dst, uint64_t len)
+{
+    if (len == 0)
+        return 0u;
+    uint64_t head = (16u - (dst & 15u)) & 15u;
+    if (head > len)
+        head = len;
+    const uint64_t nvec = (len - head) >> 4;
+    return nvec ? (uint32_t)((nvec + LTHIP_RAW_PIECE_VEC - 1) / LTHIP_RAW_PIECE_VEC) : 1u;
+}
 // The block writer of the ingest sessions (block_images.hip; the host side of a batch -- BlockBatch, Ranges -- and the tables the writer
 // keeps -- BlockImageBufs -- are in ingest_buffers.h).  What a session says about the device side of a batch:
 struct BlockBatchDev

@@ -11,11 +11,23 @@
 //            the caller's scratch -> k_restore_ranges (the decoders' verdict into the block's status word; with verify the (offset,
 //            length) of every chunk) -> lthip_hash_ranges_by_id -> k_restore_compare -> k_restore_scatter over the call's entries.
 //            Nothing is allocated and nothing is waited for: the session's tables were sized by create.
+//   base     (lthip_restore_create_from_base) a version that lies restored in HBM is a second source.  The host expands it as it expands
+//            the target: per distinct chunk the offset of its first occurrence in a resident asset.  Its chunk hashes go into a second
+//            lthip_seen; k_restore_resolve gives an occurrence to the base when the base holds its hash with the same size at a resident
+//            offset, and to the StoreIndex otherwise.  Base-fed occurrences are compacted in OCCURRENCE order (a scan over flags) into
+//            (source offset, destination, length, base chunk); the base chunks that feed something are listed for verify.  All counts
+//            come back with the plan's one read-back.
+//   carry    k_restore_carry_bounds flags every entry that does not continue the one before it in source AND destination (with verify:
+//            after the listed base chunks were hashed where they lie and compared, k_restore_carry_compare; an entry of a chunk that
+//            differs is a boundary of its own and gets no pieces) -> scan -> k_restore_carry_runs: a boundary that starts a run finds
+//            the next boundary by bisection of the scan and writes {source, destination, length} and the run's pieces into its slot ->
+//            scan -> k_raw_copy (k_gather.hip).  An unchanged asset is one run.
 // The scatter and a decoder's second pass cost one more read and write of the output than decoding into place would: about a tenth on top
 // of the bare decoder calls (profiles/restore_rate.json).
 #include "lthip_internal.h"
 #include "restore_parse.h"
 #include "store_layout.h"
+#include "version_diff.h"
 
 #include <new>
 #include <unordered_map>
@@ -41,44 +53,195 @@ struct RItem
 };
 
 // ---- plan ----
+// what the plan kernels know of the base (all null without one): per occurrence its position among the base's chunks (lthip_seen_find),
+// per base chunk its size and the offset of its first resident occurrence (NOWHERE: none)
+constexpr uint64_t NOWHERE = ~0ull;
+struct BasePlan
+{
+    const uint32_t* opos;
+    const uint32_t* size;
+    const uint64_t* off;
+};
+__device__ __forceinline__ bool base_feeds(const BasePlan& bp, uint32_t i, uint32_t len, uint32_t* q)
+{
+    if (!bp.opos)
+        return false;
+    *q = bp.opos[i];
+    return *q != NONE && bp.size[*q] == len && bp.off[*q] != NOWHERE;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1)
+        v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// counters: [0] occurrences neither source resolves, [5] bytes the base feeds
 __global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint32_t* __restrict__ csize,
                                   const uint32_t* __restrict__ cblock, uint32_t* __restrict__ hist, unsigned long long* __restrict__ bbytes,
-                                  unsigned long long* unresolved)
+                                  unsigned long long* counters, BasePlan bp, uint32_t* __restrict__ oflag, uint32_t* __restrict__ bfeed,
+                                  uint32_t* __restrict__ bmark)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool miss = false;
+    unsigned long long fed = 0;
     if (i < n)
     {
-        const uint32_t p = pos[i];
-        const uint32_t b = p == NONE ? NONE : cblock[p];
-        if (b == NONE || csize[p] != olen[i])
-            miss = true;
+        const uint32_t len = olen[i];
+        uint32_t q = NONE;
+        if (base_feeds(bp, i, len, &q)) // the base wins when both hold the chunk
+        {
+            oflag[i] = 1u;
+            atomicAdd(&bfeed[q], 1u);
+            bmark[q] = 1u;
+            fed = len;
+        }
         else
         {
-            atomicAdd(&hist[b], 1u);
-            atomicAdd(&bbytes[b], (unsigned long long)olen[i]);
+            if (oflag)
+                oflag[i] = 0u;
+            const uint32_t p = pos[i];
+            const uint32_t b = p == NONE ? NONE : cblock[p];
+            if (b == NONE || csize[p] != len)
+                miss = true;
+            else
+            {
+                atomicAdd(&hist[b], 1u);
+                atomicAdd(&bbytes[b], (unsigned long long)len);
+            }
         }
     }
     const uint64_t m = __builtin_amdgcn_ballot_w64(miss);
     if (m && (threadIdx.x & 63) == 0)
-        atomicAdd(unresolved, (unsigned long long)__builtin_popcountll(m));
+        atomicAdd(counters, (unsigned long long)__builtin_popcountll(m));
+    if (bp.opos)
+    {
+        fed = wave_sum(fed);
+        if (fed && (threadIdx.x & 63) == 0)
+            atomicAdd(counters + 5, fed);
+    }
 }
 
-// the order of a block's entries is whatever the atomics give; the output does not depend on it
+// the order of a block's entries is whatever the atomics give; the output does not depend on it.  The base's entries keep the order of
+// the occurrences (ofirst: the scan of the flags): that order is what makes runs.
 __global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint64_t* __restrict__ odst,
                                const uint32_t* __restrict__ csize, const uint32_t* __restrict__ cblock, const uint32_t* __restrict__ coff,
-                               const uint32_t* __restrict__ firsts, uint32_t* __restrict__ cursor, uint4* __restrict__ entries)
+                               const uint32_t* __restrict__ firsts, uint32_t* __restrict__ cursor, uint4* __restrict__ entries, BasePlan bp,
+                               const uint32_t* __restrict__ ofirst, uint64_t* __restrict__ ksrc, uint64_t* __restrict__ kdst,
+                               uint32_t* __restrict__ klen, uint32_t* __restrict__ kchunk)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
+    const uint32_t len = olen[i];
+    const uint64_t d = odst[i];
+    uint32_t q = NONE;
+    if (base_feeds(bp, i, len, &q))
+    {
+        const uint32_t k = ofirst[i];
+        ksrc[k] = bp.off[q];
+        kdst[k] = d;
+        klen[k] = len;
+        kchunk[k] = q;
+        return;
+    }
     const uint32_t p = pos[i];
     const uint32_t b = p == NONE ? NONE : cblock[p];
-    if (b == NONE || csize[p] != olen[i])
+    if (b == NONE || csize[p] != len)
         return;
     const uint32_t slot = firsts[b] + atomicAdd(&cursor[b], 1u);
-    const uint64_t d = odst[i];
-    entries[slot] = make_uint4(coff[p], olen[i], (uint32_t)d, (uint32_t)(d >> 32));
+    entries[slot] = make_uint4(coff[p], len, (uint32_t)d, (uint32_t)(d >> 32));
+}
+
+// the base chunks that feed something, in chunk order (mfirst: the scan of their marks): the ranges verify hashes, and their 1 KiB
+// leaves summed (counters[6]: lthip_hash_ranges_by_id wants the total)
+__global__ void k_restore_carry_marked(uint32_t n, const uint32_t* __restrict__ bmark, const uint32_t* __restrict__ mfirst,
+                                       const uint32_t* __restrict__ bsize, const uint64_t* __restrict__ boff, uint64_t* __restrict__ voff,
+                                       uint32_t* __restrict__ vlen, uint32_t* __restrict__ vchunk, unsigned long long* counters)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long leaves = 0;
+    if (q < n && bmark[q])
+    {
+        const uint32_t k = mfirst[q], len = bsize[q];
+        voff[k] = boff[q];
+        vlen[k] = len;
+        vchunk[k] = q;
+        leaves = len ? ((unsigned long long)len + 1023u) >> 10 : 1u;
+    }
+    leaves = wave_sum(leaves);
+    if (leaves && (threadIdx.x & 63) == 0)
+        atomicAdd(counters + 6, leaves);
+}
+
+// ---- carry ----
+// counters: [2] base chunks whose hash differed, [3] the occurrences they would have fed, [4] and their bytes
+__global__ void k_restore_carry_compare(uint32_t n, const uint64_t* __restrict__ vhash, const uint32_t* __restrict__ vchunk,
+                                        const uint64_t* __restrict__ bhash, const uint32_t* __restrict__ bsize,
+                                        const uint32_t* __restrict__ bfeed, uint32_t* __restrict__ bbad, unsigned long long* counters)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n)
+        return;
+    const uint32_t q = vchunk[k];
+    const bool bad = vhash[k] != bhash[q];
+    bbad[q] = bad ? 1u : 0u;
+    if (bad)
+    {
+        atomicAdd(counters + 2, 1ull);
+        atomicAdd(counters + 3, (unsigned long long)bfeed[q]);
+        atomicAdd(counters + 4, (unsigned long long)bfeed[q] * bsize[q]);
+    }
+}
+
+// bound[i] = 1: entry i does not continue entry i - 1 -- it starts a run, or (bbad, verify) it is left out and breaks one
+__global__ void k_restore_carry_bounds(uint32_t n, const uint64_t* __restrict__ ksrc, const uint64_t* __restrict__ kdst,
+                                       const uint32_t* __restrict__ klen, const uint32_t* __restrict__ kchunk, const uint32_t* __restrict__ bbad,
+                                       uint32_t* __restrict__ bound)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    bool b = i == 0 || (bbad && (bbad[kchunk[i]] || bbad[kchunk[i - 1]]));
+    if (!b)
+    {
+        const uint64_t len = klen[i - 1];
+        b = ksrc[i] != ksrc[i - 1] + len || kdst[i] != kdst[i - 1] + len;
+    }
+    bound[i] = b ? 1u : 0u;
+}
+
+// rank = the exclusive scan of bound (n + 1 entries).  A boundary that starts a run ends it before the next boundary: the first j > i
+// with rank[j + 1] > rank[i] + 1, found by bisection (rank is monotone), or the end of the list.  The entries of a run follow each other
+// in the destination, so its length is the end of its last entry - its start.
+__global__ void k_restore_carry_runs(uint32_t n, const uint64_t* __restrict__ ksrc, const uint64_t* __restrict__ kdst,
+                                     const uint32_t* __restrict__ klen, const uint32_t* __restrict__ kchunk, const uint32_t* __restrict__ bbad,
+                                     const uint32_t* __restrict__ bound, const uint32_t* __restrict__ rank, uint64_t* __restrict__ run_src,
+                                     uint64_t* __restrict__ run_dst, uint64_t* __restrict__ run_len, uint32_t* __restrict__ pieces)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    uint32_t np = 0;
+    if (bound[i] && !(bbad && bbad[kchunk[i]]))
+    {
+        const uint32_t r = rank[i] + 1u; // boundaries up to and including i
+        uint32_t lo = i, hi = n;         // rank[lo + 1] == r (no boundary in (i, lo]); hi == n or rank[hi + 1] > r
+        while (hi - lo > 1)
+        {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (rank[mid + 1] > r)
+                hi = mid;
+            else
+                lo = mid;
+        }
+        const uint64_t d = kdst[i], len = kdst[lo] + klen[lo] - d;
+        run_src[i] = ksrc[i];
+        run_dst[i] = d;
+        run_len[i] = len;
+        np = lthip_raw_pieces(d, len);
+    }
+    pieces[i] = np;
 }
 
 // ---- a delivered image against the StoreIndex: one wave per image ----
@@ -267,20 +430,31 @@ struct lthip_restore
     uint64_t block_chunks = 0; // the blocks' chunk counts summed: m for an index whose blocks share no chunk position
     uint64_t assets_selected = 0, needed = 0, needed_delivered = 0, delivered_all = 0, unneeded = 0;
     bool finished = false;
+    // the base: its distinct chunks, what of the plan it feeds (the read-back of create), whether carry has queued it
+    bool has_base = false, carried = false;
+    uint32_t nub = 0, ncarry = 0, nmarked = 0, base_max_chunk = 0;
+    uint64_t out_bytes = 0, base_window = 0, carry_bytes = 0, carry_leaves = 0;
     // the StoreIndex and the plan on the host
     std::vector<uint64_t> bhash, bbytes, bleaves;
     std::vector<uint32_t> bcnt, btag, braw, firsts, status;
     std::vector<uint8_t> delivered, in_call;
     std::unordered_map<uint64_t, uint32_t> block_of_hash;
     // the device side: one allocation for what lives as long as the session, one for what only the plan needs
-    lthip_seen* seen = nullptr;
+    lthip_seen *seen = nullptr, *seen_base = nullptr;
     void *d_mem = nullptr, *d_tmp = nullptr;
     uint64_t *d_chash = nullptr, *d_bhash = nullptr, *d_voff = nullptr, *d_vhash = nullptr;
     uint32_t *d_csize = nullptr, *d_cblock = nullptr, *d_coff = nullptr, *d_bcoff = nullptr, *d_bcnt = nullptr, *d_btag = nullptr, *d_braw = nullptr,
              *d_status = nullptr, *d_firsts = nullptr, *d_outsz = nullptr, *d_vlen = nullptr, *d_vblock = nullptr, *d_vchunk = nullptr;
     uint4* d_entries = nullptr;
     RItem* d_items = nullptr;
-    unsigned long long* d_counters = nullptr; // [0] occurrences the StoreIndex does not resolve, [1] chunks whose hash differed
+    // [0] occurrences neither source resolves, [1] chunks of blocks whose hash differed, [2] base chunks whose hash differed, [3] the
+    // occurrences those would have fed, [4] and their bytes, [5] bytes the base feeds, [6] 1 KiB leaves of the base chunks that feed
+    unsigned long long* d_counters = nullptr;
+    // base-fed entries in occurrence order (room for every occurrence: how many the base feeds is known after the plan has run), per
+    // base chunk {hash, size, offset in d_base, occurrences fed, hash differed}, and with verify the ranges of the chunks that feed
+    uint64_t *d_ksrc = nullptr, *d_kdst = nullptr, *d_uhash = nullptr, *d_uoff = nullptr, *d_cvoff = nullptr, *d_cvhash = nullptr;
+    uint32_t *d_klen = nullptr, *d_kchunk = nullptr, *d_usize = nullptr, *d_ufeed = nullptr, *d_ubad = nullptr, *d_cvlen = nullptr,
+             *d_cvchunk = nullptr;
     // host tables of a lthip_restore_blocks call, kept for their capacity
     std::vector<RItem> items;
     std::vector<uint32_t> outsz, group[3], c_size, c_cap;
@@ -295,6 +469,11 @@ struct lthip_restore
         if (verify)
             c.take(&d_voff, block_chunks), c.take(&d_vhash, block_chunks), c.take(&d_vlen, block_chunks), c.take(&d_vblock, block_chunks),
                 c.take(&d_vchunk, block_chunks);
+        if (has_base)
+            c.take(&d_ksrc, nocc), c.take(&d_kdst, nocc), c.take(&d_klen, nocc), c.take(&d_kchunk, nocc), c.take(&d_uhash, nub),
+                c.take(&d_uoff, nub), c.take(&d_usize, nub), c.take(&d_ufeed, nub), c.take(&d_ubad, nub);
+        if (has_base && verify)
+            c.take(&d_cvoff, nub), c.take(&d_cvhash, nub), c.take(&d_cvlen, nub), c.take(&d_cvchunk, nub);
     }
 };
 
@@ -320,6 +499,7 @@ extern "C" void lthip_restore_destroy(lthip_restore* r)
     if (r->d_mem || r->d_tmp)
         (void)hipStreamSynchronize(r->ctx->stream);
     lthip_seen_destroy(r->seen);
+    lthip_seen_destroy(r->seen_base);
     if (r->d_mem)
         (void)hipFree(r->d_mem);
     if (r->d_tmp)
@@ -327,11 +507,12 @@ extern "C" void lthip_restore_destroy(lthip_restore* r)
     delete r;
 }
 
-static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, const void* version_index, size_t vi_size, const void* store_index,
-                         size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes)
+// `base` is optional: lthip_restore_create passes none, and then every step that serves it is skipped
+static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, const lthip_restore_base* base, const void* version_index,
+                         size_t vi_size, const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes)
 {
     lthip_ctx* ctx = r->ctx;
-    restore_parse::VersionIndex vi;
+    restore_parse::VersionIndex vi, bvi;
     restore_parse::StoreIndex si;
     if (restore_parse::parse_version_index(version_index, vi_size, &vi))
         return lthip_fail(ctx, EBADF, "lthip_restore_create", "malformed version index");
@@ -348,6 +529,50 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         r->verify = cfg->struct_size >= 12 && cfg->verify ? 1u : 0u;
     }
     r->hash_identifier = vi.hash_identifier;
+    r->out_bytes = out_bytes;
+    // ---- the base: per distinct chunk the offset of its first occurrence in a resident asset ----
+    std::vector<uint64_t> uhash, uoff;
+    std::vector<uint32_t> usize;
+    if (base)
+    {
+        if (base->struct_size < sizeof(lthip_restore_base) || base->struct_size > 4096)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "base->struct_size must be set to sizeof(lthip_restore_base)");
+        if (restore_parse::parse_version_index(base->version_index, (size_t)base->version_index_size, &bvi))
+            return lthip_fail(ctx, EBADF, "lthip_restore_create_from_base", "malformed version index of the base");
+        if (bvi.hash_identifier != vi.hash_identifier)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "the base and the target carry different hash identifiers");
+        if (bvi.asset_count && !base->asset_offsets)
+            return EINVAL;
+        r->has_base = true;
+        r->base_window = base->base_bytes;
+        const uint32_t nub = r->nub = bvi.chunk_count;
+        if (nub > 0x7FFFFFFFu)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "more than 2^31 - 1 chunks in the base");
+        uhash.resize(nub), usize.resize(nub), uoff.assign(nub, NOWHERE);
+        for (uint32_t c = 0; c < nub; ++c)
+        {
+            uhash[c] = bvi.chunk_hashes[c];
+            usize[c] = bvi.chunk_sizes[c];
+            r->base_max_chunk = std::max(r->base_max_chunk, usize[c]);
+        }
+        for (uint64_t a = 0; a < bvi.asset_count; ++a)
+        {
+            const uint64_t off = base->asset_offsets[a], size = bvi.asset_sizes[a];
+            if (off == restore_parse::SKIP || !size)
+                continue;
+            if (off > base->base_bytes || size > base->base_bytes - off)
+                return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "a resident asset's window leaves the base");
+            const uint64_t start = bvi.asset_chunk_index_starts[a], count = bvi.asset_chunk_counts[a];
+            uint64_t at = off;
+            for (uint64_t k = 0; k < count; ++k)
+            {
+                const uint32_t c = bvi.asset_chunk_indexes[start + k];
+                if (uoff[c] == NOWHERE)
+                    uoff[c] = at;
+                at += usize[c];
+            }
+        }
+    }
     // ---- occurrences of the selected assets: destination = the asset's offset + the sizes of its chunks so far ----
     std::vector<uint64_t> ohash, odst;
     std::vector<uint32_t> olen;
@@ -427,12 +652,17 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     uint64_t *t_ohash = nullptr, *t_odst = nullptr;
     unsigned long long* t_bbytes = nullptr;
     uint32_t *t_olen = nullptr, *t_pos = nullptr, *t_hist = nullptr, *t_cursor = nullptr, *t_first = nullptr;
+    uint32_t *t_bpos = nullptr, *t_oflag = nullptr, *t_ofirst = nullptr, *t_bfirst = nullptr, *t_bmark = nullptr, *t_mfirst = nullptr;
+    const uint32_t nub = r->nub;
     for (int pass = 0; pass < 2; ++pass)
     {
         Carver c;
         c.p = (uint8_t*)r->d_tmp;
         c.take(&t_ohash, nocc), c.take(&t_odst, nocc), c.take(&t_bbytes, nb), c.take(&t_olen, nocc), c.take(&t_pos, nocc), c.take(&t_hist, nb),
             c.take(&t_cursor, nb), c.take(&t_first, m);
+        if (base)
+            c.take(&t_bpos, nocc), c.take(&t_oflag, nocc), c.take(&t_ofirst, (size_t)nocc + 1), c.take(&t_bfirst, nub), c.take(&t_bmark, nub),
+                c.take(&t_mfirst, (size_t)nub + 1);
         if (pass == 0)
             LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_tmp, c.at + 256));
     }
@@ -445,6 +675,15 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         (err = upload(ctx, r->d_braw, r->braw.data(), (size_t)nb * 4)) || (err = upload(ctx, t_ohash, ohash.data(), (size_t)nocc * 8)) ||
         (err = upload(ctx, t_odst, odst.data(), (size_t)nocc * 8)) || (err = upload(ctx, t_olen, olen.data(), (size_t)nocc * 4)))
         return err;
+    if (base && ((err = upload(ctx, r->d_uhash, uhash.data(), (size_t)nub * 8)) || (err = upload(ctx, r->d_uoff, uoff.data(), (size_t)nub * 8)) ||
+                 (err = upload(ctx, r->d_usize, usize.data(), (size_t)nub * 4))))
+        return err;
+    if (base && nub)
+    {
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->d_ufeed, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->d_ubad, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t_bmark, 0, (size_t)nub * 4, s));
+    }
     LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, 64, s));
     if (nb)
     {
@@ -456,34 +695,68 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     // ---- the plan: hash -> position in the StoreIndex's chunk list, occurrences per block, firsts, entries block-major ----
     if ((err = lthip_seen_create(ctx, m, &r->seen)) || (err = lthip_seen_add(r->seen, m, r->d_chash, t_first, nullptr)))
         return err;
+    // ... and, with a base, hash -> position among the base's chunks: an occurrence the base feeds is not resolved against the StoreIndex
+    BasePlan bp = {nullptr, nullptr, nullptr};
+    if (base)
+    {
+        if ((err = lthip_seen_create(ctx, nub, &r->seen_base)) || (err = lthip_seen_add(r->seen_base, nub, r->d_uhash, t_bfirst, nullptr)))
+            return err;
+        if (nocc && (err = lthip_seen_find(r->seen_base, nocc, t_ohash, t_bpos)))
+            return err;
+        bp = BasePlan{t_bpos, r->d_usize, r->d_uoff};
+    }
     if (nocc)
     {
         if ((err = lthip_seen_find(r->seen, nocc, t_ohash, t_pos)))
             return err;
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
-                           (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, t_hist, t_bbytes, r->d_counters);
+                           (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, t_hist, t_bbytes, r->d_counters, bp, t_oflag, r->d_ufeed,
+                           t_bmark);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if ((err = lthip_exclusive_scan_u32(ctx, t_hist, r->d_firsts, nb, nullptr, LTHIP_K_OTHER)))
+        return err;
+    if (base && ((err = lthip_exclusive_scan_u32(ctx, t_oflag, t_ofirst, nocc, nullptr, LTHIP_K_OTHER)) ||
+                 (err = lthip_exclusive_scan_u32(ctx, t_bmark, t_mfirst, nub, nullptr, LTHIP_K_OTHER))))
         return err;
     if (nocc)
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
                            (const uint64_t*)t_odst, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, (const uint32_t*)r->d_coff,
-                           (const uint32_t*)r->d_firsts, t_cursor, r->d_entries);
+                           (const uint32_t*)r->d_firsts, t_cursor, r->d_entries, bp, (const uint32_t*)t_ofirst, r->d_ksrc, r->d_kdst, r->d_klen,
+                           r->d_kchunk);
         LTHIP_LAUNCH_CHECK(ctx);
     }
-    // ---- the one read-back: the firsts (and the bytes per block, for the statistics) and what did not resolve ----
-    unsigned long long unresolved = 0;
+    if (base && r->verify && nub)
+    {
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_carry_marked, dim3((nub + 255u) / 256u), dim3(256), 0, s, nub, (const uint32_t*)t_bmark,
+                           (const uint32_t*)t_mfirst, (const uint32_t*)r->d_usize, (const uint64_t*)r->d_uoff, r->d_cvoff, r->d_cvlen,
+                           r->d_cvchunk, r->d_counters);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    // ---- the one read-back: the firsts (and the bytes per block, for the statistics), what did not resolve, what the base feeds ----
+    unsigned long long counters[8] = {0};
     LTHIP_CHECK(ctx, hipMemcpyAsync(r->firsts.data(), r->d_firsts, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
     if (nb)
         LTHIP_CHECK(ctx, hipMemcpyAsync(r->bbytes.data(), t_bbytes, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-    LTHIP_CHECK(ctx, hipMemcpyAsync(&unresolved, r->d_counters, 8, hipMemcpyDeviceToHost, s));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(counters, r->d_counters, sizeof counters, hipMemcpyDeviceToHost, s));
+    if (base)
+    {
+        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->ncarry, t_ofirst + nocc, 4, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->nmarked, t_mfirst + nub, 4, hipMemcpyDeviceToHost, s));
+    }
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-    if (unresolved)
-        return lthip_fail(ctx, ENOENT, "lthip_restore_create", "a selected asset needs a chunk the store index does not hold (or holds with another size)");
+    if (counters[0])
+        return lthip_fail(ctx, ENOENT, base ? "lthip_restore_create_from_base" : "lthip_restore_create",
+                          base ? "a selected asset needs a chunk that neither the base nor the store index holds (or holds with another size)"
+                               : "a selected asset needs a chunk the store index does not hold (or holds with another size)");
+    r->carry_bytes = counters[5];
+    r->carry_leaves = counters[6];
+    lthip_seen_destroy(r->seen_base);
+    r->seen_base = nullptr;
     LTHIP_CHECK(ctx, hipFree(r->d_tmp));
     r->d_tmp = nullptr;
     for (uint32_t b = 0; b < nb; ++b)
@@ -491,8 +764,9 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     return 0;
 }
 
-extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const void* version_index, size_t vi_size,
-                                    const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes, lthip_restore** out)
+static int restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_restore_base* base, const void* version_index,
+                          size_t vi_size, const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes,
+                          lthip_restore** out)
 {
     if (!ctx || !out || !version_index || !store_index)
         return EINVAL;
@@ -504,7 +778,7 @@ extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* 
     int err;
     try
     {
-        err = restore_build(r, cfg, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes);
+        err = restore_build(r, cfg, base, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes);
     }
     catch (const std::bad_alloc&)
     {
@@ -517,6 +791,23 @@ extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* 
     }
     *out = r;
     return 0;
+}
+
+extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const void* version_index, size_t vi_size,
+                                    const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes, lthip_restore** out)
+{
+    return restore_create(ctx, cfg, nullptr, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes, out);
+}
+
+extern "C" int lthip_restore_create_from_base(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_restore_base* base,
+                                              const void* version_index, size_t vi_size, const void* store_index, size_t si_size,
+                                              const uint64_t* asset_offsets, uint64_t out_bytes, lthip_restore** out)
+{
+    if (out)
+        *out = nullptr;
+    if (!base || !base->version_index)
+        return EINVAL;
+    return restore_create(ctx, cfg, base, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes, out);
 }
 
 extern "C" int lthip_restore_needed_blocks(const lthip_restore* r, uint64_t* block_hashes, uint64_t capacity, uint64_t* out_count)
@@ -723,16 +1014,125 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
     }
 }
 
+static int carry_queue(lthip_restore* r, const void* d_base, void* d_out)
+{
+    lthip_ctx* ctx = r->ctx;
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint32_t n = r->ncarry;
+    const size_t n2 = ((size_t)n + 2) & ~(size_t)1;
+    // [n u64 run source][n u64 run destination][n u64 run length][n u32 pieces][n + 1 u32 first piece][n u32 boundary][n + 1 u32 rank]
+    void* tab = nullptr;
+    int err = lthip_scratch(ctx, S_CARRY_RUNS, n2 * 40, &tab);
+    if (err)
+        return err;
+    uint64_t* run_src = (uint64_t*)tab;
+    uint64_t* run_dst = run_src + n2;
+    uint64_t* run_len = run_dst + n2;
+    uint32_t* pieces = (uint32_t*)(run_len + n2);
+    uint32_t* first_piece = pieces + n2;
+    uint32_t* bound = first_piece + n2;
+    uint32_t* rank = bound + n2;
+    // ---- verify: the base chunks that feed something, hashed where they lie, before anything of them is copied ----
+    const uint32_t* bbad = nullptr;
+    if (r->verify && r->nmarked)
+    {
+        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, d_base, r->nmarked, r->d_cvoff, r->d_cvlen, r->base_max_chunk, r->carry_leaves,
+                                           r->d_cvhash)))
+            return err;
+        LaunchTimer tm(ctx, LTHIP_K_OTHER);
+        hipLaunchKernelGGL(k_restore_carry_compare, dim3((r->nmarked + 255u) / 256u), dim3(256), 0, s, r->nmarked, (const uint64_t*)r->d_cvhash,
+                           (const uint32_t*)r->d_cvchunk, (const uint64_t*)r->d_uhash, (const uint32_t*)r->d_usize, (const uint32_t*)r->d_ufeed,
+                           r->d_ubad, r->d_counters);
+        LTHIP_LAUNCH_CHECK(ctx);
+        bbad = r->d_ubad;
+    }
+    // ---- runs: boundaries, their scan, a slot per entry that starts a run, the pieces' scan, the copy ----
+    {
+        LaunchTimer tm(ctx, LTHIP_K_GATHER);
+        hipLaunchKernelGGL(k_restore_carry_bounds, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint64_t*)r->d_ksrc, (const uint64_t*)r->d_kdst,
+                           (const uint32_t*)r->d_klen, (const uint32_t*)r->d_kchunk, bbad, bound);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    if ((err = lthip_exclusive_scan_u32(ctx, bound, rank, n, nullptr, LTHIP_K_GATHER)))
+        return err;
+    {
+        LaunchTimer tm(ctx, LTHIP_K_GATHER);
+        hipLaunchKernelGGL(k_restore_carry_runs, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint64_t*)r->d_ksrc, (const uint64_t*)r->d_kdst,
+                           (const uint32_t*)r->d_klen, (const uint32_t*)r->d_kchunk, bbad, (const uint32_t*)bound, (const uint32_t*)rank, run_src,
+                           run_dst, run_len, pieces);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    if ((err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, n, nullptr, LTHIP_K_GATHER)))
+        return err;
+    return lthip_raw_copy_runs(ctx, first_piece, n, run_src, run_dst, run_len, d_base, d_out, r->carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
+}
+
+extern "C" int lthip_restore_carry(lthip_restore* r, const void* d_base, void* d_out)
+{
+    if (!r)
+        return EINVAL;
+    lthip_ctx* ctx = r->ctx;
+    // ---- the refusals, before anything is queued or changed ----
+    if (!r->has_base)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "the session was created without a base");
+    if (r->carried)
+        return lthip_fail(ctx, EEXIST, "lthip_restore_carry", "the base was carried before");
+    if (r->ncarry)
+    {
+        if (!d_base || !d_out)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "null base or output");
+        const uint64_t b0 = (uint64_t)(uintptr_t)d_base, o0 = (uint64_t)(uintptr_t)d_out;
+        if (b0 < o0 + r->out_bytes && o0 < b0 + r->base_window)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "the base and the output overlap: the update is out of place");
+        const int err = carry_queue(r, d_base, d_out);
+        if (err)
+            return err;
+    }
+    r->carried = true;
+    r->finished = false;
+    return 0;
+}
+
+extern "C" int lthip_version_diff(const void* source_vi, size_t source_size, const void* target_vi, size_t target_size, uint32_t* source_removed,
+                                  uint32_t* target_added, uint32_t* source_content_modified, uint32_t* target_content_modified,
+                                  uint32_t* source_permissions_modified, uint32_t* target_permissions_modified, uint32_t counts[4])
+{
+    if (!source_vi || !target_vi || !counts)
+        return EINVAL;
+    try
+    {
+        version_diff::Lists d;
+        const int err = version_diff::diff(source_vi, source_size, target_vi, target_size, &d);
+        if (err)
+            return err;
+        const std::vector<uint32_t>* lists[6] = {&d.source_removed, &d.target_added, &d.source_content, &d.target_content, &d.source_permissions,
+                                                 &d.target_permissions};
+        uint32_t* outs[6] = {source_removed, target_added, source_content_modified, target_content_modified, source_permissions_modified,
+                             target_permissions_modified};
+        for (int k = 0; k < 6; ++k)
+            if (outs[k] && !lists[k]->empty())
+                memcpy(outs[k], lists[k]->data(), lists[k]->size() * 4);
+        counts[0] = (uint32_t)d.source_removed.size(), counts[1] = (uint32_t)d.target_added.size();
+        counts[2] = (uint32_t)d.source_content.size(), counts[3] = (uint32_t)d.source_permissions.size();
+        return 0;
+    }
+    catch (const std::bad_alloc&)
+    {
+        return ENOMEM;
+    }
+}
+
 extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
 {
     if (!r || (out && (out->struct_size < 16 || out->struct_size > 4096)))
         return EINVAL;
     lthip_ctx* ctx = r->ctx;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    unsigned long long mismatched = 0;
+    unsigned long long counters[5] = {0}; // (d_counters' [1] .. [4])
     if (r->nb)
         LTHIP_CHECK(ctx, hipMemcpyAsync(r->status.data(), r->d_status, (size_t)r->nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LTHIP_CHECK(ctx, hipMemcpyAsync(&mismatched, r->d_counters + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(counters + 1, r->d_counters + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
     r->finished = true;
     lthip_restore_result res;
@@ -742,7 +1142,15 @@ extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
     res.blocks_needed = r->needed;
     res.blocks_delivered = r->delivered_all;
     res.blocks_unneeded = r->unneeded;
-    res.chunks_mismatched = mismatched;
+    res.chunks_mismatched = counters[1];
+    res.base_occurrences = r->ncarry;
+    res.base_bytes = r->carry_bytes;
+    res.base_chunks_mismatched = counters[2];
+    if (r->carried) // (what a mismatched base chunk would have fed was left out of the runs)
+    {
+        res.occurrences_written = r->ncarry - counters[3];
+        res.bytes_written = r->carry_bytes - counters[4];
+    }
     for (uint32_t b = 0; b < r->nb; ++b)
     {
         if (!r->delivered[b] || !r->is_needed(b))
@@ -763,7 +1171,7 @@ extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
         res.struct_size = have < sizeof res ? have : sizeof res;
         memcpy(out, &res, (size_t)res.struct_size);
     }
-    return res.blocks_bad ? EBADF : r->needed_delivered < r->needed ? ENOENT : 0;
+    return res.blocks_bad || res.base_chunks_mismatched ? EBADF : r->needed_delivered < r->needed || (r->ncarry && !r->carried) ? ENOENT : 0;
 }
 
 extern "C" int lthip_restore_block_status(const lthip_restore* r, uint32_t count, const uint64_t* block_hashes, uint32_t* status)

@@ -2,7 +2,7 @@
 // (layout src/longtail.c:2551-2584) and the StoreIndex (:8913-8931).  A blob is untrusted bytes of any alignment: every word is read
 // with memcpy, every array is placed by 64-bit arithmetic on 32-bit counts (which cannot overflow) and checked against the blob's size
 // before it is touched, and every index read from the blob is checked before it is used.  Anything short, of another version or
-// inconsistent is EBADF.  Included by restore.hip and by the stand-alone driver tests/san/restore_parse_driver.cpp.
+// inconsistent is EBADF.  Included by restore.hip, by version_diff.h and by the stand-alone driver tests/san/restore_parse_driver.cpp.
 #pragma once
 #include <errno.h>
 #include <stddef.h>
@@ -41,18 +41,32 @@ struct U64s
         return v;
     }
 };
+struct U16s
+{
+    const uint8_t* p = nullptr;
+    uint16_t operator[](uint64_t i) const
+    {
+        uint16_t v;
+        memcpy(&v, p + i * 2u, 2);
+        return v;
+    }
+};
 
 struct VersionIndex
 {
     uint32_t hash_identifier = 0, target_chunk_size = 0, asset_count = 0, chunk_count = 0, asset_chunk_index_count = 0;
+    U64s path_hashes, content_hashes;                       // [asset_count]
     U64s asset_sizes;                                       // [asset_count]
     U32s asset_chunk_counts, asset_chunk_index_starts;      // [asset_count]
     U32s asset_chunk_indexes;                               // [asset_chunk_index_count]
     U64s chunk_hashes;                                      // [chunk_count]
     U32s chunk_sizes;                                       // [chunk_count]
     U32s name_offsets;                                      // [asset_count] into name_data
+    U16s permissions;                                       // [asset_count]
     const uint8_t* name_data = nullptr;                     // the rest of the blob
     uint64_t name_data_size = 0;
+    // strlen of asset a's path (parse_version_index has found its terminator inside the name data)
+    uint32_t path_length(uint64_t a) const { return (uint32_t)strlen((const char*)name_data + name_offsets[a]); }
 };
 
 struct StoreIndex
@@ -68,7 +82,8 @@ struct StoreIndex
 // chunk (twice the target, src/longtail.c:1985-1987) does not fit the 32 bits of a chunk size, fewer chunk indexes than chunks
 // (Longtail_GetVersionIndexDataSize refuses it), an asset whose path does not start and end inside the name data, an asset whose
 // chunk-index run leaves the index array, a chunk index that names no chunk, an asset whose chunk sizes do not sum to its size.  Path
-// and content hashes, tags and permissions are placed (the blob must hold them) but not read.
+// and content hashes and permissions are placed and handed out (the blob must hold them; version_diff.h reads them), tags are placed
+// but not read.
 inline int parse_version_index(const void* blob, size_t size, VersionIndex* out)
 {
     if (!blob || size < 24)
@@ -93,7 +108,11 @@ inline int parse_version_index(const void* blob, size_t size, VersionIndex* out)
     const uint64_t need = 24u + na * 32u + ni * 4u + nu * 16u + na * 6u;
     if ((uint64_t)size < need)
         return EBADF;
-    uint64_t o = 24u + na * 16u; // (m_PathHashes, m_ContentHashes)
+    uint64_t o = 24u;
+    v.path_hashes.p = p + o;
+    o += na * 8u;
+    v.content_hashes.p = p + o;
+    o += na * 8u;
     v.asset_sizes.p = p + o;
     o += na * 8u;
     v.asset_chunk_counts.p = p + o;
@@ -107,7 +126,9 @@ inline int parse_version_index(const void* blob, size_t size, VersionIndex* out)
     v.chunk_sizes.p = p + o;
     o += nu * 8u; // (m_ChunkSizes, m_ChunkTags)
     v.name_offsets.p = p + o;
-    o += na * 6u; // (m_NameOffsets, m_Permissions)
+    o += na * 4u;
+    v.permissions.p = p + o;
+    o += na * 2u;
     v.name_data = p + o;
     v.name_data_size = (uint64_t)size - o;
     for (uint64_t a = 0; a < na; ++a)

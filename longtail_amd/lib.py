@@ -168,6 +168,9 @@ class HipLib:
         sig("lthip_restore_blocks", i32, [vp, u32, vp, vp, vp, vp, vp, u64, vp])
         sig("lthip_restore_finish", i32, [vp, vp])
         sig("lthip_restore_block_status", i32, [vp, u32, vp, vp])
+        sig("lthip_restore_create_from_base", i32, [vp, vp, vp, vp, sz, vp, sz, vp, u64, P(vp)])
+        sig("lthip_restore_carry", i32, [vp, vp, vp])
+        sig("lthip_version_diff", i32, [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1067,7 +1070,12 @@ class RestoreConfig(C.Structure):
 class RestoreResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_uint64) for n in (
         "assets_selected", "occurrences", "occurrences_written", "bytes_written", "blocks_needed", "blocks_delivered", "blocks_unneeded",
-        "blocks_bad", "chunks_mismatched", "decoded_bytes")]
+        "blocks_bad", "chunks_mismatched", "decoded_bytes", "base_occurrences", "base_bytes", "base_chunks_mismatched")]
+
+
+class RestoreBase(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64), ("version_index", C.c_void_p), ("version_index_size", C.c_uint64), ("asset_offsets", C.c_void_p),
+                ("base_bytes", C.c_uint64)]
 
 
 RESTORE_SKIP = 0xFFFFFFFFFFFFFFFF  # include/longtail_hip.h LTHIP_RESTORE_SKIP
@@ -1077,7 +1085,11 @@ RESTORE_NOT_DELIVERED, RESTORE_BAD_HEADER, RESTORE_BAD_PAYLOAD, RESTORE_BAD_CHUN
 class Restore:
     """lthip_restore: stored-block images in HBM back into a version's assets, asset a at asset_offsets[a] of one device buffer
     (include/longtail_hip.h, "the restore session").  layout() -> offsets; needed_blocks() -> which blocks to fetch; blocks() per batch of
-    images; finish() -> (0 / ENOENT: blocks outstanding / EBADF: a bad block, the result)."""
+    images; finish() -> (0 / ENOENT: blocks outstanding / EBADF: a bad block, the result).
+
+    base = (version_index, asset_offsets, base_bytes) of a version that lies restored in device memory: the chunks it shares with the
+    target are planned as copies from it (carry(base_tensor, out), in any order with blocks()), needed_blocks() shrinks to the blocks that
+    hold a chunk no resident asset has, and store_index may be the small one an incremental ingest returned."""
 
     SKIP = RESTORE_SKIP
 
@@ -1096,16 +1108,22 @@ class Restore:
             raise LongtailHipError(err, "lthip_restore_layout")
         return offsets, int(total.value)
 
-    def __init__(self, ctx: "Context", version_index: bytes, store_index: bytes, asset_offsets, out_bytes: int, verify: bool = True):
+    def __init__(self, ctx: "Context", version_index: bytes, store_index: bytes, asset_offsets, out_bytes: int, verify: bool = True, base=None):
         self.ctx = ctx
         self.h = None
         vi, si = np.frombuffer(version_index, np.uint8), np.frombuffer(store_index, np.uint8)
         offs = _u64arr(asset_offsets)
         cfg = RestoreConfig(C.sizeof(RestoreConfig), 1 if verify else 0)
         h = C.c_void_p()
-        ctx._check(ctx.lib.dll.lthip_restore_create(ctx.h, C.byref(cfg), vi.ctypes.data if len(vi) else None, len(vi),
-                                                    si.ctypes.data if len(si) else None, len(si), offs.ctypes.data if len(offs) else None,
-                                                    out_bytes, C.byref(h)), "lthip_restore_create")
+        args = (vi.ctypes.data if len(vi) else None, len(vi), si.ctypes.data if len(si) else None, len(si),
+                offs.ctypes.data if len(offs) else None, out_bytes, C.byref(h))
+        if base is None:
+            ctx._check(ctx.lib.dll.lthip_restore_create(ctx.h, C.byref(cfg), *args), "lthip_restore_create")
+        else:
+            bvi, boffs = np.frombuffer(base[0], np.uint8), _u64arr(base[1])
+            desc = RestoreBase(C.sizeof(RestoreBase), bvi.ctypes.data if len(bvi) else None, len(bvi), boffs.ctypes.data if len(boffs) else None,
+                               int(base[2]))
+            ctx._check(ctx.lib.dll.lthip_restore_create_from_base(ctx.h, C.byref(cfg), C.byref(desc), *args), "lthip_restore_create_from_base")
         self.h = h
         self._keep = []
 
@@ -1145,9 +1163,17 @@ class Restore:
                                                               _ptr(scratch), _numel(scratch), _ptr(out)), "lthip_restore_blocks")
         self._keep.append((images, scratch, out))
 
+    def carry(self, base_tensor, out):
+        """Queues the copy of every occurrence the base feeds from `base_tensor` (the device uint8 tensor the base's asset offsets refer
+        to) into `out`; once per session, in any order with blocks().  Asynchronous on the context's stream: the tensors are kept until
+        finish() or close()."""
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_carry(self.h, _ptr(base_tensor) or None, _ptr(out) or None), "lthip_restore_carry")
+        self._keep.append((base_tensor, out))
+
     def finish(self):
-        """-> (code, RestoreResult): 0, errno.ENOENT (needed blocks are outstanding: deliver them and call again) or errno.EBADF (a
-        delivered block was bad).  The session's one full synchronisation."""
+        """-> (code, RestoreResult): 0, errno.ENOENT (needed blocks are outstanding, or the base has not been carried: deliver / carry
+        and call again) or errno.EBADF (a delivered block was bad, or with verify a chunk of the base).  The session's one full
+        synchronisation."""
         res = RestoreResult()
         res.struct_size = C.sizeof(RestoreResult)
         code = self.ctx.lib.dll.lthip_restore_finish(self.h, C.byref(res))
@@ -1163,6 +1189,24 @@ class Restore:
         self.ctx._check(self.ctx.lib.dll.lthip_restore_block_status(self.h, len(h), h.ctypes.data if len(h) else None,
                                                                     out.ctypes.data if len(h) else None), "lthip_restore_block_status")
         return out
+
+
+def version_diff(source_vi: bytes, target_vi: bytes, lib: Optional[HipLib] = None):
+    """lthip_version_diff, host only: what changed between two serialized VersionIndexes, the lists of Longtail_CreateVersionDiff ->
+    (source_removed, target_added, source_content_modified, target_content_modified, source_permissions_modified,
+    target_permissions_modified): uint32 arrays of asset indices."""
+    dll = (lib or load()).dll
+    a, b = np.frombuffer(source_vi, np.uint8), np.frombuffer(target_vi, np.uint8)
+    args = (a.ctypes.data if len(a) else None, len(a), b.ctypes.data if len(b) else None, len(b))
+    counts = np.zeros(4, np.uint32)
+    err = dll.lthip_version_diff(*args, None, None, None, None, None, None, counts.ctypes.data)
+    if err:
+        raise LongtailHipError(err, "lthip_version_diff")
+    lists = [np.zeros(max(1, int(counts[k])), np.uint32) for k in (0, 1, 2, 2, 3, 3)]
+    err = dll.lthip_version_diff(*args, *[x.ctypes.data for x in lists], counts.ctypes.data)
+    if err:
+        raise LongtailHipError(err, "lthip_version_diff")
+    return tuple(x[: int(counts[k])] for x, k in zip(lists, (0, 1, 2, 2, 3, 3)))
 
 
 class Plan:

@@ -8,6 +8,15 @@ difference.  The output is compared with the tree once per store.  Recorded into
 repeat.  There is no threshold.
 
     python tools/restore_rate.py [--gib 4] [--repeats 3] [--out profiles/restore_rate.json]
+
+--update measures the session with a base instead (lthip_restore_create_from_base / lthip_restore_carry): the same tree is version A and
+lies in HBM, version B replaces a share of its files (--share, default one tenth), B's raw (tag 0) blocks are written against a store that
+holds A.  Timed: carry + every blocks call + finish, verify off and on, beside a full restore of B (no base, B's full StoreIndex) in the
+same process; and the carry alone (verify off), beside a device-to-device torch copy of the same number of bytes in the same process --
+that copy, not the code under test, is what the carry is measured against.  Recorded into profiles/restore_update_rate.json.  There is no
+threshold.
+
+    python tools/restore_rate.py --update [--share 0.1] [--gib 4] [--repeats 3] [--out profiles/restore_update_rate.json]
 """
 import argparse
 import json
@@ -38,6 +47,134 @@ def store_blocks(si):
     return hashes, count, cs[first + count] - cs[first]
 
 
+def update_leg(args):
+    import torch
+
+    from bench import KINDS, asset_seeds, make_tree
+    from longtail_amd.lib import Context, Ingest, IngestStream, Restore, Store, chunker_params, load
+
+    lib = load()
+    dev = torch.device("cuda", 0)
+    ctx = Context(0, lib=lib)
+    nfiles = int(args.gib * (1 << 30)) // FILE
+    n = nfiles * FILE
+    mn, av, mx = chunker_params(args.target_chunk_size)
+    p_off, p_size = np.arange(nfiles, dtype=np.uint64) * np.uint64(FILE), np.full(nfiles, FILE, np.uint64)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    seeds = asset_seeds(0x10C0FFEE, 0, nfiles)
+    data_a = torch.empty(n + 256, **u8)
+    ctx.synth_fill(data_a, p_off, p_size, seeds, KINDS["mixed"])
+    replaced = np.arange(0, nfiles, max(1, round(1 / args.share)))
+    data_b = data_a.clone()
+    ctx.synth_fill(data_b, p_off[replaced], p_size[replaced], asset_seeds(0xB0B0CAFE, 0, len(replaced)), KINDS["mixed"])
+    ctx.sync()
+    tree = make_tree("files", n, FILE)
+    whole, _keep = Ingest.tree(tree["sizes"], tree["path_offsets"], tree["perms"], tree["path_data"], np.arange(nfiles, dtype=np.uint32),
+                               np.zeros(nfiles + 1, np.uint64))
+    plan = ctx.make_plan(p_off, p_size, mn, av, mx)
+
+    def ingest(data, store):
+        """-> (vi, si, [(images, hashes, offsets, sizes)]) of the tree in `data`, raw blocks, one slice"""
+        total, d_off, d_len, d_hash, d_first = ctx.chunk_hash(plan, data)
+        vi_cap = int(lib.dll.lthip_version_index_size(nfiles, total, total, len(tree["path_data"]))) + 64
+        h_vi, h_si = torch.empty(vi_cap, dtype=torch.uint8).pin_memory(), torch.empty(16 + 32 * total + 64, dtype=torch.uint8).pin_memory()
+        st = IngestStream(ctx, whole, args.target_chunk_size, args.block_size, args.max_chunks_per_block, "none")
+        if store is not None:
+            st.set_store(store)
+        arena, tail = torch.empty(st.arena_bound(n, total), **u8), torch.empty(st.arena_bound(0, 0), **u8)
+        st.slice(0, nfiles, data, d_off, d_len, d_hash, d_first, total, arena)
+        _, offs0, sizes0 = st.images()
+        offs0, sizes0 = offs0.copy(), sizes0.copy()
+        res = st.finish(tail, h_vi, h_si)
+        _, offs1, sizes1 = st.images()
+        vi, si = bytes(h_vi.numpy()[: res.version_index_size]), bytes(h_si.numpy()[: res.store_index_size])
+        st.close()
+        hashes = store_blocks(si)[0]
+        stored = int(sizes0.astype(np.int64).sum() + sizes1.astype(np.int64).sum())
+        keep = max(64, int((offs0.astype(np.int64) + sizes0.astype(np.int64)).max()) if len(offs0) else 0)
+        arena = arena[:keep].clone()  # (the bound is the whole tree's: keep what was written)
+        return vi, si, [(arena, hashes[: len(offs0)], offs0, sizes0), (tail, hashes[len(offs0) :], offs1.copy(), sizes1.copy())], stored
+
+    vi_a, si_a, _calls_a, _ = ingest(data_a, None)
+    del _calls_a
+    store = Store(ctx, 0)
+    store.add_index(si_a)
+    vi_b, si_missing, calls_missing, stored_missing = ingest(data_b, store)
+    _, si_full, calls_full, stored_full = ingest(data_b, None)
+    store.close()
+    offsets_a, bytes_a = Restore.layout(vi_a, 1, lib)
+    offsets_b, bytes_b = Restore.layout(vi_b, 1, lib)
+    assert bytes_a == bytes_b == n
+    out = torch.empty(n, **u8)
+    base = (vi_a, offsets_a, n)  # version A as a restore at align 1 leaves it: the tree's bytes
+    report = {"workload": f"{args.gib:g} GiB `mixed` tree ({nfiles} files of 1 MiB) resident in HBM as version A; version B replaces {len(replaced)} "
+                          "of the files; raw (tag 0) blocks; B's missing blocks were written against a store that holds A",
+              "unit": "GB/s of output (the whole of version B)", "repeats": args.repeats, "files_replaced": int(len(replaced)),
+              "stored_bytes_of_the_missing_blocks": stored_missing, "stored_bytes_of_all_blocks": stored_full}
+
+    def timed(label, vi, si, calls, with_base, verify):
+        plans, rates, result = [], [], None
+        for rep in range(args.repeats + 1):  # (the first is the warm-up: workspaces of the context)
+            out.fill_(0xA5)
+            ctx.sync()
+            t0 = time.perf_counter()
+            rs = Restore(ctx, vi, si, offsets_b, n, verify=verify, base=base if with_base else None)
+            t1 = time.perf_counter()
+            if with_base:
+                rs.carry(data_a, out)
+            for images, h, o, z in calls:
+                if len(h):
+                    rs.blocks(h, images, o, z, None, out)
+            code, result = rs.finish()
+            t2 = time.perf_counter()
+            assert code == 0 and result.bytes_written == n, (code, result.bytes_written)
+            if rep == 0:
+                assert torch.equal(out, data_b[:n]), "the restored bytes differ from version B"
+            else:
+                plans.append(round((t1 - t0) * 1e3, 2))
+                rates.append(round(n / (t2 - t1) / 1e9, 2))
+            rs.close()
+        report[label] = {"GBps": rates, "GBps_median": float(np.median(rates)), "create_ms": plans, "blocks_needed": int(result.blocks_needed),
+                         "base_occurrences": int(result.base_occurrences), "occurrences": int(result.occurrences),
+                         "base_bytes": int(result.base_bytes)}
+        print(label, json.dumps(report[label]), flush=True)
+        return result
+
+    for verify in (False, True):
+        v = "verify" if verify else "no_verify"
+        res = timed(f"update_{v}", vi_b, si_missing, calls_missing, True, verify)
+        timed(f"full_restore_{v}", vi_b, si_full, calls_full, False, verify)
+    # ---- the carry alone, beside a device-to-device copy of as many bytes ----
+    carried = int(res.base_bytes)
+    carry_ms, copy_ms = [], []
+    for rep in range(args.repeats + 1):
+        rs = Restore(ctx, vi_b, si_missing, offsets_b, n, verify=False, base=base)
+        ctx.sync()
+        t0 = time.perf_counter()
+        rs.carry(data_a, out)
+        ctx.sync()
+        t1 = time.perf_counter()
+        rs.close()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        out[:carried].copy_(data_a[:carried])
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        if rep:
+            carry_ms.append(round((t1 - t0) * 1e3, 3))
+            copy_ms.append(round((t3 - t2) * 1e3, 3))
+    gbps = lambda ms: round(carried / (float(np.median(ms)) * 1e-3) / 1e9, 2)
+    report["carry_alone"] = {"bytes": carried, "ms": carry_ms, "GBps_median": gbps(carry_ms), "torch_copy_ms": copy_ms,
+                             "torch_copy_GBps_median": gbps(copy_ms), "carry_over_copy": round(gbps(carry_ms) / gbps(copy_ms), 3)}
+    print("carry_alone", json.dumps(report["carry_alone"]), flush=True)
+    plan.close()
+    ctx.close()
+    path = Path(args.out if args.out else ROOT / "profiles" / "restore_update_rate.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(report, indent=1) + "\n")
+    print("wrote", path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -45,8 +182,13 @@ def main():
     ap.add_argument("--target-chunk-size", type=int, default=65536)
     ap.add_argument("--block-size", type=int, default=8 << 20)
     ap.add_argument("--max-chunks-per-block", type=int, default=1024)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "restore_rate.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/restore_rate.json, with --update profiles/restore_update_rate.json")
+    ap.add_argument("--update", action="store_true", help="the session with a base: version A resident, version B restored from it")
+    ap.add_argument("--share", type=float, default=0.1, help="--update: the share of the files that version B replaces")
     args = ap.parse_args()
+    if args.update:
+        return update_leg(args)
+    args.out = args.out or str(ROOT / "profiles" / "restore_rate.json")
 
     import torch
 
