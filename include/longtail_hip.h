@@ -931,6 +931,49 @@ LTHIP_EXPORT int lthip_version_diff(const void* source_version_index, size_t sou
                                     uint32_t* target_content_modified, uint32_t* source_permissions_modified,
                                     uint32_t* target_permissions_modified, uint32_t counts[4]);
 
+/* ---- updating a resident version in place (restore.hip, restore_layout.h) -------------------------------------------------------------
+ * Longtail_ChangeVersion (src/longtail.c:8013) works in place: it leaves unchanged files alone and rewrites the rest.  This is its
+ * device side.  The base's and the target's asset offsets are offsets into ONE buffer d_buf of max(base_bytes, out_bytes) bytes; the
+ * session is created with lthip_restore_create_from_base as before.  An update then costs what changed, not what the version weighs.
+ *   layout_in_place  host only.  Assets are matched by path hash.  A target asset of size > 0 is KEPT when the base has a resident asset
+ *                  (offset != LTHIP_RESTORE_SKIP) with the same path hash, size and content hash: it gets that asset's offset.  The
+ *                  GAPS are [0, base_bytes) minus the kept windows, ascending, each with a cursor at its start.  Every other target
+ *                  asset of size > 0, in asset order, goes into the first gap where round_up(cursor, align) + size <= the gap's end, and
+ *                  the cursor moves to its end; one that fits no gap is appended at round_up(end, align), `end` starting at base_bytes.
+ *                  Assets of size 0 and directories get offset 0.  *total_bytes: the highest end of any target window (it may lie
+ *                  below base_bytes); *kept_assets: how many were kept.  Every output may be NULL.  New assets deliberately land on the
+ *                  old bytes of modified ones: carry_in_place makes that safe.  EBADF: a malformed blob, or two assets of one version
+ *                  with the same path hash.  EINVAL: align is no power of two, a NULL blob or NULL base_offsets, the hash identifiers
+ *                  differ, a resident base asset leaves [0, base_bytes), two kept windows overlap.
+ *   carry_in_place  a base-fed entry of the plan whose source offset equals its destination is KEPT: nothing is queued for it.  Every
+ *                  other one is MOVED (a base chunk's place is its FIRST place in the base, so a duplicate chunk inside an unchanged
+ *                  asset can count as moved although its bytes are right; in_place_stats shows it).  Maximal runs are built as carry
+ *                  builds them -- a run is all kept or all moved -- and the moved runs are packed into d_scratch, slots 16-byte aligned;
+ *                  pass 1 copies every moved run d_buf -> d_scratch, pass 2 d_scratch -> d_buf, both with k_raw_copy.  All reads come
+ *                  before all writes, so any arrangement is safe: an asset shifted by fewer bytes than its length, two assets that swap
+ *                  places, a store-fed chunk that lands on the old bytes of a moved one.  THE CARRY COMES FIRST: EINVAL once a blocks
+ *                  call of the session has queued work (a scatter may have overwritten a source), and after it a blocks call whose d_out
+ *                  is not d_buf is EINVAL.  cfg.verify: as carry, the feeding base chunks are hashed where they lie before pass 1; a
+ *                  moved occurrence of a chunk that differs is left out of both passes and its destination keeps what the buffer held,
+ *                  a kept one stays what it is, both count in base_chunks_mismatched and finish returns EBADF.  Without verify the base
+ *                  is trusted.  EINVAL: no base; d_buf NULL while base-fed entries exist; d_scratch NULL or overlapping
+ *                  [d_buf, d_buf + max(base_bytes, out_bytes)) while moved entries exist; more than 64 GiB would move (the slots are
+ *                  placed by a 32-bit scan of 16-byte units).  ENOMEM: scratch_bytes below in_place_scratch_bound.  EEXIST: a carry of
+ *                  either kind was called before.  A refused call queues and changes nothing.  A session in which everything is kept
+ *                  accepts a NULL scratch and queues no copy.  Like carry it never waits, reads nothing back and allocates nothing
+ *                  (scratch-pool growth and the BLAKE3 long-chunk exception apart); finish and the result are as for carry, and
+ *                  occurrences_written / bytes_written include kept occurrences: they are in place and good.
+ *   in_place_scratch_bound  host arithmetic over counters taken with the plan's one read-back: moved bytes + 16 x moved occurrences
+ *                  + 64 (0 when nothing moves, and for a session without a base).
+ *   in_place_stats  out[4] = {kept occurrences, kept bytes, moved occurrences, moved bytes}; all 0 for a session without a base. */
+LTHIP_EXPORT int lthip_restore_layout_in_place(const void* base_version_index, size_t base_size, const uint64_t* base_offsets, uint64_t base_bytes,
+                                               const void* target_version_index, size_t target_size, uint64_t align,
+                                               uint64_t* target_offsets /*may be NULL*/, uint32_t* asset_count, uint64_t* total_bytes,
+                                               uint32_t* kept_assets);
+LTHIP_EXPORT size_t lthip_restore_in_place_scratch_bound(const lthip_restore* restore);
+LTHIP_EXPORT int lthip_restore_in_place_stats(const lthip_restore* restore, uint64_t out[4]);
+LTHIP_EXPORT int lthip_restore_carry_in_place(lthip_restore* restore, void* d_buf, void* d_scratch, uint64_t scratch_bytes);
+
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets
  * (src/longtail.c:2396-2458).  lthip_job_count / lthip_make_jobs list the jobs of a tree exactly as :2399-2404 / :2432-2457 do

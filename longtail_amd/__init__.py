@@ -28,4 +28,4 @@ def build(verbose: bool = False) -> Path:
     return LIB_PATH
 
 
-from .lib import HipLib, Context, LongtailHipError, Restore, load, version_diff  # noqa: E402,F401
+from .lib import HipLib, Context, LongtailHipError, Restore, load, restore_layout_in_place, version_diff  # noqa: E402,F401

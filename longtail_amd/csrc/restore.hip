@@ -22,9 +22,15 @@
 //            differs is a boundary of its own and gets no pieces) -> scan -> k_restore_carry_runs: a boundary that starts a run finds
 //            the next boundary by bisection of the scan and writes {source, destination, length} and the run's pieces into its slot ->
 //            scan -> k_raw_copy (k_gather.hip).  An unchanged asset is one run.
+//   in place (lthip_restore_carry_in_place) the base and the target share one buffer.  The same runs; k_restore_in_place_classify drops
+//            the runs whose source is their destination (kept: nothing is queued) and gives every other run a 16-byte aligned slot in the
+//            caller's scratch -> scans -> k_restore_in_place_slots -> k_raw_copy twice: every moved run buffer -> scratch, then scratch ->
+//            buffer.  All reads come before all writes, so runs may overlap each other in any way.  How many entries move, and their bytes,
+//            is counted by k_restore_fill and comes back with the plan's one read-back: the scratch bound is host arithmetic.
 // The scatter and a decoder's second pass cost one more read and write of the output than decoding into place would: about a tenth on top
 // of the bare decoder calls (profiles/restore_rate.json).
 #include "lthip_internal.h"
+#include "restore_layout.h"
 #include "restore_parse.h"
 #include "store_layout.h"
 #include "version_diff.h"
@@ -76,7 +82,7 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
     return v;
 }
 
-// counters: [0] occurrences neither source resolves, [5] bytes the base feeds
+// counters: [0] occurrences neither source resolves, [5] bytes the base feeds ([8], [9]: k_restore_fill)
 __global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint32_t* __restrict__ csize,
                                   const uint32_t* __restrict__ cblock, uint32_t* __restrict__ hist, unsigned long long* __restrict__ bbytes,
                                   unsigned long long* counters, BasePlan bp, uint32_t* __restrict__ oflag, uint32_t* __restrict__ bfeed,
@@ -128,29 +134,47 @@ __global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, con
                                const uint32_t* __restrict__ csize, const uint32_t* __restrict__ cblock, const uint32_t* __restrict__ coff,
                                const uint32_t* __restrict__ firsts, uint32_t* __restrict__ cursor, uint4* __restrict__ entries, BasePlan bp,
                                const uint32_t* __restrict__ ofirst, uint64_t* __restrict__ ksrc, uint64_t* __restrict__ kdst,
-                               uint32_t* __restrict__ klen, uint32_t* __restrict__ kchunk)
+                               uint32_t* __restrict__ klen, uint32_t* __restrict__ kchunk, unsigned long long* counters)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const uint32_t len = olen[i];
-    const uint64_t d = odst[i];
-    uint32_t q = NONE;
-    if (base_feeds(bp, i, len, &q))
+    unsigned long long moved = 0; // bytes of a base-fed entry whose source offset is not its destination (counters[8], [9]: in place)
+    bool is_moved = false;
+    if (i < n)
     {
-        const uint32_t k = ofirst[i];
-        ksrc[k] = bp.off[q];
-        kdst[k] = d;
-        klen[k] = len;
-        kchunk[k] = q;
-        return;
+        const uint32_t len = olen[i];
+        const uint64_t d = odst[i];
+        uint32_t q = NONE;
+        if (base_feeds(bp, i, len, &q))
+        {
+            const uint32_t k = ofirst[i];
+            const uint64_t src = bp.off[q];
+            ksrc[k] = src;
+            kdst[k] = d;
+            klen[k] = len;
+            kchunk[k] = q;
+            is_moved = src != d;
+            moved = is_moved ? len : 0u;
+        }
+        else
+        {
+            const uint32_t p = pos[i];
+            const uint32_t b = p == NONE ? NONE : cblock[p];
+            if (b != NONE && csize[p] == len)
+            {
+                const uint32_t slot = firsts[b] + atomicAdd(&cursor[b], 1u);
+                entries[slot] = make_uint4(coff[p], len, (uint32_t)d, (uint32_t)(d >> 32));
+            }
+        }
     }
-    const uint32_t p = pos[i];
-    const uint32_t b = p == NONE ? NONE : cblock[p];
-    if (b == NONE || csize[p] != len)
+    if (!bp.opos)
         return;
-    const uint32_t slot = firsts[b] + atomicAdd(&cursor[b], 1u);
-    entries[slot] = make_uint4(coff[p], len, (uint32_t)d, (uint32_t)(d >> 32));
+    const uint64_t m = __builtin_amdgcn_ballot_w64(is_moved);
+    moved = wave_sum(moved);
+    if (m && (threadIdx.x & 63) == 0)
+    {
+        atomicAdd(counters + 8, (unsigned long long)__builtin_popcountll(m));
+        atomicAdd(counters + 9, moved);
+    }
 }
 
 // the base chunks that feed something, in chunk order (mfirst: the scan of their marks): the ranges verify hashes, and their 1 KiB
@@ -242,6 +266,41 @@ __global__ void k_restore_carry_runs(uint32_t n, const uint64_t* __restrict__ ks
         np = lthip_raw_pieces(d, len);
     }
     pieces[i] = np;
+}
+
+// ---- the carry in place: behind k_restore_carry_runs.  A run whose source is its destination is KEPT and loses its pieces (a run is all
+// kept or all moved: the distance from source to destination is constant over it).  A moved run goes through the caller's scratch: it
+// gets the 16-byte units of its slot there and the pieces of its way IN (a slot starts on a 16-byte boundary); `pieces` stays what its
+// way back OUT needs. ----
+__global__ void k_restore_in_place_classify(uint32_t n, const uint64_t* __restrict__ run_src, const uint64_t* __restrict__ run_dst,
+                                            const uint64_t* __restrict__ run_len, uint32_t* __restrict__ pieces, uint32_t* __restrict__ pieces_in,
+                                            uint32_t* __restrict__ units)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    uint32_t in = 0, u = 0;
+    if (pieces[i])
+    {
+        if (run_src[i] == run_dst[i])
+            pieces[i] = 0u;
+        else
+        {
+            const uint64_t len = run_len[i];
+            in = lthip_raw_pieces(0, len);
+            u = (uint32_t)((len + 15u) >> 4); // (the moved bytes and their padding stay below 2^36: lthip_restore_carry_in_place)
+        }
+    }
+    pieces_in[i] = in;
+    units[i] = u;
+}
+
+// first_unit = the exclusive scan of the units: where every run's slot starts in the scratch
+__global__ void k_restore_in_place_slots(uint32_t n, const uint32_t* __restrict__ first_unit, uint64_t* __restrict__ run_slot)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n)
+        run_slot[i] = (uint64_t)first_unit[i] << 4;
 }
 
 // ---- a delivered image against the StoreIndex: one wave per image ----
@@ -433,7 +492,10 @@ struct lthip_restore
     // the base: its distinct chunks, what of the plan it feeds (the read-back of create), whether carry has queued it
     bool has_base = false, carried = false;
     uint32_t nub = 0, ncarry = 0, nmarked = 0, base_max_chunk = 0;
-    uint64_t out_bytes = 0, base_window = 0, carry_bytes = 0, carry_leaves = 0;
+    uint64_t out_bytes = 0, base_window = 0, carry_bytes = 0, carry_leaves = 0, moved_occ = 0, moved_bytes = 0;
+    // in place: blocks calls that queued work (an in-place carry comes before them), the buffer an in-place carry was given
+    bool blocks_queued = false, in_place = false;
+    void* in_place_buf = nullptr;
     // the StoreIndex and the plan on the host
     std::vector<uint64_t> bhash, bbytes, bleaves;
     std::vector<uint32_t> bcnt, btag, braw, firsts, status;
@@ -448,7 +510,8 @@ struct lthip_restore
     uint4* d_entries = nullptr;
     RItem* d_items = nullptr;
     // [0] occurrences neither source resolves, [1] chunks of blocks whose hash differed, [2] base chunks whose hash differed, [3] the
-    // occurrences those would have fed, [4] and their bytes, [5] bytes the base feeds, [6] 1 KiB leaves of the base chunks that feed
+    // occurrences those would have fed, [4] and their bytes, [5] bytes the base feeds, [6] 1 KiB leaves of the base chunks that feed,
+    // [8] base-fed entries whose source offset is not their destination (moved: an update in place copies them) [9] and their bytes
     unsigned long long* d_counters = nullptr;
     // base-fed entries in occurrence order (room for every occurrence: how many the base feeds is known after the plan has run), per
     // base chunk {hash, size, offset in d_base, occurrences fed, hash differed}, and with verify the ranges of the chunks that feed
@@ -465,7 +528,7 @@ struct lthip_restore
     {
         c.take(&d_chash, m), c.take(&d_csize, m), c.take(&d_cblock, m), c.take(&d_coff, m);
         c.take(&d_bhash, nb), c.take(&d_bcoff, nb), c.take(&d_bcnt, nb), c.take(&d_btag, nb), c.take(&d_braw, nb), c.take(&d_status, nb);
-        c.take(&d_firsts, (size_t)nb + 1), c.take(&d_entries, nocc), c.take(&d_items, items_cap), c.take(&d_outsz, items_cap), c.take(&d_counters, 8);
+        c.take(&d_firsts, (size_t)nb + 1), c.take(&d_entries, nocc), c.take(&d_items, items_cap), c.take(&d_outsz, items_cap), c.take(&d_counters, 10);
         if (verify)
             c.take(&d_voff, block_chunks), c.take(&d_vhash, block_chunks), c.take(&d_vlen, block_chunks), c.take(&d_vblock, block_chunks),
                 c.take(&d_vchunk, block_chunks);
@@ -684,7 +747,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         LTHIP_CHECK(ctx, hipMemsetAsync(r->d_ubad, 0, (size_t)nub * 4, s));
         LTHIP_CHECK(ctx, hipMemsetAsync(t_bmark, 0, (size_t)nub * 4, s));
     }
-    LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, 64, s));
+    LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, 80, s));
     if (nb)
     {
         LTHIP_CHECK(ctx, hipMemsetAsync(r->d_status, 0, (size_t)nb * 4, s));
@@ -726,7 +789,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
                            (const uint64_t*)t_odst, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, (const uint32_t*)r->d_coff,
                            (const uint32_t*)r->d_firsts, t_cursor, r->d_entries, bp, (const uint32_t*)t_ofirst, r->d_ksrc, r->d_kdst, r->d_klen,
-                           r->d_kchunk);
+                           r->d_kchunk, r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (base && r->verify && nub)
@@ -738,7 +801,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         LTHIP_LAUNCH_CHECK(ctx);
     }
     // ---- the one read-back: the firsts (and the bytes per block, for the statistics), what did not resolve, what the base feeds ----
-    unsigned long long counters[8] = {0};
+    unsigned long long counters[10] = {0};
     LTHIP_CHECK(ctx, hipMemcpyAsync(r->firsts.data(), r->d_firsts, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
     if (nb)
         LTHIP_CHECK(ctx, hipMemcpyAsync(r->bbytes.data(), t_bbytes, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
@@ -755,6 +818,8 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
                                : "a selected asset needs a chunk the store index does not hold (or holds with another size)");
     r->carry_bytes = counters[5];
     r->carry_leaves = counters[6];
+    r->moved_occ = counters[8];
+    r->moved_bytes = counters[9];
     lthip_seen_destroy(r->seen_base);
     r->seen_base = nullptr;
     LTHIP_CHECK(ctx, hipFree(r->d_tmp));
@@ -864,6 +929,7 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
     const size_t k = r->group[0].size() + r->group[1].size() + r->group[2].size();
     if (!k)
         return 0;
+    r->blocks_queued = true;
     r->items.clear(), r->outsz.clear();
     uint64_t slot = 0, entries = 0, ranges = 0, leaves = 0;
     for (int g = 0; g < 3; ++g)
@@ -1002,6 +1068,8 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
         refused = ENOMEM, why = "scratch below lthip_restore_scratch_bound";
     if (!refused && ((scratch && !d_scratch) || (any_needed && !d_out)))
         refused = EINVAL, why = "null scratch or output";
+    if (!refused && any_needed && r->in_place_buf && d_out != r->in_place_buf)
+        refused = EINVAL, why = "the base was carried in place: the output is that buffer";
     if (refused)
         return lthip_fail(ctx, refused, "lthip_restore_blocks", why);
     try
@@ -1014,25 +1082,17 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
     }
 }
 
-static int carry_queue(lthip_restore* r, const void* d_base, void* d_out)
+// d_scratch == null: out of place, d_base -> d_out.  Otherwise in place: d_base == d_out is the one buffer, and the moved runs go through
+// d_scratch (16-byte aligned, lthip_restore_in_place_scratch_bound), all reads before all writes.
+static int carry_queue(lthip_restore* r, const void* d_base, void* d_out, void* d_scratch)
 {
     lthip_ctx* ctx = r->ctx;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint32_t n = r->ncarry;
     const size_t n2 = ((size_t)n + 2) & ~(size_t)1;
-    // [n u64 run source][n u64 run destination][n u64 run length][n u32 pieces][n + 1 u32 first piece][n u32 boundary][n + 1 u32 rank]
-    void* tab = nullptr;
-    int err = lthip_scratch(ctx, S_CARRY_RUNS, n2 * 40, &tab);
-    if (err)
-        return err;
-    uint64_t* run_src = (uint64_t*)tab;
-    uint64_t* run_dst = run_src + n2;
-    uint64_t* run_len = run_dst + n2;
-    uint32_t* pieces = (uint32_t*)(run_len + n2);
-    uint32_t* first_piece = pieces + n2;
-    uint32_t* bound = first_piece + n2;
-    uint32_t* rank = bound + n2;
+    const bool in_place = r->in_place;
+    int err;
     // ---- verify: the base chunks that feed something, hashed where they lie, before anything of them is copied ----
     const uint32_t* bbad = nullptr;
     if (r->verify && r->nmarked)
@@ -1047,6 +1107,20 @@ static int carry_queue(lthip_restore* r, const void* d_base, void* d_out)
         LTHIP_LAUNCH_CHECK(ctx);
         bbad = r->d_ubad;
     }
+    if (in_place && !r->moved_occ) // everything the base feeds lies where it belongs: no copy is queued
+        return 0;
+    // [n u64 run source][n u64 run destination][n u64 run length][n u32 pieces][n + 1 u32 first piece][n u32 boundary][n + 1 u32 rank]
+    // in place, behind them: [n u64 run slot][n u32 pieces in][n + 1 u32 first piece in][n u32 units][n + 1 u32 first unit]
+    void* tab = nullptr;
+    if ((err = lthip_scratch(ctx, S_CARRY_RUNS, n2 * (in_place ? 64 : 40), &tab)))
+        return err;
+    uint64_t* run_src = (uint64_t*)tab;
+    uint64_t* run_dst = run_src + n2;
+    uint64_t* run_len = run_dst + n2;
+    uint32_t* pieces = (uint32_t*)(run_len + n2);
+    uint32_t* first_piece = pieces + n2;
+    uint32_t* bound = first_piece + n2;
+    uint32_t* rank = bound + n2;
     // ---- runs: boundaries, their scan, a slot per entry that starts a run, the pieces' scan, the copy ----
     {
         LaunchTimer tm(ctx, LTHIP_K_GATHER);
@@ -1063,9 +1137,37 @@ static int carry_queue(lthip_restore* r, const void* d_base, void* d_out)
                            run_dst, run_len, pieces);
         LTHIP_LAUNCH_CHECK(ctx);
     }
-    if ((err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, n, nullptr, LTHIP_K_GATHER)))
+    if (!in_place)
+    {
+        if ((err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, n, nullptr, LTHIP_K_GATHER)))
+            return err;
+        return lthip_raw_copy_runs(ctx, first_piece, n, run_src, run_dst, run_len, d_base, d_out, r->carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
+    }
+    // ---- in place: kept runs drop out, moved runs get a slot; pass 1 buffer -> scratch, pass 2 scratch -> buffer ----
+    uint64_t* run_slot = (uint64_t*)(rank + n2);
+    uint32_t* pieces_in = (uint32_t*)(run_slot + n2);
+    uint32_t* first_piece_in = pieces_in + n2;
+    uint32_t* units = first_piece_in + n2;
+    uint32_t* first_unit = units + n2;
+    {
+        LaunchTimer tm(ctx, LTHIP_K_GATHER);
+        hipLaunchKernelGGL(k_restore_in_place_classify, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint64_t*)run_src,
+                           (const uint64_t*)run_dst, (const uint64_t*)run_len, pieces, pieces_in, units);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    if ((err = lthip_exclusive_scan_u32(ctx, units, first_unit, n, nullptr, LTHIP_K_GATHER)) ||
+        (err = lthip_exclusive_scan_u32(ctx, pieces_in, first_piece_in, n, nullptr, LTHIP_K_GATHER)) ||
+        (err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, n, nullptr, LTHIP_K_GATHER)))
         return err;
-    return lthip_raw_copy_runs(ctx, first_piece, n, run_src, run_dst, run_len, d_base, d_out, r->carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
+    {
+        LaunchTimer tm(ctx, LTHIP_K_GATHER);
+        hipLaunchKernelGGL(k_restore_in_place_slots, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint32_t*)first_unit, run_slot);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    const uint64_t pieces_bound = r->moved_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + r->moved_occ;
+    if ((err = lthip_raw_copy_runs(ctx, first_piece_in, n, run_src, run_slot, run_len, d_base, d_scratch, pieces_bound)))
+        return err;
+    return lthip_raw_copy_runs(ctx, first_piece, n, run_slot, run_dst, run_len, d_scratch, d_out, pieces_bound);
 }
 
 extern "C" int lthip_restore_carry(lthip_restore* r, const void* d_base, void* d_out)
@@ -1085,13 +1187,87 @@ extern "C" int lthip_restore_carry(lthip_restore* r, const void* d_base, void* d
         const uint64_t b0 = (uint64_t)(uintptr_t)d_base, o0 = (uint64_t)(uintptr_t)d_out;
         if (b0 < o0 + r->out_bytes && o0 < b0 + r->base_window)
             return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "the base and the output overlap: the update is out of place");
-        const int err = carry_queue(r, d_base, d_out);
+        const int err = carry_queue(r, d_base, d_out, nullptr);
         if (err)
             return err;
     }
     r->carried = true;
     r->finished = false;
     return 0;
+}
+
+// what the moved runs need in the caller's scratch: their bytes, every run's slot rounded up to 16 bytes (a run holds at least one moved
+// occurrence), and room to start the first slot on a 16-byte boundary
+static uint64_t in_place_bound(const lthip_restore* r) { return r->moved_occ ? r->moved_bytes + 16u * r->moved_occ + 64u : 0u; }
+
+extern "C" size_t lthip_restore_in_place_scratch_bound(const lthip_restore* r) { return r && r->has_base ? (size_t)in_place_bound(r) : 0; }
+
+extern "C" int lthip_restore_in_place_stats(const lthip_restore* r, uint64_t out[4])
+{
+    if (!r || !out)
+        return EINVAL;
+    out[0] = r->has_base ? r->ncarry - r->moved_occ : 0u;
+    out[1] = r->has_base ? r->carry_bytes - r->moved_bytes : 0u;
+    out[2] = r->has_base ? r->moved_occ : 0u;
+    out[3] = r->has_base ? r->moved_bytes : 0u;
+    return 0;
+}
+
+extern "C" int lthip_restore_carry_in_place(lthip_restore* r, void* d_buf, void* d_scratch, uint64_t scratch_bytes)
+{
+    if (!r)
+        return EINVAL;
+    lthip_ctx* ctx = r->ctx;
+    // ---- the refusals, before anything is queued or changed ----
+    if (!r->has_base)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "the session was created without a base");
+    if (r->carried)
+        return lthip_fail(ctx, EEXIST, "lthip_restore_carry_in_place", "the base was carried before");
+    if (r->blocks_queued)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "a blocks call has queued work: the carry in place comes first");
+    if (r->ncarry && !d_buf)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "null buffer");
+    void* scratch = nullptr;
+    if (r->moved_occ)
+    {
+        const uint64_t bound = in_place_bound(r);
+        if (bound >> 36) // (the slots are placed by a 32-bit scan of 16-byte units)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "more than 64 GiB would move: update out of place");
+        if (!d_scratch)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "null scratch");
+        const uint64_t b0 = (uint64_t)(uintptr_t)d_buf, s0 = (uint64_t)(uintptr_t)d_scratch;
+        if (s0 < b0 + std::max(r->base_window, r->out_bytes) && b0 < s0 + std::max(bound, scratch_bytes))
+            return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "the scratch overlaps the buffer");
+        if (scratch_bytes < bound)
+            return lthip_fail(ctx, ENOMEM, "lthip_restore_carry_in_place", "scratch below lthip_restore_in_place_scratch_bound");
+        scratch = (void*)(uintptr_t)((s0 + 15u) & ~(uint64_t)15u);
+    }
+    r->in_place = true;
+    const int err = r->ncarry ? carry_queue(r, d_buf, d_buf, scratch) : 0;
+    if (err)
+    {
+        r->in_place = false;
+        return err;
+    }
+    r->in_place_buf = d_buf;
+    r->carried = true;
+    r->finished = false;
+    return 0;
+}
+
+extern "C" int lthip_restore_layout_in_place(const void* base_vi, size_t base_vi_size, const uint64_t* base_offsets, uint64_t base_bytes,
+                                             const void* target_vi, size_t target_vi_size, uint64_t align, uint64_t* target_offsets,
+                                             uint32_t* asset_count, uint64_t* total_bytes, uint32_t* kept_assets)
+{
+    try
+    {
+        return restore_layout::in_place(base_vi, base_vi_size, base_offsets, base_bytes, target_vi, target_vi_size, align, target_offsets, asset_count,
+                                        total_bytes, kept_assets);
+    }
+    catch (const std::bad_alloc&)
+    {
+        return ENOMEM;
+    }
 }
 
 extern "C" int lthip_version_diff(const void* source_vi, size_t source_size, const void* target_vi, size_t target_size, uint32_t* source_removed,

@@ -171,6 +171,10 @@ class HipLib:
         sig("lthip_restore_create_from_base", i32, [vp, vp, vp, vp, sz, vp, sz, vp, u64, P(vp)])
         sig("lthip_restore_carry", i32, [vp, vp, vp])
         sig("lthip_version_diff", i32, [vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp])
+        sig("lthip_restore_layout_in_place", i32, [vp, sz, vp, u64, vp, sz, u64, vp, P(u32), P(u64), P(u32)])
+        sig("lthip_restore_in_place_scratch_bound", sz, [vp])
+        sig("lthip_restore_in_place_stats", i32, [vp, vp])
+        sig("lthip_restore_carry_in_place", i32, [vp, vp, vp, u64])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1170,6 +1174,24 @@ class Restore:
         self.ctx._check(self.ctx.lib.dll.lthip_restore_carry(self.h, _ptr(base_tensor) or None, _ptr(out) or None), "lthip_restore_carry")
         self._keep.append((base_tensor, out))
 
+    def in_place_scratch_bound(self) -> int:
+        """Bytes of scratch carry_in_place needs: moved bytes + 16 x moved occurrences + 64, or 0 when nothing moves."""
+        return int(self.ctx.lib.dll.lthip_restore_in_place_scratch_bound(self.h))
+
+    def in_place_stats(self):
+        """-> (kept occurrences, kept bytes, moved occurrences, moved bytes) of what the base feeds, when base and target share a buffer."""
+        out = np.zeros(4, np.uint64)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_in_place_stats(self.h, out.ctypes.data), "lthip_restore_in_place_stats")
+        return tuple(int(x) for x in out)
+
+    def carry_in_place(self, buf, scratch):
+        """Queues the update in place: `buf` (a device uint8 tensor of max(base bytes, out bytes)) holds the base and becomes the target;
+        what moves goes through `scratch` (at least in_place_scratch_bound() bytes; None when nothing moves), all reads before all writes.
+        Once per session and before the first blocks() call, whose `out` is then `buf`.  Asynchronous on the context's stream."""
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_carry_in_place(self.h, _ptr(buf) or None, _ptr(scratch) or None, _numel(scratch)),
+                        "lthip_restore_carry_in_place")
+        self._keep.append((buf, scratch))
+
     def finish(self):
         """-> (code, RestoreResult): 0, errno.ENOENT (needed blocks are outstanding, or the base has not been carried: deliver / carry
         and call again) or errno.EBADF (a delivered block was bad, or with verify a chunk of the base).  The session's one full
@@ -1207,6 +1229,22 @@ def version_diff(source_vi: bytes, target_vi: bytes, lib: Optional[HipLib] = Non
     if err:
         raise LongtailHipError(err, "lthip_version_diff")
     return tuple(x[: int(counts[k])] for x, k in zip(lists, (0, 1, 2, 2, 3, 3)))
+
+
+def restore_layout_in_place(base_vi: bytes, base_offsets, base_bytes: int, target_vi: bytes, align: int = 1, lib: Optional[HipLib] = None):
+    """lthip_restore_layout_in_place, host only: where the target's assets go in the buffer the base lies restored in -- unchanged assets
+    keep their offsets, the others fill the gaps first fit or are appended -> (target offsets: uint64 array, total bytes, kept assets)."""
+    dll = (lib or load()).dll
+    a, b, offs = np.frombuffer(base_vi, np.uint8), np.frombuffer(target_vi, np.uint8), _u64arr(base_offsets)
+    n = int(np.frombuffer(target_vi[12:16], np.uint32)[0]) if len(target_vi) >= 16 else 0
+    out = np.zeros(max(n, 1), np.uint64)
+    count, total, kept = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+    err = dll.lthip_restore_layout_in_place(a.ctypes.data if len(a) else None, len(a), offs.ctypes.data, int(base_bytes),
+                                            b.ctypes.data if len(b) else None, len(b), align, out.ctypes.data, C.byref(count), C.byref(total),
+                                            C.byref(kept))
+    if err:
+        raise LongtailHipError(err, "lthip_restore_layout_in_place")
+    return out[: count.value], int(total.value), int(kept.value)
 
 
 class Plan:

@@ -17,6 +17,15 @@ that copy, not the code under test, is what the carry is measured against.  Reco
 threshold.
 
     python tools/restore_rate.py --update [--share 0.1] [--gib 4] [--repeats 3] [--out profiles/restore_update_rate.json]
+
+--update --in-place measures the update IN PLACE on the same tree (lthip_restore_layout_in_place / lthip_restore_carry_in_place): version A
+lies in the buffer that becomes version B.  Three things are timed in one process, alternated repeat by repeat, verify off and on: the
+out-of-place update (carry + blocks + finish), the in-place update (carry_in_place + blocks + finish; the buffer is a fresh copy of A every
+time, made outside the timing) and the full restore of B.  The out-of-place update of the same process is what the in-place figure is read
+against.  Recorded into profiles/restore_update_in_place_rate.json: the three times, in_place_stats, the blocks fetched and the scratch
+used.  There is no threshold.
+
+    python tools/restore_rate.py --update --in-place [--share 0.1] [--gib 4] [--repeats 3]
 """
 import argparse
 import json
@@ -112,6 +121,75 @@ def update_leg(args):
               "unit": "GB/s of output (the whole of version B)", "repeats": args.repeats, "files_replaced": int(len(replaced)),
               "stored_bytes_of_the_missing_blocks": stored_missing, "stored_bytes_of_all_blocks": stored_full}
 
+    if args.in_place:
+        from longtail_amd.lib import restore_layout_in_place
+
+        offsets_ip, bytes_ip, kept_assets = restore_layout_in_place(vi_a, offsets_a, n, vi_b, 1, lib)
+        assert bytes_ip == n
+        report["unit"] = "milliseconds of carry + every blocks call + finish; GB/s of output (the whole of version B)"
+        report["assets_kept_by_the_layout"] = kept_assets
+
+        def once(kind, verify):
+            """-> (ms of the calls behind create, finish's result, the session's in_place_stats and scratch bound)"""
+            in_place, with_base = kind == "in_place", kind != "full_restore"
+            offs = offsets_ip if in_place else offsets_b
+            vi, si, calls = (vi_b, si_missing, calls_missing) if with_base else (vi_b, si_full, calls_full)
+            dst = data_a[:n].clone() if in_place else out
+            if not in_place:
+                out.fill_(0xA5)
+            rs = Restore(ctx, vi, si, offs, n, verify=verify, base=base if with_base else None)
+            stats, bound = rs.in_place_stats(), rs.in_place_scratch_bound()
+            scratch = torch.empty(bound, **u8) if in_place and bound else None
+            ctx.sync()
+            t0 = time.perf_counter()
+            if in_place:
+                rs.carry_in_place(dst, scratch)
+            elif with_base:
+                rs.carry(data_a, dst)
+            for images, h, o, z in calls:
+                if len(h):
+                    rs.blocks(h, images, o, z, None, dst)
+            code, result = rs.finish()
+            ms = (time.perf_counter() - t0) * 1e3
+            assert code == 0 and result.bytes_written == n, (code, result.bytes_written)
+            if in_place:  # asset a of B at offsets_ip[a]: every file has 1 MiB, so the windows are the tree's in some order
+                for a in np.random.default_rng(1).choice(nfiles, 64, replace=False).tolist() + replaced[:8].tolist():
+                    assert torch.equal(dst[int(offs[a]) : int(offs[a]) + FILE], data_b[a * FILE : (a + 1) * FILE]), a
+                if np.array_equal(offs, offsets_b):
+                    assert torch.equal(dst, data_b[:n]), "the buffer differs from version B"
+            else:
+                assert torch.equal(dst, data_b[:n]), "the restored bytes differ from version B"
+            rs.close()
+            return ms, result, stats, bound
+
+        kinds = ("update_out_of_place", "in_place", "full_restore")
+        for verify in (False, True):
+            ms = {k: [] for k in kinds}
+            info = {}
+            for rep in range(args.repeats + 1):  # (the first is the warm-up: workspaces of the context)
+                for k in kinds:
+                    t, result, stats, bound = once(k, verify)
+                    info[k] = (result, stats, bound)
+                    if rep:
+                        ms[k].append(round(t, 3))
+            entry = {}
+            for k in kinds:
+                med = float(np.median(ms[k]))
+                entry[k] = {"ms": ms[k], "ms_median": med, "GBps_median": round(n / (med * 1e-3) / 1e9, 2), "blocks_fetched": int(info[k][0].blocks_needed)}
+            stats, bound = info["in_place"][1], info["in_place"][2]
+            entry["in_place"].update(in_place_stats=dict(zip(("kept_occurrences", "kept_bytes", "moved_occurrences", "moved_bytes"), stats)),
+                                     scratch_bytes=bound, moved_share_of_the_base_fed_bytes=round(stats[3] / max(1, stats[1] + stats[3]), 4))
+            entry["in_place_over_out_of_place"] = round(entry["in_place"]["ms_median"] / entry["update_out_of_place"]["ms_median"], 3)
+            report["verify" if verify else "no_verify"] = entry
+            print("verify" if verify else "no_verify", json.dumps(entry), flush=True)
+        plan.close()
+        ctx.close()
+        path = Path(args.out if args.out else ROOT / "profiles" / "restore_update_in_place_rate.json")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(report, indent=1) + "\n")
+        print("wrote", path)
+        return
+
     def timed(label, vi, si, calls, with_base, verify):
         plans, rates, result = [], [], None
         for rep in range(args.repeats + 1):  # (the first is the warm-up: workspaces of the context)
@@ -184,6 +262,7 @@ def main():
     ap.add_argument("--max-chunks-per-block", type=int, default=1024)
     ap.add_argument("--out", default=None, help="default: profiles/restore_rate.json, with --update profiles/restore_update_rate.json")
     ap.add_argument("--update", action="store_true", help="the session with a base: version A resident, version B restored from it")
+    ap.add_argument("--in-place", action="store_true", help="--update: the out-of-place update, the update in place and the full restore, alternated")
     ap.add_argument("--share", type=float, default=0.1, help="--update: the share of the files that version B replaces")
     args = ap.parse_args()
     if args.update:
