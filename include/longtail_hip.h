@@ -846,7 +846,7 @@ typedef struct lthip_restore_config
 typedef struct lthip_restore_result
 {
     uint64_t struct_size;       /* IN: sizeof(lthip_restore_result) of the caller's header; the library fills at most that */
-    uint64_t assets_selected;   /* assets with an offset other than LTHIP_RESTORE_SKIP */
+    uint64_t assets_selected;   /* assets with an offset other than LTHIP_RESTORE_SKIP; create_windows: distinct assets a window names */
     uint64_t occurrences;       /* planned chunk writes */
     uint64_t occurrences_written, bytes_written; /* those fed by delivered, good blocks and, once carried, by good chunks of the base */
     uint64_t blocks_needed, blocks_delivered /* all accepted blocks, unneeded ones included */, blocks_unneeded, blocks_bad;
@@ -973,6 +973,72 @@ LTHIP_EXPORT int lthip_restore_layout_in_place(const void* base_version_index, s
 LTHIP_EXPORT size_t lthip_restore_in_place_scratch_bound(const lthip_restore* restore);
 LTHIP_EXPORT int lthip_restore_in_place_stats(const lthip_restore* restore, uint64_t out[4]);
 LTHIP_EXPORT int lthip_restore_carry_in_place(lthip_restore* restore, void* d_buf, void* d_scratch, uint64_t scratch_bytes);
+
+/* ---- byte windows of assets: part of an asset, a rank's share (restore.hip, restore_windows.h) -----------------------------------------
+ * The restore session at the granularity of the byte -- the device side of the reference's ranged read (BlockStoreStorageAPI_Read over
+ * ReadFromBlock, lib/blockstorestorage/longtail_blockstorestorage.c:728 / :245): a part of a file out of a store, a restore divided
+ * over ranks by the jobs the ingest is divided by, an asset or a version that does not fit one output buffer.
+ *   create_windows  lthip_restore_create with windows[window_count] (host, read before the call returns) in place of asset_offsets.  A
+ *                  window [offset, offset + length) of asset `asset` plans one occurrence per chunk of the asset from the one that holds
+ *                  byte `offset` to the one that holds byte `offset + length - 1`, each CLIPPED to the window -- `skip` bytes into the
+ *                  chunk, `clip` bytes long -- and written at dst + (its position inside the window).  The two chunks are found by
+ *                  bisection over the asset's chunk prefix sums: a small window into an asset of 500 000 chunks does not walk them per
+ *                  window.  Windows may name the same asset, and the same bytes, any number of times: each is its own occurrences.
+ *                  Overlapping destinations are not checked (as asset offsets are not).  One window {a, 0, 0, size of a, offset of a}
+ *                  per selected asset IS lthip_restore_create: the same output, needed_blocks and result -- that call and
+ *                  lthip_restore_create_from_base are callers of the same routine.  It returns an ordinary lthip_restore:
+ *                  needed_blocks, scratch_bound, blocks, finish, block_status and destroy work on it unchanged.
+ *                    needed_blocks shrinks to the blocks that hold a chunk some window overlaps.
+ *                    ENOENT only for a chunk some window overlaps that the StoreIndex does not hold (or holds with another size -- the
+ *                           chunk's FULL size is compared, whatever the clip): a StoreIndex that lacks chunks no window touches is
+ *                           accepted, so a rank may hold a partial StoreIndex.
+ *                    EINVAL asset >= the version's asset count; reserved != 0; windows == NULL with window_count > 0; offset + length
+ *                           beyond the asset's size; dst + length beyond out_bytes (both with overflow, and also for length 0); more
+ *                           than 0x7FFFFFF0 occurrences in total (found before anything of that size is allocated).
+ *                    Everything else is refused as lthip_restore_create refuses it; on any error nothing stays allocated and the
+ *                    context stays usable.
+ *                  A window of length 0 -- the only window a directory or an empty file admits -- plans nothing.
+ *                  result.assets_selected: the distinct assets named by at least one window, whatever its length; occurrences,
+ *                  occurrences_written and bytes_written count clipped occurrences and clipped bytes.
+ *                  THE GUARANTEE is unchanged and per block: with verify every chunk of a delivered block is hashed WHOLE, also the
+ *                  chunks a window uses a part of or not at all, so a block with a bad chunk outside every window still contributes
+ *                  nothing; nothing is written outside [dst, dst + length) of any window.
+ *                  A window session has no base: lthip_restore_carry and lthip_restore_carry_in_place return EINVAL on it.
+ *   asset_sizes    host only.  sizes[asset count] (may be NULL), *asset_count and *target_chunk_size (may be NULL) of a serialized
+ *                  VersionIndex: what lthip_job_count / lthip_make_jobs / lthip_partition_jobs want, for a caller that holds the
+ *                  version as a blob.  EINVAL a NULL blob, EBADF as lthip_restore_layout.
+ *   rank_windows   host arithmetic.  The share of `rank` as windows into a dense output buffer of that rank's own: its jobs of size > 0
+ *                  in job order; a job that continues the one before it -- the same asset, its offset the end of that one -- joins its
+ *                  window; a window's dst is the end of the window before it rounded up to `align` (a power of two, EINVAL otherwise;
+ *                  the first window lies at 0); *out_bytes (may be NULL) = the end of the last window.  *window_count is always
+ *                  filled; windows NULL or capacity below the count: the count (and *out_bytes) only, nothing is written -- ENOMEM
+ *                  when windows were given.  Deterministic: every rank can compute every rank's table, which is what puts a file
+ *                  together again from the ranks' buffers.
+ * Out of scope: windows together with a base (create_from_base, carry, carry_in_place); decoding only the part of a tagged block that a
+ * window needs -- a block is decoded whole, as the reference's ReadFromBlock does, so the cost follows the blocks needed; a cache of
+ * decoded blocks between sessions -- the reference puts lib/lrublockstore in front for that. */
+typedef struct lthip_restore_window
+{
+    uint32_t asset;    /* index into the VersionIndex's assets */
+    uint32_t reserved; /* 0 */
+    uint64_t offset;   /* first byte of the asset that is wanted */
+    uint64_t length;   /* 0: the window plans nothing */
+    uint64_t dst;      /* where that byte goes in d_out */
+} lthip_restore_window; /* 32 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(lthip_restore_window) == 32, "lthip_restore_window is 32 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(lthip_restore_window) == 32, "lthip_restore_window is 32 bytes");
+#endif
+LTHIP_EXPORT int lthip_restore_create_windows(lthip_ctx* ctx, const lthip_restore_config* config, const void* version_index,
+                                              size_t version_index_size, const void* store_index, size_t store_index_size,
+                                              uint64_t window_count, const lthip_restore_window* windows /*host*/, uint64_t out_bytes,
+                                              lthip_restore** out);
+LTHIP_EXPORT int lthip_restore_asset_sizes(const void* version_index, size_t version_index_size, uint64_t* sizes /*may be NULL*/,
+                                           uint32_t* asset_count, uint32_t* target_chunk_size);
+LTHIP_EXPORT int lthip_restore_rank_windows(uint64_t job_count, const uint32_t* job_asset, const uint64_t* job_offset, const uint64_t* job_size,
+                                            const uint32_t* job_rank, uint32_t rank, uint64_t align, lthip_restore_window* windows,
+                                            uint64_t capacity, uint64_t* window_count, uint64_t* out_bytes);
 
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets

@@ -7,6 +7,11 @@
 //            the StoreIndex's chunk hashes go into an lthip_seen, lthip_seen_find gives every occurrence the position of its chunk,
 //            k_restore_resolve checks the size and counts occurrences per block, an exclusive scan gives every block its first entry,
 //            k_restore_fill places (offset in block, length, destination) block-major.  The block_count + 1 firsts come back once.
+//   windows  (lthip_restore_create_windows, restore_windows.h) the occurrences are those of byte windows of assets, each CLIPPED to its
+//            window: next to the chunk's full length it carries `skip` bytes into the chunk and `clip` bytes to write.  k_restore_resolve
+//            still compares the full length with the StoreIndex's size and counts `clip` bytes; k_restore_fill places (offset in block +
+//            skip, clip, destination).  A clipped occurrence is an ordinary entry: check, decode, verify and scatter do not know of it.
+//            The sessions of whole assets are the same routine with one window per selected asset and no skip / clip tables at all.
 //   blocks   k_restore_check_images (a wave per image, against the device copy of the StoreIndex) -> the decoders into 64-byte slots of
 //            the caller's scratch -> k_restore_ranges (the decoders' verdict into the block's status word; with verify the (offset,
 //            length) of every chunk) -> lthip_hash_ranges_by_id -> k_restore_compare -> k_restore_scatter over the call's entries.
@@ -32,6 +37,7 @@
 #include "lthip_internal.h"
 #include "restore_layout.h"
 #include "restore_parse.h"
+#include "restore_windows.h"
 #include "store_layout.h"
 #include "version_diff.h"
 
@@ -83,10 +89,11 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 }
 
 // counters: [0] occurrences neither source resolves, [5] bytes the base feeds ([8], [9]: k_restore_fill)
-__global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint32_t* __restrict__ csize,
-                                  const uint32_t* __restrict__ cblock, uint32_t* __restrict__ hist, unsigned long long* __restrict__ bbytes,
-                                  unsigned long long* counters, BasePlan bp, uint32_t* __restrict__ oflag, uint32_t* __restrict__ bfeed,
-                                  uint32_t* __restrict__ bmark)
+// (oclip: the bytes a clipped occurrence writes, null when every occurrence is its whole chunk)
+__global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen,
+                                  const uint32_t* __restrict__ oclip, const uint32_t* __restrict__ csize, const uint32_t* __restrict__ cblock,
+                                  uint32_t* __restrict__ hist, unsigned long long* __restrict__ bbytes, unsigned long long* counters,
+                                  BasePlan bp, uint32_t* __restrict__ oflag, uint32_t* __restrict__ bfeed, uint32_t* __restrict__ bmark)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool miss = false;
@@ -113,7 +120,7 @@ __global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, 
             else
             {
                 atomicAdd(&hist[b], 1u);
-                atomicAdd(&bbytes[b], (unsigned long long)len);
+                atomicAdd(&bbytes[b], (unsigned long long)(oclip ? oclip[i] : len));
             }
         }
     }
@@ -130,8 +137,9 @@ __global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, 
 
 // the order of a block's entries is whatever the atomics give; the output does not depend on it.  The base's entries keep the order of
 // the occurrences (ofirst: the scan of the flags): that order is what makes runs.
-__global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint64_t* __restrict__ odst,
-                               const uint32_t* __restrict__ csize, const uint32_t* __restrict__ cblock, const uint32_t* __restrict__ coff,
+__global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint32_t* __restrict__ oskip,
+                               const uint32_t* __restrict__ oclip, const uint64_t* __restrict__ odst, const uint32_t* __restrict__ csize,
+                               const uint32_t* __restrict__ cblock, const uint32_t* __restrict__ coff,
                                const uint32_t* __restrict__ firsts, uint32_t* __restrict__ cursor, uint4* __restrict__ entries, BasePlan bp,
                                const uint32_t* __restrict__ ofirst, uint64_t* __restrict__ ksrc, uint64_t* __restrict__ kdst,
                                uint32_t* __restrict__ klen, uint32_t* __restrict__ kchunk, unsigned long long* counters)
@@ -162,7 +170,9 @@ __global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, con
             if (b != NONE && csize[p] == len)
             {
                 const uint32_t slot = firsts[b] + atomicAdd(&cursor[b], 1u);
-                entries[slot] = make_uint4(coff[p], len, (uint32_t)d, (uint32_t)(d >> 32));
+                // (skip + clip <= len == csize[p]: the entry stays inside its chunk, and the block's raw size is below 2^32)
+                const uint32_t skip = oskip ? oskip[i] : 0u, clip = oclip ? oclip[i] : len;
+                entries[slot] = make_uint4(coff[p] + skip, clip, (uint32_t)d, (uint32_t)(d >> 32));
             }
         }
     }
@@ -570,9 +580,20 @@ extern "C" void lthip_restore_destroy(lthip_restore* r)
     delete r;
 }
 
+// What a session writes: byte windows of assets (lthip_restore_create_windows), or whole assets at asset_offsets -- which become one
+// window per selected asset once the VersionIndex has been read.
+struct Wanted
+{
+    const char* who;
+    const uint64_t* asset_offsets;
+    bool by_window;
+    uint64_t window_count;
+    const restore_windows::Window* windows;
+};
+
 // `base` is optional: lthip_restore_create passes none, and then every step that serves it is skipped
 static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, const lthip_restore_base* base, const void* version_index,
-                         size_t vi_size, const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes)
+                         size_t vi_size, const void* store_index, size_t si_size, const Wanted& wanted, uint64_t out_bytes)
 {
     lthip_ctx* ctx = r->ctx;
     restore_parse::VersionIndex vi, bvi;
@@ -583,7 +604,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         return lthip_fail(ctx, EBADF, "lthip_restore_create", "malformed store index");
     if (si.chunk_count && si.hash_identifier != vi.hash_identifier)
         return lthip_fail(ctx, EINVAL, "lthip_restore_create", "the version index and the store index carry different hash identifiers");
-    if (vi.asset_count && !asset_offsets)
+    if (!wanted.by_window && vi.asset_count && !wanted.asset_offsets)
         return EINVAL;
     if (cfg)
     {
@@ -636,33 +657,28 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
             }
         }
     }
-    // ---- occurrences of the selected assets: destination = the asset's offset + the sizes of its chunks so far ----
-    std::vector<uint64_t> ohash, odst;
-    std::vector<uint32_t> olen;
-    for (uint64_t a = 0; a < vi.asset_count; ++a)
+    // ---- occurrences: per window and chunk it touches (hash, full length, skip, clip, destination); a selected asset is one window of
+    // all its bytes at its offset (a directory or an empty file: a window of no bytes, whatever its offset) ----
+    restore_windows::Occurrences occ;
     {
-        const uint64_t off = asset_offsets[a], size = vi.asset_sizes[a];
-        if (off == restore_parse::SKIP)
-            continue;
-        ++r->assets_selected;
-        if (!size)
-            continue; // directories and empty files plan nothing
-        if (off > out_bytes || size > out_bytes - off)
-            return lthip_fail(ctx, EINVAL, "lthip_restore_create", "a selected asset's window leaves the output");
-        const uint64_t start = vi.asset_chunk_index_starts[a], count = vi.asset_chunk_counts[a];
-        if (ohash.size() + count > 0x7FFFFFF0ull)
-            return lthip_fail(ctx, EINVAL, "lthip_restore_create", "more than 2^31 chunk writes in one session");
-        uint64_t at = off;
-        for (uint64_t k = 0; k < count; ++k)
-        {
-            const uint32_t c = vi.asset_chunk_indexes[start + k];
-            const uint32_t len = vi.chunk_sizes[c];
-            ohash.push_back(vi.chunk_hashes[c]);
-            odst.push_back(at);
-            olen.push_back(len);
-            at += len;
-        }
+        std::vector<restore_windows::Window> whole;
+        if (!wanted.by_window)
+            for (uint64_t a = 0; a < vi.asset_count; ++a)
+            {
+                const uint64_t off = wanted.asset_offsets[a], size = vi.asset_sizes[a];
+                if (off != restore_parse::SKIP)
+                    whole.push_back(restore_windows::Window{(uint32_t)a, 0u, 0u, size, size ? off : 0u});
+            }
+        const char* why = "";
+        const int refused = wanted.by_window ? restore_windows::expand(vi, wanted.window_count, wanted.windows, out_bytes, &occ, &why)
+                                             : restore_windows::expand(vi, whole.size(), whole.data(), out_bytes, &occ, &why);
+        if (refused)
+            return lthip_fail(ctx, refused, wanted.who, why);
     }
+    r->assets_selected = occ.assets_selected;
+    const std::vector<uint64_t>&ohash = occ.hash, &odst = occ.dst;
+    const std::vector<uint32_t>& olen = occ.len;
+    const bool clipped = !occ.clip.empty();
     // ---- the StoreIndex: per block its tables, per chunk position the block that holds it and where ----
     const uint32_t nb = r->nb = si.block_count, m = r->m = si.chunk_count;
     const uint32_t nocc = r->nocc = (uint32_t)ohash.size();
@@ -714,7 +730,8 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     r->carve(place, nb);
     uint64_t *t_ohash = nullptr, *t_odst = nullptr;
     unsigned long long* t_bbytes = nullptr;
-    uint32_t *t_olen = nullptr, *t_pos = nullptr, *t_hist = nullptr, *t_cursor = nullptr, *t_first = nullptr;
+    uint32_t *t_olen = nullptr, *t_pos = nullptr, *t_hist = nullptr, *t_cursor = nullptr, *t_first = nullptr, *t_oskip = nullptr,
+             *t_oclip = nullptr;
     uint32_t *t_bpos = nullptr, *t_oflag = nullptr, *t_ofirst = nullptr, *t_bfirst = nullptr, *t_bmark = nullptr, *t_mfirst = nullptr;
     const uint32_t nub = r->nub;
     for (int pass = 0; pass < 2; ++pass)
@@ -723,6 +740,8 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         c.p = (uint8_t*)r->d_tmp;
         c.take(&t_ohash, nocc), c.take(&t_odst, nocc), c.take(&t_bbytes, nb), c.take(&t_olen, nocc), c.take(&t_pos, nocc), c.take(&t_hist, nb),
             c.take(&t_cursor, nb), c.take(&t_first, m);
+        if (clipped)
+            c.take(&t_oskip, nocc), c.take(&t_oclip, nocc);
         if (base)
             c.take(&t_bpos, nocc), c.take(&t_oflag, nocc), c.take(&t_ofirst, (size_t)nocc + 1), c.take(&t_bfirst, nub), c.take(&t_bmark, nub),
                 c.take(&t_mfirst, (size_t)nub + 1);
@@ -737,6 +756,9 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         (err = upload(ctx, r->d_bcnt, r->bcnt.data(), (size_t)nb * 4)) || (err = upload(ctx, r->d_btag, r->btag.data(), (size_t)nb * 4)) ||
         (err = upload(ctx, r->d_braw, r->braw.data(), (size_t)nb * 4)) || (err = upload(ctx, t_ohash, ohash.data(), (size_t)nocc * 8)) ||
         (err = upload(ctx, t_odst, odst.data(), (size_t)nocc * 8)) || (err = upload(ctx, t_olen, olen.data(), (size_t)nocc * 4)))
+        return err;
+    if (clipped &&
+        ((err = upload(ctx, t_oskip, occ.skip.data(), (size_t)nocc * 4)) || (err = upload(ctx, t_oclip, occ.clip.data(), (size_t)nocc * 4))))
         return err;
     if (base && ((err = upload(ctx, r->d_uhash, uhash.data(), (size_t)nub * 8)) || (err = upload(ctx, r->d_uoff, uoff.data(), (size_t)nub * 8)) ||
                  (err = upload(ctx, r->d_usize, usize.data(), (size_t)nub * 4))))
@@ -774,8 +796,8 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
             return err;
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
-                           (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, t_hist, t_bbytes, r->d_counters, bp, t_oflag, r->d_ufeed,
-                           t_bmark);
+                           (const uint32_t*)t_oclip, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, t_hist, t_bbytes, r->d_counters, bp,
+                           t_oflag, r->d_ufeed, t_bmark);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if ((err = lthip_exclusive_scan_u32(ctx, t_hist, r->d_firsts, nb, nullptr, LTHIP_K_OTHER)))
@@ -787,9 +809,9 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
-                           (const uint64_t*)t_odst, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, (const uint32_t*)r->d_coff,
-                           (const uint32_t*)r->d_firsts, t_cursor, r->d_entries, bp, (const uint32_t*)t_ofirst, r->d_ksrc, r->d_kdst, r->d_klen,
-                           r->d_kchunk, r->d_counters);
+                           (const uint32_t*)t_oskip, (const uint32_t*)t_oclip, (const uint64_t*)t_odst, (const uint32_t*)r->d_csize,
+                           (const uint32_t*)r->d_cblock, (const uint32_t*)r->d_coff, (const uint32_t*)r->d_firsts, t_cursor, r->d_entries, bp,
+                           (const uint32_t*)t_ofirst, r->d_ksrc, r->d_kdst, r->d_klen, r->d_kchunk, r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (base && r->verify && nub)
@@ -813,9 +835,9 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     }
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
     if (counters[0])
-        return lthip_fail(ctx, ENOENT, base ? "lthip_restore_create_from_base" : "lthip_restore_create",
+        return lthip_fail(ctx, ENOENT, wanted.who,
                           base ? "a selected asset needs a chunk that neither the base nor the store index holds (or holds with another size)"
-                               : "a selected asset needs a chunk the store index does not hold (or holds with another size)");
+                               : "a selected asset or window needs a chunk the store index does not hold (or holds with another size)");
     r->carry_bytes = counters[5];
     r->carry_leaves = counters[6];
     r->moved_occ = counters[8];
@@ -830,8 +852,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
 }
 
 static int restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_restore_base* base, const void* version_index,
-                          size_t vi_size, const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes,
-                          lthip_restore** out)
+                          size_t vi_size, const void* store_index, size_t si_size, const Wanted& wanted, uint64_t out_bytes, lthip_restore** out)
 {
     if (!ctx || !out || !version_index || !store_index)
         return EINVAL;
@@ -843,7 +864,7 @@ static int restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const
     int err;
     try
     {
-        err = restore_build(r, cfg, base, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes);
+        err = restore_build(r, cfg, base, version_index, vi_size, store_index, si_size, wanted, out_bytes);
     }
     catch (const std::bad_alloc&)
     {
@@ -861,7 +882,35 @@ static int restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const
 extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const void* version_index, size_t vi_size,
                                     const void* store_index, size_t si_size, const uint64_t* asset_offsets, uint64_t out_bytes, lthip_restore** out)
 {
-    return restore_create(ctx, cfg, nullptr, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes, out);
+    return restore_create(ctx, cfg, nullptr, version_index, vi_size, store_index, si_size,
+                          Wanted{"lthip_restore_create", asset_offsets, false, 0, nullptr}, out_bytes, out);
+}
+
+static_assert(sizeof(lthip_restore_window) == sizeof(restore_windows::Window) &&
+                  offsetof(lthip_restore_window, dst) == offsetof(restore_windows::Window, dst),
+              "restore_windows.h restates lthip_restore_window");
+
+extern "C" int lthip_restore_create_windows(lthip_ctx* ctx, const lthip_restore_config* cfg, const void* version_index, size_t vi_size,
+                                            const void* store_index, size_t si_size, uint64_t window_count, const lthip_restore_window* windows,
+                                            uint64_t out_bytes, lthip_restore** out)
+{
+    return restore_create(ctx, cfg, nullptr, version_index, vi_size, store_index, si_size,
+                          Wanted{"lthip_restore_create_windows", nullptr, true, window_count,
+                                 reinterpret_cast<const restore_windows::Window*>(windows)},
+                          out_bytes, out);
+}
+
+extern "C" int lthip_restore_asset_sizes(const void* version_index, size_t size, uint64_t* sizes, uint32_t* asset_count, uint32_t* target_chunk_size)
+{
+    return restore_windows::asset_sizes(version_index, size, sizes, asset_count, target_chunk_size);
+}
+
+extern "C" int lthip_restore_rank_windows(uint64_t job_count, const uint32_t* job_asset, const uint64_t* job_offset, const uint64_t* job_size,
+                                          const uint32_t* job_rank, uint32_t rank, uint64_t align, lthip_restore_window* windows, uint64_t capacity,
+                                          uint64_t* window_count, uint64_t* out_bytes)
+{
+    return restore_windows::rank_windows(job_count, job_asset, job_offset, job_size, job_rank, rank, align,
+                                         reinterpret_cast<restore_windows::Window*>(windows), capacity, window_count, out_bytes);
 }
 
 extern "C" int lthip_restore_create_from_base(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_restore_base* base,
@@ -872,7 +921,8 @@ extern "C" int lthip_restore_create_from_base(lthip_ctx* ctx, const lthip_restor
         *out = nullptr;
     if (!base || !base->version_index)
         return EINVAL;
-    return restore_create(ctx, cfg, base, version_index, vi_size, store_index, si_size, asset_offsets, out_bytes, out);
+    return restore_create(ctx, cfg, base, version_index, vi_size, store_index, si_size,
+                          Wanted{"lthip_restore_create_from_base", asset_offsets, false, 0, nullptr}, out_bytes, out);
 }
 
 extern "C" int lthip_restore_needed_blocks(const lthip_restore* r, uint64_t* block_hashes, uint64_t capacity, uint64_t* out_count)

@@ -175,6 +175,9 @@ class HipLib:
         sig("lthip_restore_in_place_scratch_bound", sz, [vp])
         sig("lthip_restore_in_place_stats", i32, [vp, vp])
         sig("lthip_restore_carry_in_place", i32, [vp, vp, vp, u64])
+        sig("lthip_restore_create_windows", i32, [vp, vp, vp, sz, vp, sz, u64, vp, u64, P(vp)])
+        sig("lthip_restore_asset_sizes", i32, [vp, sz, vp, P(u32), P(u32)])
+        sig("lthip_restore_rank_windows", i32, [u64, vp, vp, vp, vp, u32, u64, vp, u64, P(u64), P(u64)])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1082,6 +1085,26 @@ class RestoreBase(C.Structure):
                 ("base_bytes", C.c_uint64)]
 
 
+class RestoreWindow(C.Structure):
+    """lthip_restore_window: bytes [offset, offset + length) of asset `asset`, written at `dst` of the output."""
+    _fields_ = [("asset", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64), ("length", C.c_uint64), ("dst", C.c_uint64)]
+
+
+RESTORE_WINDOW_DTYPE = np.dtype([("asset", "<u4"), ("reserved", "<u4"), ("offset", "<u8"), ("length", "<u8"), ("dst", "<u8")])
+
+
+def _window_table(windows) -> np.ndarray:
+    """(n, 4) uint64 rows of (asset, offset, length, dst), or a sequence of such tuples -> the lthip_restore_window array."""
+    rows = np.asarray(windows if len(windows) else np.zeros((0, 4)), dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[1] != 4:
+        raise ValueError("windows: (n, 4) rows of (asset, offset, length, dst)")
+    if len(rows) and int(rows[:, 0].max()) > 0xFFFFFFFF:
+        raise ValueError("windows: an asset index above 32 bits")
+    table = np.zeros(len(rows), RESTORE_WINDOW_DTYPE)
+    table["asset"], table["offset"], table["length"], table["dst"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3]
+    return table
+
+
 RESTORE_SKIP = 0xFFFFFFFFFFFFFFFF  # include/longtail_hip.h LTHIP_RESTORE_SKIP
 RESTORE_NOT_DELIVERED, RESTORE_BAD_HEADER, RESTORE_BAD_PAYLOAD, RESTORE_BAD_CHUNK = 1, 2, 4, 8
 
@@ -1093,7 +1116,10 @@ class Restore:
 
     base = (version_index, asset_offsets, base_bytes) of a version that lies restored in device memory: the chunks it shares with the
     target are planned as copies from it (carry(base_tensor, out), in any order with blocks()), needed_blocks() shrinks to the blocks that
-    hold a chunk no resident asset has, and store_index may be the small one an incremental ingest returned."""
+    hold a chunk no resident asset has, and store_index may be the small one an incremental ingest returned.
+
+    windows = (n, 4) uint64 rows of (asset, offset, length, dst), with asset_offsets None: the session restores byte windows of assets
+    (lthip_restore_create_windows) -- part of a file, or a rank's share from restore_rank_windows.  No base with windows."""
 
     SKIP = RESTORE_SKIP
 
@@ -1112,13 +1138,27 @@ class Restore:
             raise LongtailHipError(err, "lthip_restore_layout")
         return offsets, int(total.value)
 
-    def __init__(self, ctx: "Context", version_index: bytes, store_index: bytes, asset_offsets, out_bytes: int, verify: bool = True, base=None):
+    def __init__(self, ctx: "Context", version_index: bytes, store_index: bytes, asset_offsets, out_bytes: int, verify: bool = True, base=None,
+                 windows=None):
         self.ctx = ctx
         self.h = None
+        if windows is not None and asset_offsets is not None:
+            raise ValueError("give asset_offsets or windows, not both")
+        if windows is not None and base is not None:
+            raise ValueError("a window session has no base")
         vi, si = np.frombuffer(version_index, np.uint8), np.frombuffer(store_index, np.uint8)
-        offs = _u64arr(asset_offsets)
         cfg = RestoreConfig(C.sizeof(RestoreConfig), 1 if verify else 0)
         h = C.c_void_p()
+        if windows is not None:
+            table = _window_table(windows)
+            ctx._check(ctx.lib.dll.lthip_restore_create_windows(ctx.h, C.byref(cfg), vi.ctypes.data if len(vi) else None, len(vi),
+                                                                si.ctypes.data if len(si) else None, len(si), len(table),
+                                                                table.ctypes.data if len(table) else None, out_bytes, C.byref(h)),
+                       "lthip_restore_create_windows")
+            self.h = h
+            self._keep = []
+            return
+        offs = _u64arr(asset_offsets)
         args = (vi.ctypes.data if len(vi) else None, len(vi), si.ctypes.data if len(si) else None, len(si),
                 offs.ctypes.data if len(offs) else None, out_bytes, C.byref(h))
         if base is None:
@@ -1229,6 +1269,42 @@ def version_diff(source_vi: bytes, target_vi: bytes, lib: Optional[HipLib] = Non
     if err:
         raise LongtailHipError(err, "lthip_version_diff")
     return tuple(x[: int(counts[k])] for x, k in zip(lists, (0, 1, 2, 2, 3, 3)))
+
+
+def restore_asset_sizes(version_index: bytes, lib: Optional[HipLib] = None):
+    """lthip_restore_asset_sizes, host only -> (asset sizes: uint64 array, target chunk size) of a serialized VersionIndex: what
+    lthip_make_jobs and lthip_partition_jobs want."""
+    dll = (lib or load()).dll
+    raw = np.frombuffer(version_index, np.uint8)
+    n, target = C.c_uint32(0), C.c_uint32(0)
+    err = dll.lthip_restore_asset_sizes(raw.ctypes.data if len(raw) else None, len(raw), None, C.byref(n), C.byref(target))
+    if err:
+        raise LongtailHipError(err, "lthip_restore_asset_sizes")
+    sizes = np.zeros(n.value, np.uint64)
+    err = dll.lthip_restore_asset_sizes(raw.ctypes.data, len(raw), sizes.ctypes.data if len(sizes) else None, C.byref(n), C.byref(target))
+    if err:
+        raise LongtailHipError(err, "lthip_restore_asset_sizes")
+    return sizes, int(target.value)
+
+
+def restore_rank_windows(job_asset, job_offset, job_size, job_rank, rank: int, align: int = 1, lib: Optional[HipLib] = None):
+    """lthip_restore_rank_windows, host only: the jobs of `rank` (lthip_make_jobs / lthip_partition_jobs tables) as windows into a dense
+    output of that rank's own -> ((n, 4) uint64 rows of (asset, offset, length, dst), out_bytes): what Restore(windows=...) takes."""
+    dll = (lib or load()).dll
+    ja, jo, js, jr = _u32arr(job_asset), _u64arr(job_offset), _u64arr(job_size), _u32arr(job_rank)
+    assert len(ja) == len(jo) == len(js) == len(jr)
+    ptrs = [x.ctypes.data if len(x) else None for x in (ja, jo, js, jr)]
+    n, total = C.c_uint64(0), C.c_uint64(0)
+    err = dll.lthip_restore_rank_windows(len(ja), *ptrs, rank, align, None, 0, C.byref(n), C.byref(total))
+    if err:
+        raise LongtailHipError(err, "lthip_restore_rank_windows")
+    table = np.zeros(n.value, RESTORE_WINDOW_DTYPE)
+    err = dll.lthip_restore_rank_windows(len(ja), *ptrs, rank, align, table.ctypes.data if len(table) else None, len(table), C.byref(n),
+                                         C.byref(total))
+    if err:
+        raise LongtailHipError(err, "lthip_restore_rank_windows")
+    rows = np.stack([table["asset"].astype(np.uint64), table["offset"], table["length"], table["dst"]], axis=1) if len(table) else np.zeros((0, 4), np.uint64)
+    return rows, int(total.value)
 
 
 def restore_layout_in_place(base_vi: bytes, base_offsets, base_bytes: int, target_vi: bytes, align: int = 1, lib: Optional[HipLib] = None):

@@ -26,6 +26,15 @@ against.  Recorded into profiles/restore_update_in_place_rate.json: the three ti
 used.  There is no threshold.
 
     python tools/restore_rate.py --update --in-place [--share 0.1] [--gib 4] [--repeats 3]
+
+--windows FRACTION measures a window session (lthip_restore_create_windows): the first FRACTION of every file of the same tree, the windows
+dense in an output of their own, fed only the blocks the session needs -- beside the full restore of the tree in the same process, the two
+alternated repeat by repeat, raw, LZ4 and zstd stores, verify off and on.  Reported per store: the blocks needed, GB/s of output (the
+windows' bytes), the milliseconds of the calls behind create, and the plan time (create_windows).  The expectation is a cost that follows
+the blocks needed -- a block is decoded whole; the report says what was measured.  Recorded into profiles/restore_windows_rate.json.  There
+is no threshold.
+
+    python tools/restore_rate.py --windows 0.25 [--gib 4] [--repeats 3] [--out profiles/restore_windows_rate.json]
 """
 import argparse
 import json
@@ -253,6 +262,112 @@ def update_leg(args):
     print("wrote", path)
 
 
+def windows_leg(args):
+    import torch
+
+    from bench import KINDS, asset_seeds, make_tree
+    from longtail_amd.lib import Context, Ingest, IngestStream, Restore, chunker_params, load
+
+    lib = load()
+    dev = torch.device("cuda", 0)
+    ctx = Context(0, lib=lib)
+    nfiles = int(args.gib * (1 << 30)) // FILE
+    n = nfiles * FILE
+    wlen = max(1, min(FILE, int(FILE * args.windows)))
+    wn = nfiles * wlen
+    mn, av, mx = chunker_params(args.target_chunk_size)
+    p_off, p_size = np.arange(nfiles, dtype=np.uint64) * np.uint64(FILE), np.full(nfiles, FILE, np.uint64)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    data = torch.empty(n + 256, **u8)
+    ctx.synth_fill(data, p_off, p_size, asset_seeds(0x10C0FFEE, 0, nfiles), KINDS["mixed"])
+    plan = ctx.make_plan(p_off, p_size, mn, av, mx)
+    total, d_off, d_len, d_hash, d_first = ctx.chunk_hash(plan, data)
+    tree = make_tree("files", n, FILE)
+    whole, _keep = Ingest.tree(tree["sizes"], tree["path_offsets"], tree["perms"], tree["path_data"], np.arange(nfiles, dtype=np.uint32),
+                               np.zeros(nfiles + 1, np.uint64))
+    vi_cap = int(lib.dll.lthip_version_index_size(nfiles, total, total, len(tree["path_data"]))) + 64
+    h_vi, h_si = torch.empty(vi_cap, dtype=torch.uint8).pin_memory(), torch.empty(16 + 32 * total + 64, dtype=torch.uint8).pin_memory()
+    out = torch.empty(n, **u8)
+    want = data[:n].view(nfiles, FILE)[:, :wlen].reshape(-1)  # the windows, dense
+    windows = np.stack([np.arange(nfiles), np.zeros(nfiles), np.full(nfiles, wlen), np.arange(nfiles) * wlen], axis=1).astype(np.uint64)
+    report = {"workload": f"{args.gib:g} GiB `mixed` tree ({nfiles} files of 1 MiB), written by lthip_ingest_stream in one slice; the window session "
+                          f"restores the first {wlen} bytes of every file ({wlen / FILE:.4g} of the tree) from the blocks it needs, the full session "
+                          "the whole tree, alternated in one process: all lthip_restore_blocks calls + lthip_restore_finish",
+              "unit": "GB/s of output (windows: the windows' bytes; full: the tree's bytes)", "repeats": args.repeats, "fraction": wlen / FILE,
+              "stores": {}}
+    for codec, tag in TAGS.items():
+        st = IngestStream(ctx, whole, args.target_chunk_size, args.block_size, args.max_chunks_per_block, codec, compression_type=tag or None)
+        arena, tail = torch.empty(st.arena_bound(n, total), **u8), torch.empty(st.arena_bound(0, 0), **u8)
+        st.slice(0, nfiles, data, d_off, d_len, d_hash, d_first, total, arena)
+        _, offs0, sizes0 = st.images()
+        offs0, sizes0 = offs0.copy(), sizes0.copy()
+        res = st.finish(tail, h_vi, h_si)
+        _, offs1, sizes1 = st.images()
+        offs1, sizes1 = offs1.copy(), sizes1.copy()
+        vi, si = bytes(h_vi.numpy()[: res.version_index_size]), bytes(h_si.numpy()[: res.store_index_size])
+        st.close()
+        hashes, counts, raws = store_blocks(si)
+        calls = [(arena, hashes[: len(offs0)], offs0, sizes0), (tail, hashes[len(offs0) :], offs1, sizes1)]
+        offsets, out_bytes = Restore.layout(vi, 1, lib)
+        assert out_bytes == n
+        entry = {"blocks": int(res.blocks), "raw_bytes_of_the_blocks": int(raws.sum())}
+        scratch = torch.empty(max(64, int(((raws + 63) // 64 * 64).sum()) if tag else 64), **u8)  # (room for every block of a call)
+
+        def once(kind, verify):
+            """-> (ms of create, ms of the blocks calls + finish, the result)"""
+            out.fill_(0xA5)
+            ctx.sync()
+            t0 = time.perf_counter()
+            if kind == "windows":
+                rs = Restore(ctx, vi, si, None, wn, verify=verify, windows=windows)
+            else:
+                rs = Restore(ctx, vi, si, offsets, n, verify=verify)
+            t1 = time.perf_counter()
+            needed = set(rs.needed_blocks().tolist()) if kind == "windows" else None
+            ctx.sync()
+            t2 = time.perf_counter()
+            for images, h, o, z in calls:
+                pick = np.array([x in needed for x in h.tolist()], bool) if needed is not None else np.ones(len(h), bool)
+                if pick.any():
+                    rs.blocks(h[pick], images, o[pick], z[pick], scratch, out)
+            code, result = rs.finish()
+            t3 = time.perf_counter()
+            nbytes = wn if kind == "windows" else n
+            assert code == 0 and result.bytes_written == nbytes, (code, result.bytes_written)
+            assert torch.equal(out[:nbytes], want if kind == "windows" else data[:n]), "the restored bytes differ from the tree"
+            rs.close()
+            return (t1 - t0) * 1e3, (t3 - t2) * 1e3, result
+
+        for verify in (False, True):
+            ms = {k: [] for k in ("windows", "full")}
+            plans = {k: [] for k in ms}
+            results = {}
+            for rep in range(args.repeats + 1):  # (the first is the warm-up: workspaces of the context)
+                for k in ms:
+                    create_ms, run_ms, results[k] = once(k, verify)
+                    if rep:
+                        plans[k].append(round(create_ms, 2))
+                        ms[k].append(round(run_ms, 3))
+            v = {}
+            for k, nbytes in (("windows", wn), ("full", n)):
+                med = float(np.median(ms[k]))
+                v[k] = {"ms": ms[k], "ms_median": med, "GBps_median": round(nbytes / (med * 1e-3) / 1e9, 2), "create_ms": plans[k],
+                        "blocks_needed": int(results[k].blocks_needed), "occurrences": int(results[k].occurrences),
+                        "decoded_bytes": int(results[k].decoded_bytes)}
+            v["windows_over_full_ms"] = round(v["windows"]["ms_median"] / v["full"]["ms_median"], 3)
+            v["blocks_needed_over_all"] = round(v["windows"]["blocks_needed"] / max(1, v["full"]["blocks_needed"]), 3)
+            entry["verify" if verify else "no_verify"] = v
+        report["stores"][codec] = entry
+        print(codec, json.dumps(entry), flush=True)
+        del arena, tail, scratch
+    plan.close()
+    ctx.close()
+    path = Path(args.out if args.out else ROOT / "profiles" / "restore_windows_rate.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(report, indent=1) + "\n")
+    print("wrote", path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -264,7 +379,11 @@ def main():
     ap.add_argument("--update", action="store_true", help="the session with a base: version A resident, version B restored from it")
     ap.add_argument("--in-place", action="store_true", help="--update: the out-of-place update, the update in place and the full restore, alternated")
     ap.add_argument("--share", type=float, default=0.1, help="--update: the share of the files that version B replaces")
+    ap.add_argument("--windows", type=float, default=None, metavar="FRACTION",
+                    help="a window session over the first FRACTION of every file, beside the full restore (profiles/restore_windows_rate.json)")
     args = ap.parse_args()
+    if args.windows is not None:
+        return windows_leg(args)
     if args.update:
         return update_leg(args)
     args.out = args.out or str(ROOT / "profiles" / "restore_rate.json")
