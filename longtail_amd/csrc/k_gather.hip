@@ -1,8 +1,9 @@
 // k_gather.hip -- block assembly on the device: WriteContentBlockJob builds a stored block by
 // reading every chunk of the block into one contiguous buffer (src/longtail.c:4640-4721).  With the assets already
-// resident in HBM that is a gather of byte ranges: one workgroup per chunk, 16-byte stores, source realigned with
-// v_alignbit.  Only needed when a block is not already one contiguous range of the asset buffer (dedup holes,
+// resident in HBM that is a gather of byte ranges: one workgroup per chunk, copied by lthip_wg_copy (k_copy.h).
+// Only needed when a block is not already one contiguous range of the asset buffer (dedup holes,
 // assets whose sizes are not multiples of 16).
+#include "k_copy.h"
 #include "lthip_internal.h"
 #include "store_layout.h"
 
@@ -12,7 +13,6 @@
 namespace
 {
 
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int GT = 256;
 
 __global__ __launch_bounds__(GT) void k_gather_ranges(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_offsets,
@@ -22,37 +22,9 @@ __global__ __launch_bounds__(GT) void k_gather_ranges(const uint8_t* __restrict_
     const uint64_t i = blockIdx.x;
     if (i >= count)
         return;
-    const int tid = threadIdx.x;
     const uint8_t* s = src + src_offsets[i];
     uint8_t* d = dst + dst_offsets[i];
-    uint32_t n = lens[i];
-    uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
-    if (head > n)
-        head = n;
-    if ((uint32_t)tid < head)
-        d[tid] = s[tid];
-    d += head;
-    s += head;
-    n -= head;
-    const uint32_t nvec = n >> 4;
-    const uint32_t mis = (uint32_t)((uintptr_t)s & 3u);
-    const uint32_t sh = mis * 8u;
-    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s - mis);
-    for (uint32_t v = tid; v < nvec; v += GT)
-    {
-        const uint32_t* q = s4 + v * 4u;
-        const u32x4_a4 a = *reinterpret_cast<const u32x4_a4*>(q);
-        const uint32_t e = mis ? q[4] : 0u;
-        uint4 o;
-        o.x = __builtin_amdgcn_alignbit(a.y, a.x, sh);
-        o.y = __builtin_amdgcn_alignbit(a.z, a.y, sh);
-        o.z = __builtin_amdgcn_alignbit(a.w, a.z, sh);
-        o.w = __builtin_amdgcn_alignbit(e, a.w, sh);
-        *reinterpret_cast<uint4*>(d + (uint64_t)v * 16u) = o;
-    }
-    const uint32_t done = nvec << 4;
-    if ((uint32_t)tid < n - done)
-        d[done + tid] = s[done + tid];
+    lthip_wg_copy<GT>(d, s, lens[i], threadIdx.x);
 }
 
 // Pinned host memory <-> HBM by the CUs.  The box's SDMA engines move ONE direction at a time (tools/pcie_duplex_probe.py,
@@ -190,30 +162,6 @@ __global__ __launch_bounds__(64) void k_raw_runs(const uint64_t* __restrict__ bl
         run_len[open_slot] = pos - open_dst;
         pieces[open_slot] = lthip_raw_pieces(open_dst, pos - open_dst);
     }
-}
-
-// four dwords at a 4-byte aligned address (and the fifth, when the source is not: it holds the last bytes of the vector) -> 16 bytes of
-// the source.  No dword is touched that holds no byte of the vector.
-struct RawVec
-{
-    u32x4_a4 a;
-    uint32_t e;
-};
-__device__ __forceinline__ RawVec raw_load(const uint32_t* __restrict__ q, uint32_t mis)
-{
-    RawVec r;
-    r.a = *reinterpret_cast<const u32x4_a4*>(q);
-    r.e = mis ? q[4] : 0u;
-    return r;
-}
-__device__ __forceinline__ uint4 raw_align(const RawVec& r, uint32_t sh)
-{
-    uint4 o;
-    o.x = __builtin_amdgcn_alignbit(r.a.y, r.a.x, sh);
-    o.y = __builtin_amdgcn_alignbit(r.a.z, r.a.y, sh);
-    o.z = __builtin_amdgcn_alignbit(r.a.w, r.a.z, sh);
-    o.w = __builtin_amdgcn_alignbit(r.e, r.a.w, sh);
-    return o;
 }
 
 __global__ __launch_bounds__(GT) void k_raw_copy(const uint32_t* __restrict__ first_piece /* [slots + 1] */, uint32_t slots,

@@ -30,6 +30,7 @@
 //                    literals (from the source) and sequence body (from the stream) into the single final block with 16-byte
 //                    stores.  Blocks without a single match were laid out by K5: only their header is written.
 //   decode           k_lz4_decode.hip
+#include "k_copy.h"
 #include "lthip_internal.h"
 
 #include <string>
@@ -86,8 +87,6 @@ __host__ __device__ __forceinline__ uint32_t lz4_len_bytes(uint32_t len) { retur
 // ... of a length below 65 536 (what a lane's record holds) without a branch and without a 32-bit multiply: (len + 240) / 255 is the
 // same number for every len (0 below 15), and n / 255 = n * 0x8081 >> 23 is exact for n < 66 299
 __device__ __forceinline__ uint32_t lz4_len_bytes16(uint32_t len) { return __umul24(len + 240u, 0x8081u) >> 23; }
-
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
 // ---------------------------------------------------------------------------------------------------
 // K5

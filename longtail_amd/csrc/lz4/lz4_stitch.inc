@@ -154,40 +154,12 @@ __global__ __launch_bounds__(64) void k_lz4_stitch_scan(const Lz4Block* __restri
 // ---------------------------------------------------------------------------------------------------
 // K6b: one workgroup per segment moves its pieces into place
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wg_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n, int tid,
-                                        int nthreads)
+// a wave copies n bytes (k_copy.h)
+__device__ __forceinline__ void wg_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n, int lane)
 {
-    if (n == 0)
-        return;
-    uint32_t head = (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u);
-    if (head > n)
-        head = n;
-    if ((uint32_t)tid < head)
-        dst[tid] = src[tid];
-    dst += head;
-    src += head;
-    n -= head;
-    const uint32_t nvec = n >> 4;
-    const uint32_t mis = (uint32_t)((uintptr_t)src & 3u);
-    const uint32_t sh = mis * 8u;
-    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src - mis);
-    for (uint32_t v = tid; v < nvec; v += nthreads)
-    {
-        const uint32_t* q = s4 + v * 4u;
-        const u32x4_a4 a = *reinterpret_cast<const u32x4_a4*>(q);
-        const uint32_t e = mis ? q[4] : 0u;
-        uint4 o;
-        o.x = __builtin_amdgcn_alignbit(a.y, a.x, sh);
-        o.y = __builtin_amdgcn_alignbit(a.z, a.y, sh);
-        o.z = __builtin_amdgcn_alignbit(a.w, a.z, sh);
-        o.w = __builtin_amdgcn_alignbit(e, a.w, sh);
-        *reinterpret_cast<uint4*>(dst + (uint64_t)v * 16u) = o;
-    }
-    const uint32_t done = nvec << 4;
-    if ((uint32_t)tid < n - done)
-        dst[done + tid] = src[done + tid];
+    if (n)
+        lthip_wg_copy<64>(dst, src, n, lane);
 }
-
 
 constexpr int K6_THREADS = 256;
 
@@ -232,12 +204,12 @@ __global__ __launch_bounds__(K6_THREADS) void k_lz4_stitch_copy(const uint8_t* _
         if (m.seq_bytes)
         {
             wg_emit_header(d + pl.hdr_pos, pl.hdr_lits, stream[0] & 15u, lane, 64);
-            wg_copy(d + pl.first_lit_dst, s, m.first_lit_len, lane, 64);
+            wg_copy(d + pl.first_lit_dst, s, m.first_lit_len, lane);
             const uint32_t skip = m.first_hdr_bytes + m.first_lit_len;
-            wg_copy(d + pl.body_dst, stream + skip, m.seq_bytes - skip, lane, 64);
+            wg_copy(d + pl.body_dst, stream + skip, m.seq_bytes - skip, lane);
             tail = m.tail_lits;
         }
-        wg_copy(d + runs[pl.run] + pl.tail_rel, s + (len - tail), tail, lane, 64);
+        wg_copy(d + runs[pl.run] + pl.tail_rel, s + (len - tail), tail, lane);
         if (i + 1 == blk.nseg)
             wg_emit_header(d + bo.final_hdr_pos, bo.final_lits, 0u, lane, 64);
     }

@@ -3,10 +3,12 @@
 // and DecompressBlock (compressblockstore.c:271-338).
 //
 //   create   the host expands the VersionIndex into OCCURRENCES (chunk hash, destination, length) -- prefix arithmetic over
-//            m_AssetChunkIndexes and m_ChunkSizes -- and the StoreIndex into per-chunk (block, offset in block).  The device resolves:
-//            the StoreIndex's chunk hashes go into an lthip_seen, lthip_seen_find gives every occurrence the position of its chunk,
+//            m_AssetChunkIndexes and m_ChunkSizes, restore_windows.h -- and the StoreIndex into per-chunk (block, offset in block),
+//            restore_plan.h: the plan's host tables are plain headers that a sanitizer reaches without a GPU.  The device resolves: the
+//            StoreIndex's chunk hashes go into an lthip_seen, lthip_seen_find gives every occurrence the position of its chunk,
 //            k_restore_resolve checks the size and counts occurrences per block, an exclusive scan gives every block its first entry,
-//            k_restore_fill places (offset in block, length, destination) block-major.  The block_count + 1 firsts come back once.
+//            k_restore_fill places (offset in block, length, destination) block-major; where an occurrence comes from is decided by one
+//            routine, resolve(), for both.  The block_count + 1 firsts come back once.
 //   windows  (lthip_restore_create_windows, restore_windows.h) the occurrences are those of byte windows of assets, each CLIPPED to its
 //            window: next to the chunk's full length it carries `skip` bytes into the chunk and `clip` bytes to write.  k_restore_resolve
 //            still compares the full length with the StoreIndex's size and counts `clip` bytes; k_restore_fill places (offset in block +
@@ -14,8 +16,9 @@
 //            The sessions of whole assets are the same routine with one window per selected asset and no skip / clip tables at all.
 //   blocks   k_restore_check_images (a wave per image, against the device copy of the StoreIndex) -> the decoders into 64-byte slots of
 //            the caller's scratch -> k_restore_ranges (the decoders' verdict into the block's status word; with verify the (offset,
-//            length) of every chunk) -> lthip_hash_ranges_by_id -> k_restore_compare -> k_restore_scatter over the call's entries.
-//            Nothing is allocated and nothing is waited for: the session's tables were sized by create.
+//            length) of every chunk) -> lthip_hash_ranges_by_id -> k_restore_compare -> k_restore_scatter over the call's entries
+//            (the copy: lthip_wg_copy, k_copy.h).  Nothing is allocated and nothing is waited for: the session's tables were sized by
+//            create.
 //   base     (lthip_restore_create_from_base) a version that lies restored in HBM is a second source.  The host expands it as it expands
 //            the target: per distinct chunk the offset of its first occurrence in a resident asset.  Its chunk hashes go into a second
 //            lthip_seen; k_restore_resolve gives an occurrence to the base when the base holds its hash with the same size at a resident
@@ -32,12 +35,14 @@
 //            caller's scratch -> scans -> k_restore_in_place_slots -> k_raw_copy twice: every moved run buffer -> scratch, then scratch ->
 //            buffer.  All reads come before all writes, so runs may overlap each other in any way.  How many entries move, and their bytes,
 //            is counted by k_restore_fill and comes back with the plan's one read-back: the scratch bound is host arithmetic.
+// Device tables travel to the kernels as views by value, what the kernels count for the host has names (Counters), and every table set
+// is sub-allocated by a Carver: the session's allocation, the plan's temporaries, the carry's tables in the context's scratch.
 // The scatter and a decoder's second pass cost one more read and write of the output than decoding into place would: about a tenth on top
 // of the bare decoder calls (profiles/restore_rate.json).
+#include "k_copy.h"
 #include "lthip_internal.h"
 #include "restore_layout.h"
-#include "restore_parse.h"
-#include "restore_windows.h"
+#include "restore_plan.h"
 #include "store_layout.h"
 #include "version_diff.h"
 
@@ -47,9 +52,9 @@
 namespace
 {
 
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+using restore_plan::NONE;
+using restore_plan::NOWHERE;
 constexpr int RT = 256;
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 // one delivered, needed block of a lthip_restore_blocks call
 struct RItem
@@ -64,22 +69,108 @@ struct RItem
     uint32_t vfirst; // its first chunk among the call's verify ranges
 };
 
-// ---- plan ----
-// what the plan kernels know of the base (all null without one): per occurrence its position among the base's chunks (lthip_seen_find),
-// per base chunk its size and the offset of its first resident occurrence (NOWHERE: none)
-constexpr uint64_t NOWHERE = ~0ull;
-struct BasePlan
+// what the kernels count for the host: the plan's one read-back takes all of it, lthip_restore_finish the mismatches
+struct Counters
 {
-    const uint32_t* opos;
-    const uint32_t* size;
-    const uint64_t* off;
+    unsigned long long unresolved;         // occurrences neither source resolves
+    unsigned long long block_chunks_bad;   // chunks of blocks whose hash differed
+    unsigned long long base_chunks_bad;    // base chunks whose hash differed,
+    unsigned long long base_bad_occ;       // the occurrences those would have fed
+    unsigned long long base_bad_bytes;     // and their bytes
+    unsigned long long base_bytes;         // bytes the base feeds
+    unsigned long long base_verify_leaves; // 1 KiB leaves of the base chunks that feed (lthip_hash_ranges_by_id wants the total)
+    unsigned long long moved_occ;          // base-fed entries whose source offset is not their destination (an update in place copies
+    unsigned long long moved_bytes;        // them) and their bytes
 };
-__device__ __forceinline__ bool base_feeds(const BasePlan& bp, uint32_t i, uint32_t len, uint32_t* q)
+
+// sub-allocation of one device allocation.  A table set's carve(Carver(), ...) takes nothing and returns the bytes it needs;
+// carve(Carver(memory), ...) makes the same calls again and hands out the pieces.
+struct Carver
 {
-    if (!bp.opos)
-        return false;
-    *q = bp.opos[i];
-    return *q != NONE && bp.size[*q] == len && bp.off[*q] != NOWHERE;
+    uint8_t* p;
+    size_t at = 0;
+    explicit Carver(void* memory = nullptr) : p((uint8_t*)memory) {}
+    template <class T> void take(T** out, size_t count)
+    {
+        if (p)
+            *out = reinterpret_cast<T*>(p + at);
+        at += (count * sizeof(T) + 255u) & ~(size_t)255u;
+    }
+};
+
+// ---- device tables, handed to the kernels by value ----
+// the StoreIndex: per chunk position (hash, size, the block that holds it or NONE, offset in that block), per block (hash, first chunk
+// position, chunk count, tag, raw size)
+struct StoreView
+{
+    uint64_t *chash = nullptr, *bhash = nullptr;
+    uint32_t *csize = nullptr, *cblock = nullptr, *coff = nullptr, *bcoff = nullptr, *bcnt = nullptr, *btag = nullptr, *braw = nullptr;
+};
+// the occurrences: position of the chunk in the StoreIndex's chunk list (lthip_seen_find) and among the base's chunks (null without a
+// base), the chunk's FULL length, destination; skip / clip: what a clipped occurrence leaves out and writes, null when every occurrence
+// is its whole chunk
+struct OccView
+{
+    uint32_t *pos = nullptr, *bpos = nullptr, *len = nullptr, *skip = nullptr, *clip = nullptr;
+    uint64_t* dst = nullptr;
+};
+// per distinct chunk of the base {hash, size, offset of its first resident occurrence (NOWHERE: none), occurrences fed, hash differed}
+struct BaseView
+{
+    uint64_t *hash = nullptr, *off = nullptr;
+    uint32_t *size = nullptr, *feed = nullptr, *bad = nullptr;
+};
+// base-fed entries in occurrence order (room for every occurrence: how many the base feeds is known after the plan has run)
+struct CarryView
+{
+    uint64_t *src = nullptr, *dst = nullptr;
+    uint32_t *len = nullptr, *chunk = nullptr;
+};
+// the byte ranges verify hashes: the chunks of a call's blocks, or (block unused) the base chunks that feed something
+struct RangeView
+{
+    uint64_t *off = nullptr, *hash = nullptr;
+    uint32_t *len = nullptr, *block = nullptr, *chunk = nullptr;
+};
+
+// ---- plan ----
+// what only the plan needs, in an allocation of its own
+struct PlanTmp
+{
+    uint64_t* ohash = nullptr;
+    OccView occ;
+    unsigned long long* bbytes = nullptr;                   // per block: the bytes its entries write
+    uint32_t *hist = nullptr, *cursor = nullptr;            // per block: its entries counted, and handed out
+    uint32_t *first = nullptr, *bfirst = nullptr;           // lthip_seen_add's answers, not read
+    uint32_t *oflag = nullptr, *ofirst = nullptr;           // per occurrence: the base feeds it, and the scan of that
+    uint32_t *bmark = nullptr, *mfirst = nullptr;           // per base chunk: it feeds something, and the scan of that
+    size_t carve(Carver c, size_t nocc, size_t nb, size_t m, size_t nub, bool clipped, bool base)
+    {
+        c.take(&ohash, nocc), c.take(&occ.dst, nocc), c.take(&bbytes, nb), c.take(&occ.len, nocc), c.take(&occ.pos, nocc), c.take(&hist, nb),
+            c.take(&cursor, nb), c.take(&first, m);
+        if (clipped)
+            c.take(&occ.skip, nocc), c.take(&occ.clip, nocc);
+        if (base)
+            c.take(&occ.bpos, nocc), c.take(&oflag, nocc), c.take(&ofirst, nocc + 1), c.take(&bfirst, nub), c.take(&bmark, nub),
+                c.take(&mfirst, nub + 1);
+        return c.at;
+    }
+};
+
+// where occurrence i comes from.  q != NONE: base chunk q -- the base holds its hash with the same size at a resident offset, and wins
+// when both hold the chunk.  Else b != NONE: position p of the StoreIndex's chunk list, in block b.  Else nowhere.
+struct Resolved
+{
+    uint32_t q, p, b;
+};
+__device__ __forceinline__ Resolved resolve(const OccView& o, const BaseView& base, const StoreView& sv, uint32_t i)
+{
+    const uint32_t len = o.len[i], q = o.bpos ? o.bpos[i] : NONE;
+    if (q != NONE && base.size[q] == len && base.off[q] != NOWHERE)
+        return Resolved{q, NONE, NONE};
+    const uint32_t p = o.pos[i];
+    const uint32_t b = p == NONE ? NONE : sv.cblock[p];
+    return b != NONE && sv.csize[p] == len ? Resolved{NONE, p, b} : Resolved{NONE, NONE, NONE};
 }
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 {
@@ -88,245 +179,227 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
     return v;
 }
 
-// counters: [0] occurrences neither source resolves, [5] bytes the base feeds ([8], [9]: k_restore_fill)
-// (oclip: the bytes a clipped occurrence writes, null when every occurrence is its whole chunk)
-__global__ void k_restore_resolve(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen,
-                                  const uint32_t* __restrict__ oclip, const uint32_t* __restrict__ csize, const uint32_t* __restrict__ cblock,
-                                  uint32_t* __restrict__ hist, unsigned long long* __restrict__ bbytes, unsigned long long* counters,
-                                  BasePlan bp, uint32_t* __restrict__ oflag, uint32_t* __restrict__ bfeed, uint32_t* __restrict__ bmark)
+__global__ void k_restore_resolve(uint32_t n, PlanTmp t, BaseView base, StoreView sv, Counters* counters)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool miss = false;
     unsigned long long fed = 0;
     if (i < n)
     {
-        const uint32_t len = olen[i];
-        uint32_t q = NONE;
-        if (base_feeds(bp, i, len, &q)) // the base wins when both hold the chunk
+        const uint32_t len = t.occ.len[i];
+        const Resolved r = resolve(t.occ, base, sv, i);
+        if (t.oflag)
+            t.oflag[i] = r.q != NONE ? 1u : 0u;
+        if (r.q != NONE)
         {
-            oflag[i] = 1u;
-            atomicAdd(&bfeed[q], 1u);
-            bmark[q] = 1u;
+            atomicAdd(&base.feed[r.q], 1u);
+            t.bmark[r.q] = 1u;
             fed = len;
         }
+        else if (r.b == NONE)
+            miss = true;
         else
         {
-            if (oflag)
-                oflag[i] = 0u;
-            const uint32_t p = pos[i];
-            const uint32_t b = p == NONE ? NONE : cblock[p];
-            if (b == NONE || csize[p] != len)
-                miss = true;
-            else
-            {
-                atomicAdd(&hist[b], 1u);
-                atomicAdd(&bbytes[b], (unsigned long long)(oclip ? oclip[i] : len));
-            }
+            atomicAdd(&t.hist[r.b], 1u);
+            atomicAdd(&t.bbytes[r.b], (unsigned long long)(t.occ.clip ? t.occ.clip[i] : len));
         }
     }
     const uint64_t m = __builtin_amdgcn_ballot_w64(miss);
     if (m && (threadIdx.x & 63) == 0)
-        atomicAdd(counters, (unsigned long long)__builtin_popcountll(m));
-    if (bp.opos)
+        atomicAdd(&counters->unresolved, (unsigned long long)__builtin_popcountll(m));
+    if (t.occ.bpos)
     {
         fed = wave_sum(fed);
         if (fed && (threadIdx.x & 63) == 0)
-            atomicAdd(counters + 5, fed);
+            atomicAdd(&counters->base_bytes, fed);
     }
 }
 
 // the order of a block's entries is whatever the atomics give; the output does not depend on it.  The base's entries keep the order of
 // the occurrences (ofirst: the scan of the flags): that order is what makes runs.
-__global__ void k_restore_fill(uint32_t n, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ olen, const uint32_t* __restrict__ oskip,
-                               const uint32_t* __restrict__ oclip, const uint64_t* __restrict__ odst, const uint32_t* __restrict__ csize,
-                               const uint32_t* __restrict__ cblock, const uint32_t* __restrict__ coff,
-                               const uint32_t* __restrict__ firsts, uint32_t* __restrict__ cursor, uint4* __restrict__ entries, BasePlan bp,
-                               const uint32_t* __restrict__ ofirst, uint64_t* __restrict__ ksrc, uint64_t* __restrict__ kdst,
-                               uint32_t* __restrict__ klen, uint32_t* __restrict__ kchunk, unsigned long long* counters)
+__global__ void k_restore_fill(uint32_t n, PlanTmp t, BaseView base, StoreView sv, const uint32_t* __restrict__ firsts,
+                               uint4* __restrict__ entries, CarryView carry, Counters* counters)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long moved = 0; // bytes of a base-fed entry whose source offset is not its destination (counters[8], [9]: in place)
+    unsigned long long moved = 0; // bytes of a base-fed entry whose source offset is not its destination
     bool is_moved = false;
     if (i < n)
     {
-        const uint32_t len = olen[i];
-        const uint64_t d = odst[i];
-        uint32_t q = NONE;
-        if (base_feeds(bp, i, len, &q))
+        const uint32_t len = t.occ.len[i];
+        const uint64_t d = t.occ.dst[i];
+        const Resolved r = resolve(t.occ, base, sv, i);
+        if (r.q != NONE)
         {
-            const uint32_t k = ofirst[i];
-            const uint64_t src = bp.off[q];
-            ksrc[k] = src;
-            kdst[k] = d;
-            klen[k] = len;
-            kchunk[k] = q;
+            const uint32_t k = t.ofirst[i];
+            const uint64_t src = base.off[r.q];
+            carry.src[k] = src;
+            carry.dst[k] = d;
+            carry.len[k] = len;
+            carry.chunk[k] = r.q;
             is_moved = src != d;
             moved = is_moved ? len : 0u;
         }
-        else
+        else if (r.b != NONE)
         {
-            const uint32_t p = pos[i];
-            const uint32_t b = p == NONE ? NONE : cblock[p];
-            if (b != NONE && csize[p] == len)
-            {
-                const uint32_t slot = firsts[b] + atomicAdd(&cursor[b], 1u);
-                // (skip + clip <= len == csize[p]: the entry stays inside its chunk, and the block's raw size is below 2^32)
-                const uint32_t skip = oskip ? oskip[i] : 0u, clip = oclip ? oclip[i] : len;
-                entries[slot] = make_uint4(coff[p] + skip, clip, (uint32_t)d, (uint32_t)(d >> 32));
-            }
+            const uint32_t slot = firsts[r.b] + atomicAdd(&t.cursor[r.b], 1u);
+            // (skip + clip <= len == csize[p]: the entry stays inside its chunk, and the block's raw size is below 2^32)
+            const uint32_t skip = t.occ.skip ? t.occ.skip[i] : 0u, clip = t.occ.clip ? t.occ.clip[i] : len;
+            entries[slot] = make_uint4(sv.coff[r.p] + skip, clip, (uint32_t)d, (uint32_t)(d >> 32));
         }
     }
-    if (!bp.opos)
+    if (!t.occ.bpos)
         return;
     const uint64_t m = __builtin_amdgcn_ballot_w64(is_moved);
     moved = wave_sum(moved);
     if (m && (threadIdx.x & 63) == 0)
     {
-        atomicAdd(counters + 8, (unsigned long long)__builtin_popcountll(m));
-        atomicAdd(counters + 9, moved);
+        atomicAdd(&counters->moved_occ, (unsigned long long)__builtin_popcountll(m));
+        atomicAdd(&counters->moved_bytes, moved);
     }
 }
 
 // the base chunks that feed something, in chunk order (mfirst: the scan of their marks): the ranges verify hashes, and their 1 KiB
-// leaves summed (counters[6]: lthip_hash_ranges_by_id wants the total)
-__global__ void k_restore_carry_marked(uint32_t n, const uint32_t* __restrict__ bmark, const uint32_t* __restrict__ mfirst,
-                                       const uint32_t* __restrict__ bsize, const uint64_t* __restrict__ boff, uint64_t* __restrict__ voff,
-                                       uint32_t* __restrict__ vlen, uint32_t* __restrict__ vchunk, unsigned long long* counters)
+// leaves summed
+__global__ void k_restore_carry_marked(uint32_t n, PlanTmp t, BaseView base, RangeView v, Counters* counters)
 {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long leaves = 0;
-    if (q < n && bmark[q])
+    if (q < n && t.bmark[q])
     {
-        const uint32_t k = mfirst[q], len = bsize[q];
-        voff[k] = boff[q];
-        vlen[k] = len;
-        vchunk[k] = q;
+        const uint32_t k = t.mfirst[q], len = base.size[q];
+        v.off[k] = base.off[q];
+        v.len[k] = len;
+        v.chunk[k] = q;
         leaves = len ? ((unsigned long long)len + 1023u) >> 10 : 1u;
     }
     leaves = wave_sum(leaves);
     if (leaves && (threadIdx.x & 63) == 0)
-        atomicAdd(counters + 6, leaves);
+        atomicAdd(&counters->base_verify_leaves, leaves);
 }
 
 // ---- carry ----
-// counters: [2] base chunks whose hash differed, [3] the occurrences they would have fed, [4] and their bytes
-__global__ void k_restore_carry_compare(uint32_t n, const uint64_t* __restrict__ vhash, const uint32_t* __restrict__ vchunk,
-                                        const uint64_t* __restrict__ bhash, const uint32_t* __restrict__ bsize,
-                                        const uint32_t* __restrict__ bfeed, uint32_t* __restrict__ bbad, unsigned long long* counters)
+__global__ void k_restore_carry_compare(uint32_t n, RangeView v, BaseView base, Counters* counters)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n)
         return;
-    const uint32_t q = vchunk[k];
-    const bool bad = vhash[k] != bhash[q];
-    bbad[q] = bad ? 1u : 0u;
+    const uint32_t q = v.chunk[k];
+    const bool bad = v.hash[k] != base.hash[q];
+    base.bad[q] = bad ? 1u : 0u;
     if (bad)
     {
-        atomicAdd(counters + 2, 1ull);
-        atomicAdd(counters + 3, (unsigned long long)bfeed[q]);
-        atomicAdd(counters + 4, (unsigned long long)bfeed[q] * bsize[q]);
+        atomicAdd(&counters->base_chunks_bad, 1ull);
+        atomicAdd(&counters->base_bad_occ, (unsigned long long)base.feed[q]);
+        atomicAdd(&counters->base_bad_bytes, (unsigned long long)base.feed[q] * base.size[q]);
     }
 }
 
+// the carry's tables in the context's scratch, one slot per base-fed entry: per entry that starts a run {source, destination, length}
+// and the run's pieces, the pieces' scan, and what finds the runs: boundary flags and their scan.  In place, behind them: per moved run
+// its slot in the caller's scratch, the pieces of its way in and their scan, the 16-byte units of its slot and their scan.
+struct RunTables
+{
+    uint64_t *src = nullptr, *dst = nullptr, *len = nullptr, *slot = nullptr;
+    uint32_t *pieces = nullptr, *first_piece = nullptr, *bound = nullptr, *rank = nullptr;
+    uint32_t *pieces_in = nullptr, *first_piece_in = nullptr, *units = nullptr, *first_unit = nullptr;
+    size_t carve(Carver c, size_t n, bool in_place)
+    {
+        c.take(&src, n), c.take(&dst, n), c.take(&len, n), c.take(&pieces, n), c.take(&first_piece, n + 1), c.take(&bound, n),
+            c.take(&rank, n + 1);
+        if (in_place)
+            c.take(&slot, n), c.take(&pieces_in, n), c.take(&first_piece_in, n + 1), c.take(&units, n), c.take(&first_unit, n + 1);
+        return c.at;
+    }
+};
+
 // bound[i] = 1: entry i does not continue entry i - 1 -- it starts a run, or (bbad, verify) it is left out and breaks one
-__global__ void k_restore_carry_bounds(uint32_t n, const uint64_t* __restrict__ ksrc, const uint64_t* __restrict__ kdst,
-                                       const uint32_t* __restrict__ klen, const uint32_t* __restrict__ kchunk, const uint32_t* __restrict__ bbad,
-                                       uint32_t* __restrict__ bound)
+__global__ void k_restore_carry_bounds(uint32_t n, CarryView k, const uint32_t* __restrict__ bbad, RunTables runs)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    bool b = i == 0 || (bbad && (bbad[kchunk[i]] || bbad[kchunk[i - 1]]));
+    bool b = i == 0 || (bbad && (bbad[k.chunk[i]] || bbad[k.chunk[i - 1]]));
     if (!b)
     {
-        const uint64_t len = klen[i - 1];
-        b = ksrc[i] != ksrc[i - 1] + len || kdst[i] != kdst[i - 1] + len;
+        const uint64_t len = k.len[i - 1];
+        b = k.src[i] != k.src[i - 1] + len || k.dst[i] != k.dst[i - 1] + len;
     }
-    bound[i] = b ? 1u : 0u;
+    runs.bound[i] = b ? 1u : 0u;
 }
 
 // rank = the exclusive scan of bound (n + 1 entries).  A boundary that starts a run ends it before the next boundary: the first j > i
 // with rank[j + 1] > rank[i] + 1, found by bisection (rank is monotone), or the end of the list.  The entries of a run follow each other
 // in the destination, so its length is the end of its last entry - its start.
-__global__ void k_restore_carry_runs(uint32_t n, const uint64_t* __restrict__ ksrc, const uint64_t* __restrict__ kdst,
-                                     const uint32_t* __restrict__ klen, const uint32_t* __restrict__ kchunk, const uint32_t* __restrict__ bbad,
-                                     const uint32_t* __restrict__ bound, const uint32_t* __restrict__ rank, uint64_t* __restrict__ run_src,
-                                     uint64_t* __restrict__ run_dst, uint64_t* __restrict__ run_len, uint32_t* __restrict__ pieces)
+__global__ void k_restore_carry_runs(uint32_t n, CarryView k, const uint32_t* __restrict__ bbad, RunTables runs)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
     uint32_t np = 0;
-    if (bound[i] && !(bbad && bbad[kchunk[i]]))
+    if (runs.bound[i] && !(bbad && bbad[k.chunk[i]]))
     {
-        const uint32_t r = rank[i] + 1u; // boundaries up to and including i
-        uint32_t lo = i, hi = n;         // rank[lo + 1] == r (no boundary in (i, lo]); hi == n or rank[hi + 1] > r
+        const uint32_t r = runs.rank[i] + 1u; // boundaries up to and including i
+        uint32_t lo = i, hi = n;              // rank[lo + 1] == r (no boundary in (i, lo]); hi == n or rank[hi + 1] > r
         while (hi - lo > 1)
         {
             const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (rank[mid + 1] > r)
+            if (runs.rank[mid + 1] > r)
                 hi = mid;
             else
                 lo = mid;
         }
-        const uint64_t d = kdst[i], len = kdst[lo] + klen[lo] - d;
-        run_src[i] = ksrc[i];
-        run_dst[i] = d;
-        run_len[i] = len;
+        const uint64_t d = k.dst[i], len = k.dst[lo] + k.len[lo] - d;
+        runs.src[i] = k.src[i];
+        runs.dst[i] = d;
+        runs.len[i] = len;
         np = lthip_raw_pieces(d, len);
     }
-    pieces[i] = np;
+    runs.pieces[i] = np;
 }
 
 // ---- the carry in place: behind k_restore_carry_runs.  A run whose source is its destination is KEPT and loses its pieces (a run is all
 // kept or all moved: the distance from source to destination is constant over it).  A moved run goes through the caller's scratch: it
 // gets the 16-byte units of its slot there and the pieces of its way IN (a slot starts on a 16-byte boundary); `pieces` stays what its
 // way back OUT needs. ----
-__global__ void k_restore_in_place_classify(uint32_t n, const uint64_t* __restrict__ run_src, const uint64_t* __restrict__ run_dst,
-                                            const uint64_t* __restrict__ run_len, uint32_t* __restrict__ pieces, uint32_t* __restrict__ pieces_in,
-                                            uint32_t* __restrict__ units)
+__global__ void k_restore_in_place_classify(uint32_t n, RunTables runs)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
     uint32_t in = 0, u = 0;
-    if (pieces[i])
+    if (runs.pieces[i])
     {
-        if (run_src[i] == run_dst[i])
-            pieces[i] = 0u;
+        if (runs.src[i] == runs.dst[i])
+            runs.pieces[i] = 0u;
         else
         {
-            const uint64_t len = run_len[i];
+            const uint64_t len = runs.len[i];
             in = lthip_raw_pieces(0, len);
             u = (uint32_t)((len + 15u) >> 4); // (the moved bytes and their padding stay below 2^36: lthip_restore_carry_in_place)
         }
     }
-    pieces_in[i] = in;
-    units[i] = u;
+    runs.pieces_in[i] = in;
+    runs.units[i] = u;
 }
 
 // first_unit = the exclusive scan of the units: where every run's slot starts in the scratch
-__global__ void k_restore_in_place_slots(uint32_t n, const uint32_t* __restrict__ first_unit, uint64_t* __restrict__ run_slot)
+__global__ void k_restore_in_place_slots(uint32_t n, RunTables runs)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
-        run_slot[i] = (uint64_t)first_unit[i] << 4;
+        runs.slot[i] = (uint64_t)runs.first_unit[i] << 4;
 }
 
 // ---- a delivered image against the StoreIndex: one wave per image ----
 __global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __restrict__ items, uint32_t k, const uint8_t* __restrict__ images,
-                                                             const uint64_t* __restrict__ bhash, const uint32_t* __restrict__ bcoff,
-                                                             const uint32_t* __restrict__ bcnt, const uint32_t* __restrict__ btag,
-                                                             const uint32_t* __restrict__ braw, uint32_t hash_identifier,
-                                                             const uint64_t* __restrict__ chash, const uint32_t* __restrict__ csize,
-                                                             uint32_t* __restrict__ status)
+                                                             StoreView sv, uint32_t hash_identifier, uint32_t* __restrict__ status)
 {
     const uint32_t i = blockIdx.x;
     if (i >= k)
         return;
     const uint32_t lane = threadIdx.x;
     const RItem it = items[i];
-    const uint32_t b = it.block, n = bcnt[b], tag = btag[b], c0 = bcoff[b], raw = braw[b];
+    const uint32_t b = it.block, n = sv.bcnt[b], tag = sv.btag[b], c0 = sv.bcoff[b], raw = sv.braw[b];
     const uint64_t hdr = 20ull + 12ull * n + (tag ? 8u : 0u);
     uint32_t st = 0;
     if ((uint64_t)it.size < hdr) // (nothing of it is read)
@@ -337,15 +410,15 @@ __global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __rest
         bool bad = false;
         if (lane == 0)
         {
-            const uint64_t h = bhash[b];
+            const uint64_t h = sv.bhash[b];
             bad = w[0] != (uint32_t)h || w[1] != (uint32_t)(h >> 32) || w[2] != hash_identifier || w[3] != n || w[4] != tag;
             if (tag) // [raw size][compressed size] behind the BlockIndex
                 bad = bad || w[5ull + 3ull * n] != raw || (uint64_t)w[6ull + 3ull * n] != (uint64_t)it.size - hdr;
         }
         for (uint32_t j = lane; j < n; j += 64)
         {
-            const uint64_t h = chash[c0 + j];
-            bad = bad || w[5ull + 2ull * j] != (uint32_t)h || w[6ull + 2ull * j] != (uint32_t)(h >> 32) || w[5ull + 2ull * n + j] != csize[c0 + j];
+            const uint64_t h = sv.chash[c0 + j];
+            bad = bad || w[5ull + 2ull * j] != (uint32_t)h || w[6ull + 2ull * j] != (uint32_t)(h >> 32) || w[5ull + 2ull * n + j] != sv.csize[c0 + j];
         }
         if (__builtin_amdgcn_ballot_w64(bad))
             st = LTHIP_RESTORE_BAD_HEADER;
@@ -359,10 +432,7 @@ __global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __rest
 // ---- behind the decoders: their verdict into the status word; with verify, the byte range of every chunk of the good blocks (a bad
 // block's chunks become empty ranges at offset 0: nothing of it is read) ----
 __global__ __launch_bounds__(64) void k_restore_ranges(const RItem* __restrict__ items, uint32_t k, const uint32_t* __restrict__ outsz,
-                                                       const uint32_t* __restrict__ bcoff, const uint32_t* __restrict__ bcnt,
-                                                       const uint32_t* __restrict__ csize, const uint32_t* __restrict__ coff,
-                                                       uint32_t* __restrict__ status, uint32_t verify, uint64_t base, uint64_t* __restrict__ voff,
-                                                       uint32_t* __restrict__ vlen, uint32_t* __restrict__ vblock, uint32_t* __restrict__ vchunk)
+                                                       StoreView sv, uint32_t* __restrict__ status, uint32_t verify, uint64_t base, RangeView v)
 {
     const uint32_t i = blockIdx.x;
     if (i >= k)
@@ -377,39 +447,35 @@ __global__ __launch_bounds__(64) void k_restore_ranges(const RItem* __restrict__
         status[b] = st;
     if (!verify)
         return;
-    const uint32_t c0 = bcoff[b], n = bcnt[b];
+    const uint32_t c0 = sv.bcoff[b], n = sv.bcnt[b];
     for (uint32_t j = lane; j < n; j += 64)
     {
         const uint32_t r = it.vfirst + j, c = c0 + j;
-        voff[r] = st ? 0ull : it.src - base + coff[c];
-        vlen[r] = st ? 0u : csize[c];
-        vblock[r] = b;
-        vchunk[r] = c;
+        v.off[r] = st ? 0ull : it.src - base + sv.coff[c];
+        v.len[r] = st ? 0u : sv.csize[c];
+        v.block[r] = b;
+        v.chunk[r] = c;
     }
 }
 
-__global__ void k_restore_compare(uint32_t n, const uint64_t* __restrict__ vhash, const uint32_t* __restrict__ vblock,
-                                  const uint32_t* __restrict__ vchunk, const uint64_t* __restrict__ chash, uint32_t* status,
-                                  unsigned long long* mismatched)
+__global__ void k_restore_compare(uint32_t n, RangeView v, const uint64_t* __restrict__ chash, uint32_t* status, Counters* counters)
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n)
         return;
-    const uint32_t b = vblock[r];
+    const uint32_t b = v.block[r];
     // (the header and payload bits were final before this launch; only the chunk bit is set beside these reads)
     if (__hip_atomic_load(&status[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (LTHIP_RESTORE_BAD_HEADER | LTHIP_RESTORE_BAD_PAYLOAD))
         return;
-    if (vhash[r] != chash[vchunk[r]])
+    if (v.hash[r] != chash[v.chunk[r]])
     {
         atomicOr(&status[b], LTHIP_RESTORE_BAD_CHUNK);
-        atomicAdd(mismatched, 1ull);
+        atomicAdd(&counters->block_chunks_bad, 1ull);
     }
 }
 
-// ---- the scatter: a workgroup per entry of the call's blocks, block-major.  The copy is k_gather_ranges' (k_gather.hip): the head up to
-// the destination's 16-byte boundary and the tail by bytes, in between 16-byte stores of a source realigned from dwords with v_alignbit.
-// The dwords loaded are those that hold a byte of the vector: q[0..3] always do (the source lies mis < 4 bytes into q[0]), q[4] is
-// loaded only when mis != 0, and then it holds the vector's last mis bytes.  Source and destination sit at any byte positions. ----
+// ---- the scatter: a workgroup per entry of the call's blocks, block-major, copied by lthip_wg_copy (k_copy.h): source and destination
+// sit at any byte positions, and no dword is read that holds no byte of the entry ----
 __global__ __launch_bounds__(RT) void k_restore_scatter(const RItem* __restrict__ items, uint32_t k, const uint4* __restrict__ entries,
                                                         const uint32_t* __restrict__ status, const uint32_t* __restrict__ outsz,
                                                         uint32_t entry0, uint8_t* __restrict__ out)
@@ -428,37 +494,9 @@ __global__ __launch_bounds__(RT) void k_restore_scatter(const RItem* __restrict_
     if (status[it.block] != 0u || outsz[lo] != it.raw) // no byte of a bad block reaches the output
         return;
     const uint4 en = entries[it.ebase + (e - it.efirst)];
-    const int tid = threadIdx.x;
     const uint8_t* s = reinterpret_cast<const uint8_t*>(it.src) + en.x;
     uint8_t* d = out + ((uint64_t)en.z | ((uint64_t)en.w << 32));
-    uint32_t n = en.y;
-    uint32_t head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
-    if (head > n)
-        head = n;
-    if ((uint32_t)tid < head)
-        d[tid] = s[tid];
-    d += head;
-    s += head;
-    n -= head;
-    const uint32_t nvec = n >> 4;
-    const uint32_t mis = (uint32_t)((uintptr_t)s & 3u);
-    const uint32_t sh = mis * 8u;
-    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s - mis);
-    for (uint32_t v = tid; v < nvec; v += RT)
-    {
-        const uint32_t* q = s4 + (size_t)v * 4u;
-        const u32x4_a4 a = *reinterpret_cast<const u32x4_a4*>(q);
-        const uint32_t x = mis ? q[4] : 0u;
-        uint4 o;
-        o.x = __builtin_amdgcn_alignbit(a.y, a.x, sh);
-        o.y = __builtin_amdgcn_alignbit(a.z, a.y, sh);
-        o.z = __builtin_amdgcn_alignbit(a.w, a.z, sh);
-        o.w = __builtin_amdgcn_alignbit(x, a.w, sh);
-        *reinterpret_cast<uint4*>(d + (size_t)v * 16u) = o;
-    }
-    const uint32_t done = nvec << 4;
-    if ((uint32_t)tid < n - done)
-        d[done + tid] = s[done + tid];
+    lthip_wg_copy<RT>(d, s, en.y, threadIdx.x);
 }
 
 // host table -> device through the staging ring, in pieces, so that no staging slot grows to the size of an index
@@ -474,18 +512,7 @@ int upload(lthip_ctx* ctx, void* d_dst, const void* h_src, size_t bytes)
     return 0;
 }
 
-// sub-allocation of one device allocation: sizes first (p == null), then the same calls again hand out the pieces
-struct Carver
-{
-    uint8_t* p = nullptr;
-    size_t at = 0;
-    template <class T> void take(T** out, size_t count)
-    {
-        if (p)
-            *out = reinterpret_cast<T*>(p + at);
-        at += (count * sizeof(T) + 255u) & ~(size_t)255u;
-    }
-};
+template <class T> int upload(lthip_ctx* ctx, T* d_dst, const std::vector<T>& h_src) { return upload(ctx, d_dst, h_src.data(), h_src.size() * sizeof(T)); }
 
 uint64_t round64(uint64_t x) { return (x + 63u) & ~(uint64_t)63u; }
 
@@ -511,42 +538,38 @@ struct lthip_restore
     std::vector<uint32_t> bcnt, btag, braw, firsts, status;
     std::vector<uint8_t> delivered, in_call;
     std::unordered_map<uint64_t, uint32_t> block_of_hash;
-    // the device side: one allocation for what lives as long as the session, one for what only the plan needs
+    // the device side: one allocation for what lives as long as the session, one for what only the plan needs (PlanTmp)
     lthip_seen *seen = nullptr, *seen_base = nullptr;
     void *d_mem = nullptr, *d_tmp = nullptr;
-    uint64_t *d_chash = nullptr, *d_bhash = nullptr, *d_voff = nullptr, *d_vhash = nullptr;
-    uint32_t *d_csize = nullptr, *d_cblock = nullptr, *d_coff = nullptr, *d_bcoff = nullptr, *d_bcnt = nullptr, *d_btag = nullptr, *d_braw = nullptr,
-             *d_status = nullptr, *d_firsts = nullptr, *d_outsz = nullptr, *d_vlen = nullptr, *d_vblock = nullptr, *d_vchunk = nullptr;
+    StoreView sv;
+    uint32_t *d_status = nullptr, *d_firsts = nullptr, *d_outsz = nullptr;
     uint4* d_entries = nullptr;
     RItem* d_items = nullptr;
-    // [0] occurrences neither source resolves, [1] chunks of blocks whose hash differed, [2] base chunks whose hash differed, [3] the
-    // occurrences those would have fed, [4] and their bytes, [5] bytes the base feeds, [6] 1 KiB leaves of the base chunks that feed,
-    // [8] base-fed entries whose source offset is not their destination (moved: an update in place copies them) [9] and their bytes
-    unsigned long long* d_counters = nullptr;
-    // base-fed entries in occurrence order (room for every occurrence: how many the base feeds is known after the plan has run), per
-    // base chunk {hash, size, offset in d_base, occurrences fed, hash differed}, and with verify the ranges of the chunks that feed
-    uint64_t *d_ksrc = nullptr, *d_kdst = nullptr, *d_uhash = nullptr, *d_uoff = nullptr, *d_cvoff = nullptr, *d_cvhash = nullptr;
-    uint32_t *d_klen = nullptr, *d_kchunk = nullptr, *d_usize = nullptr, *d_ufeed = nullptr, *d_ubad = nullptr, *d_cvlen = nullptr,
-             *d_cvchunk = nullptr;
+    Counters* d_counters = nullptr;
+    RangeView ranges; // verify: the chunks of a blocks call
+    BaseView base;
+    CarryView carry;
+    RangeView base_ranges; // verify: the base chunks that feed something
     // host tables of a lthip_restore_blocks call, kept for their capacity
     std::vector<RItem> items;
     std::vector<uint32_t> outsz, group[3], c_size, c_cap;
     std::vector<uint64_t> c_src, c_dst;
 
     bool is_needed(uint32_t b) const { return firsts[b + 1] != firsts[b]; }
-    void carve(Carver& c, size_t items_cap)
+    size_t carve(Carver c, size_t items_cap)
     {
-        c.take(&d_chash, m), c.take(&d_csize, m), c.take(&d_cblock, m), c.take(&d_coff, m);
-        c.take(&d_bhash, nb), c.take(&d_bcoff, nb), c.take(&d_bcnt, nb), c.take(&d_btag, nb), c.take(&d_braw, nb), c.take(&d_status, nb);
-        c.take(&d_firsts, (size_t)nb + 1), c.take(&d_entries, nocc), c.take(&d_items, items_cap), c.take(&d_outsz, items_cap), c.take(&d_counters, 10);
+        c.take(&sv.chash, m), c.take(&sv.csize, m), c.take(&sv.cblock, m), c.take(&sv.coff, m);
+        c.take(&sv.bhash, nb), c.take(&sv.bcoff, nb), c.take(&sv.bcnt, nb), c.take(&sv.btag, nb), c.take(&sv.braw, nb), c.take(&d_status, nb);
+        c.take(&d_firsts, (size_t)nb + 1), c.take(&d_entries, nocc), c.take(&d_items, items_cap), c.take(&d_outsz, items_cap), c.take(&d_counters, 1);
         if (verify)
-            c.take(&d_voff, block_chunks), c.take(&d_vhash, block_chunks), c.take(&d_vlen, block_chunks), c.take(&d_vblock, block_chunks),
-                c.take(&d_vchunk, block_chunks);
+            c.take(&ranges.off, block_chunks), c.take(&ranges.hash, block_chunks), c.take(&ranges.len, block_chunks),
+                c.take(&ranges.block, block_chunks), c.take(&ranges.chunk, block_chunks);
         if (has_base)
-            c.take(&d_ksrc, nocc), c.take(&d_kdst, nocc), c.take(&d_klen, nocc), c.take(&d_kchunk, nocc), c.take(&d_uhash, nub),
-                c.take(&d_uoff, nub), c.take(&d_usize, nub), c.take(&d_ufeed, nub), c.take(&d_ubad, nub);
+            c.take(&carry.src, nocc), c.take(&carry.dst, nocc), c.take(&carry.len, nocc), c.take(&carry.chunk, nocc), c.take(&base.hash, nub),
+                c.take(&base.off, nub), c.take(&base.size, nub), c.take(&base.feed, nub), c.take(&base.bad, nub);
         if (has_base && verify)
-            c.take(&d_cvoff, nub), c.take(&d_cvhash, nub), c.take(&d_cvlen, nub), c.take(&d_cvchunk, nub);
+            c.take(&base_ranges.off, nub), c.take(&base_ranges.hash, nub), c.take(&base_ranges.len, nub), c.take(&base_ranges.chunk, nub);
+        return c.at;
     }
 };
 
@@ -614,9 +637,10 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     }
     r->hash_identifier = vi.hash_identifier;
     r->out_bytes = out_bytes;
+    const char* why = "";
+    int refused;
     // ---- the base: per distinct chunk the offset of its first occurrence in a resident asset ----
-    std::vector<uint64_t> uhash, uoff;
-    std::vector<uint32_t> usize;
+    restore_plan::BaseTable bt;
     if (base)
     {
         if (base->struct_size < sizeof(lthip_restore_base) || base->struct_size > 4096)
@@ -629,219 +653,130 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
             return EINVAL;
         r->has_base = true;
         r->base_window = base->base_bytes;
-        const uint32_t nub = r->nub = bvi.chunk_count;
-        if (nub > 0x7FFFFFFFu)
-            return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "more than 2^31 - 1 chunks in the base");
-        uhash.resize(nub), usize.resize(nub), uoff.assign(nub, NOWHERE);
-        for (uint32_t c = 0; c < nub; ++c)
-        {
-            uhash[c] = bvi.chunk_hashes[c];
-            usize[c] = bvi.chunk_sizes[c];
-            r->base_max_chunk = std::max(r->base_max_chunk, usize[c]);
-        }
-        for (uint64_t a = 0; a < bvi.asset_count; ++a)
-        {
-            const uint64_t off = base->asset_offsets[a], size = bvi.asset_sizes[a];
-            if (off == restore_parse::SKIP || !size)
-                continue;
-            if (off > base->base_bytes || size > base->base_bytes - off)
-                return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "a resident asset's window leaves the base");
-            const uint64_t start = bvi.asset_chunk_index_starts[a], count = bvi.asset_chunk_counts[a];
-            uint64_t at = off;
-            for (uint64_t k = 0; k < count; ++k)
-            {
-                const uint32_t c = bvi.asset_chunk_indexes[start + k];
-                if (uoff[c] == NOWHERE)
-                    uoff[c] = at;
-                at += usize[c];
-            }
-        }
+        r->nub = bvi.chunk_count;
+        if ((refused = restore_plan::base_table(bvi, base->asset_offsets, base->base_bytes, &bt, &why)))
+            return lthip_fail(ctx, refused, "lthip_restore_create_from_base", why);
+        r->base_max_chunk = bt.max_chunk;
     }
-    // ---- occurrences: per window and chunk it touches (hash, full length, skip, clip, destination); a selected asset is one window of
-    // all its bytes at its offset (a directory or an empty file: a window of no bytes, whatever its offset) ----
-    restore_windows::Occurrences occ;
-    {
-        std::vector<restore_windows::Window> whole;
-        if (!wanted.by_window)
-            for (uint64_t a = 0; a < vi.asset_count; ++a)
-            {
-                const uint64_t off = wanted.asset_offsets[a], size = vi.asset_sizes[a];
-                if (off != restore_parse::SKIP)
-                    whole.push_back(restore_windows::Window{(uint32_t)a, 0u, 0u, size, size ? off : 0u});
-            }
-        const char* why = "";
-        const int refused = wanted.by_window ? restore_windows::expand(vi, wanted.window_count, wanted.windows, out_bytes, &occ, &why)
-                                             : restore_windows::expand(vi, whole.size(), whole.data(), out_bytes, &occ, &why);
-        if (refused)
-            return lthip_fail(ctx, refused, wanted.who, why);
-    }
-    r->assets_selected = occ.assets_selected;
-    const std::vector<uint64_t>&ohash = occ.hash, &odst = occ.dst;
-    const std::vector<uint32_t>& olen = occ.len;
-    const bool clipped = !occ.clip.empty();
     // ---- the StoreIndex: per block its tables, per chunk position the block that holds it and where ----
-    const uint32_t nb = r->nb = si.block_count, m = r->m = si.chunk_count;
-    const uint32_t nocc = r->nocc = (uint32_t)ohash.size();
-    if (m > 0x7FFFFFFFu)
-        return lthip_fail(ctx, EINVAL, "lthip_restore_create", "more than 2^31 - 1 chunks in the store index");
-    std::vector<uint64_t> chash(m);
-    std::vector<uint32_t> csize(m), cblock(m, NONE), coff(m, 0u), bcoff(nb);
-    for (uint32_t c = 0; c < m; ++c)
+    restore_plan::StoreTables st;
+    if ((refused = restore_plan::store_tables(si, &st, &why)))
+        return lthip_fail(ctx, refused, "lthip_restore_create", why);
+    const uint32_t nb = r->nb = si.block_count, m = r->m = si.chunk_count, nub = r->nub;
+    r->max_chunk = st.max_chunk;
+    r->block_chunks = st.block_chunks;
+    // ---- occurrences: per window and chunk it touches (hash, full length, skip, clip, destination) ----
+    restore_windows::Occurrences occ;
+    if (wanted.by_window)
+        refused = restore_windows::expand(vi, wanted.window_count, wanted.windows, out_bytes, &occ, &why);
+    else
     {
-        chash[c] = si.chunk_hashes[c];
-        csize[c] = si.chunk_sizes[c];
-        r->max_chunk = std::max(r->max_chunk, csize[c]);
+        const std::vector<restore_windows::Window> whole = restore_plan::whole_asset_windows(vi, wanted.asset_offsets);
+        refused = restore_windows::expand(vi, whole.size(), whole.data(), out_bytes, &occ, &why);
     }
-    r->bhash.resize(nb), r->bcnt.resize(nb), r->btag.resize(nb), r->braw.resize(nb), r->bleaves.resize(nb);
-    for (uint32_t b = 0; b < nb; ++b)
-    {
-        r->bhash[b] = si.block_hashes[b];
-        bcoff[b] = si.block_chunk_offsets[b];
-        r->bcnt[b] = si.block_chunk_counts[b];
-        r->btag[b] = si.block_tags[b];
-        uint64_t off = 0, leaves = 0;
-        for (uint32_t k = 0; k < r->bcnt[b]; ++k)
-        {
-            const uint32_t c = bcoff[b] + k;
-            if (cblock[c] == NONE) // (blocks that share a chunk position: no writer produces them; the first block keeps it)
-            {
-                cblock[c] = b;
-                coff[c] = (uint32_t)off;
-            }
-            off += csize[c];
-            leaves += csize[c] ? ((uint64_t)csize[c] + 1023u) >> 10 : 1u;
-        }
-        r->braw[b] = (uint32_t)off; // (below 4 GiB: parse_store_index)
-        r->block_chunks += r->bcnt[b];
-        r->bleaves[b] = leaves;
-        r->block_of_hash.emplace(r->bhash[b], b);
-    }
-    if (r->block_chunks > 0x7FFFFFFFull)
-        return lthip_fail(ctx, EINVAL, "lthip_restore_create", "the store index's blocks list more than 2^31 - 1 chunks");
-    r->delivered.assign(nb, 0), r->in_call.assign(nb, 0), r->status.assign(nb, 0u);
-    r->firsts.assign((size_t)nb + 1, 0u), r->bbytes.assign(nb, 0ull);
+    if (refused)
+        return lthip_fail(ctx, refused, wanted.who, why);
+    r->assets_selected = occ.assets_selected;
+    const uint32_t nocc = r->nocc = (uint32_t)occ.hash.size();
+    const bool clipped = !occ.clip.empty();
     // ---- device memory: the session's, and the plan's temporaries ----
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    Carver size_of;
-    r->carve(size_of, nb);
-    LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_mem, size_of.at + 256));
-    Carver place;
-    place.p = (uint8_t*)r->d_mem;
-    r->carve(place, nb);
-    uint64_t *t_ohash = nullptr, *t_odst = nullptr;
-    unsigned long long* t_bbytes = nullptr;
-    uint32_t *t_olen = nullptr, *t_pos = nullptr, *t_hist = nullptr, *t_cursor = nullptr, *t_first = nullptr, *t_oskip = nullptr,
-             *t_oclip = nullptr;
-    uint32_t *t_bpos = nullptr, *t_oflag = nullptr, *t_ofirst = nullptr, *t_bfirst = nullptr, *t_bmark = nullptr, *t_mfirst = nullptr;
-    const uint32_t nub = r->nub;
-    for (int pass = 0; pass < 2; ++pass)
-    {
-        Carver c;
-        c.p = (uint8_t*)r->d_tmp;
-        c.take(&t_ohash, nocc), c.take(&t_odst, nocc), c.take(&t_bbytes, nb), c.take(&t_olen, nocc), c.take(&t_pos, nocc), c.take(&t_hist, nb),
-            c.take(&t_cursor, nb), c.take(&t_first, m);
-        if (clipped)
-            c.take(&t_oskip, nocc), c.take(&t_oclip, nocc);
-        if (base)
-            c.take(&t_bpos, nocc), c.take(&t_oflag, nocc), c.take(&t_ofirst, (size_t)nocc + 1), c.take(&t_bfirst, nub), c.take(&t_bmark, nub),
-                c.take(&t_mfirst, (size_t)nub + 1);
-        if (pass == 0)
-            LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_tmp, c.at + 256));
-    }
+    LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_mem, r->carve(Carver(), nb) + 256));
+    r->carve(Carver(r->d_mem), nb);
+    PlanTmp t;
+    LTHIP_CHECK(ctx, lthip_hip_malloc(&r->d_tmp, t.carve(Carver(), nocc, nb, m, nub, clipped, base != nullptr) + 256));
+    t.carve(Carver(r->d_tmp), nocc, nb, m, nub, clipped, base != nullptr);
+    // ---- upload ----
+    const StoreView& sv = r->sv;
     hipStream_t s = ctx->stream;
     int err;
-    if ((err = upload(ctx, r->d_chash, chash.data(), (size_t)m * 8)) || (err = upload(ctx, r->d_csize, csize.data(), (size_t)m * 4)) ||
-        (err = upload(ctx, r->d_cblock, cblock.data(), (size_t)m * 4)) || (err = upload(ctx, r->d_coff, coff.data(), (size_t)m * 4)) ||
-        (err = upload(ctx, r->d_bhash, r->bhash.data(), (size_t)nb * 8)) || (err = upload(ctx, r->d_bcoff, bcoff.data(), (size_t)nb * 4)) ||
-        (err = upload(ctx, r->d_bcnt, r->bcnt.data(), (size_t)nb * 4)) || (err = upload(ctx, r->d_btag, r->btag.data(), (size_t)nb * 4)) ||
-        (err = upload(ctx, r->d_braw, r->braw.data(), (size_t)nb * 4)) || (err = upload(ctx, t_ohash, ohash.data(), (size_t)nocc * 8)) ||
-        (err = upload(ctx, t_odst, odst.data(), (size_t)nocc * 8)) || (err = upload(ctx, t_olen, olen.data(), (size_t)nocc * 4)))
+    if ((err = upload(ctx, sv.chash, st.chash)) || (err = upload(ctx, sv.csize, st.csize)) || (err = upload(ctx, sv.cblock, st.cblock)) ||
+        (err = upload(ctx, sv.coff, st.coff)) || (err = upload(ctx, sv.bhash, st.bhash)) || (err = upload(ctx, sv.bcoff, st.bcoff)) ||
+        (err = upload(ctx, sv.bcnt, st.bcnt)) || (err = upload(ctx, sv.btag, st.btag)) || (err = upload(ctx, sv.braw, st.braw)) ||
+        (err = upload(ctx, t.ohash, occ.hash)) || (err = upload(ctx, t.occ.dst, occ.dst)) || (err = upload(ctx, t.occ.len, occ.len)))
         return err;
-    if (clipped &&
-        ((err = upload(ctx, t_oskip, occ.skip.data(), (size_t)nocc * 4)) || (err = upload(ctx, t_oclip, occ.clip.data(), (size_t)nocc * 4))))
+    if (clipped && ((err = upload(ctx, t.occ.skip, occ.skip)) || (err = upload(ctx, t.occ.clip, occ.clip))))
         return err;
-    if (base && ((err = upload(ctx, r->d_uhash, uhash.data(), (size_t)nub * 8)) || (err = upload(ctx, r->d_uoff, uoff.data(), (size_t)nub * 8)) ||
-                 (err = upload(ctx, r->d_usize, usize.data(), (size_t)nub * 4))))
+    if (base && ((err = upload(ctx, r->base.hash, bt.hash)) || (err = upload(ctx, r->base.off, bt.off)) || (err = upload(ctx, r->base.size, bt.size))))
         return err;
+    // what of the StoreIndex the host keeps
+    r->bhash = std::move(st.bhash), r->bleaves = std::move(st.bleaves);
+    r->bcnt = std::move(st.bcnt), r->btag = std::move(st.btag), r->braw = std::move(st.braw);
+    for (uint32_t b = 0; b < nb; ++b)
+        r->block_of_hash.emplace(r->bhash[b], b);
+    r->delivered.assign(nb, 0), r->in_call.assign(nb, 0), r->status.assign(nb, 0u);
+    r->firsts.assign((size_t)nb + 1, 0u), r->bbytes.assign(nb, 0ull);
     if (base && nub)
     {
-        LTHIP_CHECK(ctx, hipMemsetAsync(r->d_ufeed, 0, (size_t)nub * 4, s));
-        LTHIP_CHECK(ctx, hipMemsetAsync(r->d_ubad, 0, (size_t)nub * 4, s));
-        LTHIP_CHECK(ctx, hipMemsetAsync(t_bmark, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->base.feed, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->base.bad, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t.bmark, 0, (size_t)nub * 4, s));
     }
-    LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, 80, s));
+    LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, sizeof(Counters), s));
     if (nb)
     {
         LTHIP_CHECK(ctx, hipMemsetAsync(r->d_status, 0, (size_t)nb * 4, s));
-        LTHIP_CHECK(ctx, hipMemsetAsync(t_hist, 0, (size_t)nb * 4, s));
-        LTHIP_CHECK(ctx, hipMemsetAsync(t_cursor, 0, (size_t)nb * 4, s));
-        LTHIP_CHECK(ctx, hipMemsetAsync(t_bbytes, 0, (size_t)nb * 8, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t.hist, 0, (size_t)nb * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t.cursor, 0, (size_t)nb * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(t.bbytes, 0, (size_t)nb * 8, s));
     }
     // ---- the plan: hash -> position in the StoreIndex's chunk list, occurrences per block, firsts, entries block-major ----
-    if ((err = lthip_seen_create(ctx, m, &r->seen)) || (err = lthip_seen_add(r->seen, m, r->d_chash, t_first, nullptr)))
+    if ((err = lthip_seen_create(ctx, m, &r->seen)) || (err = lthip_seen_add(r->seen, m, sv.chash, t.first, nullptr)))
         return err;
     // ... and, with a base, hash -> position among the base's chunks: an occurrence the base feeds is not resolved against the StoreIndex
-    BasePlan bp = {nullptr, nullptr, nullptr};
     if (base)
     {
-        if ((err = lthip_seen_create(ctx, nub, &r->seen_base)) || (err = lthip_seen_add(r->seen_base, nub, r->d_uhash, t_bfirst, nullptr)))
+        if ((err = lthip_seen_create(ctx, nub, &r->seen_base)) || (err = lthip_seen_add(r->seen_base, nub, r->base.hash, t.bfirst, nullptr)))
             return err;
-        if (nocc && (err = lthip_seen_find(r->seen_base, nocc, t_ohash, t_bpos)))
+        if (nocc && (err = lthip_seen_find(r->seen_base, nocc, t.ohash, t.occ.bpos)))
             return err;
-        bp = BasePlan{t_bpos, r->d_usize, r->d_uoff};
     }
     if (nocc)
     {
-        if ((err = lthip_seen_find(r->seen, nocc, t_ohash, t_pos)))
+        if ((err = lthip_seen_find(r->seen, nocc, t.ohash, t.occ.pos)))
             return err;
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
-                           (const uint32_t*)t_oclip, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_cblock, t_hist, t_bbytes, r->d_counters, bp,
-                           t_oflag, r->d_ufeed, t_bmark);
+        hipLaunchKernelGGL(k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, t, r->base, sv, r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
     }
-    if ((err = lthip_exclusive_scan_u32(ctx, t_hist, r->d_firsts, nb, nullptr, LTHIP_K_OTHER)))
+    if ((err = lthip_exclusive_scan_u32(ctx, t.hist, r->d_firsts, nb, nullptr, LTHIP_K_OTHER)))
         return err;
-    if (base && ((err = lthip_exclusive_scan_u32(ctx, t_oflag, t_ofirst, nocc, nullptr, LTHIP_K_OTHER)) ||
-                 (err = lthip_exclusive_scan_u32(ctx, t_bmark, t_mfirst, nub, nullptr, LTHIP_K_OTHER))))
+    if (base && ((err = lthip_exclusive_scan_u32(ctx, t.oflag, t.ofirst, nocc, nullptr, LTHIP_K_OTHER)) ||
+                 (err = lthip_exclusive_scan_u32(ctx, t.bmark, t.mfirst, nub, nullptr, LTHIP_K_OTHER))))
         return err;
     if (nocc)
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, (const uint32_t*)t_pos, (const uint32_t*)t_olen,
-                           (const uint32_t*)t_oskip, (const uint32_t*)t_oclip, (const uint64_t*)t_odst, (const uint32_t*)r->d_csize,
-                           (const uint32_t*)r->d_cblock, (const uint32_t*)r->d_coff, (const uint32_t*)r->d_firsts, t_cursor, r->d_entries, bp,
-                           (const uint32_t*)t_ofirst, r->d_ksrc, r->d_kdst, r->d_klen, r->d_kchunk, r->d_counters);
+        hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, t, r->base, sv, (const uint32_t*)r->d_firsts,
+                           r->d_entries, r->carry, r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (base && r->verify && nub)
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_carry_marked, dim3((nub + 255u) / 256u), dim3(256), 0, s, nub, (const uint32_t*)t_bmark,
-                           (const uint32_t*)t_mfirst, (const uint32_t*)r->d_usize, (const uint64_t*)r->d_uoff, r->d_cvoff, r->d_cvlen,
-                           r->d_cvchunk, r->d_counters);
+        hipLaunchKernelGGL(k_restore_carry_marked, dim3((nub + 255u) / 256u), dim3(256), 0, s, nub, t, r->base, r->base_ranges, r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     // ---- the one read-back: the firsts (and the bytes per block, for the statistics), what did not resolve, what the base feeds ----
-    unsigned long long counters[10] = {0};
+    Counters counters = {};
     LTHIP_CHECK(ctx, hipMemcpyAsync(r->firsts.data(), r->d_firsts, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
     if (nb)
-        LTHIP_CHECK(ctx, hipMemcpyAsync(r->bbytes.data(), t_bbytes, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-    LTHIP_CHECK(ctx, hipMemcpyAsync(counters, r->d_counters, sizeof counters, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(r->bbytes.data(), t.bbytes, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(&counters, r->d_counters, sizeof counters, hipMemcpyDeviceToHost, s));
     if (base)
     {
-        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->ncarry, t_ofirst + nocc, 4, hipMemcpyDeviceToHost, s));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->nmarked, t_mfirst + nub, 4, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->ncarry, t.ofirst + nocc, 4, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->nmarked, t.mfirst + nub, 4, hipMemcpyDeviceToHost, s));
     }
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-    if (counters[0])
+    if (counters.unresolved)
         return lthip_fail(ctx, ENOENT, wanted.who,
                           base ? "a selected asset needs a chunk that neither the base nor the store index holds (or holds with another size)"
                                : "a selected asset or window needs a chunk the store index does not hold (or holds with another size)");
-    r->carry_bytes = counters[5];
-    r->carry_leaves = counters[6];
-    r->moved_occ = counters[8];
-    r->moved_bytes = counters[9];
+    r->carry_bytes = counters.base_bytes;
+    r->carry_leaves = counters.base_verify_leaves;
+    r->moved_occ = counters.moved_occ;
+    r->moved_bytes = counters.moved_bytes;
     lthip_seen_destroy(r->seen_base);
     r->seen_base = nullptr;
     LTHIP_CHECK(ctx, hipFree(r->d_tmp));
@@ -1012,8 +947,7 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_check_images, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint8_t*)d_images,
-                           (const uint64_t*)r->d_bhash, (const uint32_t*)r->d_bcoff, (const uint32_t*)r->d_bcnt, (const uint32_t*)r->d_btag,
-                           (const uint32_t*)r->d_braw, r->hash_identifier, (const uint64_t*)r->d_chash, (const uint32_t*)r->d_csize, r->d_status);
+                           r->sv, r->hash_identifier, r->d_status);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     // ---- decode: one call per codec; sizes and places from the StoreIndex and image_sizes alone ----
@@ -1046,18 +980,17 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_ranges, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint32_t*)r->d_outsz,
-                           (const uint32_t*)r->d_bcoff, (const uint32_t*)r->d_bcnt, (const uint32_t*)r->d_csize, (const uint32_t*)r->d_coff, r->d_status,
-                           r->verify, base, r->d_voff, r->d_vlen, r->d_vblock, r->d_vchunk);
+                           r->sv, r->d_status, r->verify, base, r->ranges);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (r->verify && ranges)
     {
-        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, (const void*)(uintptr_t)base, ranges, r->d_voff, r->d_vlen, r->max_chunk, leaves,
-                                           r->d_vhash)))
+        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, (const void*)(uintptr_t)base, ranges, r->ranges.off, r->ranges.len, r->max_chunk,
+                                           leaves, r->ranges.hash)))
             return err;
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_compare, dim3((uint32_t)((ranges + 255u) / 256u)), dim3(256), 0, s, (uint32_t)ranges, (const uint64_t*)r->d_vhash,
-                           (const uint32_t*)r->d_vblock, (const uint32_t*)r->d_vchunk, (const uint64_t*)r->d_chash, r->d_status, r->d_counters + 1);
+        hipLaunchKernelGGL(k_restore_compare, dim3((uint32_t)((ranges + 255u) / 256u)), dim3(256), 0, s, (uint32_t)ranges, r->ranges,
+                           (const uint64_t*)r->sv.chash, r->d_status, r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     LaunchTimer tm(ctx, LTHIP_K_GATHER);
@@ -1140,84 +1073,67 @@ static int carry_queue(lthip_restore* r, const void* d_base, void* d_out, void* 
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const uint32_t n = r->ncarry;
-    const size_t n2 = ((size_t)n + 2) & ~(size_t)1;
     const bool in_place = r->in_place;
     int err;
     // ---- verify: the base chunks that feed something, hashed where they lie, before anything of them is copied ----
     const uint32_t* bbad = nullptr;
     if (r->verify && r->nmarked)
     {
-        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, d_base, r->nmarked, r->d_cvoff, r->d_cvlen, r->base_max_chunk, r->carry_leaves,
-                                           r->d_cvhash)))
+        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, d_base, r->nmarked, r->base_ranges.off, r->base_ranges.len, r->base_max_chunk,
+                                           r->carry_leaves, r->base_ranges.hash)))
             return err;
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_carry_compare, dim3((r->nmarked + 255u) / 256u), dim3(256), 0, s, r->nmarked, (const uint64_t*)r->d_cvhash,
-                           (const uint32_t*)r->d_cvchunk, (const uint64_t*)r->d_uhash, (const uint32_t*)r->d_usize, (const uint32_t*)r->d_ufeed,
-                           r->d_ubad, r->d_counters);
+        hipLaunchKernelGGL(k_restore_carry_compare, dim3((r->nmarked + 255u) / 256u), dim3(256), 0, s, r->nmarked, r->base_ranges, r->base,
+                           r->d_counters);
         LTHIP_LAUNCH_CHECK(ctx);
-        bbad = r->d_ubad;
+        bbad = r->base.bad;
     }
     if (in_place && !r->moved_occ) // everything the base feeds lies where it belongs: no copy is queued
         return 0;
-    // [n u64 run source][n u64 run destination][n u64 run length][n u32 pieces][n + 1 u32 first piece][n u32 boundary][n + 1 u32 rank]
-    // in place, behind them: [n u64 run slot][n u32 pieces in][n + 1 u32 first piece in][n u32 units][n + 1 u32 first unit]
+    RunTables runs;
     void* tab = nullptr;
-    if ((err = lthip_scratch(ctx, S_CARRY_RUNS, n2 * (in_place ? 64 : 40), &tab)))
+    if ((err = lthip_scratch(ctx, S_CARRY_RUNS, runs.carve(Carver(), n, in_place), &tab)))
         return err;
-    uint64_t* run_src = (uint64_t*)tab;
-    uint64_t* run_dst = run_src + n2;
-    uint64_t* run_len = run_dst + n2;
-    uint32_t* pieces = (uint32_t*)(run_len + n2);
-    uint32_t* first_piece = pieces + n2;
-    uint32_t* bound = first_piece + n2;
-    uint32_t* rank = bound + n2;
+    runs.carve(Carver(tab), n, in_place);
     // ---- runs: boundaries, their scan, a slot per entry that starts a run, the pieces' scan, the copy ----
     {
         LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_carry_bounds, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint64_t*)r->d_ksrc, (const uint64_t*)r->d_kdst,
-                           (const uint32_t*)r->d_klen, (const uint32_t*)r->d_kchunk, bbad, bound);
+        hipLaunchKernelGGL(k_restore_carry_bounds, dim3((n + 255u) / 256u), dim3(256), 0, s, n, r->carry, bbad, runs);
         LTHIP_LAUNCH_CHECK(ctx);
     }
-    if ((err = lthip_exclusive_scan_u32(ctx, bound, rank, n, nullptr, LTHIP_K_GATHER)))
+    if ((err = lthip_exclusive_scan_u32(ctx, runs.bound, runs.rank, n, nullptr, LTHIP_K_GATHER)))
         return err;
     {
         LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_carry_runs, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint64_t*)r->d_ksrc, (const uint64_t*)r->d_kdst,
-                           (const uint32_t*)r->d_klen, (const uint32_t*)r->d_kchunk, bbad, (const uint32_t*)bound, (const uint32_t*)rank, run_src,
-                           run_dst, run_len, pieces);
+        hipLaunchKernelGGL(k_restore_carry_runs, dim3((n + 255u) / 256u), dim3(256), 0, s, n, r->carry, bbad, runs);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (!in_place)
     {
-        if ((err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, n, nullptr, LTHIP_K_GATHER)))
+        if ((err = lthip_exclusive_scan_u32(ctx, runs.pieces, runs.first_piece, n, nullptr, LTHIP_K_GATHER)))
             return err;
-        return lthip_raw_copy_runs(ctx, first_piece, n, run_src, run_dst, run_len, d_base, d_out, r->carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
+        return lthip_raw_copy_runs(ctx, runs.first_piece, n, runs.src, runs.dst, runs.len, d_base, d_out,
+                                   r->carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
     }
     // ---- in place: kept runs drop out, moved runs get a slot; pass 1 buffer -> scratch, pass 2 scratch -> buffer ----
-    uint64_t* run_slot = (uint64_t*)(rank + n2);
-    uint32_t* pieces_in = (uint32_t*)(run_slot + n2);
-    uint32_t* first_piece_in = pieces_in + n2;
-    uint32_t* units = first_piece_in + n2;
-    uint32_t* first_unit = units + n2;
     {
         LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_in_place_classify, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint64_t*)run_src,
-                           (const uint64_t*)run_dst, (const uint64_t*)run_len, pieces, pieces_in, units);
+        hipLaunchKernelGGL(k_restore_in_place_classify, dim3((n + 255u) / 256u), dim3(256), 0, s, n, runs);
         LTHIP_LAUNCH_CHECK(ctx);
     }
-    if ((err = lthip_exclusive_scan_u32(ctx, units, first_unit, n, nullptr, LTHIP_K_GATHER)) ||
-        (err = lthip_exclusive_scan_u32(ctx, pieces_in, first_piece_in, n, nullptr, LTHIP_K_GATHER)) ||
-        (err = lthip_exclusive_scan_u32(ctx, pieces, first_piece, n, nullptr, LTHIP_K_GATHER)))
+    if ((err = lthip_exclusive_scan_u32(ctx, runs.units, runs.first_unit, n, nullptr, LTHIP_K_GATHER)) ||
+        (err = lthip_exclusive_scan_u32(ctx, runs.pieces_in, runs.first_piece_in, n, nullptr, LTHIP_K_GATHER)) ||
+        (err = lthip_exclusive_scan_u32(ctx, runs.pieces, runs.first_piece, n, nullptr, LTHIP_K_GATHER)))
         return err;
     {
         LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_in_place_slots, dim3((n + 255u) / 256u), dim3(256), 0, s, n, (const uint32_t*)first_unit, run_slot);
+        hipLaunchKernelGGL(k_restore_in_place_slots, dim3((n + 255u) / 256u), dim3(256), 0, s, n, runs);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     const uint64_t pieces_bound = r->moved_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + r->moved_occ;
-    if ((err = lthip_raw_copy_runs(ctx, first_piece_in, n, run_src, run_slot, run_len, d_base, d_scratch, pieces_bound)))
+    if ((err = lthip_raw_copy_runs(ctx, runs.first_piece_in, n, runs.src, runs.slot, runs.len, d_base, d_scratch, pieces_bound)))
         return err;
-    return lthip_raw_copy_runs(ctx, first_piece, n, run_slot, run_dst, run_len, d_scratch, d_out, pieces_bound);
+    return lthip_raw_copy_runs(ctx, runs.first_piece, n, runs.slot, runs.dst, runs.len, d_scratch, d_out, pieces_bound);
 }
 
 extern "C" int lthip_restore_carry(lthip_restore* r, const void* d_base, void* d_out)
@@ -1355,10 +1271,10 @@ extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
         return EINVAL;
     lthip_ctx* ctx = r->ctx;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    unsigned long long counters[5] = {0}; // (d_counters' [1] .. [4])
+    Counters counters = {};
     if (r->nb)
         LTHIP_CHECK(ctx, hipMemcpyAsync(r->status.data(), r->d_status, (size_t)r->nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    LTHIP_CHECK(ctx, hipMemcpyAsync(counters + 1, r->d_counters + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(&counters, r->d_counters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
     r->finished = true;
     lthip_restore_result res;
@@ -1368,14 +1284,14 @@ extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
     res.blocks_needed = r->needed;
     res.blocks_delivered = r->delivered_all;
     res.blocks_unneeded = r->unneeded;
-    res.chunks_mismatched = counters[1];
+    res.chunks_mismatched = counters.block_chunks_bad;
     res.base_occurrences = r->ncarry;
     res.base_bytes = r->carry_bytes;
-    res.base_chunks_mismatched = counters[2];
+    res.base_chunks_mismatched = counters.base_chunks_bad;
     if (r->carried) // (what a mismatched base chunk would have fed was left out of the runs)
     {
-        res.occurrences_written = r->ncarry - counters[3];
-        res.bytes_written = r->carry_bytes - counters[4];
+        res.occurrences_written = r->ncarry - counters.base_bad_occ;
+        res.bytes_written = r->carry_bytes - counters.base_bad_bytes;
     }
     for (uint32_t b = 0; b < r->nb; ++b)
     {

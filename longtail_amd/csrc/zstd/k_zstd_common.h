@@ -5,6 +5,8 @@
 #pragma once
 #include <type_traits>
 
+#include "../k_copy.h"
+
 #define ZB_LANES 64u
 #define ZB_UNROLL _Pragma("unroll")
 #define ZB_FN __device__ __forceinline__ /* inlined so that LDS / global address spaces are known at every access */
@@ -91,8 +93,6 @@ constexpr size_t Z_WORK_STRIDE = Z_WORK_SEQS + Z_WORK_SBITS;
 constexpr uint32_t ZHDR = 13u;
 constexpr int ZT = 256;
 
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
 // The pieces (zstd blocks) of a frame written here are independent of each other: matches never leave their 64 KiB window group,
 // offsets are never repeat codes, every block carries its own entropy tables.  A frame of two or more pieces says so in a trailing
 // SKIPPABLE frame (magic 0x184D2A5D, 4 bytes of data "LTP\1": any zstd decoder skips it, zstd_decompress.c:1068-1085), which lets
@@ -151,33 +151,7 @@ __device__ __forceinline__ uint32_t z_is_trailer2_head(const uint8_t* d, uint64_
 // a workgroup of ZT threads copies n bytes, 16-byte stores, source of any alignment
 __device__ __forceinline__ void wg_copy16(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n, int tid)
 {
-    uint32_t head = (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u);
-    if (head > n)
-        head = n;
-    if ((uint32_t)tid < head)
-        dst[tid] = src[tid];
-    dst += head;
-    src += head;
-    n -= head;
-    const uint32_t nvec = n >> 4;
-    const uint32_t mis = (uint32_t)((uintptr_t)src & 3u);
-    const uint32_t sh = mis * 8u;
-    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src - mis);
-    for (uint32_t v = tid; v < nvec; v += ZT)
-    {
-        const uint32_t* q = s4 + v * 4u;
-        const u32x4_a4 a = *reinterpret_cast<const u32x4_a4*>(q);
-        const uint32_t e = mis ? q[4] : 0u;
-        uint4 o;
-        o.x = __builtin_amdgcn_alignbit(a.y, a.x, sh);
-        o.y = __builtin_amdgcn_alignbit(a.z, a.y, sh);
-        o.z = __builtin_amdgcn_alignbit(a.w, a.z, sh);
-        o.w = __builtin_amdgcn_alignbit(e, a.w, sh);
-        *reinterpret_cast<uint4*>(dst + (uint64_t)v * 16u) = o;
-    }
-    const uint32_t done = nvec << 4;
-    if ((uint32_t)tid < n - done)
-        dst[done + tid] = src[done + tid];
+    lthip_wg_copy<ZT>(dst, src, n, tid);
 }
 
 } // namespace
