@@ -328,7 +328,20 @@ LTHIP_EXPORT int lthip_meow_stream_final(lthip_ctx* ctx, const void* d_tail, uin
  * d_out_sizes[b] = payload size, or 0 when it does not fit (LZ4CompressionAPI_Compress -> ENOMEM).
  * The offset/size tables are HOST arrays (copied to the device by the call).  The calls queue their work on the context's
  * stream and return (results are ready after lthip_ctx_sync or any later work on the stream); a call of any size is cut
- * into internal batches of LTHIP_BATCH_BYTES of input (environment, default 8 GiB) so that the scratch stays bounded. */
+ * into internal batches of LTHIP_BATCH_BYTES of input (environment, default 8 GiB) so that the scratch stays bounded.
+ *
+ * Windows -- for the four block codec calls (lthip_lz4_compress_blocks, lthip_lz4_decompress_blocks,
+ * lthip_zstd_compress_blocks[_q], lthip_zstd_decompress_blocks):
+ *   - A call writes no byte of d_dst outside [dst_offsets[b], dst_offsets[b] + dst_caps[b]) for any block b, whatever the payload
+ *     contains and whether the block's result is a size, 0 or 0xFFFFFFFF.
+ *   - Bytes inside the window beyond the returned size are unspecified, and so is the whole window of a refused block (result 0 from
+ *     an encoder, 0xFFFFFFFF from a decoder): the encoders place bytes before they know whether the payload fits, a decoder stops
+ *     where it finds the damage.
+ *   - Source and destination windows may lie at any byte position, and the destination windows of different blocks may touch, with
+ *     no gap between them.
+ *   - Reads stay inside the 16-byte aligned hull of a block's source window (k_lz4_decode.hip, k_copy.h): a source needs no padding
+ *     beyond the allocation granule of the device.
+ * tests/test_gpu_codec_windows.py holds the calls to the first three (tests/codec_windows_util.py: guarded and packed layouts). */
 LTHIP_EXPORT size_t lthip_lz4_bound(size_t size); /* LZ4_COMPRESSBOUND, lib/lz4/ext/lz4.h:215 */
 LTHIP_EXPORT int lthip_lz4_compress_blocks(lthip_ctx* ctx, const void* d_src, uint32_t block_count,
                                            const uint64_t* src_offsets, const uint32_t* src_sizes, void* d_dst,
@@ -367,7 +380,9 @@ LTHIP_EXPORT int lthip_gather_ranges(lthip_ctx* ctx, const void* d_src, uint64_t
  * ZSTD_decompressDCtx.  A compressed piece is a run of small zstd blocks (one per 4 KiB of content, one set of entropy
  * tables per piece) and the frame ends with a skippable frame holding the directory of block sizes, which lets
  * lthip_zstd_decompress_blocks decode every block on a lane of its own (LTHIP_ZSTD_SUB=0: one block per
- * piece).  Same calling convention as lthip_lz4_compress_blocks. */
+ * piece).  Same calling convention as lthip_lz4_compress_blocks.  A capacity that holds the frame but not its directory (12 bytes +
+ * 2 per 4 KiB of content) gives the frame without it -- still a standard frame, which this library decodes block-parallel like any
+ * other encoder's --, a smaller one gives 0. */
 LTHIP_EXPORT size_t lthip_zstd_bound(size_t size); /* ZSTD_COMPRESSBOUND, lib/zstd/ext/zstd.h:232 */
 LTHIP_EXPORT int lthip_zstd_compress_blocks(lthip_ctx* ctx, const void* d_src, uint32_t block_count,
                                             const uint64_t* src_offsets, const uint32_t* src_sizes, void* d_dst,
