@@ -151,62 +151,71 @@ __global__ void k_ing_sum_u32(const uint32_t* __restrict__ v, uint32_t n, unsign
 
 } // namespace
 
+// host tables of the job layout: the chunks of every asset and their exclusive sum (assets + 1), and for a rank of several the first
+// chunk of each of its own jobs in the arrays of all ranks (own jobs + 1)
+struct JobTables
+{
+    std::vector<uint32_t> starts, counts, gfirst;
+};
+
+// Every buffer and event frees itself (ingest_buffers.h); the initial values are stated here, once.
 struct lthip_ingest
 {
-    lthip_ctx* ctx;
-    lthip_ingest_config cfg;
+    lthip_ctx* ctx = nullptr;
+    lthip_ingest_config cfg = {};
     // ---- index phase ----
-    DBuf d_first, d_isfirst, d_rank, d_idx, d_uh, d_us, d_ut, d_starts, d_tags, d_counts, d_paths, d_aoff, d_alen, d_ph, d_ch;
+    ViWorkspace vi; // the VersionIndex builder's tables (index_kernels.h); the owned chunks' compaction reads its d_starts / d_tags too
+    DBuf d_first, d_counts;
     DBuf d_gfirst, d_owned, d_orank, d_l2g, d_mu_hash, d_mu_len, d_mu_off, d_mu_tag;
     // what the target already holds (lthip_ingest_set_store; may be null): the flags of the local chunks, and for a rank of several
     // their hashes
-    const lthip_store* store;
+    const lthip_store* store = nullptr;
     DBuf d_known, d_lhash;
-    uint64_t known_chunks, known_bytes;
+    uint64_t known_chunks = 0, known_bytes = 0;
     HBuf h_counts, h_mu_len, h_mu_off, h_mu_hash, h_mu_tag, h_bhash, h_comp, h_brk;
     DBuf d_brk;
     DBuf d_bhash, d_boff, d_blen, d_comp, d_sum;
     DBuf d_gather;
     BlockImageBufs wbufs; // the block writer's tables (block_images.hip)
-    hipEvent_t ev_counts, ev_lens, ev_offs, ev_index;
+    Event ev_counts, ev_lens, ev_offs, ev_index;
     // the first-seen index of every chunk computed elsewhere (the sharded table of the multi-GPU path): consumed by the next
     // lthip_ingest_index instead of its own table pass
-    const uint32_t* ext_first;
-    uint64_t ext_unique;
+    const uint32_t* ext_first = nullptr;
+    uint64_t ext_unique = 0;
     // host state between the phases
-    uint64_t n_all, n_local, unique_all, n_mine;
+    uint64_t n_all = 0, n_local = 0, unique_all = 0, n_mine = 0;
     std::vector<uint64_t> b_first;   // nb + 1 chunk indices into the owned-unique list
     std::vector<uint64_t> b_size;    // raw bytes
     std::vector<uint8_t> b_is_range; // the block's chunks are one byte range of the rank's data
     std::vector<uint32_t> b_tag;
-    bool has_tags;
-    size_t vi_size;
-    bool indexed, written;
+    bool has_tags = false;
+    size_t vi_size = 0;
+    bool indexed = false, written = false;
     // the packing runs in slices (ingest_pack): lthip_ingest_index packs what the first codec batch takes, lthip_ingest_write the rest
     // once that batch is queued
-    uint32_t pack_next;   // first owned chunk that is in no block yet
-    uint32_t pack_avail;  // owned chunks whose lengths / break flags / tags / offsets are on the host
-    uint64_t pack_raw;    // raw bytes of the blocks so far
-    bool blocks_done;     // all blocks packed and hashed, their hashes on the way to the host (ev_index)
-    hipEvent_t ev_hashes; // the owned chunks' hashes are on the host (side stream)
-    lthip_ingest_result res;
+    uint32_t pack_next = 0;   // first owned chunk that is in no block yet
+    uint32_t pack_avail = 0;  // owned chunks whose lengths / break flags / tags / offsets are on the host
+    uint64_t pack_raw = 0;    // raw bytes of the blocks so far
+    bool blocks_done = false; // all blocks packed and hashed, their hashes on the way to the host (ev_index)
+    Event ev_hashes;          // the owned chunks' hashes are on the host (side stream)
+    lthip_ingest_result res = {};
     // the VersionIndex sections are put together by a helper thread on a context of its own (stream, staging ring, BLAKE3 scratch), so
     // that the calling thread keeps the session's context to itself and does not wait for it before lthip_ingest_finish
-    lthip_ctx* vi_ctx;
+    lthip_ctx* vi_ctx = nullptr;
     std::thread vi_thread;
-    int vi_err;
-    bool vi_pending; // prepared by lthip_ingest_index, not started yet
+    int vi_err = 0;
+    bool vi_pending = false; // prepared by lthip_ingest_index, not started yet
     // what the VersionIndex helper reads of the caller's tree AFTER lthip_ingest_index has returned: a deep copy (O(assets): sizes, path
-    // offsets, permissions, path data), so that a caller may free or reuse its lthip_ingest_tree arrays as soon as the call returns --
-    // the contract of round 2.  Only the device arrays and the output buffer live until lthip_ingest_finish (include/longtail_hip.h).
-    lthip_ingest_tree vi_tree;
+    // offsets, permissions, path data, the job tables), so that a caller may free or reuse its lthip_ingest_tree arrays as soon as the call
+    // returns -- the contract of round 2.  Only the device arrays and the output buffer live until lthip_ingest_finish (include/longtail_hip.h).
+    ViTree vi_tree = {};
     std::vector<uint64_t> vi_asset_sizes;
     std::vector<uint32_t> vi_path_offsets;
     std::vector<uint16_t> vi_permissions;
     std::vector<char> vi_path_data;
-    std::vector<uint32_t> vi_starts, vi_counts;
-    const uint64_t* vi_hashes;
-    void* vi_out;
+    JobTables vi_jobs;
+    const uint64_t* vi_hashes = nullptr;
+    void* vi_out = nullptr;
     // the codec batch being written (kept for its vectors), and the stored-block images of the last one (lthip_ingest_images): their
     // sizes are completed by lthip_ingest_finish (they need the compressed sizes)
     BlockBatch batch;
@@ -263,63 +272,31 @@ extern "C" int lthip_ingest_create(lthip_ctx* ctx, const lthip_ingest_config* cf
     g->cfg = *cfg;
     if (g->cfg.batch_bytes == 0)
         g->cfg.batch_bytes = 8ull << 30;
-    g->indexed = g->written = false;
-    g->vi_ctx = nullptr;
-    g->vi_err = 0;
-    g->vi_pending = false;
-    g->ev_counts = g->ev_lens = g->ev_index = g->ev_offs = g->ev_hashes = nullptr;
-    g->blocks_done = false;
-    g->store = nullptr;
-    g->known_chunks = g->known_bytes = 0;
-    if (hipEventCreateWithFlags(&g->ev_counts, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g->ev_lens, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g->ev_offs, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g->ev_index, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g->ev_hashes, hipEventDisableTiming) != hipSuccess)
-    {
-        lthip_ingest_destroy(g);
-        return lthip_fail(ctx, EIO, "lthip_ingest_create", "hipEventCreate");
-    }
+    for (Event* e : {&g->ev_counts, &g->ev_lens, &g->ev_offs, &g->ev_index, &g->ev_hashes})
+        if (e->create() != hipSuccess)
+        {
+            lthip_ingest_destroy(g);
+            return lthip_fail(ctx, EIO, "lthip_ingest_create", "hipEventCreate");
+        }
     *out = g;
     return 0;
 }
 
 static int ingest_vi_join(lthip_ingest* g);
 
+// Waits for what is in flight -- the helper thread with its context, the stream, the side stream's copies --, destroys what is not a
+// buffer, and deletes: nothing is freed before the streams that may touch it are idle.
 extern "C" void lthip_ingest_destroy(lthip_ingest* g)
 {
     if (!g)
         return;
     (void)hipSetDevice(g->ctx->device);
     (void)ingest_vi_join(g);
+    (void)hipStreamSynchronize(g->ctx->stream);
+    if (g->ev_hashes)
+        (void)hipEventSynchronize(g->ev_hashes);
     if (g->vi_ctx)
         lthip_ctx_destroy(g->vi_ctx);
-    (void)hipStreamSynchronize(g->ctx->stream);
-    DBuf* dev[] = {&g->d_first, &g->d_isfirst, &g->d_rank, &g->d_idx, &g->d_uh, &g->d_us, &g->d_ut, &g->d_starts, &g->d_tags, &g->d_counts,
-                   &g->d_paths, &g->d_aoff, &g->d_alen, &g->d_ph, &g->d_ch, &g->d_gfirst, &g->d_owned, &g->d_orank, &g->d_l2g, &g->d_mu_hash,
-                   &g->d_mu_len, &g->d_mu_off, &g->d_mu_tag, &g->d_bhash, &g->d_boff, &g->d_blen, &g->d_comp, &g->d_sum, &g->d_gather,
-                   &g->d_brk, &g->d_known, &g->d_lhash, &g->wbufs.d_tmpsz, &g->wbufs.d_gsrc, &g->wbufs.d_glen, &g->wbufs.d_gdst, &g->wbufs.d_bfirst,
-                   &g->wbufs.d_braw, &g->wbufs.d_bimg, &g->wbufs.d_btag};
-    for (DBuf* b : dev)
-        if (b->p)
-            (void)hipFree(b->p);
-    HBuf* pin[] = {&g->h_counts, &g->h_mu_len, &g->h_mu_off, &g->h_mu_hash, &g->h_mu_tag, &g->h_bhash, &g->h_comp, &g->h_brk};
-    for (HBuf* b : pin)
-        if (b->p)
-            (void)hipHostFree(b->p);
-    if (g->ev_counts)
-        (void)hipEventDestroy(g->ev_counts);
-    if (g->ev_lens)
-        (void)hipEventDestroy(g->ev_lens);
-    if (g->ev_offs)
-        (void)hipEventDestroy(g->ev_offs);
-    if (g->ev_index)
-        (void)hipEventDestroy(g->ev_index);
-    if (g->ev_hashes)
-    {
-        (void)hipEventSynchronize(g->ev_hashes);
-        (void)hipEventDestroy(g->ev_hashes);
-    }
     delete g;
 }
 
@@ -424,102 +401,17 @@ static int ingest_blocks_done(lthip_ingest* g)
     return 0;
 }
 
-// The serialized VersionIndex (Longtail_BuildVersionIndex :2757-2806 over InitVersionIndexFromData's section order) into the caller's
-// buffer: content hash of every asset = BLAKE3 of its chunk-hash array (:2518-2537), path hashes (:1269-1300), the sections copied or
-// written.  `ctx`: the context whose stream, staging ring and scratch it may use -- the helper thread's own, or the session's.
+// The serialized VersionIndex into the caller's buffer: steps 2 and 3 of the builder (index_kernels.h; step 1 ran on the session's
+// stream).  `ctx`: the context whose stream, staging ring and scratch it may use -- the helper thread's own, or the session's.
 static int ingest_vi_work(lthip_ingest* g, lthip_ctx* ctx)
 {
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const lthip_ingest_tree* t = &g->vi_tree;
-    const std::vector<uint32_t>&starts = g->vi_starts, &counts = g->vi_counts;
-    const uint32_t n = (uint32_t)g->n_all, na = t->asset_count;
-    const uint64_t unique = g->unique_all;
-    const uint64_t* d_all_hashes = g->vi_hashes;
-    void* h_version_index = g->vi_out;
-    int err = 0;
     if (ctx != g->ctx)
-        LTHIP_CHECK(ctx, hipStreamWaitEvent(s, g->ev_lens, 0)); // (recorded behind the first-seen pass on the session's stream)
-    // content hash of every asset = BLAKE3 of its chunk-hash array (:2518-2537); path hashes (:1269-1300)
-    std::vector<uint64_t> h_off(na);
-    std::vector<uint32_t> h_len(na);
-    uint32_t max_len = 0;
-    for (uint32_t a = 0; a < na; ++a)
-    {
-        if ((uint64_t)counts[a] * 8u > 0xFFFFFFFFull)
-            return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "asset with more than 2^29 chunks");
-        h_off[a] = (uint64_t)starts[a] * 8u;
-        h_len[a] = counts[a] * 8u;
-        max_len = std::max(max_len, h_len[a]);
-    }
-    if (na)
-    {
-        if ((err = lthip_stage_upload(ctx, g->d_aoff.p, h_off.data(), (size_t)na * 8, s)) ||
-            (err = lthip_stage_upload(ctx, g->d_alen.p, h_len.data(), (size_t)na * 4, s)))
-            return err;
-        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, n ? (const void*)d_all_hashes : g->d_paths.p, na, (const uint64_t*)g->d_aoff.p,
-                                     (const uint32_t*)g->d_alen.p, max_len, 0u, (uint64_t*)g->d_ch.p)))
-            return err;
-        max_len = 0;
-        for (uint32_t a = 0; a < na; ++a)
-        {
-            if (t->path_start_offsets[a] >= t->path_data_size)
-                return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "path offset outside the path data");
-            h_off[a] = t->path_start_offsets[a];
-            h_len[a] = (uint32_t)strnlen(t->path_data + t->path_start_offsets[a], t->path_data_size - t->path_start_offsets[a]);
-            max_len = std::max(max_len, h_len[a]);
-        }
-        // the staging ring holds 8 uploads: the offset / length tables of the content hashes were consumed by a kernel
-        // queued before these, and the uploads are ordered on the stream, so reusing d_aoff / d_alen is safe
-        if ((err = lthip_stage_upload(ctx, g->d_paths.p, t->path_data, t->path_data_size, s)) ||
-            (err = lthip_stage_upload(ctx, g->d_aoff.p, h_off.data(), (size_t)na * 8, s)) ||
-            (err = lthip_stage_upload(ctx, g->d_alen.p, h_len.data(), (size_t)na * 4, s)))
-            return err;
-        if ((err = lthip_hash_ranges_by_id(ctx, g->cfg.hash_identifier, g->d_paths.p, na, (const uint64_t*)g->d_aoff.p, (const uint32_t*)g->d_alen.p, max_len, 0u,
-                                     (uint64_t*)g->d_ph.p)))
-            return err;
-    }
-    // serialized layout (Longtail_BuildVersionIndex :2757-2806 over InitVersionIndexFromData's section order)
-    uint8_t* w = (uint8_t*)h_version_index;
-    const uint32_t head[6] = {2u /* LONGTAIL_VERSION_INDEX_VERSION_0_0_2, :16-22 */, g->cfg.hash_identifier, g->cfg.target_chunk_size, na,
-                              (uint32_t)unique, n};
-    memcpy(w, head, sizeof head);
-    w += sizeof head;
-    #define LT_D2H(SRC, BYTES)                                                                    \
-do                                                                                        \
-{                                                                                         \
-    if (BYTES)                                                                            \
-        LTHIP_CHECK(ctx, hipMemcpyAsync(w, (SRC), (BYTES), hipMemcpyDeviceToHost, s));    \
-    w += (BYTES);                                                                         \
-} while (0)
-    LT_D2H(g->d_ph.p, (size_t)na * 8);             // m_PathHashes
-    LT_D2H(g->d_ch.p, (size_t)na * 8);             // m_ContentHashes
-    memcpy(w, t->asset_sizes, (size_t)na * 8);     // m_AssetSizes
-    w += (size_t)na * 8;
-    memcpy(w, counts.data(), (size_t)na * 4);      // m_AssetChunkCounts
-    w += (size_t)na * 4;
-    memcpy(w, starts.data(), (size_t)na * 4);      // m_AssetChunkIndexStarts
-    w += (size_t)na * 4;
-    LT_D2H(g->d_idx.p, (size_t)n * 4);             // m_AssetChunkIndexes
-    LT_D2H(g->d_uh.p, (size_t)unique * 8);         // m_ChunkHashes
-    LT_D2H(g->d_us.p, (size_t)unique * 4);         // m_ChunkSizes
-    if (g->has_tags)
-        LT_D2H(g->d_ut.p, (size_t)unique * 4);     // m_ChunkTags
-    else
-    {
-        uint32_t* tg = (uint32_t*)w;               // one tag for the whole tree (what UpSync passes, cmd/main.c:1038-1046)
-        for (uint64_t i = 0; i < unique; ++i)
-            tg[i] = g->cfg.compression_type;
-        w += (size_t)unique * 4;
-    }
-    #undef LT_D2H
-    memcpy(w, t->path_start_offsets, (size_t)na * 4); // m_NameOffsets
-    w += (size_t)na * 4;
-    memcpy(w, t->permissions, (size_t)na * 2);        // m_Permissions
-    w += (size_t)na * 2;
-    memcpy(w, t->path_data, t->path_data_size);       // m_NameData
-
-    return 0;
+        LTHIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, g->ev_lens, 0)); // (recorded behind the first-seen pass on the session's stream)
+    const uint32_t n = (uint32_t)g->n_all;
+    if (const int err = lthip_vi_hashes(ctx, g->vi, g->vi_tree, g->vi_hashes, n))
+        return err;
+    return lthip_vi_sections(ctx, g->vi, g->vi_tree, n, g->unique_all, g->has_tags ? nullptr : &g->cfg.compression_type, g->vi_out);
 }
 
 // collects the helper (and what it queued): its error, if any
@@ -552,147 +444,125 @@ static int ingest_vi_start(lthip_ingest* g)
     return 0;
 }
 
-extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, const uint64_t* d_all_hashes, const uint32_t* d_all_lens,
-                                  uint64_t all_chunks, const uint64_t* d_local_offsets, const uint32_t* d_local_part_first,
-                                  uint64_t local_chunks, void* h_version_index, size_t version_index_capacity)
+// ---- lthip_ingest_index, step by step.  What the steps share of the call: ----
+struct IndexCall
 {
-    if (!g || !t || (all_chunks && (!d_all_hashes || !d_all_lens)) || (local_chunks && (!d_local_offsets || !d_local_part_first)) ||
-        (t->job_count && (!t->job_asset || !t->job_first)) ||
-        (t->asset_count && (!t->asset_sizes || !t->path_start_offsets || !t->permissions || !t->path_data)))
-        return EINVAL;
+    const lthip_ingest_tree* t;
+    const uint64_t* d_all_hashes;
+    const uint32_t* d_all_lens;
+    const uint64_t* d_local_offsets;
+    const uint32_t* d_local_part_first;
+    uint32_t n, nl, na; // chunks of all ranks, of this rank; assets
+    bool all_mine;      // a single rank: the local arrays are the global ones
+    uint64_t my_jobs;
+};
+
+// "reserve": the session's tables, by what their size follows
+static int ingest_reserve(lthip_ingest* g, const IndexCall& c)
+{
     lthip_ctx* ctx = g->ctx;
-    if (all_chunks > 0x7FFFFFF0ull || local_chunks > all_chunks)
-        return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "chunk counts out of range");
-    if (t->job_count && t->job_first[t->job_count] != all_chunks)
-        return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "job_first[job_count] must be the number of chunks");
-    if (t->asset_tags) // (before any work is queued: the session stays as it is)
-        for (uint32_t a = 0; a < t->asset_count; ++a)
-            if (const int refused = tag_refusal(g->cfg.codec, t->asset_tags[a]))
-                return lthip_fail(ctx, refused, "lthip_ingest_index", tag_refusal_text(refused));
-    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    g->vi_pending = false;
-    (void)ingest_vi_join(g); // (an index that was never finished: its helper reads what this call is about to replace ...
-    (void)hipEventSynchronize(g->ev_hashes); // ... and so does the side stream)
-    IngTrace tr("lthip_ingest_index");
-    hipStream_t s = ctx->stream;
-    const uint32_t n = (uint32_t)all_chunks, nl = (uint32_t)local_chunks, na = t->asset_count;
-    const bool all_mine = t->my_jobs == nullptr;
-    const uint64_t my_jobs = all_mine ? t->job_count : t->my_job_count;
-    g->indexed = g->written = false;
-    g->n_all = n;
-    g->n_local = nl;
-    g->has_tags = t->asset_tags != nullptr;
-    memset(&g->res, 0, sizeof g->res);
-
-    tr.mark("checks");
-    int err;
-    if ((err = reserve_dev(ctx, g->d_first, (size_t)n * 4)) || (err = reserve_dev(ctx, g->d_isfirst, (size_t)n * 4)) ||
-        (err = reserve_dev(ctx, g->d_rank, ((size_t)n + 1) * 4)) || (err = reserve_dev(ctx, g->d_idx, (size_t)n * 4)) ||
-        (err = reserve_dev(ctx, g->d_uh, (size_t)n * 8)) || (err = reserve_dev(ctx, g->d_us, (size_t)n * 4)) ||
-        (err = reserve_dev(ctx, g->d_ut, (size_t)n * 4)) || (err = reserve_dev(ctx, g->d_starts, ((size_t)na + 1) * 4)) ||
-        (err = reserve_dev(ctx, g->d_tags, (size_t)na * 4)) || (err = reserve_dev(ctx, g->d_counts, 64)) ||
-        (err = reserve_dev(ctx, g->d_paths, (size_t)t->path_data_size + 16)) || (err = reserve_dev(ctx, g->d_aoff, (size_t)na * 8)) ||
-        (err = reserve_dev(ctx, g->d_alen, (size_t)na * 4)) || (err = reserve_dev(ctx, g->d_ph, (size_t)na * 8)) ||
-        (err = reserve_dev(ctx, g->d_ch, (size_t)na * 8)) || (err = reserve_dev(ctx, g->d_gfirst, ((size_t)my_jobs + 1) * 4)) ||
-        (err = reserve_dev(ctx, g->d_owned, (size_t)nl * 4)) || (err = reserve_dev(ctx, g->d_orank, ((size_t)nl + 1) * 4)) ||
-        (err = reserve_dev(ctx, g->d_l2g, (size_t)nl * 4)) || (err = reserve_dev(ctx, g->d_mu_hash, (size_t)nl * 8)) ||
-        (err = reserve_dev(ctx, g->d_mu_len, (size_t)nl * 4)) || (err = reserve_dev(ctx, g->d_mu_off, (size_t)nl * 8)) ||
-        (err = reserve_dev(ctx, g->d_mu_tag, (size_t)nl * 4)) || (err = reserve_pinned(ctx, g->h_counts, 64)) ||
-        (err = reserve_pinned(ctx, g->h_mu_len, (size_t)nl * 4)) || (err = reserve_pinned(ctx, g->h_mu_off, (size_t)nl * 8)) ||
-        (err = reserve_pinned(ctx, g->h_brk, (size_t)nl + 16)) || (err = reserve_dev(ctx, g->d_brk, (size_t)nl + 16)) ||
-        (err = reserve_pinned(ctx, g->h_mu_hash, (size_t)nl * 8)) || (err = reserve_pinned(ctx, g->h_mu_tag, (size_t)nl * 4)) ||
-        // (per block; the number of blocks is known when the packing ends, which is after the first codec batch was queued: a block
-        // holds at least one chunk)
-        (err = reserve_dev(ctx, g->d_bhash, (size_t)nl * 8)) || (err = reserve_dev(ctx, g->d_boff, (size_t)nl * 8)) ||
-        (err = reserve_dev(ctx, g->d_blen, (size_t)nl * 4)) || (err = reserve_dev(ctx, g->d_comp, (size_t)nl * 4)) ||
-        (err = reserve_dev(ctx, g->d_sum, 8)))
-        return err;
-    if (g->store && ((err = reserve_dev(ctx, g->d_known, (size_t)nl)) || (!all_mine && (err = reserve_dev(ctx, g->d_lhash, (size_t)nl * 8)))))
-        return err;
-    tr.mark("reserve");
-    uint64_t* d_counts = (uint64_t*)g->d_counts.p; // [0] distinct hashes of all ranks, [1] chunks this rank writes (u32 in the low half)
-    volatile uint64_t* h_counts = (volatile uint64_t*)g->h_counts.p;
-
-    // ---- first-seen pass over ALL chunks (:2951-2970), unique index of every asset chunk ----
-    if (g->ext_first)
+    const size_t n = c.n, nl = c.nl;
+    int err = lthip_vi_reserve(ctx, g->vi, n, c.na, c.t->path_data_size);
+    auto dev = [&](DBuf& b, size_t bytes) { err = err ? err : reserve_dev(ctx, b, bytes); };
+    auto pin = [&](HBuf& b, size_t bytes) { err = err ? err : reserve_pinned(ctx, b, bytes); };
+    dev(g->d_first, n * 4);
+    dev(g->d_counts, 64);
+    pin(g->h_counts, 64);
+    dev(g->d_sum, 8);
+    dev(g->d_gfirst, ((size_t)c.my_jobs + 1) * 4);
+    // per local chunk -- and per block: the number of blocks is known when the packing ends, which is after the first codec batch was
+    // queued, and a block holds at least one chunk
+    for (DBuf* b : {&g->d_owned, &g->d_l2g, &g->d_mu_len, &g->d_mu_tag, &g->d_blen, &g->d_comp})
+        dev(*b, nl * 4);
+    for (DBuf* b : {&g->d_mu_hash, &g->d_mu_off, &g->d_bhash, &g->d_boff})
+        dev(*b, nl * 8);
+    dev(g->d_orank, (nl + 1) * 4);
+    dev(g->d_brk, nl + 16);
+    for (HBuf* b : {&g->h_mu_len, &g->h_mu_tag})
+        pin(*b, nl * 4);
+    for (HBuf* b : {&g->h_mu_off, &g->h_mu_hash})
+        pin(*b, nl * 8);
+    pin(g->h_brk, nl + 16);
+    if (g->store)
     {
-        // computed by the ranks together (lthip_dedup_min_ordinal on every rank's share of the hash space): nothing to insert here
-        const uint64_t u = g->ext_unique;
-        LTHIP_CHECK(ctx, hipMemcpyAsync(g->d_first.p, g->ext_first, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        if ((err = lthip_stage_upload(ctx, d_counts, &u, 8, s)))
-            return err;
-        g->ext_first = nullptr;
+        dev(g->d_known, nl);
+        if (!c.all_mine)
+            dev(g->d_lhash, nl * 8);
     }
-    else if ((err = lthip_dedup_first_seen(ctx, n, d_all_hashes, (uint32_t*)g->d_first.p, d_counts)))
-        return err;
-    tr.mark("first-seen");
+    return err;
+}
 
-    // ---- host tables that only depend on the job layout (and its validation): 0.05-0.1 ms on the 64 GiB tree, while the first-seen pass
-    // (0.55 ms) is running ----
-    std::vector<uint32_t> starts((size_t)na + 1, 0), counts(na, 0);
+// "first-seen": the pass over ALL chunks (:2951-2970) into d_first, the number of distinct hashes into d_counts[0] -- or the index the
+// ranks computed together (lthip_ingest_set_first_seen: lthip_dedup_min_ordinal on every rank's share of the hash space), consumed here
+static int ingest_first_seen(lthip_ingest* g, const IndexCall& c)
+{
+    lthip_ctx* ctx = g->ctx;
+    if (!g->ext_first)
+        return lthip_dedup_first_seen(ctx, c.n, c.d_all_hashes, (uint32_t*)g->d_first.p, (uint64_t*)g->d_counts.p);
+    const uint64_t u = g->ext_unique;
+    LTHIP_CHECK(ctx, hipMemcpyAsync(g->d_first.p, g->ext_first, (size_t)c.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    g->ext_first = nullptr;
+    return lthip_stage_upload(ctx, g->d_counts.p, &u, 8, ctx->stream);
+}
+
+// "tables": the job layout validated and its host tables built -- 0.05-0.1 ms on the 64 GiB tree, while the first-seen pass (0.55 ms) runs
+static int ingest_job_tables(lthip_ctx* ctx, const IndexCall& c, JobTables& jt)
+{
+    const lthip_ingest_tree* t = c.t;
+    jt.starts.assign((size_t)c.na + 1, 0);
+    jt.counts.assign(c.na, 0);
     for (uint64_t j = 0; j < t->job_count; ++j)
     {
-        if (t->job_asset[j] >= na || t->job_first[j + 1] < t->job_first[j])
+        if (t->job_asset[j] >= c.na || t->job_first[j + 1] < t->job_first[j])
             return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "bad job table");
-        counts[t->job_asset[j]] += (uint32_t)(t->job_first[j + 1] - t->job_first[j]);
+        jt.counts[t->job_asset[j]] += (uint32_t)(t->job_first[j + 1] - t->job_first[j]);
     }
-    for (uint32_t a = 0; a < na; ++a)
-        starts[a + 1] = starts[a] + counts[a];
-    if (starts[na] != n)
+    for (uint32_t a = 0; a < c.na; ++a)
+        jt.starts[a + 1] = jt.starts[a] + jt.counts[a];
+    if (jt.starts[c.na] != c.n)
         return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "jobs do not cover the chunk arrays");
-    std::vector<uint32_t> gfirst;
-    if (!all_mine)
+    if (c.all_mine)
+        return c.nl == c.n ? 0 : lthip_fail(ctx, EINVAL, "lthip_ingest_index", "without my_jobs the local arrays are the global ones");
+    jt.gfirst.resize((size_t)c.my_jobs + 1);
+    uint64_t mine = 0;
+    for (uint64_t m = 0; m < c.my_jobs; ++m)
     {
-        gfirst.resize((size_t)my_jobs + 1);
-        uint64_t mine = 0;
-        for (uint64_t m = 0; m < my_jobs; ++m)
-        {
-            const uint64_t j = t->my_jobs[m];
-            if (j >= t->job_count || (m && j <= t->my_jobs[m - 1]))
-                return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "my_jobs must be ascending job indices");
-            gfirst[m] = (uint32_t)t->job_first[j];
-            mine += t->job_first[j + 1] - t->job_first[j];
-        }
-        gfirst[my_jobs] = 0;
-        if (mine != nl)
-            return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "own jobs do not add up to the local chunk count");
+        const uint64_t j = t->my_jobs[m];
+        if (j >= t->job_count || (m && j <= t->my_jobs[m - 1]))
+            return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "my_jobs must be ascending job indices");
+        jt.gfirst[m] = (uint32_t)t->job_first[j];
+        mine += t->job_first[j + 1] - t->job_first[j];
     }
-    else if (nl != n)
-        return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "without my_jobs the local arrays are the global ones");
+    jt.gfirst[c.my_jobs] = 0;
+    if (mine != c.nl)
+        return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "own jobs do not add up to the local chunk count");
+    return 0;
+}
 
-    tr.mark("tables");
-    if ((err = lthip_stage_upload(ctx, g->d_starts.p, starts.data(), ((size_t)na + 1) * 4, s)))
-        return err;
-    if (g->has_tags && na && (err = lthip_stage_upload(ctx, g->d_tags.p, t->asset_tags, (size_t)na * 4, s)))
-        return err;
-    if (!all_mine && (err = lthip_stage_upload(ctx, g->d_gfirst.p, gfirst.data(), ((size_t)my_jobs + 1) * 4, s)))
-        return err;
-    const bool want_vi = h_version_index != nullptr;
-    if (n)
-    {
-        const uint32_t blocks = (uint32_t)div_up_u64(n, 256);
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_vi_mark, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_first.p, (uint64_t)n, (uint32_t*)g->d_isfirst.p);
-        if ((err = lthip_exclusive_scan_u32(ctx, (const uint32_t*)g->d_isfirst.p, (uint32_t*)g->d_rank.p, n, nullptr, LTHIP_K_OTHER)))
-            return err;
-        hipLaunchKernelGGL(k_vi_compact, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_first.p, (const uint32_t*)g->d_rank.p,
-                           (uint64_t)n, d_all_hashes, d_all_lens, (const uint32_t*)g->d_starts.p, na,
-                           g->has_tags ? (const uint32_t*)g->d_tags.p : (const uint32_t*)nullptr, (uint32_t*)g->d_idx.p,
-                           (uint64_t*)g->d_uh.p, (uint32_t*)g->d_us.p, (uint32_t*)g->d_ut.p);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    // ---- the chunks this rank writes: first-seen, in one of its own jobs (and not in the store), in version order ----
+// "owned": the chunks this rank writes -- first-seen, in one of its own jobs (and not in the store), in version order: the store lookup,
+// the ownership mark, the known-chunk statistics, the scan and the compaction; their number to the host (h_counts[2] + h_counts[3])
+static int ingest_owned(lthip_ingest* g, const IndexCall& c)
+{
+    lthip_ctx* ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    const uint32_t nl = c.nl, blocks = (uint32_t)div_up_u64(nl, 256);
+    uint64_t* d_counts = (uint64_t*)g->d_counts.p;
+    volatile uint64_t* h_counts = (volatile uint64_t*)g->h_counts.p;
+    const uint32_t* d_gfirst = c.all_mine ? nullptr : (const uint32_t*)g->d_gfirst.p;
+    const uint32_t* d_tags = g->has_tags ? (const uint32_t*)g->vi.d_tags.p : nullptr;
+    int err;
     h_counts[2] = h_counts[3] = h_counts[4] = h_counts[5] = 0;
+    if (!nl)
+        return 0;
     const uint8_t* d_known = nullptr; // (no store: k_ing_owned gets a null flag pointer)
-    if (nl && g->store)
+    if (g->store)
     {
-        const uint32_t blocks = (uint32_t)div_up_u64(nl, 256);
-        const uint64_t* d_local_hashes = d_all_hashes; // (a single rank: the local arrays are the global ones)
-        if (!all_mine)
+        const uint64_t* d_local_hashes = c.d_all_hashes; // (a single rank: the local arrays are the global ones)
+        if (!c.all_mine)
         {
             LaunchTimer tm(ctx, LTHIP_K_OTHER);
-            hipLaunchKernelGGL(k_ing_local_hashes, dim3(blocks), dim3(256), 0, s, d_local_part_first, (uint32_t)my_jobs,
-                               (const uint32_t*)g->d_gfirst.p, nl, d_all_hashes, (uint64_t*)g->d_lhash.p);
+            hipLaunchKernelGGL(k_ing_local_hashes, dim3(blocks), dim3(256), 0, s, c.d_local_part_first, (uint32_t)c.my_jobs, d_gfirst, nl, c.d_all_hashes,
+                               (uint64_t*)g->d_lhash.p);
             LTHIP_LAUNCH_CHECK(ctx);
             d_local_hashes = (const uint64_t*)g->d_lhash.p;
         }
@@ -700,58 +570,66 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
             return err;
         d_known = (const uint8_t*)g->d_known.p;
     }
-    if (nl)
+    LaunchTimer tm(ctx, LTHIP_K_OTHER);
+    hipLaunchKernelGGL(k_ing_owned, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_first.p, c.d_local_part_first, (uint32_t)c.my_jobs, d_gfirst, nl,
+                       (uint32_t*)g->d_owned.p, (uint32_t*)g->d_l2g.p, d_known);
+    if (d_known)
     {
-        const uint32_t blocks = (uint32_t)div_up_u64(nl, 256);
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_ing_owned, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_first.p, d_local_part_first, (uint32_t)my_jobs,
-                           all_mine ? (const uint32_t*)nullptr : (const uint32_t*)g->d_gfirst.p, nl, (uint32_t*)g->d_owned.p,
-                           (uint32_t*)g->d_l2g.p, d_known);
-        if (d_known)
-        {
-            LTHIP_CHECK(ctx, hipMemsetAsync(d_counts + 4, 0, 16, s));
-            hipLaunchKernelGGL(k_ing_known_stats, dim3(std::min(blocks, 1024u)), dim3(256), 0, s, (const uint32_t*)g->d_first.p,
-                               (const uint32_t*)g->d_l2g.p, d_known, d_all_lens, nl, (unsigned long long*)(d_counts + 4));
-            LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 4), d_counts + 4, 16, hipMemcpyDeviceToHost, s));
-        }
-        if ((err = lthip_exclusive_scan_u32(ctx, (const uint32_t*)g->d_owned.p, (uint32_t*)g->d_orank.p, nl, nullptr, LTHIP_K_OTHER)))
-            return err;
-        hipLaunchKernelGGL(k_ing_compact, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_owned.p, (const uint32_t*)g->d_orank.p,
-                           (const uint32_t*)g->d_l2g.p, nl, d_all_hashes, d_all_lens, d_local_offsets, (const uint32_t*)g->d_starts.p, na,
-                           g->has_tags ? (const uint32_t*)g->d_tags.p : (const uint32_t*)nullptr, (uint64_t*)g->d_mu_hash.p,
-                           (uint32_t*)g->d_mu_len.p, (uint64_t*)g->d_mu_off.p, (uint32_t*)g->d_mu_tag.p);
-        LTHIP_LAUNCH_CHECK(ctx);
-        // number of owned chunks = orank[nl - 1] + owned[nl - 1]; the scan wrote nl entries, so read both
-        LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 2), (const uint32_t*)g->d_orank.p + (nl - 1), 4, hipMemcpyDeviceToHost, s));
-        LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 3), (const uint32_t*)g->d_owned.p + (nl - 1), 4, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(d_counts + 4, 0, 16, s));
+        hipLaunchKernelGGL(k_ing_known_stats, dim3(std::min(blocks, 1024u)), dim3(256), 0, s, (const uint32_t*)g->d_first.p, (const uint32_t*)g->d_l2g.p,
+                           d_known, c.d_all_lens, nl, (unsigned long long*)(d_counts + 4));
+        LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 4), d_counts + 4, 16, hipMemcpyDeviceToHost, s));
     }
-    LTHIP_CHECK(ctx, hipMemcpyAsync((void*)h_counts, d_counts, 8, hipMemcpyDeviceToHost, s));
+    if ((err = lthip_exclusive_scan_u32(ctx, (const uint32_t*)g->d_owned.p, (uint32_t*)g->d_orank.p, nl, nullptr, LTHIP_K_OTHER)))
+        return err;
+    hipLaunchKernelGGL(k_ing_compact, dim3(blocks), dim3(256), 0, s, (const uint32_t*)g->d_owned.p, (const uint32_t*)g->d_orank.p,
+                       (const uint32_t*)g->d_l2g.p, nl, c.d_all_hashes, c.d_all_lens, c.d_local_offsets, (const uint32_t*)g->vi.d_starts.p, c.na, d_tags,
+                       (uint64_t*)g->d_mu_hash.p, (uint32_t*)g->d_mu_len.p, (uint64_t*)g->d_mu_off.p, (uint32_t*)g->d_mu_tag.p);
+    LTHIP_LAUNCH_CHECK(ctx);
+    // number of owned chunks = orank[nl - 1] + owned[nl - 1]; the scan wrote nl entries, so read both
+    LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 2), (const uint32_t*)g->d_orank.p + (nl - 1), 4, hipMemcpyDeviceToHost, s));
+    LTHIP_CHECK(ctx, hipMemcpyAsync((void*)(h_counts + 3), (const uint32_t*)g->d_owned.p + (nl - 1), 4, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// "queued" / "counts": the one read-back of the call -- [0] distinct hashes of all ranks, [2] + [3] chunks this rank writes (u32 in the
+// low halves), [4] / [5] chunks and bytes the store held -- and the wait for it
+static int ingest_counts(lthip_ingest* g, const IndexCall& c, IngTrace& tr)
+{
+    lthip_ctx* ctx = g->ctx;
+    volatile uint64_t* h_counts = (volatile uint64_t*)g->h_counts.p;
+    LTHIP_CHECK(ctx, hipMemcpyAsync((void*)h_counts, g->d_counts.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     tr.mark("queued");
-    LTHIP_CHECK(ctx, hipEventRecord(g->ev_counts, s));
+    LTHIP_CHECK(ctx, hipEventRecord(g->ev_counts, ctx->stream));
     LTHIP_CHECK(ctx, hipEventSynchronize(g->ev_counts));
-    tr.mark("counts");
-    const uint64_t unique = h_counts[0];
-    const uint32_t nm = nl ? (uint32_t)(h_counts[2] & 0xFFFFFFFFu) + (uint32_t)(h_counts[3] & 0xFFFFFFFFu) : 0u;
-    g->unique_all = unique;
-    g->n_mine = nm;
+    g->unique_all = h_counts[0];
+    g->n_mine = c.nl ? (uint32_t)(h_counts[2] & 0xFFFFFFFFu) + (uint32_t)(h_counts[3] & 0xFFFFFFFFu) : 0u;
     g->known_chunks = h_counts[4];
     g->known_bytes = h_counts[5];
+    return 0;
+}
 
-    // ---- the host needs the owned chunks' lengths, offsets (and tags) for the packing and the codec calls.  Of the offsets the packing
-    // loop reads only whether a chunk continues the range of the one before: a byte per chunk from k_ing_breaks.  The copies are 44 MB on
-    // the 64 GiB tree (0.8 ms of the link), and the first codec batch needs the head of the lists only: the chunks of about that batch
-    // are copied on the session's stream (ev_lens), the rest -- and the chunk hashes, which lthip_ingest_finish reads -- by the side
-    // stream next to the codec kernels (ev_offs, ev_hashes)
+// "lists": the host needs the owned chunks' lengths, offsets (and tags) for the packing and the codec calls.  Of the offsets the packing
+// loop reads only whether a chunk continues the range of the one before: a byte per chunk from k_ing_breaks.  The copies are 44 MB on
+// the 64 GiB tree (0.8 ms of the link), and the first codec batch needs the head of the lists only: the chunks of about that batch
+// are copied on the session's stream (ev_lens), the rest -- and the chunk hashes, which lthip_ingest_finish reads -- by the side
+// stream next to the codec kernels (ev_offs, ev_hashes)
+static int ingest_lists(lthip_ingest* g, const IndexCall& c)
+{
+    lthip_ctx* ctx = g->ctx;
+    hipStream_t s = ctx->stream;
+    const uint32_t nm = (uint32_t)g->n_mine;
+    int err;
     uint32_t head = nm;
     {
         LTHIP_ABLATION_ENV(env_slices, "LTHIP_INGEST_PACK_SLICES");
         uint64_t tree_bytes = 0;
-        for (uint32_t a = 0; a < na; ++a)
-            tree_bytes += t->asset_sizes[a];
-        if (env_slices.get() != 0 && n && tree_bytes > 2 * g->cfg.batch_bytes)
+        for (uint32_t a = 0; a < c.na; ++a)
+            tree_bytes += c.t->asset_sizes[a];
+        if (env_slices.get() != 0 && c.n && tree_bytes > 2 * g->cfg.batch_bytes)
         {
             // chunks of one batch at the tree's mean chunk size, a quarter more, and the chunks of one more block
-            const double per_byte = (double)n / (double)tree_bytes;
+            const double per_byte = (double)c.n / (double)tree_bytes;
             const double want = 1.25 * per_byte * (double)g->cfg.batch_bytes + 2.0 * g->cfg.max_chunks_per_block + 4096.0;
             if (want < (double)nm)
                 head = (uint32_t)want;
@@ -789,68 +667,133 @@ extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, c
     if (nm)
         LTHIP_CHECK(ctx, hipMemcpyAsync(g->h_mu_hash.p, g->d_mu_hash.p, (size_t)nm * 8, hipMemcpyDeviceToHost, s2)); // StoreIndex, read in finish
     LTHIP_CHECK(ctx, hipEventRecord(g->ev_hashes, s2));
+    return 0;
+}
 
-    tr.mark("lists");
-    // ---- greedy packing of the owned chunks (Longtail_CreateStoreIndex :6801-6860): here the blocks of the first codec batch ----
-    LTHIP_CHECK(ctx, hipEventSynchronize(g->ev_lens));
+// "pack": greedy packing of the owned chunks (Longtail_CreateStoreIndex :6801-6860), here the blocks of the first codec batch -- once
+// the head of the lists is on the host
+static int ingest_pack_first(lthip_ingest* g)
+{
+    LTHIP_CHECK(g->ctx, hipEventSynchronize(g->ev_lens));
     g->b_first.clear();
+    g->b_first.push_back(0);
     g->b_size.clear();
     g->b_is_range.clear();
     g->b_tag.clear();
-    g->b_first.push_back(0);
     g->pack_next = 0;
     g->pack_raw = 0;
     g->blocks_done = false;
     g->written = false;
     ingest_pack(g, g->cfg.batch_bytes + 2ull * g->cfg.max_block_size);
-    tr.mark("pack");
+    return 0;
+}
 
-    // ---- the VersionIndex sections: 1.2-2.4 ms of host work on the 64 GiB tree (the tables of 65 536 assets, the tag column
-    // of 2.1 M chunks) plus copies and two small hash launches, none of which the rest of the session waits for: a helper thread with a
-    // context of its own does them (LTHIP_INGEST_VI_THREAD=0: the calling thread, on the session's context), started by ingest_vi_start once
-    // the first codec batch is queued -- a thread's start is 0.1 ms -- and collected by lthip_ingest_finish.
+// "helper": the VersionIndex sections are 1.2-2.4 ms of host work on the 64 GiB tree (the tables of 65 536 assets, the tag column of
+// 2.1 M chunks) plus copies and two small hash launches, none of which the rest of the session waits for: a helper thread with a
+// context of its own does them (LTHIP_INGEST_VI_THREAD=0: the calling thread, on the session's context), started by ingest_vi_start once
+// the first codec batch is queued -- a thread's start is 0.1 ms -- and collected by lthip_ingest_finish.  Here: what it will read, the
+// caller's tree as a deep copy.
+static int ingest_vi_prepare(lthip_ingest* g, const IndexCall& c, ViTree view, JobTables& jt, void* h_version_index, size_t capacity)
+{
+    g->vi_size = lthip_version_index_size(c.na, g->unique_all, c.n, view.path_data_size);
+    if (capacity < g->vi_size)
+        return lthip_fail(g->ctx, ENOMEM, "lthip_ingest_index", "version index buffer too small");
+    g->vi_asset_sizes.assign(view.asset_sizes, view.asset_sizes + c.na);
+    g->vi_path_offsets.assign(view.path_offsets, view.path_offsets + c.na);
+    g->vi_permissions.assign(view.permissions, view.permissions + c.na);
+    g->vi_path_data.assign(view.path_data, view.path_data + view.path_data_size);
+    g->vi_jobs.starts.swap(jt.starts);
+    g->vi_jobs.counts.swap(jt.counts);
+    view.asset_sizes = g->vi_asset_sizes.data();
+    view.path_offsets = g->vi_path_offsets.data();
+    view.permissions = g->vi_permissions.data();
+    view.path_data = g->vi_path_data.data();
+    view.starts = g->vi_jobs.starts.data();
+    view.counts = g->vi_jobs.counts.data();
+    g->vi_tree = view;
+    g->vi_hashes = c.d_all_hashes;
+    g->vi_out = h_version_index;
+    g->vi_pending = true; // (ingest_vi_start: behind the first codec batch's launches, or in lthip_ingest_finish)
+    return 0;
+}
+
+// The order of the steps is the performance design.  It holds to this:
+//   * the job tables are built after the first-seen pass is queued and before anything waits: the host works while the device does;
+//   * the host waits exactly three times: on entry for an index that was never finished (ingest_vi_join, ev_hashes), for the counts
+//     (ev_counts), and for the head of the lists before the first packing slice (ev_lens);
+//   * the VersionIndex helper is only prepared here: lthip_ingest_write starts it behind its first codec batch, or lthip_ingest_finish;
+//   * what a refused call leaves untouched stays untouched: the argument and tag checks run before any state is changed, the
+//     VersionIndex builder's refusals before any of its work is queued (they need the job tables);
+//   * LTHIP_INGEST_TRACE prints the host time of each step under the name its function carries.
+extern "C" int lthip_ingest_index(lthip_ingest* g, const lthip_ingest_tree* t, const uint64_t* d_all_hashes, const uint32_t* d_all_lens,
+                                  uint64_t all_chunks, const uint64_t* d_local_offsets, const uint32_t* d_local_part_first,
+                                  uint64_t local_chunks, void* h_version_index, size_t version_index_capacity)
+{
+    if (!g || !t || (all_chunks && (!d_all_hashes || !d_all_lens)) || (local_chunks && (!d_local_offsets || !d_local_part_first)) ||
+        (t->job_count && (!t->job_asset || !t->job_first)) ||
+        (t->asset_count && (!t->asset_sizes || !t->path_start_offsets || !t->permissions || !t->path_data)))
+        return EINVAL;
+    lthip_ctx* ctx = g->ctx;
+    if (all_chunks > 0x7FFFFFF0ull || local_chunks > all_chunks)
+        return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "chunk counts out of range");
+    if (t->job_count && t->job_first[t->job_count] != all_chunks)
+        return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "job_first[job_count] must be the number of chunks");
+    if (t->asset_tags) // (before any work is queued: the session stays as it is)
+        for (uint32_t a = 0; a < t->asset_count; ++a)
+            if (const int refused = tag_refusal(g->cfg.codec, t->asset_tags[a]))
+                return lthip_fail(ctx, refused, "lthip_ingest_index", tag_refusal_text(refused));
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    g->vi_pending = false;
+    (void)ingest_vi_join(g); // (an index that was never finished: its helper reads what this call is about to replace ...
+    (void)hipEventSynchronize(g->ev_hashes); // ... and so does the side stream)
+    IngTrace tr("lthip_ingest_index");
+    const bool all_mine = t->my_jobs == nullptr;
+    const IndexCall c = {t, d_all_hashes, d_all_lens, d_local_offsets, d_local_part_first, (uint32_t)all_chunks, (uint32_t)local_chunks,
+                         t->asset_count, all_mine, all_mine ? t->job_count : t->my_job_count};
+    g->indexed = g->written = false;
+    g->n_all = c.n;
+    g->n_local = c.nl;
+    g->has_tags = t->asset_tags != nullptr;
     g->vi_size = 0;
-    if (want_vi)
-    {
-        const size_t size = lthip_version_index_size(na, unique, n, t->path_data_size);
-        g->vi_size = size;
-        if (version_index_capacity < size)
-            return lthip_fail(ctx, ENOMEM, "lthip_ingest_index", "version index buffer too small");
-        for (uint32_t a = 0; a < na; ++a)
-        {
-            if ((uint64_t)counts[a] * 8u > 0xFFFFFFFFull)
-                return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "asset with more than 2^29 chunks");
-            if (t->path_start_offsets[a] >= t->path_data_size)
-                return lthip_fail(ctx, EINVAL, "lthip_ingest_index", "path offset outside the path data");
-        }
-        g->vi_tree = *t;
-        g->vi_asset_sizes.assign(t->asset_sizes, t->asset_sizes + na);
-        g->vi_path_offsets.assign(t->path_start_offsets, t->path_start_offsets + na);
-        g->vi_permissions.assign(t->permissions, t->permissions + na);
-        g->vi_path_data.assign(t->path_data, t->path_data + t->path_data_size);
-        g->vi_tree.asset_sizes = g->vi_asset_sizes.data();
-        g->vi_tree.path_start_offsets = g->vi_path_offsets.data();
-        g->vi_tree.permissions = g->vi_permissions.data();
-        g->vi_tree.path_data = g->vi_path_data.data();
-        g->vi_tree.asset_tags = nullptr; // (not read after the call)
-        g->vi_tree.job_asset = nullptr;
-        g->vi_tree.job_first = nullptr;
-        g->vi_tree.my_jobs = nullptr;
-        g->vi_starts.swap(starts);
-        g->vi_counts.swap(counts);
-        g->vi_hashes = d_all_hashes;
-        g->vi_out = h_version_index;
-        g->vi_pending = true; // (ingest_vi_start: behind the first codec batch's launches, or in lthip_ingest_finish)
-    }
+    memset(&g->res, 0, sizeof g->res);
+    tr.mark("checks");
 
+    int err;
+    JobTables jt;
+    if ((err = ingest_reserve(g, c)))
+        return err;
+    tr.mark("reserve");
+    if ((err = ingest_first_seen(g, c)))
+        return err;
+    tr.mark("first-seen");
+    if ((err = ingest_job_tables(ctx, c, jt)))
+        return err;
+    const ViTree view = {c.na, t->asset_sizes, t->path_start_offsets, t->permissions, t->path_data, t->path_data_size, jt.counts.data(), jt.starts.data(),
+                         g->cfg.hash_identifier, g->cfg.target_chunk_size};
+    if (h_version_index && (err = lthip_vi_refusals(ctx, view, "lthip_ingest_index")))
+        return err;
+    tr.mark("tables");
+    // the unique lists (the builder's step 1) and the owned chunks, on the session's stream behind the first-seen pass
+    if ((!all_mine && (err = lthip_stage_upload(ctx, g->d_gfirst.p, jt.gfirst.data(), jt.gfirst.size() * 4, ctx->stream))) ||
+        (err = vi_unique_lists(ctx, g->vi, (const uint32_t*)g->d_first.p, c.n, d_all_hashes, d_all_lens, jt.starts.data(), t->asset_tags, c.na)) ||
+        (err = ingest_owned(g, c)) || (err = ingest_counts(g, c, tr)))
+        return err;
+    tr.mark("counts");
+    if ((err = ingest_lists(g, c)))
+        return err;
+    tr.mark("lists");
+    if ((err = ingest_pack_first(g)))
+        return err;
+    tr.mark("pack");
+    if (h_version_index && (err = ingest_vi_prepare(g, c, view, jt, h_version_index, version_index_capacity)))
+        return err;
     tr.mark("helper");
-    g->res.chunks_all = n;
-    g->res.unique_all = unique;
-    g->res.chunks_local = nl;
-    g->res.unique_local = nm;
-    g->res.blocks = 0; // (ingest_blocks_done)
-    g->res.raw_bytes = 0;
-    g->res.version_index_size = g->vi_size;
+
+    g->res.chunks_all = c.n;
+    g->res.unique_all = g->unique_all;
+    g->res.chunks_local = c.nl;
+    g->res.unique_local = g->n_mine;
+    g->res.version_index_size = g->vi_size; // (blocks and raw_bytes: ingest_blocks_done)
     g->indexed = true;
     return 0;
 }

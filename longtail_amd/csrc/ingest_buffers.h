@@ -6,15 +6,49 @@
 #include "lthip_internal.h"
 #include "store_layout.h"
 
-struct DBuf
+#include <utility>
+
+// a device / pinned buffer that frees itself, and an event that destroys itself: members of the sessions and of the bulk calls' local
+// workspaces, so that no destroy function lists them.  Movable, not copyable.  (The owner sets the device before they go.)
+template <hipError_t (*Release)(void*)> struct OwnedBuf
 {
     void* p = nullptr;
     size_t cap = 0;
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    OwnedBuf& operator=(OwnedBuf&& o) noexcept // (what this one held leaves with `o`)
+    {
+        std::swap(p, o.p), std::swap(cap, o.cap);
+        return *this;
+    }
+    ~OwnedBuf() { (void)release(); }
+    hipError_t release()
+    {
+        const hipError_t e = p ? Release(p) : hipSuccess;
+        p = nullptr, cap = 0;
+        return e;
+    }
 };
-struct HBuf
+typedef OwnedBuf<hipFree> DBuf;
+typedef OwnedBuf<hipHostFree> HBuf;
+
+struct Event
 {
-    void* p = nullptr;
-    size_t cap = 0;
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept
+    {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event()
+    {
+        if (e)
+            (void)hipEventDestroy(e);
+    }
+    hipError_t create() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    operator hipEvent_t() const { return e; }
 };
 
 // the codec of one block and, for zstd, the parse: one key per codec call
@@ -139,7 +173,7 @@ namespace
 {
 
 // room for `bytes` in a buffer: kept when it has them, else replaced by one an eighth larger (what it held is dropped)
-template <class Buf, class Alloc> int reserve_buf(lthip_ctx* ctx, Buf& b, size_t bytes, hipError_t (*release)(void*), Alloc alloc)
+template <class Buf, class Alloc> int reserve_buf(lthip_ctx* ctx, Buf& b, size_t bytes, Alloc alloc)
 {
     if (bytes == 0)
         bytes = 256;
@@ -148,19 +182,17 @@ template <class Buf, class Alloc> int reserve_buf(lthip_ctx* ctx, Buf& b, size_t
     if (b.p)
     {
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        LTHIP_CHECK(ctx, release(b.p));
-        b.p = nullptr;
-        b.cap = 0;
+        LTHIP_CHECK(ctx, b.release());
     }
     const size_t cap = bytes + bytes / 8 + 4096;
     LTHIP_CHECK(ctx, alloc(&b.p, cap));
     b.cap = cap;
     return 0;
 }
-int reserve_dev(lthip_ctx* ctx, DBuf& b, size_t bytes) { return reserve_buf(ctx, b, bytes, hipFree, lthip_hip_malloc); }
+int reserve_dev(lthip_ctx* ctx, DBuf& b, size_t bytes) { return reserve_buf(ctx, b, bytes, lthip_hip_malloc); }
 int reserve_pinned(lthip_ctx* ctx, HBuf& b, size_t bytes)
 {
-    return reserve_buf(ctx, b, bytes, hipHostFree, [](void** p, size_t n) { return lthip_hip_host_malloc(p, n, hipHostMallocDefault); });
+    return reserve_buf(ctx, b, bytes, [](void** p, size_t n) { return lthip_hip_host_malloc(p, n, hipHostMallocDefault); });
 }
 
 // ---- which codec writes a block (enum lthip_codec of the session x the block's tag) ----

@@ -26,43 +26,43 @@
 
 struct lthip_ingest_stream
 {
-    lthip_ctx* ctx;
-    lthip_ingest_config cfg;
+    lthip_ctx* ctx = nullptr;
+    lthip_ingest_config cfg = {};
     // ---- the tree (deep copy) ----
-    uint32_t na;
+    uint32_t na = 0;
     std::vector<uint64_t> asset_sizes;
     std::vector<uint32_t> path_offsets;
     std::vector<uint16_t> permissions;
     std::vector<char> path_data;
     std::vector<uint32_t> tags; // per asset: the caller's, or cfg.compression_type
-    uint64_t njobs;
+    uint64_t njobs = 0;
     std::vector<uint32_t> job_asset;
     std::vector<uint64_t> job_size;
     std::vector<uint32_t> asset_chunks; // chunks of every asset so far
     // ---- state ----
-    lthip_seen* seen;
-    const lthip_store* store;                        // what the target already holds (may be null): its chunks are not written
-    uint64_t unique_all, known_chunks, known_bytes;  // the version's distinct chunks so far; those of them the store held
-    uint64_t next_job;
-    bool started; // a slice call has begun work: the store can no longer be attached or detached
-    bool closed;  // finish has closed the open block: no more slices
-    int sticky;  // a failure after work had started: what every later call returns
+    lthip_seen* seen = nullptr;
+    const lthip_store* store = nullptr;                          // what the target already holds (may be null): its chunks are not written
+    uint64_t unique_all = 0, known_chunks = 0, known_bytes = 0; // the version's distinct chunks so far; those of them the store held
+    uint64_t next_job = 0;
+    bool started = false; // a slice call has begun work: the store can no longer be attached or detached
+    bool closed = false;  // finish has closed the open block: no more slices
+    int sticky = 0;       // a failure after work had started: what every later call returns
     // ---- every chunk of the tree so far: hash and length (pinned: the slices' lists are copied straight into them) ----
     HBuf h_all_hash, h_all_len;
-    uint64_t n_all;
+    uint64_t n_all = 0;
     // ---- the unique list and the blocks it is packed into ----
     std::vector<uint64_t> u_hash;
     std::vector<uint32_t> u_len, u_tag;
-    std::vector<uint64_t> b_first; // nb + 1 indices into the unique list
+    std::vector<uint64_t> b_first{0}; // nb + 1 indices into the unique list
     std::vector<uint64_t> b_size;
     std::vector<uint32_t> b_tag;
     std::vector<uint64_t> b_hash; // collected from the batch records (blocks [0, b_hash.size()))
     std::vector<uint32_t> b_comp;
-    uint64_t gathered_blocks, gathered_bytes;
+    uint64_t gathered_blocks = 0, gathered_bytes = 0;
     // ---- the open block: chunks [b_first.back(), u_len.size()), their bytes back to back in d_carry ----
     DBuf d_carry;
     std::vector<uint64_t> carry_off;
-    uint64_t carry_bytes;
+    uint64_t carry_bytes = 0;
     // ---- per call ----
     HBuf h_first, h_off, h_pf, h_known;
     DBuf d_known;
@@ -71,13 +71,13 @@ struct lthip_ingest_stream
     BlockImageBufs wbufs; // the block writer's tables (block_images.hip)
     DBuf d_vh, d_vl; // finish: the kept lists on the device
     std::vector<uint64_t> u_src; // byte offset in the slice's data of the chunks this slice added to the unique list
-    hipEvent_t ev_lists, ev_call;
+    Event ev_lists, ev_call;
     // what a call's launches produce for the host: [nb u64 block hashes][nb u32 compressed sizes], behind an event
     struct Batch
     {
         HBuf h;
-        uint64_t nb;
-        hipEvent_t ev;
+        uint64_t nb = 0;
+        Event ev;
     };
     std::vector<Batch> pending, spare;
     // ---- the blocks of the call being written (kept for its vectors), and the images of the last call ----
@@ -127,7 +127,7 @@ int stream_collect(Stream* s, bool wait)
         const uint32_t* comp = (const uint32_t*)((const uint8_t*)b.h.p + b.nb * 8);
         s->b_hash.insert(s->b_hash.end(), hashes, hashes + b.nb);
         s->b_comp.insert(s->b_comp.end(), comp, comp + b.nb);
-        s->spare.push_back(b);
+        s->spare.push_back(std::move(b));
     }
     s->pending.erase(s->pending.begin(), s->pending.begin() + done);
     return 0;
@@ -248,25 +248,18 @@ int stream_emit(Stream* s, size_t b0, size_t b1, const void* d_data, uint64_t fr
         (err = lthip_block_headers(ctx, s->wbufs, bt, dev, s->cfg, true)))
         return err;
     // ---- block hashes and compressed sizes on their way to the host ----
-    Stream::Batch rec;
-    if (!s->spare.empty())
+    if (s->spare.empty())
     {
-        rec = s->spare.back();
-        s->spare.pop_back();
+        Stream::Batch fresh;
+        LTHIP_CHECK(ctx, fresh.ev.create());
+        s->spare.push_back(std::move(fresh));
     }
-    else
-    {
-        rec.h = HBuf();
-        rec.ev = nullptr;
-        LTHIP_CHECK(ctx, hipEventCreateWithFlags(&rec.ev, hipEventDisableTiming));
-    }
-    rec.nb = cnt;
-    if ((err = reserve_pinned(ctx, rec.h, cnt * 12)))
-    {
-        s->spare.push_back(rec); // (destroy frees it)
+    if ((err = reserve_pinned(ctx, s->spare.back().h, cnt * 12)))
         return err;
-    }
-    s->pending.push_back(rec);
+    s->pending.push_back(std::move(s->spare.back()));
+    s->spare.pop_back();
+    Stream::Batch& rec = s->pending.back();
+    rec.nb = cnt;
     LTHIP_CHECK(ctx, hipMemcpyAsync(rec.h.p, s->d_bhash.p, cnt * 8, hipMemcpyDeviceToHost, st));
     LTHIP_CHECK(ctx, hipMemcpyAsync((uint8_t*)rec.h.p + cnt * 8, s->d_comp.p, cnt * 4, hipMemcpyDeviceToHost, st));
     LTHIP_CHECK(ctx, hipEventRecord(rec.ev, st));
@@ -284,24 +277,15 @@ int stream_grow_lists(Stream* s, uint64_t chunks)
     const uint64_t cap = std::max<uint64_t>(want, 2 * s->n_all);
     HBuf nh, nl;
     int err;
-    if ((err = reserve_pinned(ctx, nh, cap * 8)))
+    if ((err = reserve_pinned(ctx, nh, cap * 8)) || (err = reserve_pinned(ctx, nl, cap * 4)))
         return err;
-    if ((err = reserve_pinned(ctx, nl, cap * 4)))
-    {
-        (void)hipHostFree(nh.p);
-        return err;
-    }
     if (s->n_all)
     {
         memcpy(nh.p, s->h_all_hash.p, s->n_all * 8);
         memcpy(nl.p, s->h_all_len.p, s->n_all * 4);
     }
-    if (s->h_all_hash.p)
-        (void)hipHostFree(s->h_all_hash.p);
-    if (s->h_all_len.p)
-        (void)hipHostFree(s->h_all_len.p);
-    s->h_all_hash = nh;
-    s->h_all_len = nl;
+    s->h_all_hash = std::move(nh); // (the old lists leave with nh / nl)
+    s->h_all_len = std::move(nl);
     return 0;
 }
 
@@ -439,6 +423,7 @@ extern "C" size_t lthip_ingest_stream_arena_bound(const lthip_ingest_config* cfg
     return (size_t)(R + R / 255 + 64) + (size_t)N * (lthip_stored_block_header_size(1) + 64u + 63u);
 }
 
+// Every buffer and event of the session frees itself (ingest_buffers.h): nothing goes before the stream that may touch it is idle.
 extern "C" void lthip_ingest_stream_destroy(lthip_ingest_stream* s)
 {
     if (!s)
@@ -446,28 +431,6 @@ extern "C" void lthip_ingest_stream_destroy(lthip_ingest_stream* s)
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     lthip_seen_destroy(s->seen);
-    DBuf* dev[] = {&s->d_carry, &s->d_first, &s->d_gather, &s->d_uh, &s->d_ul, &s->d_boff, &s->d_blen, &s->d_bhash, &s->d_comp, &s->d_vh, &s->d_vl,
-                   &s->d_known, &s->d_usrc, &s->wbufs.d_tmpsz, &s->wbufs.d_gsrc, &s->wbufs.d_glen, &s->wbufs.d_gdst, &s->wbufs.d_bfirst, &s->wbufs.d_braw,
-                   &s->wbufs.d_bimg, &s->wbufs.d_btag};
-    for (DBuf* b : dev)
-        if (b->p)
-            (void)hipFree(b->p);
-    HBuf* pin[] = {&s->h_all_hash, &s->h_all_len, &s->h_first, &s->h_off, &s->h_pf, &s->h_known};
-    for (HBuf* b : pin)
-        if (b->p)
-            (void)hipHostFree(b->p);
-    for (std::vector<Stream::Batch>* list : {&s->pending, &s->spare})
-        for (Stream::Batch& b : *list)
-        {
-            if (b.h.p)
-                (void)hipHostFree(b.h.p);
-            if (b.ev)
-                (void)hipEventDestroy(b.ev);
-        }
-    if (s->ev_lists)
-        (void)hipEventDestroy(s->ev_lists);
-    if (s->ev_call)
-        (void)hipEventDestroy(s->ev_call);
     delete s;
 }
 
@@ -531,21 +494,10 @@ extern "C" int lthip_ingest_stream_create(lthip_ctx* ctx, const lthip_ingest_con
     s->job_asset.assign(t->job_asset, t->job_asset + t->job_count);
     s->job_size.swap(job_size);
     s->asset_chunks.assign(na, 0);
-    s->seen = nullptr;
-    s->store = nullptr;
-    s->unique_all = s->known_chunks = s->known_bytes = 0;
-    s->next_job = 0;
-    s->started = s->closed = false;
-    s->sticky = 0;
-    s->n_all = 0;
-    s->b_first.push_back(0);
-    s->gathered_blocks = s->gathered_bytes = 0;
-    s->carry_bytes = 0;
-    s->ev_lists = s->ev_call = nullptr;
     // the lists and the table for the chunks the tree is expected to come to (chunks average the target size or more); both grow
     const uint64_t expect = std::min<uint64_t>(cfg->target_chunk_size ? tree_bytes / cfg->target_chunk_size + t->job_count : t->job_count, 1ull << 28);
     int err = 0;
-    if (hipEventCreateWithFlags(&s->ev_lists, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ev_call, hipEventDisableTiming) != hipSuccess)
+    if (s->ev_lists.create() != hipSuccess || s->ev_call.create() != hipSuccess)
         err = lthip_fail(ctx, EIO, "lthip_ingest_stream_create", "hipEventCreate");
     if (!err)
         err = lthip_seen_create(ctx, expect, &s->seen);

@@ -10,30 +10,9 @@
 // layout, byte for byte what Longtail_WriteVersionIndexToBuffer (:3415) would write.
 #include "lthip_internal.h"
 #include "index_kernels.h"
-#include "store_layout.h"
 
 #include <algorithm>
 #include <unordered_set>
-
-namespace
-{
-
-struct DevBuf
-{
-    void* p = nullptr;
-    ~DevBuf()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-    int alloc(lthip_ctx* ctx, size_t bytes)
-    {
-        LTHIP_CHECK(ctx, lthip_hip_malloc(&p, bytes ? bytes : 16));
-        return 0;
-    }
-};
-
-} // namespace
 
 extern "C" size_t lthip_version_index_size(uint32_t asset_count, uint64_t unique_chunk_count, uint64_t asset_chunk_index_count,
                                            uint32_t path_data_size)
@@ -41,6 +20,112 @@ extern "C" size_t lthip_version_index_size(uint32_t asset_count, uint64_t unique
     // Longtail_GetVersionIndexDataSize, src/longtail.c:2551-2584
     return 6 * sizeof(uint32_t) + (size_t)asset_count * (8 + 8 + 8 + 4 + 4) + (size_t)asset_chunk_index_count * 4 +
            (size_t)unique_chunk_count * (8 + 4 + 4) + (size_t)asset_count * (4 + 2) + path_data_size;
+}
+
+int lthip_vi_reserve(lthip_ctx* ctx, ViWorkspace& w, uint64_t n, uint32_t na, uint32_t path_data_size)
+{
+    int err = 0;
+    auto room = [&](DBuf& b, size_t bytes) { err = err ? err : reserve_dev(ctx, b, bytes); };
+    for (DBuf* b : {&w.d_isfirst, &w.d_idx, &w.d_us, &w.d_ut}) // per chunk
+        room(*b, (size_t)n * 4);
+    room(w.d_rank, ((size_t)n + 1) * 4);
+    room(w.d_uh, (size_t)n * 8);
+    room(w.d_starts, ((size_t)na + 1) * 4); // per asset
+    for (DBuf* b : {&w.d_tags, &w.d_alen})
+        room(*b, (size_t)na * 4);
+    for (DBuf* b : {&w.d_aoff, &w.d_ph, &w.d_ch})
+        room(*b, (size_t)na * 8);
+    room(w.d_paths, (size_t)path_data_size + 16);
+    return err;
+}
+
+int lthip_vi_refusals(lthip_ctx* ctx, const ViTree& t, const char* who)
+{
+    for (uint32_t a = 0; a < t.na; ++a)
+    {
+        if ((uint64_t)t.counts[a] * 8u > 0xFFFFFFFFull) // (the reference's hash_size is a uint32_t as well, :2522)
+            return lthip_fail(ctx, EINVAL, who, "asset with more than 2^29 chunks");
+        if (t.path_offsets[a] >= t.path_data_size)
+            return lthip_fail(ctx, EINVAL, who, "path offset outside the path data");
+    }
+    return 0;
+}
+
+// content hash of every asset = hash of its chunk-hash array (:2518-2537); path hashes (:1269-1300).  Both through d_aoff / d_alen:
+// the uploads are ordered on the stream behind the launch that read the tables before, so reusing them is safe
+int lthip_vi_hashes(lthip_ctx* ctx, ViWorkspace& w, const ViTree& t, const uint64_t* d_chunk_hashes, uint32_t n)
+{
+    const uint32_t na = t.na;
+    if (!na)
+        return 0;
+    hipStream_t s = ctx->stream;
+    std::vector<uint64_t> h_off(na);
+    std::vector<uint32_t> h_len(na);
+    // (range a of the table: `data` + h_off[a], h_len[a] bytes)
+    auto hash_table = [&](const void* data, uint64_t* d_out) -> int {
+        int err;
+        if ((err = lthip_stage_upload(ctx, w.d_aoff.p, h_off.data(), (size_t)na * 8, s)) || (err = lthip_stage_upload(ctx, w.d_alen.p, h_len.data(), (size_t)na * 4, s)))
+            return err;
+        return lthip_hash_ranges_by_id(ctx, t.hash_identifier, data, na, (const uint64_t*)w.d_aoff.p, (const uint32_t*)w.d_alen.p,
+                                       *std::max_element(h_len.begin(), h_len.end()), 0u, d_out);
+    };
+    for (uint32_t a = 0; a < na; ++a)
+    {
+        h_off[a] = (uint64_t)t.starts[a] * 8u;
+        h_len[a] = t.counts[a] * 8u;
+    }
+    int err; // (no chunks: every range is empty, and any device pointer serves as its base)
+    if ((err = hash_table(n ? (const void*)d_chunk_hashes : w.d_paths.p, (uint64_t*)w.d_ch.p)))
+        return err;
+    for (uint32_t a = 0; a < na; ++a)
+    {
+        h_off[a] = t.path_offsets[a];
+        h_len[a] = (uint32_t)strnlen(t.path_data + t.path_offsets[a], t.path_data_size - t.path_offsets[a]);
+    }
+    if ((err = lthip_stage_upload(ctx, w.d_paths.p, t.path_data, t.path_data_size, s)))
+        return err;
+    return hash_table(w.d_paths.p, (uint64_t*)w.d_ph.p);
+}
+
+// serialized layout (Longtail_BuildVersionIndex :2757-2806 over InitVersionIndexFromData's section order)
+int lthip_vi_sections(lthip_ctx* ctx, const ViWorkspace& w, const ViTree& t, uint32_t n, uint64_t unique, const uint32_t* one_tag, void* out)
+{
+    const size_t na = t.na;
+    uint8_t* p = (uint8_t*)out;
+    auto host = [&](const void* src, size_t bytes) {
+        if (bytes)
+            memcpy(p, src, bytes);
+        p += bytes;
+    };
+    const uint32_t head[6] = {2u /* LONGTAIL_VERSION_INDEX_VERSION_0_0_2, :16-22 */, t.hash_identifier, t.target_chunk_size, t.na, (uint32_t)unique, n};
+    host(head, sizeof head);
+#define LT_D2H(SRC, BYTES)                                                                                 \
+    do                                                                                                     \
+    {                                                                                                      \
+        if (BYTES)                                                                                         \
+            LTHIP_CHECK(ctx, hipMemcpyAsync(p, (SRC).p, (BYTES), hipMemcpyDeviceToHost, ctx->stream));     \
+        p += (BYTES);                                                                                      \
+    } while (0)
+    LT_D2H(w.d_ph, na * 8);              // m_PathHashes
+    LT_D2H(w.d_ch, na * 8);              // m_ContentHashes
+    host(t.asset_sizes, na * 8);         // m_AssetSizes
+    host(t.counts, na * 4);              // m_AssetChunkCounts
+    host(t.starts, na * 4);              // m_AssetChunkIndexStarts
+    LT_D2H(w.d_idx, (size_t)n * 4);      // m_AssetChunkIndexes
+    LT_D2H(w.d_uh, (size_t)unique * 8);  // m_ChunkHashes
+    LT_D2H(w.d_us, (size_t)unique * 4);  // m_ChunkSizes
+    if (!one_tag)
+        LT_D2H(w.d_ut, (size_t)unique * 4); // m_ChunkTags
+    else // one tag for the whole tree (what UpSync passes, cmd/main.c:1038-1046)
+    {
+        std::fill_n((uint32_t*)p, unique, *one_tag);
+        p += (size_t)unique * 4;
+    }
+#undef LT_D2H
+    host(t.path_offsets, na * 4);        // m_NameOffsets
+    host(t.permissions, na * 2);         // m_Permissions
+    host(t.path_data, t.path_data_size); // m_NameData
+    return 0;
 }
 
 extern "C" int lthip_build_version_index(lthip_ctx* ctx, uint32_t asset_count, const uint64_t* asset_sizes,
@@ -62,115 +147,32 @@ extern "C" int lthip_build_version_index(lthip_ctx* ctx, uint32_t asset_count, c
         starts[a + 1] = starts[a] + asset_chunk_counts[a];
     if (starts[asset_count] != n)
         return lthip_fail(ctx, EINVAL, "version index", "asset chunk counts do not add up to the chunk total");
-
+    const ViTree t = {asset_count, asset_sizes, path_start_offsets, permissions, path_data, path_data_size, asset_chunk_counts, starts.data(),
+                      hash_identifier, target_chunk_size};
     int err;
-    DevBuf d_first, d_isfirst, d_rank, d_idx, d_uh, d_us, d_ut, d_starts, d_tags, d_uniq, d_paths, d_off, d_len, d_ph, d_ch;
-    if ((err = d_first.alloc(ctx, (size_t)n * 4)) || (err = d_isfirst.alloc(ctx, (size_t)n * 4)) ||
-        (err = d_rank.alloc(ctx, ((size_t)n + 1) * 4)) || (err = d_idx.alloc(ctx, (size_t)n * 4)) ||
-        (err = d_uh.alloc(ctx, (size_t)n * 8)) || (err = d_us.alloc(ctx, (size_t)n * 4)) || (err = d_ut.alloc(ctx, (size_t)n * 4)) ||
-        (err = d_starts.alloc(ctx, ((size_t)asset_count + 1) * 4)) || (err = d_tags.alloc(ctx, (size_t)asset_count * 4)) ||
-        (err = d_uniq.alloc(ctx, 8)) || (err = d_paths.alloc(ctx, (size_t)path_data_size + 16)) ||
-        (err = d_off.alloc(ctx, (size_t)asset_count * 8)) || (err = d_len.alloc(ctx, (size_t)asset_count * 4)) ||
-        (err = d_ph.alloc(ctx, (size_t)asset_count * 8)) || (err = d_ch.alloc(ctx, (size_t)asset_count * 8)))
+    if ((err = lthip_vi_refusals(ctx, t, "version index")))
         return err;
-
-    // ---- first-seen dedup -> unique index of every asset chunk, compact unique arrays (:2951-2970) ----
+    ViWorkspace w; // (freed on return: every path out of here has waited for the stream, or queued nothing that reads it)
+    DBuf d_first, d_uniq;
+    if ((err = reserve_dev(ctx, d_first, (size_t)n * 4)) || (err = reserve_dev(ctx, d_uniq, 8)) || (err = lthip_vi_reserve(ctx, w, n, asset_count, path_data_size)))
+        return err;
+    // ---- first-seen dedup (:2951-2970), then the three steps; the host waits once for the unique count, once for the sections ----
     uint64_t unique = 0;
-    if ((err = lthip_dedup_first_seen(ctx, n, d_chunk_hashes, (uint32_t*)d_first.p, (uint64_t*)d_uniq.p)))
-        return err;
-    LTHIP_CHECK(ctx, hipMemcpyAsync(d_starts.p, starts.data(), ((size_t)asset_count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (asset_tags && asset_count)
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_tags.p, asset_tags, (size_t)asset_count * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (n)
-    {
-        const uint32_t blocks = (uint32_t)div_up_u64(n, 256);
-        hipLaunchKernelGGL(k_vi_mark, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t*)d_first.p, (uint64_t)n,
-                           (uint32_t*)d_isfirst.p);
-        if ((err = lthip_exclusive_scan_u32(ctx, (const uint32_t*)d_isfirst.p, (uint32_t*)d_rank.p, n, nullptr, LTHIP_K_OTHER)))
-            return err;
-        hipLaunchKernelGGL(k_vi_compact, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t*)d_first.p, (const uint32_t*)d_rank.p,
-                           (uint64_t)n, d_chunk_hashes, d_chunk_lens, (const uint32_t*)d_starts.p, asset_count,
-                           asset_tags ? (const uint32_t*)d_tags.p : (const uint32_t*)nullptr, (uint32_t*)d_idx.p, (uint64_t*)d_uh.p,
-                           (uint32_t*)d_us.p, (uint32_t*)d_ut.p);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    LTHIP_CHECK(ctx, hipMemcpyAsync(&unique, d_uniq.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-
-    // ---- content hash of every asset = BLAKE3 of its chunk-hash array (:2518-2537); path hashes (:1269-1300) ----
-    std::vector<uint64_t> h_off(asset_count);
-    std::vector<uint32_t> h_len(asset_count);
-    uint32_t max_len = 0;
-    for (uint32_t a = 0; a < asset_count; ++a)
-    {
-        h_off[a] = (uint64_t)starts[a] * 8u;
-        if ((uint64_t)asset_chunk_counts[a] * 8u > 0xFFFFFFFFull)
-            return lthip_fail(ctx, EINVAL, "version index", "asset with more than 2^29 chunks");
-        h_len[a] = asset_chunk_counts[a] * 8u; // the reference's hash_size is a uint32_t as well (:2522)
-        max_len = h_len[a] > max_len ? h_len[a] : max_len;
-    }
-    if (asset_count)
-    {
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, h_off.data(), (size_t)asset_count * 8, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_len.p, h_len.data(), (size_t)asset_count * 4, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // h_off / h_len are reused below
-        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_chunk_hashes ? (const void*)d_chunk_hashes : d_paths.p, asset_count, (const uint64_t*)d_off.p,
-                                     (const uint32_t*)d_len.p, max_len, 0u, (uint64_t*)d_ch.p)))
-            return err;
-        max_len = 0;
-        for (uint32_t a = 0; a < asset_count; ++a)
-        {
-            if (path_start_offsets[a] >= path_data_size)
-                return lthip_fail(ctx, EINVAL, "version index", "path offset outside the path data");
-            h_off[a] = path_start_offsets[a];
-            h_len[a] = (uint32_t)strnlen(path_data + path_start_offsets[a], path_data_size - path_start_offsets[a]);
-            max_len = h_len[a] > max_len ? h_len[a] : max_len;
-        }
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_paths.p, path_data, path_data_size, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, h_off.data(), (size_t)asset_count * 8, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(d_len.p, h_len.data(), (size_t)asset_count * 4, hipMemcpyHostToDevice, ctx->stream));
-        LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        if ((err = lthip_hash_ranges_by_id(ctx, hash_identifier, d_paths.p, asset_count, (const uint64_t*)d_off.p, (const uint32_t*)d_len.p, max_len, 0u,
-                                     (uint64_t*)d_ph.p)))
-            return err;
-    }
+    if (!(err = lthip_dedup_first_seen(ctx, n, d_chunk_hashes, (uint32_t*)d_first.p, (uint64_t*)d_uniq.p)) &&
+        !(err = vi_unique_lists(ctx, w, (const uint32_t*)d_first.p, n, d_chunk_hashes, d_chunk_lens, starts.data(), asset_tags, asset_count)) &&
+        !(err = lthip_vi_hashes(ctx, w, t, d_chunk_hashes, n)) &&
+        hipMemcpyAsync(&unique, d_uniq.p, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        err = lthip_fail(ctx, EIO, "version index", "hipMemcpyAsync");
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-
-    // ---- serialized layout (Longtail_BuildVersionIndex :2757-2806 over InitVersionIndexFromData's section order) ----
+    if (err)
+        return err;
     const size_t size = lthip_version_index_size(asset_count, unique, n, path_data_size);
     *out_size = size;
     if (!out || out_capacity < size)
         return ENOMEM;
-    uint8_t* w = (uint8_t*)out;
-    const uint32_t head[6] = {(0u << 24) | (0u << 16) | 2u /* LONGTAIL_VERSION_INDEX_VERSION_0_0_2, :16-22 */, hash_identifier,
-                              target_chunk_size, asset_count, (uint32_t)unique, n};
-    memcpy(w, head, sizeof head);
-    w += sizeof head;
-#define LT_D2H(SRC, BYTES)                                                                      \
-    do                                                                                          \
-    {                                                                                           \
-        if (BYTES)                                                                              \
-            LTHIP_CHECK(ctx, hipMemcpy(w, (SRC), (BYTES), hipMemcpyDeviceToHost));              \
-        w += (BYTES);                                                                           \
-    } while (0)
-    LT_D2H(d_ph.p, (size_t)asset_count * 8);                  // m_PathHashes
-    LT_D2H(d_ch.p, (size_t)asset_count * 8);                  // m_ContentHashes
-    memcpy(w, asset_sizes, (size_t)asset_count * 8);          // m_AssetSizes
-    w += (size_t)asset_count * 8;
-    memcpy(w, asset_chunk_counts, (size_t)asset_count * 4);   // m_AssetChunkCounts
-    w += (size_t)asset_count * 4;
-    memcpy(w, starts.data(), (size_t)asset_count * 4);        // m_AssetChunkIndexStarts
-    w += (size_t)asset_count * 4;
-    LT_D2H(d_idx.p, (size_t)n * 4);                           // m_AssetChunkIndexes
-    LT_D2H(d_uh.p, (size_t)unique * 8);                       // m_ChunkHashes
-    LT_D2H(d_us.p, (size_t)unique * 4);                       // m_ChunkSizes
-    LT_D2H(d_ut.p, (size_t)unique * 4);                       // m_ChunkTags
-#undef LT_D2H
-    memcpy(w, path_start_offsets, (size_t)asset_count * 4);   // m_NameOffsets
-    w += (size_t)asset_count * 4;
-    memcpy(w, permissions, (size_t)asset_count * 2);          // m_Permissions
-    w += (size_t)asset_count * 2;
-    memcpy(w, path_data, path_data_size);                     // m_NameData
-    return 0;
+    err = lthip_vi_sections(ctx, w, t, n, unique, nullptr, out);
+    LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
+    return err;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -215,11 +217,11 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
             return lthip_fail(ctx, EINVAL, "stored blocks", "image offsets must be 8-byte aligned");
     BlockHashRanges r;
     r.fill(first.data(), block_count, 0);
-    DevBuf d_first, d_off, d_len, d_bh, d_raw, d_img;
+    DBuf d_first, d_off, d_len, d_bh, d_raw, d_img;
     int err;
-    if ((err = d_first.alloc(ctx, ((size_t)block_count + 1) * 4)) || (err = d_off.alloc(ctx, (size_t)block_count * 8)) ||
-        (err = d_len.alloc(ctx, (size_t)block_count * 4)) || (err = d_bh.alloc(ctx, (size_t)block_count * 8)) ||
-        (err = d_raw.alloc(ctx, (size_t)block_count * 4)) || (err = d_img.alloc(ctx, (size_t)block_count * 8)))
+    if ((err = reserve_dev(ctx, d_first, ((size_t)block_count + 1) * 4)) || (err = reserve_dev(ctx, d_off, (size_t)block_count * 8)) ||
+        (err = reserve_dev(ctx, d_len, (size_t)block_count * 4)) || (err = reserve_dev(ctx, d_bh, (size_t)block_count * 8)) ||
+        (err = reserve_dev(ctx, d_raw, (size_t)block_count * 4)) || (err = reserve_dev(ctx, d_img, (size_t)block_count * 8)))
         return err;
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_first.p, first.data(), ((size_t)block_count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     LTHIP_CHECK(ctx, hipMemcpyAsync(d_off.p, r.off.data(), (size_t)block_count * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -233,7 +235,7 @@ extern "C" int lthip_write_stored_block_headers(lthip_ctx* ctx, uint32_t block_c
                                           hash_identifier, tag, nullptr, (const uint32_t*)d_raw.p, const_cast<uint32_t*>(d_comp_sizes) /* only read: raw_mode 0 */,
                                           (const uint64_t*)d_img.p, d_arena, 0u)))
         return err;
-    LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // the DevBufs are freed on return
+    LTHIP_CHECK(ctx, lthip_stream_wait(ctx)); // the buffers are freed on return
     return 0;
 }
 
@@ -259,8 +261,8 @@ extern "C" int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_co
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t ne = (size_t)existing_count, n = (size_t)chunk_count;
     int err;
-    DevBuf d_all, d_first, d_uniq;
-    if ((err = d_all.alloc(ctx, (ne + n) * 8)) || (err = d_first.alloc(ctx, (ne + n) * 4)) || (err = d_uniq.alloc(ctx, 8)))
+    DBuf d_all, d_first, d_uniq;
+    if ((err = reserve_dev(ctx, d_all, (ne + n) * 8)) || (err = reserve_dev(ctx, d_first, (ne + n) * 4)) || (err = reserve_dev(ctx, d_uniq, 8)))
         return err;
     if (ne)
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_all.p, d_existing_hashes, ne * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -301,11 +303,11 @@ extern "C" int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_co
     std::vector<uint64_t> b_hash(nb);
     if (nb)
     {
-        DevBuf d_mh, d_o, d_l, d_bh;
+        DBuf d_mh, d_o, d_l, d_bh;
         BlockHashRanges r;
         r.fill(b_first.data(), nb, 0);
-        if ((err = d_mh.alloc(ctx, m * 8)) || (err = d_o.alloc(ctx, nb * 8)) || (err = d_l.alloc(ctx, nb * 4)) ||
-            (err = d_bh.alloc(ctx, nb * 8)))
+        if ((err = reserve_dev(ctx, d_mh, m * 8)) || (err = reserve_dev(ctx, d_o, nb * 8)) || (err = reserve_dev(ctx, d_l, nb * 4)) ||
+            (err = reserve_dev(ctx, d_bh, nb * 8)))
             return err;
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_mh.p, m_hash.data(), m * 8, hipMemcpyHostToDevice, ctx->stream));
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_o.p, r.off.data(), nb * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -536,12 +538,12 @@ extern "C" int lthip_get_existing_store_index(lthip_ctx* ctx, const void* store_
     uint64_t slots = 1024;
     while (slots < chunk_count * 2)
         slots <<= 1;
-    DevBuf d_keys, d_val, d_misc, d_chash, d_csize, d_boff, d_bcnt, d_use, d_size, d_rank, d_taken;
+    DBuf d_keys, d_val, d_misc, d_chash, d_csize, d_boff, d_bcnt, d_use, d_size, d_rank, d_taken;
     int err;
-    if ((err = d_keys.alloc(ctx, slots * 8)) || (err = d_val.alloc(ctx, slots * 4)) || (err = d_misc.alloc(ctx, 16)) ||
-        (err = d_chash.alloc(ctx, (size_t)m * 8)) || (err = d_csize.alloc(ctx, (size_t)m * 4)) || (err = d_boff.alloc(ctx, (size_t)nb * 4)) ||
-        (err = d_bcnt.alloc(ctx, (size_t)nb * 4)) || (err = d_use.alloc(ctx, (size_t)nb * 4)) || (err = d_size.alloc(ctx, (size_t)nb * 4)) ||
-        (err = d_rank.alloc(ctx, (size_t)nb * 4)) || (err = d_taken.alloc(ctx, (size_t)nb * 4)))
+    if ((err = reserve_dev(ctx, d_keys, slots * 8)) || (err = reserve_dev(ctx, d_val, slots * 4)) || (err = reserve_dev(ctx, d_misc, 16)) ||
+        (err = reserve_dev(ctx, d_chash, (size_t)m * 8)) || (err = reserve_dev(ctx, d_csize, (size_t)m * 4)) || (err = reserve_dev(ctx, d_boff, (size_t)nb * 4)) ||
+        (err = reserve_dev(ctx, d_bcnt, (size_t)nb * 4)) || (err = reserve_dev(ctx, d_use, (size_t)nb * 4)) || (err = reserve_dev(ctx, d_size, (size_t)nb * 4)) ||
+        (err = reserve_dev(ctx, d_rank, (size_t)nb * 4)) || (err = reserve_dev(ctx, d_taken, (size_t)nb * 4)))
         return err;
     if (m)
     {

@@ -8,7 +8,10 @@ WriteContent) against the reference run on the same tree (oracle/_ref):
   * R ranks (1 process, R sessions fed the job-ordered arrays the exchange would deliver, LPT / range / mod assignments, an
     asset whose parts straddle ranks): rank 0's VersionIndex is the single-rank one; every rank's StoreIndex equals
     Longtail_CreateMissingContent against a store holding the other ranks' chunks; the ranks' chunk sets partition the
-    version's unique chunks."""
+    version's unique chunks.
+  * one session over trees of different sizes (workspaces that grow, then stay larger than needed), and behind an index that was
+    never finished: every round is a fresh session's, byte for byte; a tree without chunks; the VersionIndex with its helper
+    thread on and off (ablation build)."""
 import ctypes as C
 
 import numpy as np
@@ -403,3 +406,147 @@ def test_images_as_a_host_fed_embedder_downloads_them(gpu, oracle, ref, codec):
         expect = np.concatenate([data_host[where[int(x)][0] : where[int(x)][0] + where[int(x)][1]] for x in h])
         assert got.value == raw and (out[:raw] == expect).all(), b
     ing.close()
+
+
+# ---- one session over several trees, a tree without chunks, the VersionIndex helper thread on and off --------------------------------
+LZ4_TAG, ZTD2_TAG = 0x6C7A3432, 0x7A746432
+SMALL = dict(target=4096, max_block=262144, max_chunks=64)
+
+
+def small_tree(oracle, total_bytes, seed):
+    """A dozen files of odd sizes, `total_bytes` at the most: ten of content, a duplicate of one of them, an empty one."""
+    rng = np.random.default_rng(seed)
+    each = total_bytes // 11
+    files = [(f"d{i % 3}/s{i % 2}/f{i:02d}.bin", oracle.synth(each - int(rng.integers(0, each // 4)), seed + i, i % 3)) for i in range(10)]
+    files.append(("d0/copy_of_02.bin", files[2][1].copy()))
+    files.append(("empty.bin", np.zeros(0, np.uint8)))
+    assert len(files) == 12 and sum(len(d) for _, d in files) <= total_bytes
+    return files
+
+
+def chunked(gpu, ref, files):
+    """The tree chunked and hashed as ONE rank (rank_session's probe): the local lists are the lists of all ranks."""
+    return rank_session(gpu, ref, files, SMALL["target"], 1, 0, "range", "lz4", SMALL["max_block"], SMALL["max_chunks"], 0)
+
+
+def one_shot(gpu, codec, tag=None):
+    return Ingest(gpu, SMALL["target"], SMALL["max_block"], SMALL["max_chunks"], codec, compression_type=tag)
+
+
+def index_only(gpu, ing, lists, asset_tags=None):
+    """lthip_ingest_index with a VersionIndex buffer -> the buffer (the caller keeps it alive)."""
+    paths, sizes, offs, perms, path_data = lists["infos"]
+    total = lists["total"]
+    tree, _ = Ingest.tree(sizes.copy(), offs.copy(), perms.copy(), path_data, lists["part"].job_asset.copy(), lists["first"].astype(np.uint64),
+                          asset_tags=None if asset_tags is None else asset_tags.copy())
+    vi = torch.zeros(gpu.lib.dll.lthip_version_index_size(len(sizes), total, total, len(path_data)) + 64, dtype=torch.uint8).pin_memory()
+    ing.index(tree, lists["d_hash"], lists["d_len"], total, lists["d_off"], lists["d_first"], total, vi)
+    return vi
+
+
+def round_of(gpu, ing, lists, asset_tags=None):
+    """index / write / finish -> VersionIndex, StoreIndex, every stored-block image (one codec batch: the arena holds them all), result."""
+    vi = index_only(gpu, ing, lists, asset_tags)
+    arena = torch.full((24 << 20,), 0xA5, dtype=torch.uint8, device="cuda")
+    ing.write(lists["dev"], arena)
+    si = torch.zeros(16 + 32 * max(lists["total"], 1) + 64, dtype=torch.uint8).pin_memory()
+    res = ing.finish(si)
+    first, offs, sizes = ing.images()
+    assert first == 0 and len(offs) == res.blocks
+    host = arena.cpu().numpy()
+    return dict(vi=bytes(vi.numpy()[: res.version_index_size]), si=bytes(si.numpy()[: res.store_index_size]),
+                images=[host[int(o) : int(o) + int(k)].tobytes() for o, k in zip(offs, sizes)], res=res)
+
+
+def with_asset_tags(vi_blob, asset_tags):
+    """The reference's VersionIndex (made with ONE tag) as it is with per-asset tags: a unique chunk carries the tag of the asset it is
+    first seen in (src/longtail.c:2951-2970)."""
+    vi = bytearray(vi_blob)
+    h = np.frombuffer(vi_blob[:24], np.uint32)
+    na, nu, ni = int(h[3]), int(h[4]), int(h[5])
+    assert na == len(asset_tags)
+    o = 24 + na * 24
+    counts = np.frombuffer(vi_blob[o : o + na * 4], np.uint32)
+    idx = np.frombuffer(vi_blob[o + na * 8 : o + na * 8 + ni * 4], np.uint32)
+    tags = np.zeros(nu, np.uint32)
+    owner = np.repeat(np.arange(na), counts)  # the asset of every asset chunk, in version order
+    for u, a in zip(idx[::-1], owner[::-1]):  # (backwards: the first occurrence is written last)
+        tags[u] = asset_tags[a]
+    t0 = o + na * 8 + ni * 4 + nu * 12
+    vi[t0 : t0 + nu * 4] = tags.tobytes()
+    return bytes(vi)
+
+
+def rotating_asset_tags(lists, over):
+    return np.array([over[a % len(over)] for a in range(len(lists["infos"][0]))], np.uint32)
+
+
+@pytest.mark.parametrize("codec", ["lz4", "by-tag"])
+def test_one_session_reused_over_trees_of_different_sizes(gpu, oracle, ref, codec):
+    """Workspaces that grow (1 MiB -> 8 MiB) and then stay larger than the tree needs (256 KiB), then an index that is never written or
+    finished -- its VersionIndex hand-off and its side-stream copies are collected on entry of the next index -- followed at once by a
+    whole round on another tree.  Every finished round equals a fresh session's on the same tree, byte for byte, and the reference's
+    VersionIndex."""
+    tag = ref.lz4_type if codec == "lz4" else None
+    reused = one_shot(gpu, codec, tag)
+    abandoned = []
+
+    def check(total_bytes, seed):
+        files = small_tree(oracle, total_bytes, seed)
+        lists = chunked(gpu, ref, files)
+        asset_tags = rotating_asset_tags(lists, (0, LZ4_TAG, ZTD2_TAG)) if codec == "by-tag" else None
+        got = round_of(gpu, reused, lists, asset_tags)
+        fresh = one_shot(gpu, codec, tag)
+        want = round_of(gpu, fresh, lists, asset_tags)
+        fresh.close()
+        assert got["res"].blocks == want["res"].blocks >= 1 and got["res"].unique_local == want["res"].unique_local < lists["total"]
+        assert got["vi"] == want["vi"] and got["si"] == want["si"] and got["images"] == want["images"], total_bytes
+        expect_vi, _ = ref.version_index(files, SMALL["target"], 0, ref.lz4_type if codec == "lz4" else 0)
+        assert got["vi"] == (expect_vi if asset_tags is None else with_asset_tags(expect_vi, asset_tags)), total_bytes
+
+    for total_bytes, seed in ((1 << 20, 11), (8 << 20, 12), (256 << 10, 13)):
+        check(total_bytes, seed)
+    lists = chunked(gpu, ref, small_tree(oracle, 2 << 20, 14))
+    abandoned.append(index_only(gpu, reused, lists, rotating_asset_tags(lists, (LZ4_TAG, 0)) if codec == "by-tag" else None))
+    check(3 << 19, 15)
+    reused.close()
+
+
+@pytest.mark.parametrize("tagged", [False, True])
+def test_a_tree_without_chunks_through_the_one_shot_session(gpu, ref, tagged):
+    """Directories and empty files only: all_chunks == 0 with a VersionIndex requested.  The session's VersionIndex is the bulk call's
+    and the reference's; finish reports no block and the empty StoreIndex."""
+    files = [("a/empty0.bin", np.zeros(0, np.uint8)), ("a/b/empty1.bin", np.zeros(0, np.uint8)), ("c/empty2.bin", np.zeros(0, np.uint8))]
+    lists = chunked(gpu, ref, files)
+    paths, sizes, offs, perms, path_data = lists["infos"]
+    assert lists["total"] == 0 and len(paths) > len(files)  # (the directories are assets too)
+    asset_tags = rotating_asset_tags(lists, (0, LZ4_TAG)) if tagged else None
+    ing = one_shot(gpu, "by-tag" if tagged else "lz4", None if tagged else ref.lz4_type)
+    got = round_of(gpu, ing, lists, asset_tags)
+    ing.close()
+    bulk = gpu.build_version_index(sizes, offs, perms, path_data, np.zeros(len(paths), np.uint32), lists["d_hash"], lists["d_len"], 0,
+                                   SMALL["target"], asset_tags)
+    expect_vi, _ = ref.version_index(files, SMALL["target"], 0, 0 if tagged else ref.lz4_type)
+    assert got["vi"] == bytes(bulk) == expect_vi
+    res = got["res"]
+    assert res.blocks == 0 and res.chunks_all == res.unique_all == res.unique_local == 0 and got["images"] == []
+    assert res.store_index_size == 16 and np.frombuffer(got["si"], np.uint32).tolist() == [1 << 24, 0, 0, 0]
+
+
+def test_version_index_with_the_helper_thread_on_or_off(gpu_abl, oracle, ref, monkeypatch):
+    """LTHIP_INGEST_VI_THREAD=0 (ablation build): the calling thread puts the VersionIndex sections together on the session's own
+    context instead of the helper thread on its own -- the same bytes, for a tree with tags, a duplicate file and an empty file."""
+    files = small_tree(oracle, 1 << 20, 21)
+    lists = chunked(gpu_abl, ref, files)
+    asset_tags = rotating_asset_tags(lists, (0, LZ4_TAG, ZTD2_TAG))
+    runs = []
+    for thread in (None, 0):
+        if thread is not None:
+            monkeypatch.setenv("LTHIP_INGEST_VI_THREAD", str(thread))
+            gpu_abl.lib.dll.lthip_debug_reload_env()
+        ing = one_shot(gpu_abl, "by-tag")
+        runs.append(round_of(gpu_abl, ing, lists, asset_tags))
+        ing.close()
+    assert runs[0]["vi"] == runs[1]["vi"] and runs[0]["si"] == runs[1]["si"]
+    expect_vi, _ = ref.version_index(files, SMALL["target"], 0, 0)
+    assert runs[0]["vi"] == with_asset_tags(expect_vi, asset_tags)
