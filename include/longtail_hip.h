@@ -243,8 +243,8 @@ LTHIP_EXPORT int lthip_hash_ranges(lthip_ctx* ctx, const void* d_data, uint64_t 
                                    uint64_t* d_hashes);
 
 /* BLAKE3-64 of ONE input of at most 64 KiB in one launch, read where it lies and answered where `out` points: both must be device
- * accessible (pinned host memory from lthip_malloc_pinned, or device memory).  What the plugin layer's HashBuffer uses for path
- * strings and hash arrays.  Asynchronous on the context's stream; EINVAL above 64 KiB. */
+ * accessible (pinned host memory from lthip_malloc_pinned, or device memory); `in` may have any alignment.  What the plugin layer's
+ * HashBuffer uses for path strings and hash arrays.  Asynchronous on the context's stream; EINVAL above 64 KiB. */
 LTHIP_EXPORT int lthip_hash_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out);
 
 /* Streaming BLAKE3-64 with O(1) state (Blake3Hash_BeginContext/_Hash/_EndContext, longtail_blake3.c:24-79): the caller cuts the

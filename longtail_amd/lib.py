@@ -32,6 +32,8 @@ KERNEL_IDS = {
 BLAKE2S_KERNEL_ID = 10
 HASH_BLAKE3 = 0x626C6B33  # 'blk3', lib/blake3/longtail_blake3.c
 HASH_BLAKE2 = 0x626C6B32  # 'blk2', lib/blake2/longtail_blake2.c
+B3_STREAM_BATCH = 1 << 20  # include/longtail_hip.h LTHIP_B3_STREAM_BATCH
+B3_STREAM_STACK_BYTES = 2048
 B2S_STREAM_BATCH = 1 << 20  # include/longtail_hip.h LTHIP_B2S_STREAM_BATCH
 B2S_STREAM_STATE_BYTES = 64
 HASH_MEOW = 0x6D656F77  # 'meow', lib/meowhash/longtail_meowhash.c
@@ -387,6 +389,30 @@ class Context:
             "lthip_hash_ranges",
         )
         return out[:n]
+
+    def hash_one(self, data, length: int, out) -> None:
+        """BLAKE3-64 of one input of at most 64 KiB (device or pinned memory, any alignment); the digest lands in `out` (device or
+        pinned) on the stream."""
+        self._check(self.lib.dll.lthip_hash_one(self.h, _ptr(data), length, _ptr(out)), "lthip_hash_one")
+
+    def hash_runs_u64(self, values, first, run_count: int, out=None):
+        """out[i] = BLAKE3-64 of the bytes of values[first[i] .. first[i + 1]) (device u64 / u32 tensors)."""
+        if out is None:
+            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
+        self._check(self.lib.dll.lthip_hash_runs_u64(self.h, _ptr(values), _ptr(first), run_count, _ptr(out)), "lthip_hash_runs_u64")
+        return out[:run_count]
+
+    def hash_runs_u64_bounded(self, values, first, run_count: int, total_values_bound: int, run_values_bound: int, out=None):
+        """hash_runs_u64 with the caller's upper bounds of all values and of the longest run (0 = unknown): no read-back."""
+        if out is None:
+            out = self.torch.empty(max(1, run_count), dtype=self.torch.int64, device=self._dev())
+        self._check(self.lib.dll.lthip_hash_runs_u64_bounded(self.h, _ptr(values), _ptr(first), run_count, total_values_bound, run_values_bound,
+                                                             _ptr(out)), "lthip_hash_runs_u64_bounded")
+        return out[:run_count]
+
+    def b3_stream(self, data, length: int) -> int:
+        """Streaming BLAKE3-64 of the first `length` bytes of a device tensor, batch by batch (lthip_b3_stream_batch / _final)."""
+        return self._chain_stream("lthip_b3_stream", B3_STREAM_BATCH, B3_STREAM_STACK_BYTES, data, length)
 
     # -- the chain hashes: BLAKE2s-64 ('blk2') and Meow hash v0.5, 64 bits ('meow'); `name` is the prefix of the kind's C calls --
     def _chain_ranges(self, name, data, offsets, lens, max_len, out, count_bound, d_count):
