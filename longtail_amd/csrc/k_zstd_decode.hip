@@ -137,6 +137,7 @@ struct ZFrameHdr
     uint32_t size;      // bytes of the frame header
     uint64_t content;   // Frame_Content_Size
     uint32_t checksum;  // a 4-byte content checksum follows the last block
+    uint32_t block_max; // Block_Maximum_Size: min(window, 128 KiB); the window of a single-segment frame is its content
     bool ok;
 };
 __device__ __forceinline__ ZFrameHdr z_frame_header(const uint8_t* p, uint32_t avail)
@@ -145,6 +146,7 @@ __device__ __forceinline__ ZFrameHdr z_frame_header(const uint8_t* p, uint32_t a
     h.size = 0;
     h.content = 0;
     h.checksum = 0;
+    h.block_max = ZB;
     h.ok = false;
     if (avail < 6u || p[0] != 0x28 || p[1] != 0xB5 || p[2] != 0x2F || p[3] != 0xFD)
         return h;
@@ -163,6 +165,17 @@ __device__ __forceinline__ ZFrameHdr z_frame_header(const uint8_t* p, uint32_t a
         c += 256u;
     h.size = pos + fcs;
     h.content = c;
+    if (single)
+        h.block_max = c < (uint64_t)ZB ? (uint32_t)c : ZB;
+    else
+    {
+        const uint32_t wd = p[5], wlog = 10u + (wd >> 3); // Window_Descriptor: exponent and mantissa
+        if (wlog < 17u)
+        {
+            const uint32_t w = (1u << wlog) + ((1u << wlog) >> 3) * (wd & 7u);
+            h.block_max = w < ZB ? w : ZB;
+        }
+    }
     h.checksum = (fhd >> 2) & 1u;
     h.ok = true;
     return h;
@@ -183,7 +196,7 @@ __device__ bool z_split_foreign(const uint8_t* p, const ZBlock blk, uint32_t b, 
         const uint32_t type = (bh >> 1) & 3u, bsize = bh >> 3;
         last = (bh & 1u) != 0u;
         const uint32_t body = type == 1u ? 1u : bsize;
-        if (type == 3u || bsize > ZB || body > blk.size - pos - 3u)
+        if (type == 3u || bsize > h.block_max || body > blk.size - pos - 3u) // (a block above Block_Maximum_Size: the serial decoder refuses it)
             return false;
         ZItem it;
         it.src_off = blk.src_off;

@@ -95,6 +95,25 @@ __device__ __forceinline__ ZfBlk zf_parse(const uint8_t* c, uint32_t csz)
     return f;
 }
 
+// Room in an arena (a counter that only grows, up to `cap`): a draw that does not fit leaves the counter as it was, so a block too
+// dense for the arena sends its own payload to the serial decoder and the other payloads of the call keep their room.
+__device__ __forceinline__ bool zf_draw(unsigned long long* counter, unsigned long long want, unsigned long long cap, unsigned long long* at)
+{
+    unsigned long long old = atomicAdd(counter, 0ull); // (the counter itself, not a cached copy: a draw may have been given back)
+    for (;;)
+    {
+        if (old + want > cap)
+            return false;
+        const unsigned long long seen = atomicCAS(counter, old, old + want);
+        if (seen == old)
+        {
+            *at = old;
+            return true;
+        }
+        old = seen;
+    }
+}
+
 __global__ __launch_bounds__(64) void k_zstd_blk_entropy(const uint8_t* __restrict__ src, const ZItem* __restrict__ fitems, const uint32_t* __restrict__ flist,
                                                          uint32_t nlist, uint32_t* __restrict__ slist, uint32_t* __restrict__ scount,
                                                          uint8_t* __restrict__ lit_scratch, uint64_t* __restrict__ rec_scratch,
@@ -164,11 +183,23 @@ __global__ __launch_bounds__(64) void k_zstd_blk_entropy(const uint8_t* __restri
         if (!bad)
         {
             const unsigned long long want_l = ((unsigned long long)me.nlit + 79ull) & ~15ull;
-            lit_at = atomicAdd(&bump[0], lane == 0 ? want_l : 0ull);
-            rec_at = atomicAdd(&bump[1], lane == 0 ? (unsigned long long)me.nbseq : 0ull);
+            uint32_t fits = 0;
+            if (lane == 0)
+            {
+                // the literals first (a damaged header can state at most 2^18 of them), then the records; a block whose records do
+                // not fit gives its literals' room back if nobody has drawn behind it
+                if (zf_draw(&bump[0], want_l, lit_cap, &lit_at))
+                {
+                    if (zf_draw(&bump[1], me.nbseq, rec_cap, &rec_at))
+                        fits = 1;
+                    else
+                        (void)atomicCAS(&bump[0], lit_at + want_l, lit_at);
+                }
+            }
+            fits = __builtin_amdgcn_readfirstlane(fits);
             lit_at = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(lit_at >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)lit_at);
             rec_at = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(rec_at >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)rec_at);
-            if (lit_at + want_l > lit_cap || rec_at + me.nbseq > rec_cap)
+            if (!fits)
                 { bad = true; why = __LINE__; }
         }
         uint8_t* lits = lit_scratch + lit_at;

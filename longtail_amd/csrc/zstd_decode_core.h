@@ -762,7 +762,10 @@ ZB_FN uint32_t zd_decode_payload_ex(const uint8_t* src, uint32_t src_size, uint8
                 bsize = bh >> 3;
             }
             ip += 3u;
-            if (type == 3u || bsize > ZB_BLOCK_MAX || (type != 2u && bsize > block_max))
+            /* Block_Size of every type is limited by Block_Maximum_Size = min(window, 128 KiB) (RFC 8878 3.1.1.2); the window of a
+             * single-segment frame is its content, so a compressed block LARGER than the content is malformed there
+             * (zstd_decompress_block.c: srcSize > ZSTD_blockSizeMax) */
+            if (type == 3u || bsize > ZB_BLOCK_MAX || bsize > block_max)
                 return ZD_FAIL_AT(sh);
             const uint32_t block_out0 = out_total;
             if (type == 0u)

@@ -572,8 +572,10 @@ def test_zstd_sub_block_decoder_is_the_serial_decoder_and_strict(gpu_abl, oracle
 
 def test_zstd_reference_frames_block_parallel_is_the_serial_decoder(gpu_abl, oracle, ref, monkeypatch):
     gpu = gpu_abl  # (the switches this test sets exist in the ablation build only)
-    """Frames of the REFERENCE encoder (blocks that depend on each other: window = the frame, repeat offsets, repeated tables,
-    treeless literals) are decoded block-parallel: every block's streams on a wave / lane of its own (k_zstd_blk_entropy,
+    """Frames of the REFERENCE encoder (blocks that depend on each other: window = the frame, repeat offsets, treeless literals, and
+    at the settings above level 3 tables repeated from an FSE_Compressed one -- what these frames hold is counted in
+    tests/golden/zstd_ref_census.json; the forms the reference never writes come from tests/test_gpu_zstd_format.py) are decoded
+    block-parallel: every block's streams on a wave / lane of its own (k_zstd_blk_entropy,
     k_zstd_blk_sequences), then a payload's blocks in order on one wave (k_zstd_execute_payload); whatever that path declines goes to
     the serial decoder.  All five longtail settings, sizes from a few KiB to 8 MiB + 5, raw and RLE blocks inside frames; and 300
     damaged frames: same verdict and bytes as the serial decoder (LTHIP_ZSTD_DBG=1), undamaged ones equal to the data."""

@@ -156,18 +156,30 @@ def model_decode(o, frame: np.ndarray, cap: int):
     return err, out[: n.value]
 
 
+def reference_encoder_inputs(o, setting):
+    """what test_decoder_reads_reference_encoder_output feeds the reference encoder at one setting (tests/test_zstd_format_cases.py
+    takes the census of the same frames)"""
+    rng = np.random.default_rng(setting)
+    datas = [o.synth(n, 5 + n + k, k) for k in (0, 1, 2, 11, 12, 13) for n in (0, 1, 100, 5000, 131072, 131073, 400000, 3 << 20)]
+    datas.append((np.abs(rng.normal(128, 20, 700000)).astype(np.int64) % 256).astype(np.uint8))
+    datas.append(np.frombuffer(b"the quick brown fox jumps over the lazy dog. " * 9000, np.uint8).copy())
+    return datas
+
+
 @needs_ref_build
 @pytest.mark.parametrize("setting", range(5))
 def test_decoder_reads_reference_encoder_output(model, setting):
-    """Frames from the reference's ZSTD_compressCCtx at longtail's five settings (levels 3, 3, 22, 8, 22): Huffman with
-    direct and FSE-coded weights, treeless blocks, all FSE modes incl. Repeat, repeat offsets, 1- and 4-stream literals."""
+    """Frames from the reference's ZSTD_compressCCtx at longtail's five settings (levels 3, 3, 22, 8, 22).  What they contain is
+    counted, not believed (tests/test_zstd_format_cases.py::test_reference_fixtures_contain_what_is_claimed, the summary in
+    tests/golden/zstd_ref_census.json): at every setting Huffman trees with direct and with FSE-coded weights, treeless blocks, 1- and
+    4-stream literals, Predefined / FSE_Compressed tables, RLE literal-length and match-length tables, and the first repeat offset with
+    and without literals; Repeat_Mode only at levels 22 and 8, an RLE offset table and the second and third repeat offsets only at
+    level 22.  NOT in these frames, and covered by the hand-built ones of tests/zstd_format_frames.py alone: RLE literals, Repeat_Mode
+    after a Predefined or an RLE table or across a block without sequences / a Raw / an RLE block, the 3-byte sequence count,
+    "repeat offset 1 minus one", the initial offset 4, a content checksum, an 8-byte content size."""
     r = get_ref()
     st = r.dll.refh_zstd_type(setting)
-    rng = np.random.default_rng(setting)
-    datas = [model.synth(n, 5 + n + k, k) for k in (0, 1, 2, 11, 12, 13) for n in (0, 1, 100, 5000, 131072, 131073, 400000, 3 << 20)]
-    datas.append((np.abs(rng.normal(128, 20, 700000)).astype(np.int64) % 256).astype(np.uint8))
-    datas.append(np.frombuffer(b"the quick brown fox jumps over the lazy dog. " * 9000, np.uint8).copy())
-    for d in datas:
+    for d in reference_encoder_inputs(model, setting):
         err, out = model_decode(model, r.compress(1, st, d), len(d))
         assert err == 0 and len(out) == len(d) and (out == d).all()
 
