@@ -121,7 +121,80 @@ constexpr int PW_THREADS = LTHIP_B3_PW_THREADS; // threads of a parents workgrou
 // (2048: two workgroups per CU); 1024 slots with 256 / 512 / 1024 threads 3.12 / 2.80 / 3.19 ms -- 512 threads have one merge each
 // on the first level and three workgroups of them are 24 waves per CU.
 
-__global__ __launch_bounds__(256) void k_blake3_leaves(const uint8_t* __restrict__ data,
+// The message dwords of one 64-byte block as they lie in memory: 16 dwords from the 4-byte aligned address at or below the block's
+// first byte, and the dword behind them, which holds the block's last 1..3 bytes when the leaf starts off a dword boundary.
+__device__ __forceinline__ void b3_load_interior(uint32_t (&w)[17], const uint32_t* __restrict__ src)
+{
+    const u32x4_a4 v0 = *reinterpret_cast<const u32x4_a4*>(src);
+    const u32x4_a4 v1 = *reinterpret_cast<const u32x4_a4*>(src + 4);
+    const u32x4_a4 v2 = *reinterpret_cast<const u32x4_a4*>(src + 8);
+    const u32x4_a4 v3 = *reinterpret_cast<const u32x4_a4*>(src + 12);
+    w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w;
+    w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
+    w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
+    w[12] = v3.x; w[13] = v3.y; w[14] = v3.z; w[15] = v3.w;
+    // an interior block has a block of the same leaf behind it, and this is that block's first dword: it holds a byte of the leaf
+    // whatever the alignment, so it is loaded without a test (v_alignbit with a shift of 0 does not look at it)
+    w[16] = src[16];
+}
+
+// the leaf's last block, `nd` dwords of which hold at least one of its bytes: only those are touched
+__device__ __forceinline__ void b3_load_last(uint32_t (&w)[17], const uint32_t* __restrict__ src, uint32_t nd)
+{
+#pragma unroll
+    for (int i = 0; i < 17; ++i)
+        w[i] = (uint32_t)i < nd ? src[i] : 0u;
+}
+
+// w[0 .. 15] <- the block's message words, each in the register of the dword it starts in (the dword is dead behind it): written with
+// the destination tied, because left to itself the allocator puts the sixteen words into registers of their own and two sets of
+// loaded dwords beside message and state then do not fit in 64
+__device__ __forceinline__ void b3_interior_block(uint32_t (&cv)[8], uint32_t (&w)[17], uint32_t sh, uint32_t k, uint32_t flags)
+{
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        asm("v_alignbit_b32 %0, %1, %0, %2" : "+v"(w[i]) : "v"(w[i + 1]), "v"(sh));
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        m[i] = w[i];
+    b3_compress(cv, m, k, 64u, flags);
+}
+
+__device__ __forceinline__ void b3_last_block(uint32_t (&cv)[8], const uint32_t (&w)[17], uint32_t sh, uint32_t k, uint32_t bl, uint32_t flags)
+{
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+    {
+        uint32_t v = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
+        const int rem = (int)bl - 4 * i; // valid bytes in this word
+        if (rem <= 0)
+            v = 0u;
+        else if (rem < 4)
+            v &= (1u << (8 * rem)) - 1u;
+        m[i] = v;
+    }
+    b3_compress(cv, m, k, bl, flags);
+}
+
+// Fixes a point of the program order: the chaining value is complete in front of it, and no load moves across it.  It emits nothing.
+// (Without it the compiler sinks a whole compression below the loads that follow it, and those then need a third set of registers.)
+__device__ __forceinline__ void b3_pin(uint32_t (&cv)[8])
+{
+    asm volatile("" : "+v"(cv[0]), "+v"(cv[1]), "+v"(cv[2]), "+v"(cv[3]), "+v"(cv[4]), "+v"(cv[5]), "+v"(cv[6]), "+v"(cv[7])::"memory");
+}
+
+// PIPE: the message dwords of block b + 1 are loaded while block b is compressed (two register sets that swap roles by name, the
+// loop unrolled by two).  A lane's loads are 64-line gathers, one 16-byte piece per lane and the lanes 1 KiB apart; without the
+// second set every block waits for all of its own in front of its compression and only the SIMD's other waves cover them.  The
+// addresses read are the same in both forms: a block's 16 dwords, the dword behind an interior block (block b + 1's first, which
+// the next trip reads anyway), and of the last block the dwords that hold a byte of the leaf.  !PIPE is the earlier loop, kept in
+// the ablation build (LTHIP_B3_PREFETCH=0).
+// Eight waves per SIMD are part of the launch bounds: they are what the kernel runs at (512 registers / 8 = 64 a wave), and without
+// the bound the allocator spreads the same values over 69 registers (tests/test_k3_leaf_budget.py).
+template <bool PIPE>
+__global__ __launch_bounds__(256, 8) void k_blake3_leaves(const uint8_t* __restrict__ data,
                                                        const uint64_t* __restrict__ offsets,
                                                        const uint32_t* __restrict__ lens,
                                                        const uint32_t* __restrict__ leaf_prefix, // [count+1]
@@ -162,52 +235,84 @@ __global__ __launch_bounds__(256) void k_blake3_leaves(const uint8_t* __restrict
     uint32_t cv[8] = {B3_IV0, B3_IV1, B3_IV2, B3_IV3, B3_IV4, B3_IV5, B3_IV6, B3_IV7};
     const uint32_t nblocks = llen ? (llen + 63u) >> 6 : 1u;
 
-    // interior blocks: the 64 bytes (and the spill-over dword when misaligned) are inside the leaf
-    for (uint32_t b = 0; b + 1 < nblocks; ++b)
+    if constexpr (PIPE)
     {
-        const uint32_t* src = q + b * 16u;
-        uint32_t w[17];
-        const u32x4_a4 v0 = *reinterpret_cast<const u32x4_a4*>(src);
-        const u32x4_a4 v1 = *reinterpret_cast<const u32x4_a4*>(src + 4);
-        const u32x4_a4 v2 = *reinterpret_cast<const u32x4_a4*>(src + 8);
-        const u32x4_a4 v3 = *reinterpret_cast<const u32x4_a4*>(src + 12);
-        w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w;
-        w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
-        w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
-        w[12] = v3.x; w[13] = v3.y; w[14] = v3.z; w[15] = v3.w;
-        w[16] = mis ? src[16] : 0u;
-        uint32_t m[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            m[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
-        b3_compress(cv, m, k, 64u, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
+        const uint32_t last = nblocks - 1u;
+        const uint32_t bl = llen - last * 64u;                  // 0..64 bytes in the last block
+        const uint32_t nd = bl ? (mis + bl + 3u) >> 2 : 0u;    // its dwords that intersect [p, p + bl)
+        // Blocks 0 .. last - 2 (the block behind each is interior too) go through a loop of two halves: the first compresses wa while
+        // wb is in flight, the second wb while wa is.  A lane with an odd number of them sits out the first half of the first trip,
+        // so every lane leaves at the bottom with block last - 1 in wa, and a wave makes no more trips than its longest lane needs.
+        uint32_t wa[17], wb[17];
+        uint32_t b = 0;
+        bool first_half = last > 1u && ((last - 1u) & 1u) == 0u;
+        if (last > 1u && !first_half)
+            b3_load_interior(wb, q);
+        else if (last)
+            b3_load_interior(wa, q);
+        if (last > 1u)
+        {
+#pragma unroll 1
+            for (;;)
+            {
+                if (first_half)
+                {
+                    b3_load_interior(wb, q + (b + 1u) * 16u);
+                    b3_pin(cv);
+                    b3_interior_block(cv, wa, sh, k, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
+                    b3_pin(cv);
+                    ++b;
+                }
+                first_half = true;
+                b3_load_interior(wa, q + (b + 1u) * 16u);
+                b3_pin(cv);
+                b3_interior_block(cv, wb, sh, k, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
+                b3_pin(cv);
+                ++b;
+                if (b + 1u >= last)
+                    break;
+            }
+        }
+        // block last - 1 is loaded, the last interior one: the last block's dwords are asked for before it is compressed
+        if (last)
+        {
+            b3_load_last(wb, q + last * 16u, nd);
+            b3_pin(cv);
+            b3_interior_block(cv, wa, sh, k, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
+            b3_pin(cv);
+        }
+        else
+            b3_load_last(wb, q, nd);
+        b3_last_block(cv, wb, sh, k, bl, (uint32_t)F_CHUNK_END | root | (last == 0 ? (uint32_t)F_CHUNK_START : 0u));
     }
-    // last block: 0..64 bytes, touch only dwords that hold at least one byte of the leaf
+    else
     {
+        // interior blocks: the 64 bytes (and the spill-over dword when misaligned) are inside the leaf
+        for (uint32_t b = 0; b + 1 < nblocks; ++b)
+        {
+            const uint32_t* src = q + b * 16u;
+            uint32_t w[17];
+            const u32x4_a4 v0 = *reinterpret_cast<const u32x4_a4*>(src);
+            const u32x4_a4 v1 = *reinterpret_cast<const u32x4_a4*>(src + 4);
+            const u32x4_a4 v2 = *reinterpret_cast<const u32x4_a4*>(src + 8);
+            const u32x4_a4 v3 = *reinterpret_cast<const u32x4_a4*>(src + 12);
+            w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w;
+            w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
+            w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
+            w[12] = v3.x; w[13] = v3.y; w[14] = v3.z; w[15] = v3.w;
+            w[16] = mis ? src[16] : 0u;
+            uint32_t m[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                m[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
+            b3_compress(cv, m, k, 64u, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
+        }
+        // last block: 0..64 bytes, touch only dwords that hold at least one byte of the leaf
         const uint32_t b = nblocks - 1u;
         const uint32_t bl = llen - b * 64u;
-        const uint32_t* src = q + b * 16u;
-        const uint32_t nd = bl ? (mis + bl + 3u) >> 2 : 0u; // dwords that intersect [p, p+bl)
         uint32_t w[17];
-#pragma unroll
-        for (int i = 0; i < 17; ++i)
-            w[i] = (uint32_t)i < nd ? src[i] : 0u;
-        uint32_t m[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-        {
-            uint32_t v = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
-            const int rem = (int)bl - 4 * i; // valid bytes in this word
-            if (rem <= 0)
-                v = 0u;
-            else if (rem < 4)
-                v &= (1u << (8 * rem)) - 1u;
-            m[i] = v;
-        }
-        uint32_t fl = (uint32_t)F_CHUNK_END | root;
-        if (b == 0)
-            fl |= (uint32_t)F_CHUNK_START;
-        b3_compress(cv, m, k, bl, fl);
+        b3_load_last(w, q + b * 16u, bl ? (mis + bl + 3u) >> 2 : 0u); // dwords that intersect [p, p+bl)
+        b3_last_block(cv, w, sh, k, bl, (uint32_t)F_CHUNK_END | root | (b == 0 ? (uint32_t)F_CHUNK_START : 0u));
     }
     uint4* out = reinterpret_cast<uint4*>(cvs + (uint64_t)g * 8u);
     out[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
@@ -658,8 +763,15 @@ int lthip_launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d
         LaunchTimer t(ctx, LTHIP_K_B3_LEAF);
         LTHIP_ABLATION_ENV(env_pad, "LTHIP_B3_PAD_LDS"); // experiment: unused LDS limits the waves per CU
         const int pad_lds = env_pad.get() > 0 ? env_pad.get() : 0;
-        hipLaunchKernelGGL(k_blake3_leaves, dim3((uint32_t)div_up_u64(leaf_bound, 256)), dim3(256), (size_t)pad_lds, ctx->stream, d_data,
-                           d_offsets, d_lens, (const uint32_t*)lp, count_bound, d_count, (uint32_t*)cv, (uint32_t*)wf);
+#ifdef LTHIP_ABLATIONS
+        LTHIP_ABLATION_ENV(env_pf, "LTHIP_B3_PREFETCH"); // 0: every block's loads issued and waited for in front of its compression
+        if (env_pf.get() == 0)
+            hipLaunchKernelGGL(k_blake3_leaves<false>, dim3((uint32_t)div_up_u64(leaf_bound, 256)), dim3(256), (size_t)pad_lds, ctx->stream,
+                               d_data, d_offsets, d_lens, (const uint32_t*)lp, count_bound, d_count, (uint32_t*)cv, (uint32_t*)wf);
+        else
+#endif
+            hipLaunchKernelGGL(k_blake3_leaves<true>, dim3((uint32_t)div_up_u64(leaf_bound, 256)), dim3(256), (size_t)pad_lds, ctx->stream,
+                               d_data, d_offsets, d_lens, (const uint32_t*)lp, count_bound, d_count, (uint32_t*)cv, (uint32_t*)wf);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (small_trees)
