@@ -2,11 +2,6 @@
 #include "lthip_internal.h"
 #include "origin_exec.h"
 
-#include <stdlib.h>
-#include <time.h>
-
-#include <algorithm>
-
 namespace
 {
 
@@ -306,31 +301,15 @@ __device__ __forceinline__ PdTile pd_walk_tile(PdReader& r, int64_t start, const
     return rec;
 }
 
-// What a UNIT decoder (the block-parallel path further down) knows beyond the block: it owns the output range [lo, hi) of the block
-// and starts at a sequence boundary (ip0, op0) at or before lo that k_lz4_pd_link found; all values are wave-uniform.
-struct PdUnit
-{
-    int64_t lo, hi;
-    int64_t ip0, op0;
-    bool last;                // the unit that runs to the end of the payload (hi is not a limit for it)
-    const uint32_t* prev_done; // completion flag of the unit before this one (sources below lo live there)
-    bool defer;                // a source below lo: do not wait for that unit, give the unit up (it is then executed on origins)
-    uint32_t* timeout;         // set when a wait gave up (the block is reported as damaged)
-    volatile uint32_t* dbg;    // LTHIP_LZ4_PD_TRACE: host-visible progress words of this workgroup (else nullptr)
-};
-#define PD_DBG(i, v) do { if (UNIT && un.dbg && lane == 0) un.dbg[i] = (uint32_t)(v); } while (0)
-enum : uint32_t { DEC_ERROR = 0xFFFFFFFFu, DEC_UNIT_OK = 0u, DEC_UNIT_END = 1u, DEC_UNIT_DEFER = 2u };
+enum : uint32_t { DEC_ERROR = 0xFFFFFFFFu };
 
-// One payload (UNIT = false; returns the decoded size or DEC_ERROR) or one unit of it (UNIT = true; returns DEC_UNIT_OK, DEC_UNIT_END
-// when it reached the valid end of the payload, or DEC_ERROR).
+// One payload, decoded by one wave; returns the decoded size or DEC_ERROR.
 // I = index type: int32_t when every payload and capacity of the batch is below 1 GiB (half the scalar work), else int64_t
-template <typename I, bool UNIT>
+template <typename I>
 __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const I n, const I cap,
                                                    const uint32_t dec_nobatch, uint8_t* __restrict__ s_in, uint8_t* __restrict__ s_ring,
-                                                   const int lane, const PdUnit& un)
+                                                   const int lane)
 {
-    const I lo = UNIT ? (I)un.lo : (I)0;
-    const I hi = UNIT && !un.last ? (I)un.hi : cap; // nothing at or past hi is stored by this call
     const uint32_t head = (uint32_t)((uintptr_t)in & 15u);
     const uint8_t* in_al = in - head; // 16-byte aligned; payload byte p sits at aligned offset p + head
     const uint32_t g = (uint32_t)((uintptr_t)out & 15u);
@@ -368,41 +347,9 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
     else if (n > 0)
     {
         I ip = 0, op = 0;
-        I flushed = UNIT ? (lo + (I)g) & ~(I)(DEC_FLUSH - 1u) : (I)0; // aligned output offset (multiple of DEC_FLUSH) up to which the ring has been written out
+        I flushed = 0; // aligned output offset (multiple of DEC_FLUSH) up to which the ring has been written out
         I drained = flushed; // aligned output offset up to which the flush stores are known to have landed
-        // UNIT: everything that crosses to another workgroup is stored write-through and loaded past the L1 (sc1 both sides,
-        // MI355X_MICROARCH.md "inter-workgroup visibility"); a buffer descriptor of the block's output carries the cache bits
-        [[maybe_unused]] __amdgpu_buffer_rsrc_t orsrc;
-        if constexpr (UNIT)
-            orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)out_al, 0, (int)((uint32_t)cap + g), 0x00020000);
-        [[maybe_unused]] bool prev_ready = false, gave_up = false, deferred = false;
-        // sources below lo were written by the unit before this one (an offset is below 64 KiB = one unit): wait for its flag once
-        auto wait_prev = [&]() {
-            if constexpr (UNIT)
-            {
-                if (prev_ready || !un.prev_done)
-                    return;
-                uint32_t spins = 0;
-                while (__hip_atomic_load(un.prev_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-                {
-                    __builtin_amdgcn_s_sleep(32);
-                    if (++spins > (1u << 22)) // seconds: something is broken; report the block as damaged instead of hanging
-                    {
-                        gave_up = true;
-                        if (lane == 0)
-                            __hip_atomic_store(un.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-                prev_ready = true;
-            }
-        };
-        auto out_byte = [&](int64_t q) -> uint8_t { // output byte q of the block from global memory
-            if constexpr (UNIT)
-                return __builtin_amdgcn_raw_buffer_load_b8(orsrc, (int)((uint32_t)q + g), 0, 16);
-            else
-                return out[q];
-        };
+        auto out_byte = [&](int64_t q) -> uint8_t { return out[q]; }; // output byte q of the block from global memory
         I w0 = -1000;  // payload position of lane 0 of the register window
         uint32_t w = 0, wn = 0; // the window and the one 40 bytes further on (fetched while this one is parsed)
 #define RING(q) (((uint32_t)(q) + g) & (DEC_RING - 1u))
@@ -419,18 +366,7 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
                     if (P >= stop)
                         continue;
                     const uint8_t* r = s_ring + ((uint32_t)P & (DEC_RING - 1u));
-                    if constexpr (UNIT)
-                    {
-                        const I first = lo + (I)g, lim = stop < hi + (I)g ? stop : hi + (I)g; // only [lo, hi) is this unit's to store
-                        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                        if (P >= first && P + 16 <= lim)
-                            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(r), orsrc, (int)(uint32_t)P, 0, 16);
-                        else
-                            for (int k = 0; k < 16; ++k)
-                                if (P + k >= first && P + k < lim)
-                                    __builtin_amdgcn_raw_buffer_store_b8(r[k], orsrc, (int)(uint32_t)(P + k), 0, 16);
-                    }
-                    else if (P >= (I)g && P + 16 <= stop)
+                    if (P >= (I)g && P + 16 <= stop)
                         *reinterpret_cast<uint4*>(out_al + (int64_t)P) = *reinterpret_cast<const uint4*>(r);
                     else
                         for (int k = 0; k < 16; ++k)
@@ -480,10 +416,7 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
                 for (I q = 16 * (I)lane; q < bulk; q += 1024)
                 {
                     const u32x4 v = *reinterpret_cast<const u32x4_a1*>(in + (int64_t)(p + q)); // (the payload has any alignment)
-                    if constexpr (UNIT)
-                        __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, (int)(uint32_t)(o + (I)g + q), 0, 16);
-                    else
-                        *reinterpret_cast<u32x4*>(out_al + (int64_t)(o + (I)g + q)) = v;
+                    *reinterpret_cast<u32x4*>(out_al + (int64_t)(o + (I)g + q)) = v;
                 }
                 p += bulk;
                 o += bulk;
@@ -515,23 +448,7 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
                 // segments of <= 2 KiB (out[q] = out[q - off] holds for every q of a match, so a segment is a match of its own;
                 // with that bound no ring slot is overwritten before its last read and before it has been flushed)
                 uint32_t seg = ml < (I)DEC_FLUSH ? (uint32_t)ml : DEC_FLUSH;
-                if (UNIT && op - (I)off < lo)
-                {
-                    // the source starts in the unit before this one: that part (it ends at lo at the latest, so it cannot
-                    // overlap what is written here) comes from global memory once that unit has published its bytes
-                    const I gap = lo - (op - (I)off);
-                    seg = (I)seg < gap ? seg : (uint32_t)gap;
-                    if (un.defer)
-                    {
-                        deferred = true; // (whatever else the caller does with this unit is thrown away)
-                        op += ml;
-                        return;
-                    }
-                    wait_prev();
-                    for (uint32_t j = lane; j < seg; j += 64)
-                        s_ring[RING((uint32_t)op + j)] = out_byte((int64_t)op - off + j);
-                }
-                else if (off <= DEC_RING)
+                if (off <= DEC_RING)
                 {
                     const uint32_t base = (uint32_t)op - off;
                     if (off >= 64u) // a 64-byte step never reads what it writes
@@ -568,152 +485,15 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
             }
             DEC_ACC(2);
         };
-        bool entered = true;
-        if constexpr (UNIT)
-        {
-            if (lo > 0)
-            {
-                // Walk (positions only) from the sequence boundary the link pass handed over to the sequence that covers lo;
-                // sequences that end at or before lo belong to earlier units, which also check them.  The covering sequence is
-                // checked exactly as the general path below checks it and executed from lo on.
-                entered = false;
-                {
-                    PdReader rd;
-                    rd.init(in, (uint32_t)n, s_in, lane);
-                    const PdPos at = pd_walk<true>(rd, un.ip0, (uint64_t)un.op0, INT64_MAX, (uint64_t)lo, (uint64_t)cap);
-                    ip = (I)at.ip; // the covering sequence (or where the chain broke: the loop below reports it)
-                    op = (I)at.op;
-                    wa = -(I)DEC_IN; // the reader went through s_in: nothing the decoder knows about is in it any more
-                    w0 = -1000;
-                }
-                // length bytes after a token nibble of 15; `limit`: the byte at position p may be read while p < limit
-                auto more_len = [&](I& p, I& len, const I limit) -> bool {
-                    for (;;) // 64 length bytes at a time: a block of incompressible data is ONE sequence with 32 K of them
-                    {
-                        if (p >= limit)
-                            return false;
-                        (void)byte_at(p);
-                        const int d = (int)(p - w0);
-                        const uint64_t not255 = __builtin_amdgcn_ballot_w64(w != 255u) >> d;
-                        const int run = not255 ? __builtin_ctzll(not255) : 64 - d; // 255s in front of the terminator (or to the window's end)
-                        if (p + run >= limit)
-                            return false; // one of them, or the terminator, lies at or past the limit
-                        len += (I)(255 * run);
-                        p += run;
-                        if (len > cap)
-                            return false;
-                        if (not255)
-                        {
-                            len += (I)__builtin_amdgcn_readlane(w, d + run);
-                            ++p;
-                            return len <= cap;
-                        }
-                    }
-                };
-                while (ip < n)
-                {
-                    PD_DBG(4, ip);
-                    PD_DBG(5, op);
-                    I p = ip;
-                    const uint32_t token = byte_at(p++);
-                    I len = (I)(token >> 4);
-                    // general path: "ip >= n - 15" before the first length byte, "ip > n - 15" after each = may read while p < n - 15
-                    if (len == 15 && !more_len(p, len, n - 15))
-                        break;
-                    const I lits = p; // payload position of the literals
-                    if (op + len > cap - 12 || p + len > n - 8)
-                    {
-                        // the last sequence of the payload (or damage)
-                        if (p + len != n || op + len > cap || op + len < lo || (!un.last && op + len < hi))
-                            break;
-                        const I a = op > lo ? op : lo;
-                        I c = op + len - a;
-                        if (!un.last && a + c > hi)
-                            c = hi - a;
-                        if (c > 0)
-                            copy_lits(lits + (a - op), a, c);
-                        op += len;
-                        if (un.last)
-                        {
-                            flush(op + (I)g);
-                            result = DEC_UNIT_END;
-                        }
-                        else
-                        {
-                            flush(hi + (I)g);
-                            result = DEC_UNIT_OK;
-                        }
-                        break;
-                    }
-                    p += len;
-                    const I offpos = p;
-                    p += 2;
-                    I ml = (I)(token & 15);
-                    if (ml == 15 && !more_len(p, ml, n - 4)) // general path: "ip >= n - 5 + 1" before every length byte
-                        break;
-                    ml += 4;
-                    if (op + len + ml <= lo)
-                    {
-                        op += len + ml;
-                        ip = p;
-                        continue;
-                    }
-                    const uint32_t off = byte_at(offpos) | (byte_at(offpos + 1) << 8);
-                    if (off == 0 || (I)off > op + len || op + len + ml > cap - 5)
-                        break;
-                    const I lit_end = op + len;
-                    if (lit_end > lo)
-                    {
-                        const I a = op > lo ? op : lo;
-                        I c = lit_end - a;
-                        if (!un.last && a + c > hi)
-                            c = hi - a;
-                        if (c > 0)
-                            copy_lits(lits + (a - op), a, c);
-                    }
-                    op = lit_end > lo ? lit_end : lo;
-                    I rest = ml - (op - lit_end);
-                    if (!un.last && op + rest > hi)
-                        rest = hi - op;
-                    if (rest > 0)
-                        copy_match(off, rest);
-                    else if (rest < 0)
-                        op = hi; // the literals alone reached the end of the unit
-                    ip = p;
-                    entered = true;
-                    break;
-                }
-            }
-        }
         DEC_T0();
-        while (entered)
+        while (true)
         {
-            if (UNIT && deferred)
-                break;
-            if (UNIT && !un.last && op >= hi)
-            {
-                flush(hi + (I)g);
-                result = DEC_UNIT_OK;
-                break;
-            }
             if (ip >= n)
                 break;
             // ---- short sequences (no length bytes, <= 14 literals, match <= 18): everything is in the register window ----
             {
                 I d = ip - w0;
-                if constexpr (UNIT)
-                {
-                    // many waves per CU hide the latency of an LDS read: start every step with the token in lane 0, so that a
-                    // batch sees the whole window (the sliding scheme below is for a lone wave per CU)
-                    if (d != 0)
-                    {
-                        const uint32_t i = need(ip, 64);
-                        w = s_in[i + (uint32_t)lane];
-                        w0 = ip;
-                        d = 0;
-                    }
-                }
-                else if (d > 47 && d < 88) // slide: the prefetched window becomes the current one
+                if (d > 47 && d < 88) // slide: the prefetched window becomes the current one
                 {
                     w = wn;
                     w0 += 40;
@@ -733,47 +513,6 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
                 // token before it), the matches are copied by the tokens' own lanes, all at once when their sources lie before
                 // the batch, otherwise in dependency order.  The conditions are the one-sequence path's, token by token: the first
                 // token that fails any of them ends the batch and is left to the code below (which also decides about errors).
-                // ---- a literal run of 15..269 bytes (ONE length byte) and its match, the wave together: what the general code below does
-                // for such a sequence, without its window re-seeds and loops (it is 8-10 % of the sequences of this library's encoder
-                // and cost half the time).  Same conditions, same verdicts; everything else is left to the general code. ----
-                if constexpr (UNIT)
-                {
-                    const uint32_t tk0 = __builtin_amdgcn_readlane(w, 0); // d == 0 here
-                    const uint32_t e0 = __builtin_amdgcn_readlane(w, 1);
-                    if ((tk0 >> 4) == 15u && e0 != 255u)
-                    {
-                        const I lit = (I)(15u + e0), lp = ip + 2;
-                        I ml = (I)(tk0 & 15u) + 4;
-                        if (ip + 2 <= n - 15 && !(op + lit > cap - 12 || lp + lit > n - 8))
-                        {
-                            const uint32_t i = need(lp, (uint32_t)lit + 3u);
-                            const uint32_t b0 = __builtin_amdgcn_readfirstlane((uint32_t)s_in[i + (uint32_t)lit]),
-                                           b1 = __builtin_amdgcn_readfirstlane((uint32_t)s_in[i + (uint32_t)lit + 1u]),
-                                           b2 = __builtin_amdgcn_readfirstlane((uint32_t)s_in[i + (uint32_t)lit + 2u]);
-                            I adv = 2 + lit + 2;
-                            bool take = true;
-                            if ((tk0 & 15u) == 15u)
-                            {
-                                take = b2 != 255u; // longer matches: general code
-                                ml += (I)b2;
-                                adv += 1;
-                            }
-                            if (take && (un.last || op + lit + ml <= hi))
-                            {
-                                const uint32_t off = b0 | (b1 << 8);
-                                if (off == 0 || (I)off > op + lit || op + lit + ml > cap - 5)
-                                    break;
-                                for (uint32_t j = lane; j < (uint32_t)lit; j += 64)
-                                    s_ring[RING((uint32_t)op + j)] = s_in[i + j];
-                                op += lit;
-                                copy_match(off, ml);
-                                ip += adv;
-                                DEC_CNT(11);
-                                continue;
-                            }
-                        }
-                    }
-                }
                 // (a first token with 15 or more literals is for the general code: do not set a batch up for it)
                 if (d <= 40 && !dec_nobatch && (__builtin_amdgcn_readlane(w, (int)d) >> 4) != 15u)
                 {
@@ -821,7 +560,7 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
                         // the one-sequence path's conditions (a length byte at ipl + 3 + litl <= n - 6 passes the general path's
                         // "ip < n - 4" by construction)
                         const bool bad = tv && (opl + (I)litl > cap - 12 || ipl + 1 + (I)litl > n - 8 || opm + (I)mll > cap - 5 || offl == 0u ||
-                                                (I)offl > opm || (UNIT && opm - (I)offl < lo));
+                                                (I)offl > opm);
                         const uint64_t badm = __builtin_amdgcn_ballot_w64(bad);
                         if (badm)
                             vis &= (1ull << __builtin_ctzll(badm)) - 1ull;
@@ -912,11 +651,8 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
                             {
                                 // the last token's match, by the whole wave (op stands at its first byte)
                                 const uint32_t offc = __builtin_amdgcn_readlane(offl, lastl);
-                                I mlc2 = (I)__builtin_amdgcn_readlane(mll, lastl);
-                                if (UNIT && !un.last && op + mlc2 > hi)
-                                    mlc2 = hi - op;
-                                if (mlc2 > 0)
-                                    copy_match(offc, mlc2);
+                                const I mlc2 = (I)__builtin_amdgcn_readlane(mll, lastl);
+                                copy_match(offc, mlc2);
                             }
                             else if (op + (I)g - flushed >= (I)DEC_FLUSH)
                                 flush((op + (I)g) & ~(I)(DEC_FLUSH - 1u));
@@ -983,26 +719,11 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
             {
                 if (ip + len != n || op + len > cap)
                     break;
-                if (UNIT && !un.last)
-                {
-                    // the payload ends in a later unit: this one stores its part of the literals (and must be filled by them)
-                    if (op + len < hi)
-                        break;
-                    copy_lits(ip, op, hi - op);
-                    op = hi;
-                    continue;
-                }
                 copy_lits(ip, op, len);
                 op += len;
                 flush(op + (I)g);
-                result = UNIT ? (uint32_t)DEC_UNIT_END : (uint32_t)op;
+                result = (uint32_t)op;
                 break;
-            }
-            if (UNIT && !un.last && op + len >= hi)
-            {
-                copy_lits(ip, op, hi - op); // the rest of this sequence belongs to (and is checked by) the next unit
-                op = hi;
-                continue;
             }
             copy_lits(ip, op, len);
             ip += len;
@@ -1036,16 +757,10 @@ __device__ __forceinline__ uint32_t lz4_decode_one(const uint8_t* __restrict__ i
             ml += 4;
             if (op + ml > cap - 5)
                 break;
-            if (UNIT && !un.last && op + ml > hi)
-                ml = hi - op;
             copy_match(off, ml);
             DEC_CNT(11);
         }
         DEC_ACC(0);
-        if (gave_up)
-            result = DEC_ERROR;
-        if (UNIT && deferred)
-            result = DEC_UNIT_DEFER;
 #undef RING
     }
     return result;
@@ -1063,8 +778,7 @@ __global__ __launch_bounds__(64) void k_lz4_decode_lds(const uint8_t* __restrict
         return;
     const int lane = threadIdx.x;
     const Lz4Block blk = blocks[b];
-    const uint32_t result = lz4_decode_one<I, false>(src + blk.src_off, dst + blk.dst_off, (I)blk.size, (I)blk.dst_cap, dec_nobatch, s_in,
-                                                     s_ring, lane, PdUnit{});
+    const uint32_t result = lz4_decode_one<I>(src + blk.src_off, dst + blk.dst_off, (I)blk.size, (I)blk.dst_cap, dec_nobatch, s_in, s_ring, lane);
     if (lane == 0)
         out_sizes[blk.out_index] = result;
 }
@@ -1073,21 +787,26 @@ __global__ __launch_bounds__(64) void k_lz4_decode_lds(const uint8_t* __restrict
 // Block-parallel decoding.  A block is a serial object only at the level of WHERE things are: the position of a token follows from the
 // token before it and the output position from all the lengths so far.  Those positions are found first, by many waves, and then
 // the block is decoded in UNITS of 64 KiB of output, one wave each:
-//   1. k_lz4_pd_tiles   one wave per 8 KiB TILE of the payload follows the chain of tokens (lengths only, nothing is copied) from 512
+//   1. k_lz4_pd_first   one wave per block reads the block's first sequence: where it ends and where its literals lie.  A block of
+//                       incompressible data is ONE sequence; the tiles and units that lie inside it need no walk.
+//   2. k_lz4_pd_tiles   one wave per 8 KiB TILE of the payload follows the chain of tokens (lengths only, nothing is copied) from 512
 //                       bytes before its tile -- a guess -- and records where the chain enters the tile, where it leaves it and how
 //                       many bytes the sequences in between produce.  Chains that start at different positions merge as soon as
 //                       they hit a common token, so for the true entry the guess is almost always what was recorded.
-//   2. k_lz4_pd_link    one wave per block hops from tile to tile along the true chain (payload position and output position
-//                       known): a tile whose recorded entry is the true one costs a table look-up, any other tile is walked again
-//                       from the true position.  It writes the output position of every tile entry and, for every unit, the tile
-//                       in which the sequence covering the unit's first byte lives.
-//   3. k_lz4_pd_units   one wave per unit (persistent workgroups drawing tickets): walks from its tile's entry to the sequence
-//                       that covers its first output byte and decodes with lz4_decode_one<UNIT> what falls into [lo, hi).  A match
-//                       that reaches below lo reads what the unit before wrote (offsets are below 64 KiB): it waits for that
-//                       unit's flag -- tickets are drawn unit-major, so whatever a unit waits for was drawn before it and is
-//                       running or done.  Payloads of this library's encoder never wait (matches stay inside 64 KiB groups);
-//                       a payload with a sliding window decodes as a chain of units, about as fast as the serial decoder.
-//   4. k_lz4_pd_finish  result per block: the size the link pass found if every unit agreed, else the error value.
+//   3. k_lz4_pd_patch   a second guess for the tiles whose recorded entry is not where the chain of the tile before leaves it: walked
+//                       again from there, all such tiles at once, into the tile's alternative record.
+//   4. k_lz4_pd_link    one wave per block hops from tile to tile along the true chain (payload position and output position
+//                       known): a tile whose recorded entry (or alternative) is the true one costs a table look-up, any other tile is
+//                       walked again from the true position.  It writes the output position of every tile entry and, for every unit,
+//                       the tile in which the sequence covering the unit's first byte lives.
+//   5. k_lz4_po_trace<true>   one wave per unit, every unit of the call at once: walks from its tile's entry to the sequence that
+//                       covers its first output byte and executes what falls into [lo, hi), bytes straight into the block's output.
+//                       A unit that meets a source below lo (offsets are below 64 KiB: the unit before) stops and is marked.
+//                       Payloads of this library's encoder are never marked (matches stay inside 64 KiB groups).
+//   6. k_lz4_po_trace<false> + k_lz4_po_gather   the marked units (a payload with a sliding window) on ORIGINS (origin_exec.h): the
+//                       same walk records where every output byte comes from, then the bytes are gathered, unit k of every block
+//                       in launch k.
+//   7. k_lz4_pd_finish  result per block: the size the link pass found if every unit agreed, else the error value.
 // Every check of the serial decoder is made by the unit that executes the sequence (with the true positions), the positional ones
 // also by the link pass; the results (size or error) are the serial decoder's.
 // ---------------------------------------------------------------------------------------------------
@@ -1310,32 +1029,16 @@ __global__ __launch_bounds__(64) void k_lz4_pd_link(const uint8_t* __restrict__ 
     }
 }
 
-// ticket -> (unit row, block): blocks sorted by descending unit capacity, row k holds the blocks with more than k units
-struct PdTickets
-{
-    const uint32_t* order;    // block indices, most units first
-    const uint32_t* row_base; // first ticket of row k, k = 0 .. rows (row_base[rows] = number of tickets)
-    uint32_t rows;
-    uint32_t total;
-    uint32_t uniform; // != 0: every block has `rows` units (ticket = row * uniform + block)
-};
-
-#ifdef LTHIP_ABLATIONS
-#include "ablations/k_lz4_pd_units.inc"
-#endif
-
-
 // ---------------------------------------------------------------------------------------------------
-// Units given up by k_lz4_pd_units because a match reaches into the unit before (a payload with a sliding window: the reference's
-// parse), executed on ORIGINS (origin_exec.h): k_lz4_po_trace, one wave per such unit, all of them at once -- the unit's sequences
-// from the one that covers its first byte, clipped to [lo, hi), 64 at a time: a literal's origin is its position in the payload, a
-// source byte below lo becomes its output position -- then k_lz4_po_gather, launch k for unit k of every block.  The checks are
-// the serial decoder's (lz4.c:1979-2250), made with the true positions by the unit that holds the sequence's end, as in
-// lz4_decode_one<UNIT>.
+// The unit decoder of the block-parallel path: one wave per unit, all of them at once -- the unit's sequences from the one that
+// covers its first byte, clipped to [lo, hi), 64 at a time.  The checks are the serial decoder's (lz4.c:1979-2250), made with the
+// true positions by the unit that holds the sequence's end.
+//   BYTES = true   every unit of the call: the batch is executed as bytes (zo_batch_bytes) straight into the block's output.  A unit
+//                  that meets a source below its start (a payload with a sliding window: the reference's parse) stops and is marked
+//                  for the origin pass.
+//   BYTES = false  the marked units, on ORIGINS (origin_exec.h): a literal's origin is its position in the payload, a source byte
+//                  below lo becomes its output position; k_lz4_po_gather then fetches the bytes, launch k for unit k of every block.
 // ---------------------------------------------------------------------------------------------------
-// BYTES (round 3, last part): the same walk for EVERY unit, executing bytes (zo_batch_bytes) straight into the block's output -- the
-// unit decoder of the block-parallel path since then (k_lz4_pd_units / lz4_decode_one<UNIT> stays as LTHIP_LZ4_PX=0): a unit that meets
-// a source below its start stops and is marked for the origin pass, which is this kernel with BYTES = false.
 template <bool BYTES>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lz4_po_trace(const uint8_t* __restrict__ src, const PdBlock* __restrict__ blocks, uint32_t nblocks,
                                                     uint32_t unit0, const PdTile* __restrict__ tiles, const uint32_t* __restrict__ tile_op,
@@ -1667,16 +1370,14 @@ extern "C" __attribute__((visibility("default"))) int lthip_dec_prof_dump(void)
 }
 #endif
 
-// The block-parallel path for the blocks listed in `idx` (see the comment above k_lz4_pd_tiles).
+// The block-parallel path for the blocks listed in `idx` (see the comment above PdState).
 static int lz4_decompress_parallel(lthip_ctx* ctx, const void* d_src, const std::vector<uint32_t>& idx, const uint64_t* src_offsets,
                                    const uint32_t* src_sizes, void* d_dst, const uint64_t* dst_offsets, const uint32_t* dst_caps,
-                                   uint32_t* d_out_sizes, uint32_t nobatch)
+                                   uint32_t* d_out_sizes)
 {
     const uint32_t nb = (uint32_t)idx.size();
     std::vector<PdBlock> hb(nb);
     uint64_t ntiles = 0, nunits = 0;
-    uint32_t rows = 0;
-    bool small = true, uniform = true;
     for (uint32_t i = 0; i < nb; ++i)
     {
         const uint32_t b = idx[i];
@@ -1693,63 +1394,38 @@ static int lz4_decompress_parallel(lthip_ctx* ctx, const void* d_src, const std:
         pb.pad = 0;
         ntiles += pb.ntiles;
         nunits += pb.nunits_cap;
-        rows = pb.nunits_cap > rows ? pb.nunits_cap : rows;
-        uniform = uniform && pb.nunits_cap == hb[0].nunits_cap;
-        small = small && src_sizes[b] < (1u << 30) && dst_caps[b] < (1u << 30);
     }
     if (ntiles > 0x7FFFFFF0ull || nunits > 0x7FFFFFF0ull)
         return lthip_fail(ctx, EINVAL, "lz4", "too many blocks in one decode call");
-    // tickets: unit-major (every block's unit k before any block's unit k + 1), so that a unit only ever waits for lower tickets
-    std::vector<uint32_t> order(nb), row_base((size_t)rows + 1, 0u);
-    if (!uniform)
-    {
-        for (uint32_t i = 0; i < nb; ++i)
-            order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return hb[x].nunits_cap > hb[y].nunits_cap; });
-        std::vector<uint32_t> more((size_t)rows + 1, 0u); // more[k] = blocks with exactly k units, then suffix sums
-        for (uint32_t i = 0; i < nb; ++i)
-            ++more[hb[i].nunits_cap];
-        uint32_t with_more = 0; // blocks with more than k units, for k = rows - 1 .. 0
-        std::vector<uint32_t> count(rows, 0u);
-        for (uint32_t k = rows; k-- > 0;)
-        {
-            with_more += more[(size_t)k + 1];
-            count[k] = with_more;
-        }
-        for (uint32_t k = 0; k < rows; ++k)
-            row_base[(size_t)k + 1] = row_base[k] + count[k];
-    }
-    // device tables: [PdTile x ntiles][tile_op x ntiles][unit_tile x nunits][state x nb][order x nb][row_base x rows+1][done x nunits][counters x 8][first_end, first literals' position and count x nb][alt PdTile x ntiles][claim x ntiles]
+    // device tables: [tiles: PdTile x ntiles][tile_op x ntiles][unit_tile x nunits][state: PdState x nb][counters x 8]
+    //                [first: end of the first sequence, its literals' position and count x nb]
+    //                [alt: PdTile x ntiles, 16-byte aligned][claim x ntiles][mode x nunits]
+    // counters: [2] units given up, [4] [5] [6] [7] the link pass's statistics (LTHIP_LZ4_PD_STATS); the others are not used
     const size_t o_tiles = 0, o_top = o_tiles + sizeof(PdTile) * ntiles, o_ut = o_top + 4 * ntiles, o_state = o_ut + 4 * nunits,
-                 o_order = o_state + sizeof(PdState) * nb, o_rows = o_order + 4 * (size_t)nb, o_done = o_rows + 4 * ((size_t)rows + 1),
-                 o_cnt = o_done + 4 * nunits, o_first = o_cnt + 32, o_alt = (o_first + 12 * (size_t)nb + 15) & ~(size_t)15, o_claim = o_alt + sizeof(PdTile) * ntiles,
-                 o_mode = o_claim + 4 * ntiles, o_end = o_mode + 4 * nunits;
+                 o_cnt = o_state + sizeof(PdState) * nb, o_first = o_cnt + 32, o_alt = (o_first + 12 * (size_t)nb + 15) & ~(size_t)15,
+                 o_claim = o_alt + sizeof(PdTile) * ntiles, o_mode = o_claim + 4 * ntiles, o_end = o_mode + 4 * nunits;
     void *tab, *blk;
     int err = lthip_scratch(ctx, S_LZ4_STREAM, o_end, &tab);
     if (!err)
         err = lthip_scratch(ctx, S_LZ4_META, sizeof(PdBlock) * (size_t)nb, &blk);
     if (!err)
         err = lthip_stage_upload(ctx, blk, hb.data(), sizeof(PdBlock) * (size_t)nb, ctx->stream);
-    if (!err && !uniform)
-    {
-        err = lthip_stage_upload(ctx, (uint8_t*)tab + o_order, order.data(), 4 * (size_t)nb, ctx->stream);
-        if (!err)
-            err = lthip_stage_upload(ctx, (uint8_t*)tab + o_rows, row_base.data(), 4 * ((size_t)rows + 1), ctx->stream);
-    }
     if (err)
         return err;
     uint8_t* t8 = (uint8_t*)tab;
-    LTHIP_CHECK(ctx, hipMemsetAsync(t8 + o_done, 0, o_first - o_done, ctx->stream));
-    LTHIP_CHECK(ctx, hipMemsetAsync(t8 + o_alt, 0xFF, sizeof(PdTile) * ntiles, ctx->stream)); // entry = PD_NONE
-    LTHIP_CHECK(ctx, hipMemsetAsync(t8 + o_claim, 0, 4 * ntiles + 4 * nunits, ctx->stream)); // flags and counters: zero before every launch
+    // zero before every call: the counters, the claims and the units' modes; alt: entry = PD_NONE.  (tiles, tile_op, unit_tile, state
+    // and first are written by the kernels before anything reads them.)
+    LTHIP_CHECK(ctx, hipMemsetAsync(t8 + o_cnt, 0, o_first - o_cnt, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemsetAsync(t8 + o_alt, 0xFF, o_claim - o_alt, ctx->stream));
+    LTHIP_CHECK(ctx, hipMemsetAsync(t8 + o_claim, 0, o_end - o_claim, ctx->stream));
     const PdBlock* d_blocks = (const PdBlock*)blk;
     PdTile* d_tiles = (PdTile*)(t8 + o_tiles);
     uint32_t* d_top = (uint32_t*)(t8 + o_top);
     uint32_t* d_ut = (uint32_t*)(t8 + o_ut);
     PdState* d_state = (PdState*)(t8 + o_state);
-    uint32_t* d_done = (uint32_t*)(t8 + o_done);
     uint32_t* d_cnt = (uint32_t*)(t8 + o_cnt);
     uint32_t* d_first = (uint32_t*)(t8 + o_first);
+    uint32_t* d_mode = (uint32_t*)(t8 + o_mode);
     LTHIP_ABLATION_ENV(env_stats, "LTHIP_LZ4_PD_STATS");
     LTHIP_ABLATION_ENV(env_trace, "LTHIP_LZ4_PD_TRACE"); // debugging: synchronize and report after every launch
     const bool stats = env_stats.get() >= 0, trace = env_trace.get() >= 0;
@@ -1776,113 +1452,53 @@ static int lz4_decompress_parallel(lthip_ctx* ctx, const void* d_src, const std:
                        d_state, stats ? d_cnt + 4 : nullptr);
     LTHIP_LAUNCH_CHECK(ctx);
     PD_TRACE("link");
-    PdTickets tk;
-    tk.order = (const uint32_t*)(t8 + o_order);
-    tk.row_base = (const uint32_t*)(t8 + o_rows);
-    tk.rows = rows;
-    tk.total = uniform ? rows * nb : row_base[rows];
-    tk.uniform = uniform ? nb : 0u;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    LTHIP_ABLATION_ENV(env_per_cu, "LTHIP_LZ4_PD_WG_PER_CU");
-    const uint32_t per_cu = (uint32_t)(env_per_cu.get() > 0 ? env_per_cu.get() : 16); // 10 KiB of LDS each
-    const uint64_t resident = (uint64_t)ncu * per_cu;
-    const uint32_t grid = (uint32_t)(tk.total < resident ? tk.total : resident);
-    volatile uint32_t* dbg = nullptr;
-    if (trace)
-    {
-        void* hp = nullptr;
-        LTHIP_CHECK(ctx, lthip_hip_host_malloc(&hp, 32 * (size_t)grid, hipHostMallocMapped));
-        memset(hp, 0, 32 * (size_t)grid);
-        dbg = (volatile uint32_t*)hp; // host-visible progress words, freed below once the kernel is through
-    }
-    // LTHIP_LZ4_PD_WAIT=1: round 2's way -- a unit whose matches reach into the unit before WAITS for it (a chain of units)
-    LTHIP_ABLATION_ENV(env_wait, "LTHIP_LZ4_PD_WAIT");
-    const bool wait_mode = env_wait.get() > 0;
-    uint32_t* d_mode = wait_mode ? nullptr : (uint32_t*)(t8 + o_mode);
-    LTHIP_ABLATION_ENV(env_px, "LTHIP_LZ4_PX"); // 0: the unit decoder of round 2 (lz4_decode_one<UNIT> through an LDS ring: ablations/k_lz4_pd_units.inc)
-    const bool px = d_mode && env_px.get() != 0;
-#ifndef LTHIP_ABLATIONS
-    (void)d_done;
-    (void)grid;
-    (void)dbg;
-    (void)small;
-    (void)nobatch;
-#endif
-    if (px)
-        hipLaunchKernelGGL(k_lz4_po_trace<true>, dim3((uint32_t)nunits), dim3(64), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, nb, 0u,
-                           (const PdTile*)d_tiles, (const uint32_t*)d_top, (const uint32_t*)d_ut, d_state, d_mode, (uint32_t*)nullptr,
-                           (uint8_t*)d_dst, (const uint32_t*)d_first, d_cnt);
-#ifdef LTHIP_ABLATIONS
-    else if (small)
-        hipLaunchKernelGGL(k_lz4_pd_units<int32_t>, dim3(grid), dim3(64), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, (uint8_t*)d_dst, d_tiles,
-                           d_top, d_ut, d_state, d_done, d_cnt, tk, nobatch, dbg, (const uint32_t*)d_first, d_mode);
-    else
-        hipLaunchKernelGGL(k_lz4_pd_units<int64_t>, dim3(grid), dim3(64), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, (uint8_t*)d_dst, d_tiles,
-                           d_top, d_ut, d_state, d_done, d_cnt, tk, nobatch, dbg, (const uint32_t*)d_first, d_mode);
-#endif
+    hipLaunchKernelGGL(k_lz4_po_trace<true>, dim3((uint32_t)nunits), dim3(64), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, nb, 0u,
+                       (const PdTile*)d_tiles, (const uint32_t*)d_top, (const uint32_t*)d_ut, d_state, d_mode, (uint32_t*)nullptr,
+                       (uint8_t*)d_dst, (const uint32_t*)d_first, d_cnt);
     LTHIP_LAUNCH_CHECK(ctx);
-    if (d_mode)
-    {
-        // units that were given up (a payload with a sliding window): on origins, as many blocks at a time as the arena's budget
-        // allows (4 bytes per byte of output; LTHIP_ORIGIN_MIB, default: lthip_origin_budget_mib).  The one place where this call waits for the device.
-        uint32_t given_up = 0;
-        LTHIP_CHECK(ctx, hipMemcpyAsync(&given_up, d_cnt + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-        LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        if (given_up)
-        {
-            const uint64_t budget_units = (lthip_origin_budget_mib() << 20) / ((uint64_t)PD_UNIT * 4u);
-            uint64_t most = 0;
-            for (uint32_t g0 = 0; g0 < nb;)
-            {
-                uint64_t units = hb[g0].nunits_cap;
-                uint32_t g1 = g0 + 1;
-                while (g1 < nb && units + hb[g1].nunits_cap <= budget_units)
-                    units += hb[g1++].nunits_cap;
-                most = units > most ? units : most;
-                g0 = g1;
-            }
-            void* d_org;
-            if ((err = lthip_scratch(ctx, S_Z_ORG, (size_t)most * PD_UNIT * 4u + 256, &d_org)))
-                return err;
-            for (uint32_t g0 = 0; g0 < nb;)
-            {
-                uint64_t units = hb[g0].nunits_cap;
-                uint32_t g1 = g0 + 1, rows_g = hb[g0].nunits_cap;
-                while (g1 < nb && units + hb[g1].nunits_cap <= budget_units)
-                {
-                    rows_g = hb[g1].nunits_cap > rows_g ? hb[g1].nunits_cap : rows_g;
-                    units += hb[g1++].nunits_cap;
-                }
-                hipLaunchKernelGGL(k_lz4_po_trace<false>, dim3((uint32_t)units), dim3(64), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, nb, hb[g0].unit_base,
-                                   (const PdTile*)d_tiles, (const uint32_t*)d_top, (const uint32_t*)d_ut, d_state, d_mode, (uint32_t*)d_org,
-                                   (uint8_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-                LTHIP_LAUNCH_CHECK(ctx);
-                for (uint32_t k = 1; k < rows_g; ++k) // (unit 0 has nothing before it)
-                    hipLaunchKernelGGL(k_lz4_po_gather, dim3(PD_UNIT / 4096u, g1 - g0), dim3(256), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, g0, k,
-                                       hb[g0].unit_base, (const PdState*)d_state, (const uint32_t*)d_mode, (const uint32_t*)d_org, (uint8_t*)d_dst);
-                LTHIP_LAUNCH_CHECK(ctx);
-                g0 = g1;
-            }
-            PD_TRACE("origins");
-        }
-    }
-    if (trace)
-    {
-        for (int sec = 0; sec < 5 && hipStreamQuery(ctx->stream) == hipErrorNotReady; ++sec)
-        {
-            struct timespec ts = {1, 0};
-            nanosleep(&ts, nullptr);
-            fprintf(stderr, "units after %d s:", sec + 1);
-            for (uint32_t w = 0; w < grid && w < 8; ++w)
-                fprintf(stderr, " [t%u k%u ip0 %u op0 %u | pre %x %x | main %x %u]", dbg[w * 8], dbg[w * 8 + 1], dbg[w * 8 + 2], dbg[w * 8 + 3],
-                        dbg[w * 8 + 4], dbg[w * 8 + 5], dbg[w * 8 + 6], dbg[w * 8 + 7]);
-            fprintf(stderr, "\n");
-        }
-    }
     PD_TRACE("units");
-    if (dbg)
-        (void)hipHostFree((void*)dbg); // (PD_TRACE synchronised the stream)
+    // units that were given up (a payload with a sliding window): on origins, as many blocks at a time as the arena's budget
+    // allows (4 bytes per byte of output; LTHIP_ORIGIN_MIB, default: lthip_origin_budget_mib).  The one place where this call waits for the device.
+    uint32_t given_up = 0;
+    LTHIP_CHECK(ctx, hipMemcpyAsync(&given_up, d_cnt + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+    LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
+    if (given_up)
+    {
+        const uint64_t budget_units = (lthip_origin_budget_mib() << 20) / ((uint64_t)PD_UNIT * 4u);
+        uint64_t most = 0;
+        for (uint32_t g0 = 0; g0 < nb;)
+        {
+            uint64_t units = hb[g0].nunits_cap;
+            uint32_t g1 = g0 + 1;
+            while (g1 < nb && units + hb[g1].nunits_cap <= budget_units)
+                units += hb[g1++].nunits_cap;
+            most = units > most ? units : most;
+            g0 = g1;
+        }
+        void* d_org;
+        if ((err = lthip_scratch(ctx, S_Z_ORG, (size_t)most * PD_UNIT * 4u + 256, &d_org)))
+            return err;
+        for (uint32_t g0 = 0; g0 < nb;)
+        {
+            uint64_t units = hb[g0].nunits_cap;
+            uint32_t g1 = g0 + 1, rows_g = hb[g0].nunits_cap;
+            while (g1 < nb && units + hb[g1].nunits_cap <= budget_units)
+            {
+                rows_g = hb[g1].nunits_cap > rows_g ? hb[g1].nunits_cap : rows_g;
+                units += hb[g1++].nunits_cap;
+            }
+            hipLaunchKernelGGL(k_lz4_po_trace<false>, dim3((uint32_t)units), dim3(64), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, nb, hb[g0].unit_base,
+                               (const PdTile*)d_tiles, (const uint32_t*)d_top, (const uint32_t*)d_ut, d_state, d_mode, (uint32_t*)d_org,
+                               (uint8_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+            LTHIP_LAUNCH_CHECK(ctx);
+            for (uint32_t k = 1; k < rows_g; ++k) // (unit 0 has nothing before it)
+                hipLaunchKernelGGL(k_lz4_po_gather, dim3(PD_UNIT / 4096u, g1 - g0), dim3(256), 0, ctx->stream, (const uint8_t*)d_src, d_blocks, g0, k,
+                                   hb[g0].unit_base, (const PdState*)d_state, (const uint32_t*)d_mode, (const uint32_t*)d_org, (uint8_t*)d_dst);
+            LTHIP_LAUNCH_CHECK(ctx);
+            g0 = g1;
+        }
+        PD_TRACE("origins");
+    }
     hipLaunchKernelGGL(k_lz4_pd_finish, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, d_blocks, nb, d_state, d_out_sizes);
     LTHIP_LAUNCH_CHECK(ctx);
     if (stats)
@@ -1890,8 +1506,8 @@ static int lz4_decompress_parallel(lthip_ctx* ctx, const void* d_src, const std:
         uint32_t h[8] = {0};
         LTHIP_CHECK(ctx, hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        fprintf(stderr, "lz4 parallel decode: %u blocks, %llu tiles (%u walked again by the link pass), %llu units, %u tickets, timeouts %u\n", nb,
-                (unsigned long long)ntiles, h[4], (unsigned long long)nunits, tk.total, h[1]);
+        fprintf(stderr, "lz4 parallel decode: %u blocks, %llu tiles (%u walked again by the link pass), %llu units\n", nb,
+                (unsigned long long)ntiles, h[4], (unsigned long long)nunits);
         fprintf(stderr, "   link pass: %u Kcycles in all, %u Kcycles walking tiles again (summed over the blocks)\n", h[7], h[6]);
     }
     return 0;
@@ -1937,7 +1553,7 @@ extern "C" int lthip_lz4_decompress_blocks(lthip_ctx* ctx, const void* d_src, ui
     }
     LaunchTimer t(ctx, LTHIP_K_OTHER);
     int err = 0;
-    if (!par.empty() && (err = lz4_decompress_parallel(ctx, d_src, par, src_offsets, src_sizes, d_dst, dst_offsets, dst_caps, d_out_sizes, nobatch)))
+    if (!par.empty() && (err = lz4_decompress_parallel(ctx, d_src, par, src_offsets, src_sizes, d_dst, dst_offsets, dst_caps, d_out_sizes)))
         return err;
     if (hb.empty())
         return 0;

@@ -221,7 +221,9 @@ __global__ __launch_bounds__(64) void k_zstd_sub_entropy(const uint8_t* __restri
     for (;;)
     {
         // Pieces cost very different amounts (raw units next to units full of sequences): the persistent waves draw them from a
-        // counter.  (Every lane takes part in the draw -- lane 0 adds one, the others zero -- see k_lz4_pd_units for why.)
+        // counter.  Every lane takes part in the draw (lane 0 adds one, the others zero; the compiler turns it into one atomic per
+        // wave).  With "if (lane == 0) t = atomicAdd(..)" hipcc (ROCm 7.2) threaded such a loop: lane 0 and the other 63 lanes came
+        // back to the loop head separately, the 63 with t = 0, and worked on ticket 0 a second time without lane 0 -- a hang.
         __builtin_amdgcn_wave_barrier();
         uint32_t t = atomicAdd(ticket, lane == 0 ? 1u : 0u);
         t = __builtin_amdgcn_readfirstlane(t);

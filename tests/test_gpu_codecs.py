@@ -805,7 +805,7 @@ def test_origin_execution_is_the_chained_execution(gpu_abl, oracle, ref, monkeyp
     frames of the reference encoder -- are executed on ORIGINS (origin_exec.h: k_lz4_po_trace/_gather, k_zstd_fr_reps/_chain/_trace/
     _gather).  Chain-heavy data (every token / record / line repeats an earlier one: the closure of what depends on the piece before
     is the whole piece), a block of 8 MiB + 5, repeat offsets at block starts, raw and RLE blocks inside frames, two arena budgets
-    (several groups per call).  Same sizes and bytes as round 2's execution (a unit waits for the unit before: LTHIP_LZ4_PD_WAIT=1;
+    (several groups per call).  Same sizes and bytes as the serial execution (every LZ4 block on one wave: LTHIP_LZ4_SERIAL_DECODER=1;
     a frame's blocks one after the other on one wave: LTHIP_ZSTD_DBG=16) and as the data."""
     rng = np.random.default_rng(77)
     raws = [oracle.synth(n, 500 + k, k) for k, n in ((12, (8 << 20) + 5), (11, 3 << 20), (13, 2 << 20), (1, 5 << 20), (12, 131073), (2, 1 << 20))]
@@ -831,10 +831,10 @@ def test_origin_execution_is_the_chained_execution(gpu_abl, oracle, ref, monkeyp
         results["zstd", budget] = gpu_zstd_decode(gpu, zs, caps)
         n_pay, n_blocks, n_back, _ = gpu.zstd_last_decode_stats()
         assert n_pay == len(zs) and n_back == 0 and n_blocks >= sum((c + 131071) // 131072 for c in caps)
-    monkeypatch.setenv("LTHIP_LZ4_PD_WAIT", "1")
+    monkeypatch.setenv("LTHIP_LZ4_SERIAL_DECODER", "1")
     monkeypatch.setenv("LTHIP_ZSTD_DBG", "16")
     gpu.lib.dll.lthip_debug_reload_env()
-    results["lz4", "chained"] = run_lz4()
+    results["lz4", "serial"] = run_lz4()
     results["zstd", "chained"] = gpu_zstd_decode(gpu, zs, caps)
     for key, outs in results.items():
         for i, (o, r) in enumerate(zip(outs, raws)):
