@@ -1030,8 +1030,8 @@ LTHIP_EXPORT int lthip_restore_carry_in_place(lthip_restore* restore, void* d_bu
  *                  when windows were given.  Deterministic: every rank can compute every rank's table, which is what puts a file
  *                  together again from the ranks' buffers.
  * Out of scope: windows together with a base (create_from_base, carry, carry_in_place); decoding only the part of a tagged block that a
- * window needs -- a block is decoded whole, as the reference's ReadFromBlock does, so the cost follows the blocks needed; a cache of
- * decoded blocks between sessions -- the reference puts lib/lrublockstore in front for that. */
+ * window needs -- a block is decoded whole, as the reference's ReadFromBlock does, so the cost follows the blocks needed.  What a
+ * caller that reads in successive windows would decode twice stays decoded in a cache: "a cache of decoded blocks", below. */
 typedef struct lthip_restore_window
 {
     uint32_t asset;    /* index into the VersionIndex's assets */
@@ -1054,6 +1054,67 @@ LTHIP_EXPORT int lthip_restore_asset_sizes(const void* version_index, size_t ver
 LTHIP_EXPORT int lthip_restore_rank_windows(uint64_t job_count, const uint32_t* job_asset, const uint64_t* job_offset, const uint64_t* job_size,
                                             const uint32_t* job_rank, uint32_t rank, uint64_t align, lthip_restore_window* windows,
                                             uint64_t capacity, uint64_t* window_count, uint64_t* out_bytes);
+
+/* ---- a cache of decoded blocks for the restore sessions (restore.hip, block_cache.h) ---------------------------------------------------
+ * The device side of the reference's lib/lrublockstore, which it puts in front of its ranged reads: a set of decoded blocks in HBM that
+ * outlives a session.  Good blocks delivered to a session with a cache stay resident; a later session on the same context finds its
+ * needed blocks there, asks the caller only for the rest, and scatters the cached ones without fetching or decoding them again.  It
+ * pays for successive windows (a boundary block is decoded once), for several passes over one version, and for images that live on
+ * the host; it costs a copy per raw block and pays nothing for one full restore.  A session without a cache runs exactly as before.
+ *   create         slot_count slots of slot_bytes rounded up to a multiple of 64, ONE device allocation of slot_count x that.  EINVAL: a
+ *                  NULL context or out, 0 slots, 0 bytes.  ENOMEM: nothing stays allocated, the context stays usable.  A cache belongs
+ *                  to one context (and its thread); it is destroyed after every session attached to it and before the context.
+ *   entries        an entry is a block's chunks back to back (raw size bytes) at the start of a slot, keyed by (hash identifier, block
+ *                  hash).  It keeps the block's chunk count, raw size, a 64-bit digest of its (chunk hash, chunk size) table as the
+ *                  StoreIndex lists it (FNV-1a, block_cache.h), and whether the session that wrote it verified the chunks.  A block
+ *                  whose raw size exceeds the slot size is never cached.  Replacement is strict LRU over the entries that no live
+ *                  session reads (PINNED) and the slots no session is writing (RESERVED); an entry is USED by the set_cache that hit it
+ *                  and by the finish that made it visible, numbered by one host counter.  All bookkeeping is host code.
+ *   contains       host only.  held[i] = 1 when block_hashes[i] has a visible entry under hash_identifier.
+ *   clear          every entry goes.  EBUSY, and nothing changes, while an entry is pinned or a slot is reserved.
+ *   stats          out = {slots, slot bytes, resident entries, pinned entries, reserved slots, blocks hit, blocks inserted, entries
+ *                  evicted, blocks bypassed, blocks dropped as bad} -- the last five summed since create.
+ *   set_cache      once per session, after create and before the first blocks call; every kind of session takes it (whole assets,
+ *                  windows, from a base, in place).  EEXIST: a second call.  EINVAL: NULL arguments, a cache of another context, or a
+ *                  blocks call has queued work.  ENOMEM: the session's own small device tables; the session stays without a cache.
+ *                  Every needed block is looked up: it is CACHE-FED when a visible entry has its key, chunk count, raw size and
+ *                  digest -- and, for a verify session, was written by a verify session.  A verified entry is trusted as it lies and
+ *                  is not hashed again, as the reference's LRU store trusts its blocks.  Cache-fed entries are pinned until finish
+ *                  returns 0 or the session is destroyed.  needed_blocks, result.blocks_needed and scratch_bound shrink to the blocks
+ *                  that are not cache-fed; a cache-fed block delivered anyway is accepted, counted as unneeded and not touched.
+ *   from_cache     queues the scatter of every planned occurrence of the cache-fed blocks from their slots to d_out, on the context's
+ *                  stream: it never waits, reads nothing back and is timed as LTHIP_K_GATHER.  Once per session (EEXIST), in any order
+ *                  with blocks calls; EINVAL without a cache.  For an update in place it counts as a blocks call: after carry_in_place
+ *                  d_out must be that buffer, and carry_in_place after it is EINVAL.  With no cache-fed block it queues nothing and
+ *                  returns 0.  finish returns ENOENT while cache-fed blocks exist and from_cache has not been called (EBADF keeps
+ *                  precedence); result.occurrences_written and bytes_written count the cache-fed occurrences once it was.
+ *   blocks         with a cache, every needed block of the call reserves a slot when it fits one: the slot of its own entry when that
+ *                  does not match (another StoreIndex, not verified) and is not pinned, else a free slot, else the least recently
+ *                  used entry that is neither pinned nor reserved.  A tagged block is decoded INTO its slot instead of the scratch (no
+ *                  copy; the decoders' capacity is the raw size, so nothing is written outside a slot).  A raw block's payload is
+ *                  copied into its slot by k_restore_cache_copy behind the check, only when its status word is 0: no 4-byte word is
+ *                  read that holds no byte of a chunk, and nothing of an image that is not exactly header + raw size.  A block that
+ *                  gets no slot is BYPASSED and goes through the scratch as before; the output is the same either way.  The scratch
+ *                  a call demands stays lthip_restore_scratch_bound, the worst case: a caller never predicts what the cache takes.
+ *   finish         a reserved slot is invisible.  finish, which reads the status words anyway, COMMITS every reserved block whose
+ *                  status is 0 -- it becomes visible, verified = the session's verify setting -- and releases every other one.  When
+ *                  two sessions reserved the same block, the later commit replaces the earlier entry, or is dropped when that entry
+ *                  is pinned.  Destroying a session that did not finish releases its reservations and pins.
+ *   cache_stats    out = {cache-fed blocks, their raw bytes, blocks inserted, blocks bypassed (too large, or no slot to be had), inserted
+ *                  blocks dropped as bad, cache-fed entries scattered}.
+ * THE GUARANTEE extended: no byte of a bad block is ever served from the cache, and a session with a cache writes nothing outside the
+ * selected windows.  What verify-off trusts, the cache trusts for verify-off sessions: a raw block with a right header and a wrong chunk
+ * byte is served as delivered -- to sessions that do not verify, never to one that does. */
+typedef struct lthip_block_cache lthip_block_cache;
+LTHIP_EXPORT int lthip_block_cache_create(lthip_ctx* ctx, uint32_t slot_count, uint64_t slot_bytes, lthip_block_cache** out);
+LTHIP_EXPORT void lthip_block_cache_destroy(lthip_block_cache* cache);
+LTHIP_EXPORT int lthip_block_cache_contains(const lthip_block_cache* cache, uint32_t hash_identifier, uint32_t count,
+                                            const uint64_t* block_hashes /*host*/, uint8_t* held /*host*/);
+LTHIP_EXPORT int lthip_block_cache_clear(lthip_block_cache* cache);
+LTHIP_EXPORT int lthip_block_cache_stats(const lthip_block_cache* cache, uint64_t out[10]);
+LTHIP_EXPORT int lthip_restore_set_cache(lthip_restore* restore, lthip_block_cache* cache);
+LTHIP_EXPORT int lthip_restore_from_cache(lthip_restore* restore, void* d_out);
+LTHIP_EXPORT int lthip_restore_cache_stats(const lthip_restore* restore, uint64_t out[6]);
 
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets

@@ -39,6 +39,14 @@
 // is sub-allocated by a Carver: the session's allocation, the plan's temporaries, the carry's tables in the context's scratch.
 // The scatter and a decoder's second pass cost one more read and write of the output than decoding into place would: about a tenth on top
 // of the bare decoder calls (profiles/restore_rate.json).
+//   cache    (lthip_block_cache, lthip_restore_set_cache; the bookkeeping is host code, block_cache.h) a device arena of slots of one
+//            size that outlives the sessions.  A slot is a third kind of RItem::src.  set_cache looks every needed block up: a matching
+//            entry is pinned, the block is CACHE-FED and no longer needed; lthip_restore_from_cache scatters those from their slots with
+//            k_restore_scatter over an item table of its own.  A blocks call reserves a slot per needed block: a tagged block is decoded
+//            into it (the decoders' one destination base becomes the lower of scratch and arena), a raw block's payload is copied into
+//            it by k_restore_cache_copy behind the check.  finish, which reads the status words anyway, commits the good ones.
+//            Without a cache attached restore_queue computes what it always did.
+#include "block_cache.h"
 #include "k_copy.h"
 #include "lthip_internal.h"
 #include "restore_layout.h"
@@ -499,6 +507,24 @@ __global__ __launch_bounds__(RT) void k_restore_scatter(const RItem* __restrict_
     lthip_wg_copy<RT>(d, s, en.y, threadIdx.x);
 }
 
+// ---- a cache: behind k_restore_check_images, the payload of every good raw block that has a slot into that slot, in pieces of
+// CACHE_PIECE bytes (grid: the call's undecoded items x pieces).  A block whose status word is not 0 is not read: status 0 says that the
+// image is exactly its header and `raw` bytes.  slot_of[i] == 0: item i has no slot, or is decoded into it. ----
+constexpr uint32_t CACHE_PIECE = 1u << 18;
+__global__ __launch_bounds__(RT) void k_restore_cache_copy(const RItem* __restrict__ items, const uint64_t* __restrict__ slot_of,
+                                                           const uint32_t* __restrict__ status)
+{
+    const uint64_t to = slot_of[blockIdx.x];
+    if (!to)
+        return;
+    const RItem it = items[blockIdx.x];
+    const uint64_t at = (uint64_t)blockIdx.y * CACHE_PIECE;
+    if (at >= it.raw || status[it.block] != 0u)
+        return;
+    const uint64_t n = std::min<uint64_t>(CACHE_PIECE, it.raw - at);
+    lthip_wg_copy<RT>(reinterpret_cast<uint8_t*>(to + at), reinterpret_cast<const uint8_t*>(it.src + at), (uint32_t)n, threadIdx.x);
+}
+
 // host table -> device through the staging ring, in pieces, so that no staging slot grows to the size of an index
 int upload(lthip_ctx* ctx, void* d_dst, const void* h_src, size_t bytes)
 {
@@ -517,6 +543,14 @@ template <class T> int upload(lthip_ctx* ctx, T* d_dst, const std::vector<T>& h_
 uint64_t round64(uint64_t x) { return (x + 63u) & ~(uint64_t)63u; }
 
 } // namespace
+
+struct lthip_block_cache
+{
+    lthip_ctx* ctx;
+    void* arena;
+    block_cache::Table table;
+    uint64_t slot_address(uint32_t s) const { return (uint64_t)(uintptr_t)arena + (uint64_t)s * table.slot_bytes(); }
+};
 
 struct lthip_restore
 {
@@ -554,8 +588,42 @@ struct lthip_restore
     std::vector<RItem> items;
     std::vector<uint32_t> outsz, group[3], c_size, c_cap;
     std::vector<uint64_t> c_src, c_dst;
+    // the cache (null: none attached).  fed[b]: the block is cache-fed from slot cslot[b]; reserved: the delivered blocks that have a
+    // reserved slot cslot[b], until finish commits or releases them
+    lthip_block_cache* cache = nullptr;
+    bool from_cache_done = false, pins_held = false;
+    std::vector<uint64_t> h_chash, bdigest, slot_of;
+    std::vector<uint32_t> h_csize, h_bcoff, cslot, fed_blocks, reserved;
+    std::vector<uint8_t> fed;
+    uint64_t fed_bytes = 0, fed_entries = 0, c_inserted = 0, c_bypassed = 0, c_dropped = 0;
+    void* d_cmem = nullptr;
+    RItem* d_fed_items = nullptr;
+    uint32_t* d_fed_outsz = nullptr;
+    uint64_t* d_slot_of = nullptr;
 
-    bool is_needed(uint32_t b) const { return firsts[b + 1] != firsts[b]; }
+    bool is_needed(uint32_t b) const { return firsts[b + 1] != firsts[b] && !fed[b]; }
+    block_cache::Key cache_key(uint32_t b) const { return block_cache::Key{hash_identifier, bhash[b]}; }
+    block_cache::Meta cache_meta(uint32_t b) const { return block_cache::Meta{bcnt[b], braw[b], bdigest[b]}; }
+    size_t carve_cache(Carver c)
+    {
+        c.take(&d_fed_items, fed_blocks.size()), c.take(&d_fed_outsz, fed_blocks.size()), c.take(&d_slot_of, nb);
+        return c.at;
+    }
+    // gives back what the session holds of the cache: the slots it reserved and has not committed, and (pins) its pins
+    void release_cache(bool pins)
+    {
+        if (!cache)
+            return;
+        for (const uint32_t b : reserved)
+            cache->table.abort(cslot[b], false);
+        reserved.clear();
+        if (pins && pins_held)
+        {
+            for (const uint32_t b : fed_blocks)
+                cache->table.unpin(cslot[b]);
+            pins_held = false;
+        }
+    }
     size_t carve(Carver c, size_t items_cap)
     {
         c.take(&sv.chash, m), c.take(&sv.csize, m), c.take(&sv.cblock, m), c.take(&sv.coff, m);
@@ -592,10 +660,13 @@ extern "C" void lthip_restore_destroy(lthip_restore* r)
     if (!r)
         return;
     (void)hipSetDevice(r->ctx->device);
-    if (r->d_mem || r->d_tmp)
+    if (r->d_mem || r->d_tmp || r->d_cmem)
         (void)hipStreamSynchronize(r->ctx->stream);
+    r->release_cache(true); // (behind the wait: nothing of this session reads or writes a slot any more)
     lthip_seen_destroy(r->seen);
     lthip_seen_destroy(r->seen_base);
+    if (r->d_cmem)
+        (void)hipFree(r->d_cmem);
     if (r->d_mem)
         (void)hipFree(r->d_mem);
     if (r->d_tmp)
@@ -702,9 +773,10 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     // what of the StoreIndex the host keeps
     r->bhash = std::move(st.bhash), r->bleaves = std::move(st.bleaves);
     r->bcnt = std::move(st.bcnt), r->btag = std::move(st.btag), r->braw = std::move(st.braw);
+    r->h_chash = std::move(st.chash), r->h_csize = std::move(st.csize), r->h_bcoff = std::move(st.bcoff); // (for a cache's digests)
     for (uint32_t b = 0; b < nb; ++b)
         r->block_of_hash.emplace(r->bhash[b], b);
-    r->delivered.assign(nb, 0), r->in_call.assign(nb, 0), r->status.assign(nb, 0u);
+    r->delivered.assign(nb, 0), r->in_call.assign(nb, 0), r->status.assign(nb, 0u), r->fed.assign(nb, 0);
     r->firsts.assign((size_t)nb + 1, 0u), r->bbytes.assign(nb, 0ull);
     if (base && nub)
     {
@@ -915,16 +987,41 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
     if (!k)
         return 0;
     r->blocks_queued = true;
-    r->items.clear(), r->outsz.clear();
+    r->items.clear(), r->outsz.clear(), r->slot_of.clear();
     uint64_t slot = 0, entries = 0, ranges = 0, leaves = 0;
+    // a cache: every needed block reserves a slot when one is to be had; a tagged block is then decoded into it, a raw block copied.
+    // The decoders take one destination base: the lower of the scratch and the arena.
+    lthip_block_cache* const cache = r->cache;
+    const uint64_t dbase = !cache      ? (uint64_t)(uintptr_t)d_scratch
+                           : d_scratch ? std::min((uint64_t)(uintptr_t)d_scratch, (uint64_t)(uintptr_t)cache->arena)
+                                       : (uint64_t)(uintptr_t)cache->arena;
+    uint32_t copy_raw = 0; // the largest raw block that is copied into a slot
     for (int g = 0; g < 3; ++g)
         for (const uint32_t i : r->group[g])
         {
             const uint32_t b = r->block_of_hash.find(block_hashes[i])->second;
             const bool tagged = r->btag[b] != 0u;
+            uint64_t in_cache = 0;
+            if (cache)
+            {
+                const uint32_t s = cache->table.reserve(r->cache_key(b), r->cache_meta(b));
+                if (s == block_cache::NO_SLOT)
+                    ++r->c_bypassed;
+                else
+                {
+                    r->cslot[b] = s;
+                    r->reserved.push_back(b);
+                    in_cache = cache->slot_address(s);
+                    if (!tagged)
+                        copy_raw = std::max(copy_raw, r->braw[b]);
+                }
+                r->slot_of.push_back(tagged ? 0u : in_cache);
+            }
             RItem it;
             it.image = image_offsets[i];
-            it.src = tagged ? (uint64_t)(uintptr_t)d_scratch + slot : (uint64_t)(uintptr_t)d_images + image_offsets[i] + lthip_block_index_size(r->bcnt[b]);
+            it.src = !tagged    ? (uint64_t)(uintptr_t)d_images + image_offsets[i] + lthip_block_index_size(r->bcnt[b])
+                     : in_cache ? in_cache
+                                : (uint64_t)(uintptr_t)d_scratch + slot;
             it.size = image_sizes[i];
             it.block = b;
             it.raw = r->braw[b];
@@ -933,7 +1030,7 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
             it.vfirst = (uint32_t)ranges;
             r->items.push_back(it);
             r->outsz.push_back(tagged ? NONE : it.raw); // (a decoder overwrites its blocks' words; a raw block has nothing to decode)
-            if (tagged)
+            if (tagged && !in_cache)
                 slot += round64(it.raw);
             entries += r->firsts[b + 1] - r->firsts[b];
             ranges += r->bcnt[b];
@@ -950,6 +1047,15 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
                            r->sv, r->hash_identifier, r->d_status);
         LTHIP_LAUNCH_CHECK(ctx);
     }
+    if (copy_raw)
+    {
+        if ((err = upload(ctx, r->d_slot_of, r->slot_of.data(), r->group[0].size() * 8)))
+            return err;
+        LaunchTimer tm(ctx, LTHIP_K_GATHER);
+        hipLaunchKernelGGL(k_restore_cache_copy, dim3((uint32_t)r->group[0].size(), (copy_raw + CACHE_PIECE - 1u) / CACHE_PIECE), dim3(RT), 0, s,
+                           (const RItem*)r->d_items, (const uint64_t*)r->d_slot_of, (const uint32_t*)r->d_status);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
     // ---- decode: one call per codec; sizes and places from the StoreIndex and image_sizes alone ----
     size_t at = r->group[0].size();
     for (int g = 1; g < 3; ++g)
@@ -964,19 +1070,22 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
             const uint64_t hdr = lthip_stored_block_header_size(r->bcnt[it.block]);
             r->c_src.push_back(it.image + hdr);
             r->c_size.push_back((uint32_t)(it.size - hdr));
-            r->c_dst.push_back(it.src - (uint64_t)(uintptr_t)d_scratch);
-            r->c_cap.push_back(it.raw);
+            r->c_dst.push_back(it.src - dbase);
+            r->c_cap.push_back(it.raw); // (a slot holds at least the raw size of the block that reserved it)
         }
-        err = g == 1 ? lthip_lz4_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_scratch, r->c_dst.data(),
+        void* const d_dst = (void*)(uintptr_t)dbase;
+        err = g == 1 ? lthip_lz4_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_dst, r->c_dst.data(),
                                                    r->c_cap.data(), r->d_outsz + at)
-                     : lthip_zstd_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_scratch, r->c_dst.data(),
+                     : lthip_zstd_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_dst, r->c_dst.data(),
                                                     r->c_cap.data(), r->d_outsz + at);
         if (err)
             return err;
         at += cnt;
     }
     // ---- the decoders' verdict, then verify, both before the scatter ----
-    const uint64_t base = slot ? std::min((uint64_t)(uintptr_t)d_images, (uint64_t)(uintptr_t)d_scratch) : (uint64_t)(uintptr_t)d_images;
+    const uint64_t base = cache  ? std::min((uint64_t)(uintptr_t)d_images, dbase)
+                          : slot ? std::min((uint64_t)(uintptr_t)d_images, (uint64_t)(uintptr_t)d_scratch)
+                                 : (uint64_t)(uintptr_t)d_images;
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
         hipLaunchKernelGGL(k_restore_ranges, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint32_t*)r->d_outsz,
@@ -1055,14 +1164,18 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
         refused = EINVAL, why = "the base was carried in place: the output is that buffer";
     if (refused)
         return lthip_fail(ctx, refused, "lthip_restore_blocks", why);
+    int err;
     try
     {
-        return restore_queue(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, d_out);
+        err = restore_queue(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, d_out);
     }
     catch (const std::bad_alloc&)
     {
-        return lthip_fail(ctx, ENOMEM, "lthip_restore_blocks", "host tables");
+        err = lthip_fail(ctx, ENOMEM, "lthip_restore_blocks", "host tables");
     }
+    if (err) // (a call that did not queue all of its work commits nothing: no status word of it can be trusted)
+        r->release_cache(false);
+    return err;
 }
 
 // d_scratch == null: out of place, d_base -> d_out.  Otherwise in place: d_base == d_out is the one buffer, and the moved runs go through
@@ -1307,13 +1420,236 @@ extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
         if (r->btag[b] != 0u && !(r->status[b] & (LTHIP_RESTORE_BAD_HEADER | LTHIP_RESTORE_BAD_PAYLOAD)))
             res.decoded_bytes += r->braw[b];
     }
+    if (r->cache)
+    {
+        // the status words are final: a good block's reserved slot becomes an entry, every other one is given back
+        block_cache::Table& table = r->cache->table;
+        for (const uint32_t b : r->reserved)
+        {
+            if (r->status[b])
+                table.abort(r->cslot[b], true), ++r->c_dropped;
+            else if (table.commit(r->cslot[b], r->verify != 0u))
+                ++r->c_inserted;
+            else
+                ++r->c_bypassed;
+        }
+        r->reserved.clear();
+        if (r->from_cache_done)
+            for (const uint32_t b : r->fed_blocks)
+            {
+                res.occurrences_written += r->firsts[b + 1] - r->firsts[b];
+                res.bytes_written += r->bbytes[b];
+            }
+    }
+    const bool outstanding =
+        r->needed_delivered < r->needed || (r->ncarry && !r->carried) || (!r->fed_blocks.empty() && !r->from_cache_done);
+    const int code = res.blocks_bad || res.base_chunks_mismatched ? EBADF : outstanding ? ENOENT : 0;
+    if (!code)
+        r->release_cache(true); // (the session is complete: its pins go)
     if (out)
     {
         const uint64_t have = out->struct_size;
         res.struct_size = have < sizeof res ? have : sizeof res;
         memcpy(out, &res, (size_t)res.struct_size);
     }
-    return res.blocks_bad || res.base_chunks_mismatched ? EBADF : r->needed_delivered < r->needed || (r->ncarry && !r->carried) ? ENOENT : 0;
+    return code;
+}
+
+// ---- the cache of decoded blocks ----
+extern "C" int lthip_block_cache_create(lthip_ctx* ctx, uint32_t slot_count, uint64_t slot_bytes, lthip_block_cache** out)
+{
+    if (out)
+        *out = nullptr;
+    if (!ctx || !out || !slot_count || !slot_bytes || slot_bytes > (1ull << 40))
+        return EINVAL;
+    const uint64_t bytes = round64(slot_bytes);
+    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+    void* arena = nullptr;
+    LTHIP_CHECK(ctx, lthip_hip_malloc(&arena, (size_t)(bytes * slot_count)));
+    lthip_block_cache* c = nullptr;
+    try
+    {
+        c = new lthip_block_cache{ctx, arena, block_cache::Table(slot_count, bytes)};
+    }
+    catch (const std::bad_alloc&)
+    {
+        (void)hipFree(arena);
+        return lthip_fail(ctx, ENOMEM, "lthip_block_cache_create", "host tables");
+    }
+    *out = c;
+    return 0;
+}
+
+extern "C" void lthip_block_cache_destroy(lthip_block_cache* c)
+{
+    if (!c)
+        return;
+    (void)hipSetDevice(c->ctx->device);
+    (void)hipStreamSynchronize(c->ctx->stream);
+    (void)hipFree(c->arena);
+    delete c;
+}
+
+extern "C" int lthip_block_cache_contains(const lthip_block_cache* c, uint32_t hash_identifier, uint32_t count, const uint64_t* block_hashes,
+                                          uint8_t* held)
+{
+    if (!c || (count && (!block_hashes || !held)))
+        return EINVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        held[i] = c->table.lookup(block_cache::Key{hash_identifier, block_hashes[i]}) != block_cache::NO_SLOT ? 1u : 0u;
+    return 0;
+}
+
+extern "C" int lthip_block_cache_clear(lthip_block_cache* c)
+{
+    if (!c)
+        return EINVAL;
+    return c->table.clear() ? 0 : lthip_fail(c->ctx, EBUSY, "lthip_block_cache_clear", "an entry is pinned or a slot is reserved by a live session");
+}
+
+extern "C" int lthip_block_cache_stats(const lthip_block_cache* c, uint64_t out[10])
+{
+    if (!c || !out)
+        return EINVAL;
+    const block_cache::Counts& n = c->table.counts();
+    const uint64_t v[10] = {c->table.slot_count(), c->table.slot_bytes(), c->table.resident(), c->table.pinned(), c->table.reserved(),
+                            n.hits,                n.inserted,            n.evicted,           n.bypassed,        n.dropped};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+static int set_cache(lthip_restore* r, lthip_block_cache* c)
+{
+    lthip_ctx* ctx = r->ctx;
+    const uint32_t nb = r->nb;
+    // ---- which needed blocks the cache feeds: a visible entry with the same chunk count, raw size and chunk table (verify: verified) ----
+    r->bdigest.assign(nb, 0u), r->cslot.assign(nb, block_cache::NO_SLOT);
+    for (uint32_t b = 0; b < nb; ++b)
+        if (r->is_needed(b)) // (only a needed block is looked up, now or when it is delivered)
+            r->bdigest[b] = block_cache::table_digest(r->h_chash.data() + r->h_bcoff[b], r->h_csize.data() + r->h_bcoff[b], r->bcnt[b]);
+    std::vector<RItem> items;
+    std::vector<uint32_t> outsz;
+    uint64_t entries = 0, bytes = 0;
+    for (uint32_t b = 0; b < nb; ++b)
+    {
+        if (!r->is_needed(b))
+            continue;
+        const uint32_t s = c->table.lookup(r->cache_key(b));
+        if (s == block_cache::NO_SLOT || !c->table.matches(s, r->cache_meta(b), r->verify != 0u))
+            continue;
+        r->cslot[b] = s;
+        r->fed_blocks.push_back(b);
+        RItem it = {};
+        it.src = c->slot_address(s);
+        it.block = b;
+        it.raw = r->braw[b];
+        it.efirst = (uint32_t)entries;
+        it.ebase = r->firsts[b];
+        items.push_back(it);
+        outsz.push_back(it.raw);
+        entries += r->firsts[b + 1] - r->firsts[b];
+        bytes += it.raw;
+    }
+    // ---- the session's device tables for the cache; on an error the session stays as it was ----
+    int err = 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        err = lthip_fail(ctx, EIO, "lthip_restore_set_cache", "hipSetDevice");
+    else if (lthip_hip_malloc(&r->d_cmem, r->carve_cache(Carver()) + 256) != hipSuccess)
+        err = lthip_fail(ctx, ENOMEM, "lthip_restore_set_cache", "device tables");
+    if (!err)
+    {
+        r->carve_cache(Carver(r->d_cmem));
+        if (!items.empty() && !(err = upload(ctx, r->d_fed_items, items)))
+            err = upload(ctx, r->d_fed_outsz, outsz);
+    }
+    if (err)
+    {
+        if (r->d_cmem)
+        {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(r->d_cmem);
+        }
+        r->d_cmem = nullptr;
+        r->fed_blocks.clear();
+        return err;
+    }
+    for (const uint32_t b : r->fed_blocks)
+    {
+        c->table.pin(r->cslot[b]);
+        r->fed[b] = 1;
+    }
+    r->pins_held = true;
+    r->needed -= r->fed_blocks.size();
+    r->fed_entries = entries;
+    r->fed_bytes = bytes;
+    r->cache = c;
+    return 0;
+}
+
+extern "C" int lthip_restore_set_cache(lthip_restore* r, lthip_block_cache* c)
+{
+    if (!r || !c)
+        return EINVAL;
+    if (c->ctx != r->ctx)
+        return lthip_fail(r->ctx, EINVAL, "lthip_restore_set_cache", "the cache belongs to another context");
+    if (r->cache)
+        return lthip_fail(r->ctx, EEXIST, "lthip_restore_set_cache", "the session has a cache");
+    if (r->blocks_queued)
+        return lthip_fail(r->ctx, EINVAL, "lthip_restore_set_cache", "a blocks call has queued work: the cache is attached before the first one");
+    try
+    {
+        return set_cache(r, c);
+    }
+    catch (const std::bad_alloc&)
+    {
+        r->fed_blocks.clear();
+        return lthip_fail(r->ctx, ENOMEM, "lthip_restore_set_cache", "host tables");
+    }
+}
+
+extern "C" int lthip_restore_from_cache(lthip_restore* r, void* d_out)
+{
+    if (!r)
+        return EINVAL;
+    lthip_ctx* ctx = r->ctx;
+    if (!r->cache)
+        return lthip_fail(ctx, EINVAL, "lthip_restore_from_cache", "the session has no cache");
+    if (r->from_cache_done)
+        return lthip_fail(ctx, EEXIST, "lthip_restore_from_cache", "the cache-fed blocks were queued before");
+    const uint32_t k = (uint32_t)r->fed_blocks.size();
+    if (k)
+    {
+        if (!d_out)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_from_cache", "null output");
+        if (r->in_place_buf && d_out != r->in_place_buf)
+            return lthip_fail(ctx, EINVAL, "lthip_restore_from_cache", "the base was carried in place: the output is that buffer");
+        LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
+        LaunchTimer tm(ctx, LTHIP_K_GATHER);
+        constexpr uint64_t LAUNCH_ENTRIES = 1u << 23;
+        // (a cache-fed block is never delivered as needed: its status word stays 0)
+        for (uint64_t e0 = 0; e0 < r->fed_entries; e0 += LAUNCH_ENTRIES)
+            hipLaunchKernelGGL(k_restore_scatter, dim3((uint32_t)std::min(LAUNCH_ENTRIES, r->fed_entries - e0)), dim3(RT), 0, ctx->stream,
+                               (const RItem*)r->d_fed_items, k, (const uint4*)r->d_entries, (const uint32_t*)r->d_status,
+                               (const uint32_t*)r->d_fed_outsz, (uint32_t)e0, (uint8_t*)d_out);
+        LTHIP_LAUNCH_CHECK(ctx);
+        r->blocks_queued = true;
+        r->finished = false;
+    }
+    r->from_cache_done = true;
+    return 0;
+}
+
+extern "C" int lthip_restore_cache_stats(const lthip_restore* r, uint64_t out[6])
+{
+    if (!r || !out)
+        return EINVAL;
+    out[0] = r->fed_blocks.size();
+    out[1] = r->fed_bytes;
+    out[2] = r->c_inserted;
+    out[3] = r->c_bypassed;
+    out[4] = r->c_dropped;
+    out[5] = r->from_cache_done ? r->fed_entries : 0u;
+    return 0;
 }
 
 extern "C" int lthip_restore_block_status(const lthip_restore* r, uint32_t count, const uint64_t* block_hashes, uint32_t* status)

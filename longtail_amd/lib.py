@@ -180,6 +180,14 @@ class HipLib:
         sig("lthip_restore_create_windows", i32, [vp, vp, vp, sz, vp, sz, u64, vp, u64, P(vp)])
         sig("lthip_restore_asset_sizes", i32, [vp, sz, vp, P(u32), P(u32)])
         sig("lthip_restore_rank_windows", i32, [u64, vp, vp, vp, vp, u32, u64, vp, u64, P(u64), P(u64)])
+        sig("lthip_block_cache_create", i32, [vp, u32, u64, P(vp)])
+        sig("lthip_block_cache_destroy", None, [vp])
+        sig("lthip_block_cache_contains", i32, [vp, u32, u32, vp, vp])
+        sig("lthip_block_cache_clear", i32, [vp])
+        sig("lthip_block_cache_stats", i32, [vp, vp])
+        sig("lthip_restore_set_cache", i32, [vp, vp])
+        sig("lthip_restore_from_cache", i32, [vp, vp])
+        sig("lthip_restore_cache_stats", i32, [vp, vp])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1203,6 +1211,7 @@ class Restore:
             self.ctx.lib.dll.lthip_restore_destroy(self.h)
         self.h = None
         self._keep = []
+        self._cache = None  # (the session is gone: the cache it was attached to may go too)
 
     def __del__(self):
         try:
@@ -1258,6 +1267,23 @@ class Restore:
                         "lthip_restore_carry_in_place")
         self._keep.append((buf, scratch))
 
+    def set_cache(self, cache: "BlockCache"):
+        """Attaches a BlockCache of the same context, once and before the first blocks() call: needed_blocks() shrinks to the blocks the
+        cache does not feed, good delivered blocks stay in the cache.  The cache object is kept alive while the session is."""
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_set_cache(self.h, cache.h if cache is not None else None), "lthip_restore_set_cache")
+        self._cache = cache
+
+    def from_cache(self, out):
+        """Queues the scatter of the cache-fed blocks from their slots into `out`; once per session, in any order with blocks()."""
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_from_cache(self.h, _ptr(out) or None), "lthip_restore_from_cache")
+        self._keep.append((out,))
+
+    def cache_stats(self):
+        """-> (cache-fed blocks, their raw bytes, blocks inserted, blocks bypassed, blocks dropped as bad, cache-fed entries scattered)."""
+        out = np.zeros(6, np.uint64)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_cache_stats(self.h, out.ctypes.data), "lthip_restore_cache_stats")
+        return tuple(int(x) for x in out)
+
     def finish(self):
         """-> (code, RestoreResult): 0, errno.ENOENT (needed blocks are outstanding, or the base has not been carried: deliver / carry
         and call again) or errno.EBADF (a delivered block was bad, or with verify a chunk of the base).  The session's one full
@@ -1277,6 +1303,51 @@ class Restore:
         self.ctx._check(self.ctx.lib.dll.lthip_restore_block_status(self.h, len(h), h.ctypes.data if len(h) else None,
                                                                     out.ctypes.data if len(h) else None), "lthip_restore_block_status")
         return out
+
+
+BLOCK_CACHE_STATS = ("slots", "slot_bytes", "resident", "pinned", "reserved", "hits", "inserted", "evicted", "bypassed", "dropped")
+
+
+class BlockCache:
+    """lthip_block_cache: slot_count device slots of slot_bytes (rounded up to 64) that keep decoded blocks between the Restore sessions
+    of one context (include/longtail_hip.h, "a cache of decoded blocks").  Size the slots by the largest raw size among the StoreIndex's blocks (about
+    the store's max_block_size): a block larger than a slot is never cached.  Close it after every session attached to it and before the context."""
+
+    def __init__(self, ctx: "Context", slot_count: int, slot_bytes: int):
+        self.ctx = ctx
+        self.h = None
+        h = C.c_void_p()
+        ctx._check(ctx.lib.dll.lthip_block_cache_create(ctx.h, slot_count, slot_bytes, C.byref(h)), "lthip_block_cache_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.dll.lthip_block_cache_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def contains(self, hash_identifier: int, block_hashes) -> np.ndarray:
+        """Per block hash 1 when the cache holds a visible entry of it under `hash_identifier`, else 0; host only."""
+        h = _u64arr(block_hashes)
+        held = np.zeros(len(h), np.uint8)
+        self.ctx._check(self.ctx.lib.dll.lthip_block_cache_contains(self.h, hash_identifier, len(h), h.ctypes.data if len(h) else None,
+                                                                    held.ctypes.data if len(h) else None), "lthip_block_cache_contains")
+        return held
+
+    def stats(self) -> dict:
+        """-> dict of BLOCK_CACHE_STATS: the state now (slots .. reserved) and the sums since create (hits .. dropped)."""
+        out = np.zeros(10, np.uint64)
+        self.ctx._check(self.ctx.lib.dll.lthip_block_cache_stats(self.h, out.ctypes.data), "lthip_block_cache_stats")
+        return {k: int(v) for k, v in zip(BLOCK_CACHE_STATS, out)}
+
+    def clear(self):
+        """Drops every entry; LongtailHipError(EBUSY) while a live session pins an entry or has reserved a slot."""
+        self.ctx._check(self.ctx.lib.dll.lthip_block_cache_clear(self.h), "lthip_block_cache_clear")
 
 
 def version_diff(source_vi: bytes, target_vi: bytes, lib: Optional[HipLib] = None):

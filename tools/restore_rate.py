@@ -35,6 +35,14 @@ the blocks needed -- a block is decoded whole; the report says what was measured
 is no threshold.
 
     python tools/restore_rate.py --windows 0.25 [--gib 4] [--repeats 3] [--out profiles/restore_windows_rate.json]
+
+--windows FRACTION --cache measures the cache of decoded blocks (BlockCache, lthip_restore_set_cache / lthip_restore_from_cache): 1 /
+FRACTION window sessions in one process, each wanting another FRACTION of every file of the same tree.  With a cache the first session
+inserts what it is fed and the others are served from the cache; the same sessions run without a cache, alternated repeat by repeat, raw,
+LZ4 and zstd stores, verify off and on.  Recorded per session: the milliseconds behind create and set_cache (the inserting session apart
+from the served ones), set_cache's own time, and the cache's stats.  Recorded into profiles/restore_cache_rate.json.  There is no threshold.
+
+    python tools/restore_rate.py --windows 0.25 --cache [--gib 4] [--repeats 3] [--out profiles/restore_cache_rate.json]
 """
 import argparse
 import json
@@ -368,6 +376,123 @@ def windows_leg(args):
     print("wrote", path)
 
 
+def cache_leg(args):
+    """--windows FRACTION --cache: 1 / FRACTION window sessions in one process, each wanting another FRACTION of every file, with a
+    BlockCache (the first session inserts, the others are served) and without one, alternated repeat by repeat."""
+    import torch
+
+    from bench import KINDS, asset_seeds, make_tree
+    from longtail_amd.lib import BlockCache, Context, Ingest, IngestStream, Restore, chunker_params, load
+
+    lib = load()
+    dev = torch.device("cuda", 0)
+    ctx = Context(0, lib=lib)
+    nfiles = int(args.gib * (1 << 30)) // FILE
+    n = nfiles * FILE
+    wlen = max(1, min(FILE, int(FILE * args.windows)))
+    passes = max(1, FILE // wlen)
+    wn = nfiles * wlen
+    mn, av, mx = chunker_params(args.target_chunk_size)
+    p_off, p_size = np.arange(nfiles, dtype=np.uint64) * np.uint64(FILE), np.full(nfiles, FILE, np.uint64)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    data = torch.empty(n + 256, **u8)
+    ctx.synth_fill(data, p_off, p_size, asset_seeds(0x10C0FFEE, 0, nfiles), KINDS["mixed"])
+    plan = ctx.make_plan(p_off, p_size, mn, av, mx)
+    total, d_off, d_len, d_hash, d_first = ctx.chunk_hash(plan, data)
+    tree = make_tree("files", n, FILE)
+    whole, _keep = Ingest.tree(tree["sizes"], tree["path_offsets"], tree["perms"], tree["path_data"], np.arange(nfiles, dtype=np.uint32),
+                               np.zeros(nfiles + 1, np.uint64))
+    vi_cap = int(lib.dll.lthip_version_index_size(nfiles, total, total, len(tree["path_data"]))) + 64
+    h_vi, h_si = torch.empty(vi_cap, dtype=torch.uint8).pin_memory(), torch.empty(16 + 32 * total + 64, dtype=torch.uint8).pin_memory()
+    out = torch.empty(wn, **u8)
+    files = data[:n].view(nfiles, FILE)
+    want = [files[:, q * wlen : (q + 1) * wlen].reshape(-1) for q in range(passes)]
+    windows = [np.stack([np.arange(nfiles), np.full(nfiles, q * wlen), np.full(nfiles, wlen), np.arange(nfiles) * wlen], axis=1).astype(np.uint64)
+               for q in range(passes)]
+    report = {"workload": f"{args.gib:g} GiB `mixed` tree ({nfiles} files of 1 MiB), written by lthip_ingest_stream in one slice; {passes} window "
+                          f"sessions in one process, session q restores bytes [q, q + 1) x {wlen} of every file.  With a cache (one slot per "
+                          "block, slots of the largest block's raw size) the first session inserts what it is fed and the others are served "
+                          "from the cache; without one every session is fed the blocks it needs.  Alternated repeat by repeat.",
+              "unit": "milliseconds of a session behind create and set_cache: every blocks call + from_cache + finish", "repeats": args.repeats,
+              "fraction": wlen / FILE, "sessions": passes, "stores": {}}
+    for codec, tag in TAGS.items():
+        st = IngestStream(ctx, whole, args.target_chunk_size, args.block_size, args.max_chunks_per_block, codec, compression_type=tag or None)
+        arena, tail = torch.empty(st.arena_bound(n, total), **u8), torch.empty(st.arena_bound(0, 0), **u8)
+        st.slice(0, nfiles, data, d_off, d_len, d_hash, d_first, total, arena)
+        _, offs0, sizes0 = st.images()
+        offs0, sizes0 = offs0.copy(), sizes0.copy()
+        res = st.finish(tail, h_vi, h_si)
+        _, offs1, sizes1 = st.images()
+        offs1, sizes1 = offs1.copy(), sizes1.copy()
+        vi, si = bytes(h_vi.numpy()[: res.version_index_size]), bytes(h_si.numpy()[: res.store_index_size])
+        st.close()
+        hashes, counts, raws = store_blocks(si)
+        calls = [(arena, hashes[: len(offs0)], offs0, sizes0), (tail, hashes[len(offs0) :], offs1, sizes1)]
+        entry = {"blocks": int(res.blocks), "raw_bytes_of_the_blocks": int(raws.sum()), "slots": int(len(raws)), "slot_bytes": int(raws.max())}
+        scratch = torch.empty(max(64, int(((raws + 63) // 64 * 64).sum()) if tag else 64), **u8)  # (room for every block of a call)
+
+        def once(q, verify, cache):
+            """-> (ms of set_cache, ms of the calls behind it, the result, the session's cache stats)"""
+            out.fill_(0xA5)
+            rs = Restore(ctx, vi, si, None, wn, verify=verify, windows=windows[q])
+            ctx.sync()
+            t0 = time.perf_counter()
+            if cache is not None:
+                rs.set_cache(cache)
+            needed = set(rs.needed_blocks().tolist())
+            ctx.sync()
+            t1 = time.perf_counter()
+            for images, h, o, z in calls:
+                pick = np.array([x in needed for x in h.tolist()], bool)
+                if pick.any():
+                    rs.blocks(h[pick], images, o[pick], z[pick], scratch, out)
+            if cache is not None:
+                rs.from_cache(out)
+            code, result = rs.finish()
+            t2 = time.perf_counter()
+            assert code == 0 and result.bytes_written == wn, (code, result.bytes_written)
+            assert torch.equal(out, want[q]), "the restored bytes differ from the tree"
+            stats = rs.cache_stats()
+            rs.close()
+            return (t1 - t0) * 1e3, (t2 - t1) * 1e3, result, stats
+
+        for verify in (False, True):
+            ms = {k: [[] for _ in range(passes)] for k in ("cache", "no_cache")}
+            attach, stats, cache_stats = [], None, None
+            for rep in range(args.repeats + 1):  # (the first is the warm-up: workspaces of the context)
+                cache = BlockCache(ctx, len(raws), int(raws.max()))
+                for k in ("cache", "no_cache"):
+                    for q in range(passes):
+                        a_ms, run_ms, result, s = once(q, verify, cache if k == "cache" else None)
+                        if rep:
+                            ms[k][q].append(round(run_ms, 3))
+                            if k == "cache" and q:
+                                attach.append(round(a_ms, 3))
+                        if k == "cache" and q == passes - 1:
+                            stats = s
+                cache_stats = cache.stats()
+                cache.close()
+            med = lambda rows: float(np.median([x for r in rows for x in r]))
+            v = {"inserting_session_ms": ms["cache"][0], "served_sessions_ms": ms["cache"][1:], "no_cache_first_session_ms": ms["no_cache"][0],
+                 "no_cache_other_sessions_ms": ms["no_cache"][1:], "set_cache_ms_of_the_served_sessions": attach,
+                 "inserting_session_ms_median": med(ms["cache"][:1]), "served_session_ms_median": med(ms["cache"][1:]) if passes > 1 else None,
+                 "no_cache_first_session_ms_median": med(ms["no_cache"][:1]),
+                 "no_cache_other_session_ms_median": med(ms["no_cache"][1:]) if passes > 1 else None,
+                 "last_served_session_cache_stats": dict(zip(("fed_blocks", "fed_bytes", "inserted", "bypassed", "dropped", "fed_entries"), stats)),
+                 "cache_stats": cache_stats}
+            v["inserting_over_no_cache"] = round(v["inserting_session_ms_median"] / v["no_cache_first_session_ms_median"], 3)
+            entry["verify" if verify else "no_verify"] = v
+        report["stores"][codec] = entry
+        print(codec, json.dumps(entry), flush=True)
+        del arena, tail, scratch
+    plan.close()
+    ctx.close()
+    path = Path(args.out if args.out else ROOT / "profiles" / "restore_cache_rate.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(report, indent=1) + "\n")
+    print("wrote", path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -381,7 +506,13 @@ def main():
     ap.add_argument("--share", type=float, default=0.1, help="--update: the share of the files that version B replaces")
     ap.add_argument("--windows", type=float, default=None, metavar="FRACTION",
                     help="a window session over the first FRACTION of every file, beside the full restore (profiles/restore_windows_rate.json)")
+    ap.add_argument("--cache", action="store_true",
+                    help="--windows: 1 / FRACTION window sessions with a BlockCache and without one (profiles/restore_cache_rate.json)")
     args = ap.parse_args()
+    if args.cache:
+        if args.windows is None:
+            ap.error("--cache goes with --windows FRACTION")
+        return cache_leg(args)
     if args.windows is not None:
         return windows_leg(args)
     if args.update:
