@@ -1116,6 +1116,92 @@ LTHIP_EXPORT int lthip_restore_set_cache(lthip_restore* restore, lthip_block_cac
 LTHIP_EXPORT int lthip_restore_from_cache(lthip_restore* restore, void* d_out);
 LTHIP_EXPORT int lthip_restore_cache_stats(const lthip_restore* restore, uint64_t out[6]);
 
+/* ---- one-file archives: pack ingested blocks, restore from an archive (archive.hip, archive_layout.h, restore.hip) ---------------------
+ * The device side of lib/archiveblockstore: the single file golongtail's pack / unpack move around, [ArchiveIndex][block][block]...
+ * (Longtail_CreateArchiveIndex / Longtail_ReadArchiveIndex, src/longtail.c:9921-10090).  The index is
+ *   u32 version (LONGTAIL_VERSION(0,0,1))   u32 index_data_size (of the whole index)   the serialized StoreIndex
+ *   u64 block_start_offsets[nb], relative to the END of the index   u32 block_sizes[nb]   the serialized VersionIndex   pad to 8
+ * byte for byte as the reference writes it (its pad bytes are uninitialised, ours are zero; the u64 table is only 4-byte aligned when
+ * nb + m is odd, every word goes through memcpy).  The BODY behind it holds the stored-block images back to back, in any order and at
+ * ANY byte position.  File I/O is the caller's: these calls see the index in host memory and pieces of the body in HBM.
+ * THE INDEX, host only, no context:
+ *   index_size     the bytes of the index of these two blobs, (8 + S + 12 nb + V + 7) & ~7.  EBADF: a blob lthip_restore_layout / create
+ *                  would call malformed; EINVAL: the index would not fit the 32 bits of index_data_size (nothing is truncated).
+ *   write_index    the index with block b at body offset block_offsets[b], block_sizes[b] bytes long, into out[0, capacity); ENOMEM below
+ *                  index_size (nothing written).
+ *   peek           the first eight bytes of a file -> *index_bytes, so that a reader knows how much to read.  EBADF: another version.
+ *   open           deep-copies the index (it may be freed on return).  body_bytes: the size of the body (file size - index_bytes), or
+ *                  UINT64_MAX when it is not known -- lthip_archive_body_bytes is then the end of the last block.  EBADF: index_bytes is
+ *                  not the stored size (a short or over-long index); another version; counts that leave the index; a block whose
+ *                  offset + size leaves body_bytes; a block smaller than its own header (20 + 12 n, + 8 when tagged); a malformed
+ *                  StoreIndex or VersionIndex.  Blocks may lie in any order (the reference writes them as its workers complete) and may
+ *                  overlap: every image is checked against the StoreIndex when it is delivered.
+ *   store_index / version_index / block_count / block_offsets / block_sizes / body_bytes   views into the handle, valid until close.  A
+ *                  serialized VersionIndex does not store the length of its name data: as Longtail_ReadArchiveIndex does, the
+ *                  VersionIndex blob is the REST of the index, up to 7 pad bytes included; lthip_restore_* accept it as it is.
+ * THE WRITER:
+ *   append         takes `count` images exactly as lthip_ingest_stream_images / lthip_ingest_images hand them out (image i at d_arena +
+ *                  image_offsets[i], image_sizes[i] bytes; host tables, free on return) and queues ONE kernel, k_archive_pack (grid: images
+ *                  x 256 KiB pieces, the copy is lthip_wg_copy), that lays them densely from d_dst[0]: *bytes_written = the sum of the
+ *                  sizes, nothing is written at or beyond d_dst + *bytes_written, no 4-byte word is read that holds no byte of an image.
+ *                  The archive's body is the concatenation of all calls' outputs: the writer carries the cursor and records every
+ *                  block's offset and size; the caller drains d_dst (to the host, to a file) between calls.  ENOMEM before any work when
+ *                  the call's images exceed dst_capacity.  Never waits for the device (but where the context's table pool has to grow).
+ *                  Timed as LTHIP_K_GATHER.
+ *   blocks         the tables recorded so far (the writer's, valid until its next call) and the body's size.
+ *   finish         writes the index from the recorded tables.  EINVAL: the appended blocks are not the StoreIndex's block count, or an
+ *                  appended size is below that block's header size.  ENOMEM with *index_bytes filled in when h_index is NULL or the
+ *                  capacity is short: call again.  Does not wait for the device either.
+ * THE READER: the restore session fed from pieces of the body.
+ *   archive_blocks delivers every needed, not yet delivered block that lies WHOLLY inside body bytes [window_first_byte, +window_bytes),
+ *                  which lie at d_window, at whatever byte position it has there: lthip_restore_blocks without the alignment rule.
+ *                  Unneeded blocks are not touched, and neither are blocks of the archive the session's StoreIndex does not hold.
+ *                  *delivered = the blocks this call delivered; *next_byte = the lowest body offset of a needed block still outstanding,
+ *                  or lthip_archive_body_bytes when there is none: a reader that streams the file in pieces starts its next read there.
+ *                  A window that holds no complete needed block returns 0 with *delivered == 0.  The refusals (ENOTSUP, ENOMEM for a
+ *                  scratch below archive_scratch_bound, EINVAL for a null scratch or output), the queued stages and THE GUARANTEE are
+ *                  those of lthip_restore_blocks; a refused call delivers nothing and leaves the session usable.  The check is a second
+ *                  kernel, k_restore_check_images_any, that assembles every header dword from the two aligned dwords around it: no dword is
+ *                  read that holds no byte of the image, an image may end at the last byte of the allocation.  Decoders, verify, scatter
+ *                  and the cache copy take any byte position as they are.  Works with verify, with a base, with window sessions and with
+ *                  an attached cache.
+ *   archive_scratch_bound   host arithmetic: the scratch an archive_blocks call with this window needs now.
+ *   archive_ranges host only.  The body ranges {first byte, bytes} of the needed, outstanding blocks, sorted, merged where the gap between
+ *                  two is at most max_gap: ranges[2 i], ranges[2 i + 1].  ranges NULL or capacity (in ranges) too small: the count only. */
+typedef struct lthip_archive lthip_archive;
+typedef struct lthip_archive_writer lthip_archive_writer;
+LTHIP_EXPORT int lthip_archive_index_size(const void* store_index, size_t store_index_size, const void* version_index, size_t version_index_size,
+                                          uint64_t* out_bytes);
+LTHIP_EXPORT int lthip_archive_write_index(const void* store_index, size_t store_index_size, const void* version_index, size_t version_index_size,
+                                           const uint64_t* block_offsets /*host, [nb]*/, const uint32_t* block_sizes /*host, [nb]*/, void* out,
+                                           size_t capacity);
+LTHIP_EXPORT int lthip_archive_peek(const void* first_8_bytes, uint64_t* index_bytes);
+LTHIP_EXPORT int lthip_archive_open(const void* index, size_t index_bytes, uint64_t body_bytes /* UINT64_MAX: unknown */, lthip_archive** out);
+LTHIP_EXPORT void lthip_archive_close(lthip_archive* archive);
+LTHIP_EXPORT const void* lthip_archive_store_index(const lthip_archive* archive, size_t* size);
+LTHIP_EXPORT const void* lthip_archive_version_index(const lthip_archive* archive, size_t* size);
+LTHIP_EXPORT uint32_t lthip_archive_block_count(const lthip_archive* archive);
+LTHIP_EXPORT const uint64_t* lthip_archive_block_offsets(const lthip_archive* archive);
+LTHIP_EXPORT const uint32_t* lthip_archive_block_sizes(const lthip_archive* archive);
+LTHIP_EXPORT uint64_t lthip_archive_body_bytes(const lthip_archive* archive);
+LTHIP_EXPORT int lthip_archive_writer_create(lthip_ctx* ctx, lthip_archive_writer** out);
+LTHIP_EXPORT void lthip_archive_writer_destroy(lthip_archive_writer* writer);
+LTHIP_EXPORT int lthip_archive_writer_append(lthip_archive_writer* writer, const void* d_arena, uint32_t count,
+                                             const uint64_t* image_offsets /*host*/, const uint32_t* image_sizes /*host*/, void* d_dst,
+                                             uint64_t dst_capacity, uint64_t* bytes_written);
+LTHIP_EXPORT int lthip_archive_writer_blocks(const lthip_archive_writer* writer, uint64_t* block_count, const uint64_t** offsets,
+                                             const uint32_t** sizes, uint64_t* body_bytes);
+LTHIP_EXPORT int lthip_archive_writer_finish(lthip_archive_writer* writer, const void* store_index, size_t store_index_size,
+                                             const void* version_index, size_t version_index_size, void* h_index, size_t capacity,
+                                             uint64_t* index_bytes);
+LTHIP_EXPORT int lthip_restore_archive_blocks(lthip_restore* restore, const lthip_archive* archive, const void* d_window,
+                                              uint64_t window_first_byte, uint64_t window_bytes, void* d_scratch, uint64_t scratch_bytes,
+                                              void* d_out, uint32_t* delivered, uint64_t* next_byte);
+LTHIP_EXPORT size_t lthip_restore_archive_scratch_bound(const lthip_restore* restore, const lthip_archive* archive, uint64_t window_first_byte,
+                                                        uint64_t window_bytes);
+LTHIP_EXPORT int lthip_restore_archive_ranges(const lthip_restore* restore, const lthip_archive* archive, uint64_t max_gap,
+                                              uint64_t* ranges /*host, [2 * capacity]*/, uint64_t capacity, uint64_t* count);
+
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets
  * (src/longtail.c:2396-2458).  lthip_job_count / lthip_make_jobs list the jobs of a tree exactly as :2399-2404 / :2432-2457 do

@@ -130,6 +130,7 @@ enum ScratchSlot
     S_RAW_RUNS,        // ... its runs (one slot per chunk: source, destination, length), their piece counts and the scan of those
     S_RAW_TABLES,      // ... and the hash / BlockIndex tables of lthip_write_raw_block_images
     S_CARRY_RUNS,      // restore session, lthip_restore_carry: boundary flags and their scan, the runs, their piece counts and the scan of those
+    S_ARCHIVE_ITEMS,   // archive writer, lthip_archive_writer_append: {source, destination, size} of the call's images
     S_COUNT
 };
 

@@ -46,6 +46,11 @@
 //            into it (the decoders' one destination base becomes the lower of scratch and arena), a raw block's payload is copied into
 //            it by k_restore_cache_copy behind the check.  finish, which reads the status words anyway, commits the good ones.
 //            Without a cache attached restore_queue computes what it always did.
+//   archive  (lthip_restore_archive_blocks; the index is host code, archive_layout.h) the images lie in the body of a one-file archive,
+//            back to back at ANY byte position.  The host picks the needed, undelivered blocks that lie wholly inside the caller's window
+//            of the body and delivers them through the routine lthip_restore_blocks uses, without its alignment refusal; the one stage
+//            that cared, the check, runs as k_restore_check_images_any: every header dword from the two aligned dwords around it.
+#include "archive_layout.h"
 #include "block_cache.h"
 #include "k_copy.h"
 #include "lthip_internal.h"
@@ -398,9 +403,31 @@ __global__ void k_restore_in_place_slots(uint32_t n, RunTables runs)
         runs.slot[i] = (uint64_t)runs.first_unit[i] << 4;
 }
 
-// ---- a delivered image against the StoreIndex: one wave per image ----
-__global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __restrict__ items, uint32_t k, const uint8_t* __restrict__ images,
-                                                             StoreView sv, uint32_t hash_identifier, uint32_t* __restrict__ status)
+// ---- a delivered image against the StoreIndex: one wave per image.  The header's dwords come through `Words`: AlignedWords for the
+// images of lthip_restore_blocks, AnyWords for an image at any byte position (an archive's body) ----
+struct AlignedWords
+{
+    const uint32_t* w;
+    __device__ __forceinline__ explicit AlignedWords(const uint8_t* image) : w(reinterpret_cast<const uint32_t*>(image)) {} // 8-byte aligned by contract
+    __device__ __forceinline__ uint32_t operator[](uint64_t j) const { return w[j]; }
+};
+// dword j of an image that starts mis = address & 3 bytes into an aligned dword: assembled from the two aligned dwords around it
+// (v_alignbit, as k_copy.h does).  Both hold bytes of dword j, so no dword is read that holds no byte of the image: an image may end at
+// the last byte of the allocation.
+struct AnyWords
+{
+    const uint32_t* q;
+    uint32_t sh;
+    __device__ __forceinline__ explicit AnyWords(const uint8_t* image)
+        : q(reinterpret_cast<const uint32_t*>(image - ((uintptr_t)image & 3u))), sh((uint32_t)((uintptr_t)image & 3u) * 8u)
+    {
+    }
+    __device__ __forceinline__ uint32_t operator[](uint64_t j) const { return sh ? __builtin_amdgcn_alignbit(q[j + 1], q[j], sh) : q[j]; }
+};
+
+template <class Words>
+__device__ __forceinline__ void check_image(const RItem* __restrict__ items, uint32_t k, const uint8_t* __restrict__ images, const StoreView& sv,
+                                            uint32_t hash_identifier, uint32_t* __restrict__ status)
 {
     const uint32_t i = blockIdx.x;
     if (i >= k)
@@ -414,7 +441,7 @@ __global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __rest
         st = LTHIP_RESTORE_BAD_HEADER;
     else
     {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(images + it.image); // 8-byte aligned by contract
+        const Words w(images + it.image);
         bool bad = false;
         if (lane == 0)
         {
@@ -435,6 +462,18 @@ __global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __rest
     }
     if (lane == 0)
         status[b] = st;
+}
+
+__global__ __launch_bounds__(64) void k_restore_check_images(const RItem* __restrict__ items, uint32_t k, const uint8_t* __restrict__ images,
+                                                             StoreView sv, uint32_t hash_identifier, uint32_t* __restrict__ status)
+{
+    check_image<AlignedWords>(items, k, images, sv, hash_identifier, status);
+}
+
+__global__ __launch_bounds__(64) void k_restore_check_images_any(const RItem* __restrict__ items, uint32_t k, const uint8_t* __restrict__ images,
+                                                                 StoreView sv, uint32_t hash_identifier, uint32_t* __restrict__ status)
+{
+    check_image<AnyWords>(items, k, images, sv, hash_identifier, status);
 }
 
 // ---- behind the decoders: their verdict into the status word; with verify, the byte range of every chunk of the good blocks (a bad
@@ -960,8 +999,9 @@ extern "C" size_t lthip_restore_scratch_bound(const lthip_restore* r, uint32_t b
     return (size_t)bytes;
 }
 
+// any_position: the images lie at any byte positions (an archive's body) and are checked by k_restore_check_images_any
 static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images, const uint64_t* image_offsets,
-                         const uint32_t* image_sizes, void* d_scratch, void* d_out)
+                         const uint32_t* image_sizes, void* d_scratch, void* d_out, bool any_position)
 {
     lthip_ctx* ctx = r->ctx;
     // ---- the call's needed blocks in three groups: not decoded (raw blocks; an image too short to hold a payload), LZ4, zstd ----
@@ -1043,8 +1083,8 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
         return err;
     {
         LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_check_images, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint8_t*)d_images,
-                           r->sv, r->hash_identifier, r->d_status);
+        hipLaunchKernelGGL(any_position ? k_restore_check_images_any : k_restore_check_images, dim3((uint32_t)k), dim3(64), 0, s,
+                           (const RItem*)r->d_items, (uint32_t)k, (const uint8_t*)d_images, r->sv, r->hash_identifier, r->d_status);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     if (copy_raw)
@@ -1112,11 +1152,10 @@ static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t*
     return 0;
 }
 
-extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images,
-                                    const uint64_t* image_offsets, const uint32_t* image_sizes, void* d_scratch, uint64_t scratch_bytes, void* d_out)
+// lthip_restore_blocks (any_position false: an image offset that is not 8-byte aligned is refused) and lthip_restore_archive_blocks
+static int restore_deliver(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images, const uint64_t* image_offsets,
+                           const uint32_t* image_sizes, void* d_scratch, uint64_t scratch_bytes, void* d_out, bool any_position, const char* who)
 {
-    if (!r || (block_count && (!block_hashes || !d_images || !image_offsets || !image_sizes)))
-        return EINVAL;
     lthip_ctx* ctx = r->ctx;
     // ---- the refusals, before anything is queued or changed ----
     int refused = 0;
@@ -1139,7 +1178,7 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
             break;
         }
         r->in_call[b] = 1;
-        if (image_offsets[marked] & 7u)
+        if (!any_position && (image_offsets[marked] & 7u))
             refused = EINVAL, why = "image offsets must be 8-byte aligned";
         else if (r->is_needed(b))
         {
@@ -1163,19 +1202,143 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
     if (!refused && any_needed && r->in_place_buf && d_out != r->in_place_buf)
         refused = EINVAL, why = "the base was carried in place: the output is that buffer";
     if (refused)
-        return lthip_fail(ctx, refused, "lthip_restore_blocks", why);
+        return lthip_fail(ctx, refused, who, why);
     int err;
     try
     {
-        err = restore_queue(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, d_out);
+        err = restore_queue(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, d_out, any_position);
     }
     catch (const std::bad_alloc&)
     {
-        err = lthip_fail(ctx, ENOMEM, "lthip_restore_blocks", "host tables");
+        err = lthip_fail(ctx, ENOMEM, who, "host tables");
     }
     if (err) // (a call that did not queue all of its work commits nothing: no status word of it can be trusted)
         r->release_cache(false);
     return err;
+}
+
+extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images,
+                                    const uint64_t* image_offsets, const uint32_t* image_sizes, void* d_scratch, uint64_t scratch_bytes, void* d_out)
+{
+    if (!r || (block_count && (!block_hashes || !d_images || !image_offsets || !image_sizes)))
+        return EINVAL;
+    return restore_deliver(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, scratch_bytes, d_out, false,
+                           "lthip_restore_blocks");
+}
+
+// ---- fed from an archive's body (archive_layout.h): the needed, not yet delivered blocks that lie wholly inside body bytes
+// [first, first + bytes), in the archive's block order.  A block of the archive that the session's StoreIndex does not hold, or holds
+// twice in the archive, is passed over. ----
+struct ArchivePick
+{
+    std::vector<uint64_t> hashes, offsets;
+    std::vector<uint32_t> sizes;
+    uint64_t scratch = 0, next_byte = 0;
+};
+static void archive_pick(lthip_restore* r, const archive_layout::Archive& a, uint64_t first, uint64_t bytes, ArchivePick* p)
+{
+    const uint64_t end = first + bytes < first ? ~0ull : first + bytes;
+    const size_t nb = a.bhash.size();
+    p->next_byte = a.body_bytes;
+    p->hashes.reserve(nb), p->offsets.reserve(nb), p->sizes.reserve(nb); // (nothing below throws: the marks are always taken back)
+    for (size_t i = 0; i < nb; ++i)
+    {
+        const auto it = r->block_of_hash.find(a.bhash[i]);
+        if (it == r->block_of_hash.end())
+            continue;
+        const uint32_t b = it->second;
+        if (!r->is_needed(b) || r->delivered[b] || r->in_call[b])
+            continue;
+        const uint64_t off = a.offsets[i], size = a.sizes[i];
+        if (off < first || off + size > end) // (off + size does not wrap: archive_layout::open)
+        {
+            p->next_byte = std::min(p->next_byte, off);
+            continue;
+        }
+        r->in_call[b] = 1; // (a hash the archive lists twice is picked once)
+        p->hashes.push_back(a.bhash[i]), p->offsets.push_back(off - first), p->sizes.push_back((uint32_t)size);
+        if (r->btag[b] != 0u)
+            p->scratch += round64(r->braw[b]);
+    }
+    for (const uint64_t h : p->hashes)
+        r->in_call[r->block_of_hash.find(h)->second] = 0;
+}
+
+extern "C" size_t lthip_restore_archive_scratch_bound(const lthip_restore* r, const lthip_archive* archive, uint64_t window_first_byte,
+                                                      uint64_t window_bytes)
+{
+    if (!r || !archive)
+        return 0;
+    try
+    {
+        ArchivePick p;
+        archive_pick(const_cast<lthip_restore*>(r), archive->a, window_first_byte, window_bytes, &p); // (the marks are taken back)
+        return (size_t)p.scratch;
+    }
+    catch (const std::bad_alloc&)
+    {
+        return 0;
+    }
+}
+
+extern "C" int lthip_restore_archive_blocks(lthip_restore* r, const lthip_archive* archive, const void* d_window, uint64_t window_first_byte,
+                                            uint64_t window_bytes, void* d_scratch, uint64_t scratch_bytes, void* d_out, uint32_t* delivered,
+                                            uint64_t* next_byte)
+{
+    if (!r || !archive || !delivered || !next_byte)
+        return EINVAL;
+    *delivered = 0;
+    try
+    {
+        ArchivePick p;
+        archive_pick(r, archive->a, window_first_byte, window_bytes, &p);
+        *next_byte = p.next_byte;
+        const uint32_t k = (uint32_t)p.hashes.size();
+        if (!k)
+            return 0;
+        if (!d_window)
+            return lthip_fail(r->ctx, EINVAL, "lthip_restore_archive_blocks", "null window");
+        const int err = restore_deliver(r, k, p.hashes.data(), d_window, p.offsets.data(), p.sizes.data(), d_scratch, scratch_bytes, d_out, true,
+                                        "lthip_restore_archive_blocks");
+        if (err) // (refused, or not all queued: the lowest outstanding block may be one of this window's)
+        {
+            for (const uint64_t o : p.offsets)
+                *next_byte = std::min(*next_byte, window_first_byte + o);
+            return err;
+        }
+        *delivered = k;
+        return 0;
+    }
+    catch (const std::bad_alloc&)
+    {
+        return lthip_fail(r->ctx, ENOMEM, "lthip_restore_archive_blocks", "host tables");
+    }
+}
+
+extern "C" int lthip_restore_archive_ranges(const lthip_restore* r, const lthip_archive* archive, uint64_t max_gap, uint64_t* ranges, uint64_t capacity,
+                                            uint64_t* count)
+{
+    if (!r || !archive || !count)
+        return EINVAL;
+    try
+    {
+        ArchivePick p;
+        archive_pick(const_cast<lthip_restore*>(r), archive->a, 0, ~0ull, &p); // every needed, outstanding block
+        std::vector<std::pair<uint64_t, uint64_t>> v;
+        for (size_t i = 0; i < p.hashes.size(); ++i)
+            v.emplace_back(p.offsets[i], (uint64_t)p.sizes[i]);
+        archive_layout::merge_ranges(&v, max_gap);
+        *count = v.size();
+        if (!ranges || capacity < v.size())
+            return 0;
+        for (size_t i = 0; i < v.size(); ++i)
+            ranges[2 * i] = v[i].first, ranges[2 * i + 1] = v[i].second;
+        return 0;
+    }
+    catch (const std::bad_alloc&)
+    {
+        return ENOMEM;
+    }
 }
 
 // d_scratch == null: out of place, d_base -> d_out.  Otherwise in place: d_base == d_out is the one buffer, and the moved runs go through

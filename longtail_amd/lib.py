@@ -188,6 +188,25 @@ class HipLib:
         sig("lthip_restore_set_cache", i32, [vp, vp])
         sig("lthip_restore_from_cache", i32, [vp, vp])
         sig("lthip_restore_cache_stats", i32, [vp, vp])
+        sig("lthip_archive_index_size", i32, [vp, sz, vp, sz, P(u64)])
+        sig("lthip_archive_write_index", i32, [vp, sz, vp, sz, vp, vp, vp, sz])
+        sig("lthip_archive_peek", i32, [vp, P(u64)])
+        sig("lthip_archive_open", i32, [vp, sz, u64, P(vp)])
+        sig("lthip_archive_close", None, [vp])
+        sig("lthip_archive_store_index", vp, [vp, P(sz)])
+        sig("lthip_archive_version_index", vp, [vp, P(sz)])
+        sig("lthip_archive_block_count", u32, [vp])
+        sig("lthip_archive_block_offsets", vp, [vp])
+        sig("lthip_archive_block_sizes", vp, [vp])
+        sig("lthip_archive_body_bytes", u64, [vp])
+        sig("lthip_archive_writer_create", i32, [vp, P(vp)])
+        sig("lthip_archive_writer_destroy", None, [vp])
+        sig("lthip_archive_writer_append", i32, [vp, vp, u32, vp, vp, vp, u64, P(u64)])
+        sig("lthip_archive_writer_blocks", i32, [vp, P(u64), P(vp), P(vp), P(u64)])
+        sig("lthip_archive_writer_finish", i32, [vp, vp, sz, vp, sz, vp, sz, P(u64)])
+        sig("lthip_restore_archive_blocks", i32, [vp, vp, vp, u64, u64, vp, u64, vp, P(u32), P(u64)])
+        sig("lthip_restore_archive_scratch_bound", sz, [vp, vp, u64, u64])
+        sig("lthip_restore_archive_ranges", i32, [vp, vp, u64, vp, u64, P(u64)])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1284,6 +1303,32 @@ class Restore:
         self.ctx._check(self.ctx.lib.dll.lthip_restore_cache_stats(self.h, out.ctypes.data), "lthip_restore_cache_stats")
         return tuple(int(x) for x in out)
 
+    def archive_blocks(self, archive: "Archive", window, window_first_byte: int, scratch, out, window_bytes: Optional[int] = None):
+        """Delivers every needed, not yet delivered block of `archive` that lies wholly inside body bytes [window_first_byte,
+        + window_bytes), which lie at `window` (a device uint8 tensor; window_bytes defaults to its length), at whatever byte position.
+        `scratch`: at least archive_scratch_bound(archive, window_first_byte, window_bytes) bytes, or None.  -> (blocks delivered, the
+        lowest body offset of a needed block still outstanding, or the body's size).  Asynchronous like blocks()."""
+        n = _numel(window) if window_bytes is None else int(window_bytes)
+        delivered, next_byte = C.c_uint32(0), C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_archive_blocks(self.h, archive.h, _ptr(window) or None, window_first_byte, n,
+                                                                      _ptr(scratch) or None, _numel(scratch), _ptr(out) or None,
+                                                                      C.byref(delivered), C.byref(next_byte)), "lthip_restore_archive_blocks")
+        self._keep.append((window, scratch, out))
+        return int(delivered.value), int(next_byte.value)
+
+    def archive_scratch_bound(self, archive: "Archive", window_first_byte: int, window_bytes: int) -> int:
+        return int(self.ctx.lib.dll.lthip_restore_archive_scratch_bound(self.h, archive.h, window_first_byte, window_bytes))
+
+    def archive_ranges(self, archive: "Archive", max_gap: int = 0) -> np.ndarray:
+        """-> (n, 2) uint64 rows of (first body byte, bytes): the needed, outstanding blocks' ranges, sorted, merged where the gap between
+        two is at most max_gap; host only."""
+        n = C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_archive_ranges(self.h, archive.h, max_gap, None, 0, C.byref(n)), "lthip_restore_archive_ranges")
+        out = np.zeros((n.value, 2), np.uint64)
+        self.ctx._check(self.ctx.lib.dll.lthip_restore_archive_ranges(self.h, archive.h, max_gap, out.ctypes.data if len(out) else None, len(out),
+                                                                      C.byref(n)), "lthip_restore_archive_ranges")
+        return out
+
     def finish(self):
         """-> (code, RestoreResult): 0, errno.ENOENT (needed blocks are outstanding, or the base has not been carried: deliver / carry
         and call again) or errno.EBADF (a delivered block was bad, or with verify a chunk of the base).  The session's one full
@@ -1348,6 +1393,149 @@ class BlockCache:
     def clear(self):
         """Drops every entry; LongtailHipError(EBUSY) while a live session pins an entry or has reserved a slot."""
         self.ctx._check(self.ctx.lib.dll.lthip_block_cache_clear(self.h), "lthip_block_cache_clear")
+
+
+ARCHIVE_BODY_UNKNOWN = 0xFFFFFFFFFFFFFFFF
+
+
+def _blob(b):
+    raw = np.frombuffer(b, np.uint8)
+    return raw, (raw.ctypes.data if len(raw) else None)
+
+
+def archive_index_size(store_index: bytes, version_index: bytes, lib: Optional[HipLib] = None) -> int:
+    """lthip_archive_index_size, host only: the bytes of the archive index of these two blobs."""
+    (si, psi), (vi, pvi) = _blob(store_index), _blob(version_index)
+    n = C.c_uint64(0)
+    err = (lib or load()).dll.lthip_archive_index_size(psi, len(si), pvi, len(vi), C.byref(n))
+    if err:
+        raise LongtailHipError(err, "lthip_archive_index_size")
+    return int(n.value)
+
+
+def archive_write_index(store_index: bytes, version_index: bytes, block_offsets, block_sizes, lib: Optional[HipLib] = None) -> bytes:
+    """lthip_archive_write_index, host only: the archive index with block b at body offset block_offsets[b], block_sizes[b] bytes long."""
+    (si, psi), (vi, pvi) = _blob(store_index), _blob(version_index)
+    o, z = _u64arr(block_offsets), _u32arr(block_sizes)
+    assert len(o) == len(z)
+    out = np.full(archive_index_size(store_index, version_index, lib), 0xEE, np.uint8)
+    err = (lib or load()).dll.lthip_archive_write_index(psi, len(si), pvi, len(vi), o.ctypes.data if len(o) else None,
+                                                        z.ctypes.data if len(z) else None, out.ctypes.data, len(out))
+    if err:
+        raise LongtailHipError(err, "lthip_archive_write_index")
+    return out.tobytes()
+
+
+def archive_peek(first_8_bytes: bytes, lib: Optional[HipLib] = None) -> int:
+    """lthip_archive_peek: the first eight bytes of an archive -> the bytes of its index."""
+    raw = np.frombuffer(first_8_bytes[:8], np.uint8)
+    if len(raw) < 8:
+        raise LongtailHipError(errno.EBADF, "lthip_archive_peek")
+    n = C.c_uint64(0)
+    err = (lib or load()).dll.lthip_archive_peek(raw.ctypes.data, C.byref(n))
+    if err:
+        raise LongtailHipError(err, "lthip_archive_peek")
+    return int(n.value)
+
+
+class Archive:
+    """lthip_archive: the opened index of a one-file archive (include/longtail_hip.h, "one-file archives"); host only, no context.
+    `index`: the index's bytes (archive_peek says how many); body_bytes: the size of what follows it in the file, None when unknown."""
+
+    def __init__(self, index: bytes, body_bytes: Optional[int] = None, lib: Optional[HipLib] = None):
+        self.lib = lib or load()
+        self.h = None
+        raw, p = _blob(index)
+        h = C.c_void_p()
+        none = np.zeros(8, np.uint8)  # (no bytes at all are a short index: EBADF, not the EINVAL of a null pointer)
+        err = self.lib.dll.lthip_archive_open(p or none.ctypes.data, len(raw), ARCHIVE_BODY_UNKNOWN if body_bytes is None else body_bytes, C.byref(h))
+        if err:
+            raise LongtailHipError(err, "lthip_archive_open")
+        self.h = h
+        dll, n = self.lib.dll, C.c_size_t(0)
+        p = dll.lthip_archive_store_index(h, C.byref(n))
+        self.store_index = C.string_at(p, n.value)
+        p = dll.lthip_archive_version_index(h, C.byref(n))
+        self.version_index = C.string_at(p, n.value)  # (the rest of the index: up to 7 pad bytes behind the name data)
+        self.block_count = int(dll.lthip_archive_block_count(h))
+        nb = self.block_count
+        self.block_offsets = np.ctypeslib.as_array((C.c_uint64 * nb).from_address(dll.lthip_archive_block_offsets(h))).copy() if nb else np.zeros(0, np.uint64)
+        self.block_sizes = np.ctypeslib.as_array((C.c_uint32 * nb).from_address(dll.lthip_archive_block_sizes(h))).copy() if nb else np.zeros(0, np.uint32)
+        self.body_bytes = int(dll.lthip_archive_body_bytes(h))
+        self.index_bytes = len(raw)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.dll.lthip_archive_close(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ArchiveWriter:
+    """lthip_archive_writer: packs the images an ingest session left in its arena into the body of a one-file archive, call by call, and
+    writes the index from what it recorded (include/longtail_hip.h, "one-file archives")."""
+
+    def __init__(self, ctx: "Context"):
+        self.ctx = ctx
+        self.h = None
+        h = C.c_void_p()
+        ctx._check(ctx.lib.dll.lthip_archive_writer_create(ctx.h, C.byref(h)), "lthip_archive_writer_create")
+        self.h = h
+        self._keep = []
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.dll.lthip_archive_writer_destroy(self.h)
+        self.h = None
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, arena, image_offsets, image_sizes, dst, dst_capacity: Optional[int] = None) -> int:
+        """Queues the copy of the images (image i at arena[image_offsets[i]], image_sizes[i] bytes, as IngestStream.images() returns them)
+        densely to dst[0:]; -> the bytes written.  The archive's body is the concatenation of all calls' outputs: drain `dst` (after
+        Context.sync(), or behind it on the stream) before it is reused."""
+        o, z = _u64arr(image_offsets), _u32arr(image_sizes)
+        assert len(o) == len(z)
+        n = C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_archive_writer_append(self.h, _ptr(arena) or None, len(o), o.ctypes.data if len(o) else None,
+                                                                     z.ctypes.data if len(z) else None, _ptr(dst) or None,
+                                                                     _numel(dst) if dst_capacity is None else dst_capacity, C.byref(n)),
+                        "lthip_archive_writer_append")
+        self._keep = [(arena, dst)]
+        return int(n.value)
+
+    def blocks(self):
+        """-> (body offsets [u64], sizes [u32]) of every block appended so far, and the body's size."""
+        n, po, ps, body = C.c_uint64(0), C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        self.ctx._check(self.ctx.lib.dll.lthip_archive_writer_blocks(self.h, C.byref(n), C.byref(po), C.byref(ps), C.byref(body)),
+                        "lthip_archive_writer_blocks")
+        k = int(n.value)
+        if not k:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint32), int(body.value)
+        return (np.ctypeslib.as_array((C.c_uint64 * k).from_address(po.value)).copy(),
+                np.ctypeslib.as_array((C.c_uint32 * k).from_address(ps.value)).copy(), int(body.value))
+
+    def finish(self, store_index: bytes, version_index: bytes) -> bytes:
+        """-> the archive index of the two blobs with the recorded block offsets and sizes."""
+        (si, psi), (vi, pvi) = _blob(store_index), _blob(version_index)
+        n = C.c_uint64(0)
+        err = self.ctx.lib.dll.lthip_archive_writer_finish(self.h, psi, len(si), pvi, len(vi), None, 0, C.byref(n))
+        if err != errno.ENOMEM:
+            self.ctx._check(err or errno.EIO, "lthip_archive_writer_finish")
+        out = np.zeros(n.value, np.uint8)
+        self.ctx._check(self.ctx.lib.dll.lthip_archive_writer_finish(self.h, psi, len(si), pvi, len(vi), out.ctypes.data, len(out), C.byref(n)),
+                        "lthip_archive_writer_finish")
+        return out.tobytes()
 
 
 def version_diff(source_vi: bytes, target_vi: bytes, lib: Optional[HipLib] = None):
