@@ -1202,6 +1202,32 @@ LTHIP_EXPORT size_t lthip_restore_archive_scratch_bound(const lthip_restore* res
 LTHIP_EXPORT int lthip_restore_archive_ranges(const lthip_restore* restore, const lthip_archive* archive, uint64_t max_gap,
                                               uint64_t* ranges /*host, [2 * capacity]*/, uint64_t capacity, uint64_t* count);
 
+/* ---- store index operations: prune, merge, a version's chunk hashes (store_index_ops.h) -------------------------------------------------
+ * Host only, no context: what keeps a store's index in step with its blocks.  The StoreIndexes the ingest sessions return are small and
+ * many -- one per slice of a host-fed loop, one per rank, one per incremental ingest; merge folds them into the store's index, prune
+ * takes the blocks a caller deleted out of it.  The outputs are serialized StoreIndexes, byte for byte the reference's:
+ *   prune   Longtail_PruneStoreIndex (src/longtail.c:9287) + Longtail_WriteStoreIndexToBuffer: the blocks of store_index whose hash is
+ *           among keep_block_hashes[0, keep_count), in store_index's order.  Repeats and unknown hashes in the keep list change nothing;
+ *           a block hash that stands twice in store_index is kept twice; the hash identifier is store_index's even when nothing is kept.
+ *   merge   Longtail_MergeStoreIndex (:9151) + Longtail_WriteStoreIndexToBuffer: local's blocks in their order, then remote's blocks
+ *           that local does not hold.  A block hash is taken once, its first occurrence gives the tag and the chunk list (a block both
+ *           sides hold is local's).  The hash identifier is local's when local has blocks, else remote's when remote has blocks, else 0.
+ *   version_chunk_hashes   the chunk hashes of a serialized VersionIndex, in its order: *count of them into out[0, capacity).  out NULL:
+ *           the count only.  The live set of the versions a caller keeps is the concatenation (lthip_get_existing_store_index and the
+ *           store sets take duplicates).
+ * Refusals.  EINVAL: a null blob or size pointer, keep_count without a list; merge: BOTH indexes have blocks and their hash identifiers
+ * differ; a result whose block or chunk count leaves 32 bits.  EBADF: a blob lthip_restore_create would call malformed (short, another
+ * version, a block whose chunks leave the chunk list).  ENOMEM with *out_size (*count) set: out is NULL or out_capacity too small --
+ * nothing is written, call again.  Blobs and `out` may lie at any alignment; the keep list and the hash output are the caller's uint64
+ * arrays.  Input and output must not overlap.
+ * These calls do not touch a block. */
+LTHIP_EXPORT int lthip_store_index_prune(const void* store_index, size_t store_index_size, uint32_t keep_count,
+                                         const uint64_t* keep_block_hashes /*host*/, void* out, size_t out_capacity, size_t* out_size);
+LTHIP_EXPORT int lthip_store_index_merge(const void* local, size_t local_size, const void* remote, size_t remote_size, void* out,
+                                         size_t out_capacity, size_t* out_size);
+LTHIP_EXPORT int lthip_version_chunk_hashes(const void* version_index, size_t version_index_size, uint64_t* out /*host, may be NULL*/,
+                                            uint64_t capacity, uint64_t* count);
+
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets
  * (src/longtail.c:2396-2458).  lthip_job_count / lthip_make_jobs list the jobs of a tree exactly as :2399-2404 / :2432-2457 do

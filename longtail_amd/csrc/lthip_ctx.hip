@@ -1,8 +1,11 @@
 // lthip_ctx.hip -- context, scratch pools, per-kernel event timing, plans and the phase-1 orchestration
 // of liblongtail_hip.so.  Host code only; the kernels live in k_*.hip.
 #include "lthip_internal.h"
+#include "store_index_ops.h"
 
 #include <stdlib.h>
+
+#include <new>
 
 // ---------------------------------------------------------------------------------------------------
 // errors / scratch
@@ -583,6 +586,39 @@ extern "C" int lthip_pack_blocks_batch(uint64_t chunk_count, const uint32_t* chu
     *out_block_count = nb;
     *out_next_chunk = i;
     return 0;
+}
+
+// The index operations of store_index_ops.h behind the C interface: host only, no context.  An allocation that fails is ENOMEM with
+// *out_size / *count left as it was.
+extern "C" int lthip_store_index_prune(const void* store_index, size_t size, uint32_t keep_count, const uint64_t* keep_block_hashes, void* out,
+                                       size_t out_capacity, size_t* out_size)
+{
+    try
+    {
+        return store_index_ops::prune(store_index, size, keep_count, keep_block_hashes, out, out_capacity, out_size);
+    }
+    catch (const std::bad_alloc&)
+    {
+        return ENOMEM;
+    }
+}
+
+extern "C" int lthip_store_index_merge(const void* local, size_t local_size, const void* remote, size_t remote_size, void* out, size_t out_capacity,
+                                       size_t* out_size)
+{
+    try
+    {
+        return store_index_ops::merge(local, local_size, remote, remote_size, out, out_capacity, out_size);
+    }
+    catch (const std::bad_alloc&)
+    {
+        return ENOMEM;
+    }
+}
+
+extern "C" int lthip_version_chunk_hashes(const void* version_index, size_t size, uint64_t* out, uint64_t capacity, uint64_t* count)
+{
+    return store_index_ops::version_chunk_hashes(version_index, size, out, capacity, count);
 }
 
 extern "C" int lthip_divtest_eval(uint32_t discriminator, uint32_t hash)

@@ -207,6 +207,9 @@ class HipLib:
         sig("lthip_restore_archive_blocks", i32, [vp, vp, vp, u64, u64, vp, u64, vp, P(u32), P(u64)])
         sig("lthip_restore_archive_scratch_bound", sz, [vp, vp, u64, u64])
         sig("lthip_restore_archive_ranges", i32, [vp, vp, u64, vp, u64, P(u64)])
+        sig("lthip_store_index_prune", i32, [vp, sz, u32, vp, vp, sz, P(sz)])
+        sig("lthip_store_index_merge", i32, [vp, sz, vp, sz, vp, sz, P(sz)])
+        sig("lthip_version_chunk_hashes", i32, [vp, sz, vp, u64, P(u64)])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1536,6 +1539,49 @@ class ArchiveWriter:
         self.ctx._check(self.ctx.lib.dll.lthip_archive_writer_finish(self.h, psi, len(si), pvi, len(vi), out.ctypes.data, len(out), C.byref(n)),
                         "lthip_archive_writer_finish")
         return out.tobytes()
+
+
+def _sized_blob_call(fn, name: str, *args) -> bytes:
+    """A host call that ends in (out, capacity, *size): asked for the size (ENOMEM with the size set), then for the bytes."""
+    n = C.c_size_t(0)
+    err = fn(*args, None, 0, C.byref(n))
+    if err != errno.ENOMEM:
+        raise LongtailHipError(err, name)
+    out = np.full(n.value, 0xEE, np.uint8)
+    err = fn(*args, out.ctypes.data, len(out), C.byref(n))
+    if err:
+        raise LongtailHipError(err, name)
+    return out[: n.value].tobytes()
+
+
+def store_index_prune(store_index: bytes, keep_block_hashes, lib: Optional[HipLib] = None) -> bytes:
+    """lthip_store_index_prune, host only: the StoreIndex of the blocks of `store_index` whose hash is among keep_block_hashes, in its
+    order (Longtail_PruneStoreIndex, serialized)."""
+    (si, psi), keep = _blob(store_index), _u64arr(keep_block_hashes)
+    return _sized_blob_call((lib or load()).dll.lthip_store_index_prune, "lthip_store_index_prune", psi, len(si), len(keep),
+                            keep.ctypes.data if len(keep) else None)
+
+
+def store_index_merge(local: bytes, remote: bytes, lib: Optional[HipLib] = None) -> bytes:
+    """lthip_store_index_merge, host only: local's blocks, then remote's blocks that local does not hold (Longtail_MergeStoreIndex,
+    serialized)."""
+    (a, pa), (b, pb) = _blob(local), _blob(remote)
+    return _sized_blob_call((lib or load()).dll.lthip_store_index_merge, "lthip_store_index_merge", pa, len(a), pb, len(b))
+
+
+def version_chunk_hashes(version_index: bytes, lib: Optional[HipLib] = None) -> np.ndarray:
+    """lthip_version_chunk_hashes, host only: the chunk hashes of a serialized VersionIndex, in its order (uint64 array)."""
+    dll = (lib or load()).dll
+    raw, p = _blob(version_index)
+    n = C.c_uint64(0)
+    err = dll.lthip_version_chunk_hashes(p, len(raw), None, 0, C.byref(n))
+    if err not in (0, errno.ENOMEM):
+        raise LongtailHipError(err, "lthip_version_chunk_hashes")
+    out = np.zeros(n.value, np.uint64)
+    err = dll.lthip_version_chunk_hashes(p, len(raw), out.ctypes.data if len(out) else None, len(out), C.byref(n))
+    if err:
+        raise LongtailHipError(err, "lthip_version_chunk_hashes")
+    return out
 
 
 def version_diff(source_vi: bytes, target_vi: bytes, lib: Optional[HipLib] = None):
