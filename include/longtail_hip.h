@@ -790,7 +790,7 @@ LTHIP_EXPORT uint64_t lthip_ingest_stream_table_grown(const lthip_ingest_stream*
 LTHIP_EXPORT int lthip_ingest_stream_set_store(lthip_ingest_stream* stream, const lthip_store* store);
 LTHIP_EXPORT int lthip_ingest_stream_store_stats(const lthip_ingest_stream* stream, uint64_t* known_chunks, uint64_t* known_bytes);
 
-/* ---- the restore session: stored blocks back into a version's assets (restore.hip) --------------------------------------------------
+/* ---- the restore session: stored blocks back into a version's assets (restore.hip, restore_call.h) ----------------------------------
  * The device side of Longtail_WriteVersion (src/longtail.c:6471-6573 with BuildAssetWriteList :6021 and WriteAssetsFromBlock :5700) and
  * of DecompressBlock (compressblockstore.c:271-338) for a caller that holds a serialized VersionIndex, a serialized StoreIndex and the
  * stored-block images the ingest sessions (or the reference) wrote, the images already in HBM: the assets' bytes are written into ONE

@@ -7,6 +7,7 @@
 #include "k_copy.h"
 #include "lthip_internal.h"
 
+#include <memory>
 #include <new>
 
 namespace
@@ -69,22 +70,13 @@ extern "C" int lthip_archive_open(const void* index, size_t index_bytes, uint64_
         *out = nullptr;
     if (!index || !out)
         return EINVAL;
-    try
-    {
-        lthip_archive* a = new lthip_archive();
+    return lthip_guarded(nullptr, nullptr, [&] {
+        std::unique_ptr<lthip_archive> a(new lthip_archive()); // (freed when open refuses or runs out of memory)
         const int err = archive_layout::open(index, index_bytes, body_bytes, &a->a);
-        if (err)
-        {
-            delete a;
-            return err;
-        }
-        *out = a;
-        return 0;
-    }
-    catch (const std::bad_alloc&)
-    {
-        return ENOMEM;
-    }
+        if (!err)
+            *out = a.release();
+        return err;
+    });
 }
 
 extern "C" void lthip_archive_close(lthip_archive* a) { delete a; }
@@ -187,15 +179,8 @@ extern "C" int lthip_archive_writer_append(lthip_archive_writer* w, const void* 
         return lthip_fail(ctx, EINVAL, "lthip_archive_writer_append", "null arena or destination");
     if (count > 0x7FFFFFFFu || w->cursor + total < w->cursor)
         return lthip_fail(ctx, EINVAL, "lthip_archive_writer_append", "more than 2^31 - 1 images in a call");
-    int err;
-    try
-    {
-        err = writer_append(w, d_arena, count, image_offsets, image_sizes, d_dst, total, largest);
-    }
-    catch (const std::bad_alloc&)
-    {
-        err = lthip_fail(ctx, ENOMEM, "lthip_archive_writer_append", "host tables");
-    }
+    const int err = lthip_guarded(ctx, "lthip_archive_writer_append",
+                                  [&] { return writer_append(w, d_arena, count, image_offsets, image_sizes, d_dst, total, largest); });
     if (!err)
         *bytes_written = total;
     return err;

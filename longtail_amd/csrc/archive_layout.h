@@ -12,7 +12,7 @@
 // restore_parse::parse_version_index takes the name data as what is left of the blob and accepts the up to 7 trailing bytes.
 // Blocks lie in the body in ANY order (the reference writes them as its workers complete, archiveblockstore.c:70-77) and at any byte
 // position; that they overlap is not an error, every image is checked against the StoreIndex when it is delivered.
-// Included by archive.hip, restore.hip and the stand-alone driver tests/san/archive_driver.cpp.
+// Included by archive.hip, restore.hip, restore_call.h and the stand-alone driver tests/san/archive_driver.cpp.
 #pragma once
 #include "restore_parse.h"
 

@@ -593,27 +593,13 @@ extern "C" int lthip_pack_blocks_batch(uint64_t chunk_count, const uint32_t* chu
 extern "C" int lthip_store_index_prune(const void* store_index, size_t size, uint32_t keep_count, const uint64_t* keep_block_hashes, void* out,
                                        size_t out_capacity, size_t* out_size)
 {
-    try
-    {
-        return store_index_ops::prune(store_index, size, keep_count, keep_block_hashes, out, out_capacity, out_size);
-    }
-    catch (const std::bad_alloc&)
-    {
-        return ENOMEM;
-    }
+    return lthip_guarded(nullptr, nullptr, [&] { return store_index_ops::prune(store_index, size, keep_count, keep_block_hashes, out, out_capacity, out_size); });
 }
 
 extern "C" int lthip_store_index_merge(const void* local, size_t local_size, const void* remote, size_t remote_size, void* out, size_t out_capacity,
                                        size_t* out_size)
 {
-    try
-    {
-        return store_index_ops::merge(local, local_size, remote, remote_size, out, out_capacity, out_size);
-    }
-    catch (const std::bad_alloc&)
-    {
-        return ENOMEM;
-    }
+    return lthip_guarded(nullptr, nullptr, [&] { return store_index_ops::merge(local, local_size, remote, remote_size, out, out_capacity, out_size); });
 }
 
 extern "C" int lthip_version_chunk_hashes(const void* version_index, size_t size, uint64_t* out, uint64_t capacity, uint64_t* count)

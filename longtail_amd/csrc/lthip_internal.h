@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <new>
 #include <vector>
 
 #include "../../include/longtail_hip.h"
@@ -178,6 +179,18 @@ struct lthip_ctx
 };
 
 int lthip_fail(lthip_ctx* ctx, int code, const char* what, const char* detail);
+// Runs a callable that returns an errno: std::bad_alloc becomes ENOMEM, "who: host tables" in the context's error text (no context: the code alone)
+template <class F> int lthip_guarded(lthip_ctx* ctx, const char* who, F&& f)
+{
+    try
+    {
+        return f();
+    }
+    catch (const std::bad_alloc&)
+    {
+        return lthip_fail(ctx, ENOMEM, who, "host tables");
+    }
+}
 // Waits for everything queued on the context's stream (the one place the library waits for a stream).  HOW a thread waits is the
 // device's scheduling policy: lthip_set_blocking_waits (lthip_ctx.hip).
 hipError_t lthip_stream_wait(lthip_ctx* ctx);

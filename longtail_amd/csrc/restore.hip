@@ -50,17 +50,16 @@
 //            back to back at ANY byte position.  The host picks the needed, undelivered blocks that lie wholly inside the caller's window
 //            of the body and delivers them through the routine lthip_restore_blocks uses, without its alignment refusal; the one stage
 //            that cared, the check, runs as k_restore_check_images_any: every header dword from the two aligned dwords around it.
+//   call     (restore_call.h, host code) what a blocks call names, whether it is refused and what it changes: lthip_restore_blocks
+//            resolves its hashes to block indices once, the archive's pick yields indices; restore_deliver and restore_queue take those.
+//            restore_queue is five stages -- items and slots, check, decode, judge, scatter -- of which only the last knows of entries.
 #include "archive_layout.h"
 #include "block_cache.h"
 #include "k_copy.h"
 #include "lthip_internal.h"
+#include "restore_call.h"
 #include "restore_layout.h"
-#include "restore_plan.h"
-#include "store_layout.h"
 #include "version_diff.h"
-
-#include <new>
-#include <unordered_map>
 
 namespace
 {
@@ -579,7 +578,16 @@ int upload(lthip_ctx* ctx, void* d_dst, const void* h_src, size_t bytes)
 
 template <class T> int upload(lthip_ctx* ctx, T* d_dst, const std::vector<T>& h_src) { return upload(ctx, d_dst, h_src.data(), h_src.size() * sizeof(T)); }
 
-uint64_t round64(uint64_t x) { return (x + 63u) & ~(uint64_t)63u; }
+using restore_call::round64;
+
+// one kernel launch on the context's stream, timed as `kid`
+template <class K, class... A> int launch(lthip_ctx* ctx, int kid, K kernel, dim3 grid, dim3 block, A... args)
+{
+    LaunchTimer tm(ctx, kid);
+    hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, args...);
+    LTHIP_LAUNCH_CHECK(ctx);
+    return 0;
+}
 
 } // namespace
 
@@ -591,59 +599,34 @@ struct lthip_block_cache
     uint64_t slot_address(uint32_t s) const { return (uint64_t)(uintptr_t)arena + (uint64_t)s * table.slot_bytes(); }
 };
 
-struct lthip_restore
+// the base: its distinct chunks, what of the plan it feeds (the read-back of create), whether carry has queued it, the buffer of a carry in place
+struct BaseState
 {
-    lthip_ctx* ctx = nullptr;
-    uint32_t verify = 0, hash_identifier = 0;
-    uint32_t nb = 0, m = 0, nocc = 0, max_chunk = 0;
-    uint64_t block_chunks = 0; // the blocks' chunk counts summed: m for an index whose blocks share no chunk position
-    uint64_t assets_selected = 0, needed = 0, needed_delivered = 0, delivered_all = 0, unneeded = 0;
-    bool finished = false;
-    // the base: its distinct chunks, what of the plan it feeds (the read-back of create), whether carry has queued it
-    bool has_base = false, carried = false;
+    bool has_base = false, carried = false, in_place = false;
     uint32_t nub = 0, ncarry = 0, nmarked = 0, base_max_chunk = 0;
-    uint64_t out_bytes = 0, base_window = 0, carry_bytes = 0, carry_leaves = 0, moved_occ = 0, moved_bytes = 0;
-    // in place: blocks calls that queued work (an in-place carry comes before them), the buffer an in-place carry was given
-    bool blocks_queued = false, in_place = false;
+    uint64_t base_window = 0, carry_bytes = 0, carry_leaves = 0, moved_occ = 0, moved_bytes = 0;
     void* in_place_buf = nullptr;
-    // the StoreIndex and the plan on the host
-    std::vector<uint64_t> bhash, bbytes, bleaves;
-    std::vector<uint32_t> bcnt, btag, braw, firsts, status;
-    std::vector<uint8_t> delivered, in_call;
-    std::unordered_map<uint64_t, uint32_t> block_of_hash;
-    // the device side: one allocation for what lives as long as the session, one for what only the plan needs (PlanTmp)
-    lthip_seen *seen = nullptr, *seen_base = nullptr;
-    void *d_mem = nullptr, *d_tmp = nullptr;
-    StoreView sv;
-    uint32_t *d_status = nullptr, *d_firsts = nullptr, *d_outsz = nullptr;
-    uint4* d_entries = nullptr;
-    RItem* d_items = nullptr;
-    Counters* d_counters = nullptr;
-    RangeView ranges; // verify: the chunks of a blocks call
     BaseView base;
     CarryView carry;
     RangeView base_ranges; // verify: the base chunks that feed something
-    // host tables of a lthip_restore_blocks call, kept for their capacity
-    std::vector<RItem> items;
-    std::vector<uint32_t> outsz, group[3], c_size, c_cap;
-    std::vector<uint64_t> c_src, c_dst;
-    // the cache (null: none attached).  fed[b]: the block is cache-fed from slot cslot[b]; reserved: the delivered blocks that have a
-    // reserved slot cslot[b], until finish commits or releases them
+};
+
+// the cache (null: none attached).  A block with Blocks::fed is cache-fed from slot cslot[b]; reserved: the delivered blocks that have a
+// reserved slot cslot[b], until finish commits or releases them
+struct CacheLink
+{
     lthip_block_cache* cache = nullptr;
     bool from_cache_done = false, pins_held = false;
-    std::vector<uint64_t> h_chash, bdigest, slot_of;
-    std::vector<uint32_t> h_csize, h_bcoff, cslot, fed_blocks, reserved;
-    std::vector<uint8_t> fed;
+    std::vector<uint64_t> bdigest, slot_of;
+    std::vector<uint32_t> cslot, fed_blocks, reserved;
     uint64_t fed_bytes = 0, fed_entries = 0, c_inserted = 0, c_bypassed = 0, c_dropped = 0;
     void* d_cmem = nullptr;
     RItem* d_fed_items = nullptr;
     uint32_t* d_fed_outsz = nullptr;
     uint64_t* d_slot_of = nullptr;
-
-    bool is_needed(uint32_t b) const { return firsts[b + 1] != firsts[b] && !fed[b]; }
-    block_cache::Key cache_key(uint32_t b) const { return block_cache::Key{hash_identifier, bhash[b]}; }
-    block_cache::Meta cache_meta(uint32_t b) const { return block_cache::Meta{bcnt[b], braw[b], bdigest[b]}; }
-    size_t carve_cache(Carver c)
+    block_cache::Key cache_key(uint32_t hash_identifier, const restore_plan::StoreTables& st, uint32_t b) const { return {hash_identifier, st.bhash[b]}; }
+    block_cache::Meta cache_meta(const restore_plan::StoreTables& st, uint32_t b) const { return block_cache::Meta{st.bcnt[b], st.braw[b], bdigest[b]}; }
+    size_t carve_cache(Carver c, size_t nb)
     {
         c.take(&d_fed_items, fed_blocks.size()), c.take(&d_fed_outsz, fed_blocks.size()), c.take(&d_slot_of, nb);
         return c.at;
@@ -663,22 +646,70 @@ struct lthip_restore
             pins_held = false;
         }
     }
+};
+
+// host tables of a blocks call, kept for their capacity
+struct CallTables
+{
+    restore_call::Call c;
+    std::vector<RItem> items;
+    std::vector<uint32_t> outsz, c_size, c_cap;
+    std::vector<uint64_t> c_src, c_dst;
+};
+
+struct lthip_restore
+{
+    lthip_ctx* ctx = nullptr;
+    uint32_t verify = 0, hash_identifier = 0;
+    uint32_t nb = 0, m = 0, nocc = 0, max_chunk = 0;
+    uint64_t block_chunks = 0; // the blocks' chunk counts summed: m for an index whose blocks share no chunk position
+    uint64_t assets_selected = 0, out_bytes = 0;
+    bool finished = false, blocks_queued = false; // blocks_queued: a call has queued work (an in-place carry and a cache come before that)
+    restore_call::Blocks blk;                     // the StoreIndex and the plan on the host, and what was delivered
+    std::vector<uint64_t> bbytes;                 // per block: the bytes its entries write ...
+    std::vector<uint32_t> status;                 // ... and its status word, read back by finish
+    BaseState bs;
+    CacheLink cl;
+    CallTables call;
+    // the device side: one allocation for what lives as long as the session, one for what only the plan needs (PlanTmp)
+    lthip_seen *seen = nullptr, *seen_base = nullptr;
+    void *d_mem = nullptr, *d_tmp = nullptr;
+    StoreView sv;
+    uint32_t *d_status = nullptr, *d_firsts = nullptr, *d_outsz = nullptr;
+    uint4* d_entries = nullptr;
+    RItem* d_items = nullptr;
+    Counters* d_counters = nullptr;
+    RangeView ranges; // verify: the chunks of a blocks call
+
     size_t carve(Carver c, size_t items_cap)
     {
+        const size_t nub = bs.nub;
         c.take(&sv.chash, m), c.take(&sv.csize, m), c.take(&sv.cblock, m), c.take(&sv.coff, m);
         c.take(&sv.bhash, nb), c.take(&sv.bcoff, nb), c.take(&sv.bcnt, nb), c.take(&sv.btag, nb), c.take(&sv.braw, nb), c.take(&d_status, nb);
         c.take(&d_firsts, (size_t)nb + 1), c.take(&d_entries, nocc), c.take(&d_items, items_cap), c.take(&d_outsz, items_cap), c.take(&d_counters, 1);
         if (verify)
             c.take(&ranges.off, block_chunks), c.take(&ranges.hash, block_chunks), c.take(&ranges.len, block_chunks),
                 c.take(&ranges.block, block_chunks), c.take(&ranges.chunk, block_chunks);
-        if (has_base)
-            c.take(&carry.src, nocc), c.take(&carry.dst, nocc), c.take(&carry.len, nocc), c.take(&carry.chunk, nocc), c.take(&base.hash, nub),
-                c.take(&base.off, nub), c.take(&base.size, nub), c.take(&base.feed, nub), c.take(&base.bad, nub);
-        if (has_base && verify)
-            c.take(&base_ranges.off, nub), c.take(&base_ranges.hash, nub), c.take(&base_ranges.len, nub), c.take(&base_ranges.chunk, nub);
+        if (bs.has_base)
+            c.take(&bs.carry.src, nocc), c.take(&bs.carry.dst, nocc), c.take(&bs.carry.len, nocc), c.take(&bs.carry.chunk, nocc),
+                c.take(&bs.base.hash, nub), c.take(&bs.base.off, nub), c.take(&bs.base.size, nub), c.take(&bs.base.feed, nub), c.take(&bs.base.bad, nub);
+        if (bs.has_base && verify)
+            c.take(&bs.base_ranges.off, nub), c.take(&bs.base_ranges.hash, nub), c.take(&bs.base_ranges.len, nub), c.take(&bs.base_ranges.chunk, nub);
         return c.at;
     }
 };
+
+// the entries of k items in launches of 2^23 (a launch holds fewer than 2^32 threads)
+static int launch_scatter(const lthip_restore* r, const RItem* d_items, uint32_t k, uint64_t entries, const uint32_t* d_outsz, void* d_out)
+{
+    LaunchTimer tm(r->ctx, LTHIP_K_GATHER);
+    constexpr uint64_t LAUNCH_ENTRIES = 1u << 23;
+    for (uint64_t e0 = 0; e0 < entries; e0 += LAUNCH_ENTRIES)
+        hipLaunchKernelGGL(k_restore_scatter, dim3((uint32_t)std::min(LAUNCH_ENTRIES, entries - e0)), dim3(RT), 0, r->ctx->stream, d_items, k,
+                           (const uint4*)r->d_entries, (const uint32_t*)r->d_status, d_outsz, (uint32_t)e0, (uint8_t*)d_out);
+    LTHIP_LAUNCH_CHECK(r->ctx);
+    return 0;
+}
 
 extern "C" int lthip_restore_layout(const void* version_index, size_t size, uint64_t align, uint64_t* asset_offsets, uint32_t* asset_count,
                                     uint64_t* total_bytes)
@@ -699,13 +730,13 @@ extern "C" void lthip_restore_destroy(lthip_restore* r)
     if (!r)
         return;
     (void)hipSetDevice(r->ctx->device);
-    if (r->d_mem || r->d_tmp || r->d_cmem)
+    if (r->d_mem || r->d_tmp || r->cl.d_cmem)
         (void)hipStreamSynchronize(r->ctx->stream);
-    r->release_cache(true); // (behind the wait: nothing of this session reads or writes a slot any more)
+    r->cl.release_cache(true); // (behind the wait: nothing of this session reads or writes a slot any more)
     lthip_seen_destroy(r->seen);
     lthip_seen_destroy(r->seen_base);
-    if (r->d_cmem)
-        (void)hipFree(r->d_cmem);
+    if (r->cl.d_cmem)
+        (void)hipFree(r->cl.d_cmem);
     if (r->d_mem)
         (void)hipFree(r->d_mem);
     if (r->d_tmp)
@@ -761,18 +792,18 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
             return lthip_fail(ctx, EINVAL, "lthip_restore_create_from_base", "the base and the target carry different hash identifiers");
         if (bvi.asset_count && !base->asset_offsets)
             return EINVAL;
-        r->has_base = true;
-        r->base_window = base->base_bytes;
-        r->nub = bvi.chunk_count;
+        r->bs.has_base = true;
+        r->bs.base_window = base->base_bytes;
+        r->bs.nub = bvi.chunk_count;
         if ((refused = restore_plan::base_table(bvi, base->asset_offsets, base->base_bytes, &bt, &why)))
             return lthip_fail(ctx, refused, "lthip_restore_create_from_base", why);
-        r->base_max_chunk = bt.max_chunk;
+        r->bs.base_max_chunk = bt.max_chunk;
     }
     // ---- the StoreIndex: per block its tables, per chunk position the block that holds it and where ----
-    restore_plan::StoreTables st;
+    restore_plan::StoreTables& st = r->blk.st;
     if ((refused = restore_plan::store_tables(si, &st, &why)))
         return lthip_fail(ctx, refused, "lthip_restore_create", why);
-    const uint32_t nb = r->nb = si.block_count, m = r->m = si.chunk_count, nub = r->nub;
+    const uint32_t nb = r->nb = si.block_count, m = r->m = si.chunk_count, nub = r->bs.nub;
     r->max_chunk = st.max_chunk;
     r->block_chunks = st.block_chunks;
     // ---- occurrences: per window and chunk it touches (hash, full length, skip, clip, destination) ----
@@ -807,20 +838,17 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
         return err;
     if (clipped && ((err = upload(ctx, t.occ.skip, occ.skip)) || (err = upload(ctx, t.occ.clip, occ.clip))))
         return err;
-    if (base && ((err = upload(ctx, r->base.hash, bt.hash)) || (err = upload(ctx, r->base.off, bt.off)) || (err = upload(ctx, r->base.size, bt.size))))
+    if (base && ((err = upload(ctx, r->bs.base.hash, bt.hash)) || (err = upload(ctx, r->bs.base.off, bt.off)) ||
+                 (err = upload(ctx, r->bs.base.size, bt.size))))
         return err;
-    // what of the StoreIndex the host keeps
-    r->bhash = std::move(st.bhash), r->bleaves = std::move(st.bleaves);
-    r->bcnt = std::move(st.bcnt), r->btag = std::move(st.btag), r->braw = std::move(st.braw);
-    r->h_chash = std::move(st.chash), r->h_csize = std::move(st.csize), r->h_bcoff = std::move(st.bcoff); // (for a cache's digests)
-    for (uint32_t b = 0; b < nb; ++b)
-        r->block_of_hash.emplace(r->bhash[b], b);
-    r->delivered.assign(nb, 0), r->in_call.assign(nb, 0), r->status.assign(nb, 0u), r->fed.assign(nb, 0);
-    r->firsts.assign((size_t)nb + 1, 0u), r->bbytes.assign(nb, 0ull);
+    // (the staging ring has copied them: the host reads neither again, the rest of the StoreIndex stays)
+    std::vector<uint32_t>().swap(st.cblock), std::vector<uint32_t>().swap(st.coff);
+    r->blk.init();
+    r->status.assign(nb, 0u), r->bbytes.assign(nb, 0ull);
     if (base && nub)
     {
-        LTHIP_CHECK(ctx, hipMemsetAsync(r->base.feed, 0, (size_t)nub * 4, s));
-        LTHIP_CHECK(ctx, hipMemsetAsync(r->base.bad, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->bs.base.feed, 0, (size_t)nub * 4, s));
+        LTHIP_CHECK(ctx, hipMemsetAsync(r->bs.base.bad, 0, (size_t)nub * 4, s));
         LTHIP_CHECK(ctx, hipMemsetAsync(t.bmark, 0, (size_t)nub * 4, s));
     }
     LTHIP_CHECK(ctx, hipMemsetAsync(r->d_counters, 0, sizeof(Counters), s));
@@ -837,63 +865,51 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     // ... and, with a base, hash -> position among the base's chunks: an occurrence the base feeds is not resolved against the StoreIndex
     if (base)
     {
-        if ((err = lthip_seen_create(ctx, nub, &r->seen_base)) || (err = lthip_seen_add(r->seen_base, nub, r->base.hash, t.bfirst, nullptr)))
+        if ((err = lthip_seen_create(ctx, nub, &r->seen_base)) || (err = lthip_seen_add(r->seen_base, nub, r->bs.base.hash, t.bfirst, nullptr)))
             return err;
         if (nocc && (err = lthip_seen_find(r->seen_base, nocc, t.ohash, t.occ.bpos)))
             return err;
     }
-    if (nocc)
-    {
-        if ((err = lthip_seen_find(r->seen, nocc, t.ohash, t.occ.pos)))
-            return err;
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, t, r->base, sv, r->d_counters);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
+    if (nocc && ((err = lthip_seen_find(r->seen, nocc, t.ohash, t.occ.pos)) ||
+                 (err = launch(ctx, LTHIP_K_OTHER, k_restore_resolve, dim3((nocc + 255u) / 256u), dim3(256), nocc, t, r->bs.base, sv, r->d_counters))))
+        return err;
     if ((err = lthip_exclusive_scan_u32(ctx, t.hist, r->d_firsts, nb, nullptr, LTHIP_K_OTHER)))
         return err;
     if (base && ((err = lthip_exclusive_scan_u32(ctx, t.oflag, t.ofirst, nocc, nullptr, LTHIP_K_OTHER)) ||
                  (err = lthip_exclusive_scan_u32(ctx, t.bmark, t.mfirst, nub, nullptr, LTHIP_K_OTHER))))
         return err;
-    if (nocc)
-    {
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), 0, s, nocc, t, r->base, sv, (const uint32_t*)r->d_firsts,
-                           r->d_entries, r->carry, r->d_counters);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    if (base && r->verify && nub)
-    {
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_carry_marked, dim3((nub + 255u) / 256u), dim3(256), 0, s, nub, t, r->base, r->base_ranges, r->d_counters);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
+    if (nocc && (err = launch(ctx, LTHIP_K_OTHER, k_restore_fill, dim3((nocc + 255u) / 256u), dim3(256), nocc, t, r->bs.base, sv,
+                              (const uint32_t*)r->d_firsts, r->d_entries, r->bs.carry, r->d_counters)))
+        return err;
+    if (base && r->verify && nub &&
+        (err = launch(ctx, LTHIP_K_OTHER, k_restore_carry_marked, dim3((nub + 255u) / 256u), dim3(256), nub, t, r->bs.base, r->bs.base_ranges, r->d_counters)))
+        return err;
     // ---- the one read-back: the firsts (and the bytes per block, for the statistics), what did not resolve, what the base feeds ----
     Counters counters = {};
-    LTHIP_CHECK(ctx, hipMemcpyAsync(r->firsts.data(), r->d_firsts, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    LTHIP_CHECK(ctx, hipMemcpyAsync(r->blk.firsts.data(), r->d_firsts, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
     if (nb)
         LTHIP_CHECK(ctx, hipMemcpyAsync(r->bbytes.data(), t.bbytes, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
     LTHIP_CHECK(ctx, hipMemcpyAsync(&counters, r->d_counters, sizeof counters, hipMemcpyDeviceToHost, s));
     if (base)
     {
-        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->ncarry, t.ofirst + nocc, 4, hipMemcpyDeviceToHost, s));
-        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->nmarked, t.mfirst + nub, 4, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->bs.ncarry, t.ofirst + nocc, 4, hipMemcpyDeviceToHost, s));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(&r->bs.nmarked, t.mfirst + nub, 4, hipMemcpyDeviceToHost, s));
     }
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
     if (counters.unresolved)
         return lthip_fail(ctx, ENOENT, wanted.who,
                           base ? "a selected asset needs a chunk that neither the base nor the store index holds (or holds with another size)"
                                : "a selected asset or window needs a chunk the store index does not hold (or holds with another size)");
-    r->carry_bytes = counters.base_bytes;
-    r->carry_leaves = counters.base_verify_leaves;
-    r->moved_occ = counters.moved_occ;
-    r->moved_bytes = counters.moved_bytes;
+    r->bs.carry_bytes = counters.base_bytes;
+    r->bs.carry_leaves = counters.base_verify_leaves;
+    r->bs.moved_occ = counters.moved_occ;
+    r->bs.moved_bytes = counters.moved_bytes;
     lthip_seen_destroy(r->seen_base);
     r->seen_base = nullptr;
     LTHIP_CHECK(ctx, hipFree(r->d_tmp));
     r->d_tmp = nullptr;
     for (uint32_t b = 0; b < nb; ++b)
-        r->needed += r->is_needed(b);
+        r->blk.needed += r->blk.is_needed(b);
     return 0;
 }
 
@@ -907,15 +923,8 @@ static int restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const
     if (!r)
         return ENOMEM;
     r->ctx = ctx;
-    int err;
-    try
-    {
-        err = restore_build(r, cfg, base, version_index, vi_size, store_index, si_size, wanted, out_bytes);
-    }
-    catch (const std::bad_alloc&)
-    {
-        err = lthip_fail(ctx, ENOMEM, "lthip_restore_create", "host tables");
-    }
+    const int err = lthip_guarded(ctx, "lthip_restore_create",
+                                  [&] { return restore_build(r, cfg, base, version_index, vi_size, store_index, si_size, wanted, out_bytes); });
     if (err)
     {
         lthip_restore_destroy(r); // (waits for what was queued; nothing stays allocated)
@@ -975,245 +984,182 @@ extern "C" int lthip_restore_needed_blocks(const lthip_restore* r, uint64_t* blo
 {
     if (!r || !out_count)
         return EINVAL;
-    *out_count = r->needed;
-    if (!block_hashes || capacity < r->needed)
+    *out_count = r->blk.needed;
+    if (!block_hashes || capacity < r->blk.needed)
         return 0;
     uint64_t k = 0;
     for (uint32_t b = 0; b < r->nb; ++b)
-        if (r->is_needed(b))
-            block_hashes[k++] = r->bhash[b];
+        if (r->blk.is_needed(b))
+            block_hashes[k++] = r->blk.st.bhash[b];
     return 0;
 }
 
 extern "C" size_t lthip_restore_scratch_bound(const lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes)
 {
-    if (!r || (block_count && !block_hashes))
-        return 0;
-    uint64_t bytes = 0;
-    for (uint32_t i = 0; i < block_count; ++i)
-    {
-        const auto it = r->block_of_hash.find(block_hashes[i]);
-        if (it != r->block_of_hash.end() && r->is_needed(it->second) && r->btag[it->second] != 0u)
-            bytes += round64(r->braw[it->second]);
-    }
-    return (size_t)bytes;
+    return r && (!block_count || block_hashes) ? (size_t)restore_call::scratch_bound(r->blk, block_count, block_hashes) : 0;
 }
 
-// any_position: the images lie at any byte positions (an archive's body) and are checked by k_restore_check_images_any
-static int restore_queue(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images, const uint64_t* image_offsets,
-                         const uint32_t* image_sizes, void* d_scratch, void* d_out, bool any_position)
+// ---- a blocks call in five stages: items and slots, check, decode, judge, scatter.  What the first hands to the others: ----
+struct Queued
 {
-    lthip_ctx* ctx = r->ctx;
-    // ---- the call's needed blocks in three groups: not decoded (raw blocks; an image too short to hold a payload), LZ4, zstd ----
-    for (auto& g : r->group)
-        g.clear();
-    for (uint32_t i = 0; i < block_count; ++i)
-    {
-        const uint32_t b = r->block_of_hash.find(block_hashes[i])->second;
-        r->delivered[b] = 1;
-        ++r->delivered_all;
-        if (!r->is_needed(b))
+    size_t k = 0;                                            // the call's needed blocks: its items, group by group
+    uint64_t slots = 0, entries = 0, ranges = 0, leaves = 0; // summed over the items: scratch handed out, entries, chunks and their leaves
+    uint32_t copy_raw = 0;                                   // the largest raw block that is copied into a cache slot
+};
+// the lower of two addresses, a null one aside: the decoders and verify address everything they touch from one base
+static uint64_t lowest(uint64_t a, uint64_t b) { return !a ? b : !b ? a : std::min(a, b); }
+
+// Stage 1: an RItem per needed block.  A cache: every needed block reserves a slot when one is to be had; a tagged block is then decoded
+// into it, a raw block copied.  Every other tagged block gets slot_bytes of the scratch.
+static void queue_items(lthip_restore* r, const void* d_images, const uint64_t* image_offsets, const uint32_t* image_sizes, void* d_scratch, Queued* q)
+{
+    const restore_call::Blocks& blk = r->blk;
+    CallTables& t = r->call;
+    CacheLink& cl = r->cl;
+    t.items.clear(), t.outsz.clear(), cl.slot_of.clear();
+    for (const auto& group : t.c.group)
+        for (const uint32_t i : group)
         {
-            ++r->unneeded;
-            continue;
-        }
-        ++r->needed_delivered;
-        const int codec = codec_of_tag(r->btag[b]);
-        const bool payload = (uint64_t)image_sizes[i] > lthip_stored_block_header_size(r->bcnt[b]);
-        r->group[codec == LTHIP_CODEC_NONE || !payload ? 0 : codec == LTHIP_CODEC_LZ4 ? 1 : 2].push_back(i);
-    }
-    r->finished = false;
-    const size_t k = r->group[0].size() + r->group[1].size() + r->group[2].size();
-    if (!k)
-        return 0;
-    r->blocks_queued = true;
-    r->items.clear(), r->outsz.clear(), r->slot_of.clear();
-    uint64_t slot = 0, entries = 0, ranges = 0, leaves = 0;
-    // a cache: every needed block reserves a slot when one is to be had; a tagged block is then decoded into it, a raw block copied.
-    // The decoders take one destination base: the lower of the scratch and the arena.
-    lthip_block_cache* const cache = r->cache;
-    const uint64_t dbase = !cache      ? (uint64_t)(uintptr_t)d_scratch
-                           : d_scratch ? std::min((uint64_t)(uintptr_t)d_scratch, (uint64_t)(uintptr_t)cache->arena)
-                                       : (uint64_t)(uintptr_t)cache->arena;
-    uint32_t copy_raw = 0; // the largest raw block that is copied into a slot
-    for (int g = 0; g < 3; ++g)
-        for (const uint32_t i : r->group[g])
-        {
-            const uint32_t b = r->block_of_hash.find(block_hashes[i])->second;
-            const bool tagged = r->btag[b] != 0u;
+            const uint32_t b = t.c.blocks[i];
+            const bool tagged = blk.st.btag[b] != 0u;
             uint64_t in_cache = 0;
-            if (cache)
+            if (cl.cache)
             {
-                const uint32_t s = cache->table.reserve(r->cache_key(b), r->cache_meta(b));
+                const uint32_t s = cl.cache->table.reserve(cl.cache_key(r->hash_identifier, blk.st, b), cl.cache_meta(blk.st, b));
                 if (s == block_cache::NO_SLOT)
-                    ++r->c_bypassed;
+                    ++cl.c_bypassed;
                 else
                 {
-                    r->cslot[b] = s;
-                    r->reserved.push_back(b);
-                    in_cache = cache->slot_address(s);
+                    cl.cslot[b] = s;
+                    cl.reserved.push_back(b);
+                    in_cache = cl.cache->slot_address(s);
                     if (!tagged)
-                        copy_raw = std::max(copy_raw, r->braw[b]);
+                        q->copy_raw = std::max(q->copy_raw, blk.st.braw[b]);
                 }
-                r->slot_of.push_back(tagged ? 0u : in_cache);
+                cl.slot_of.push_back(tagged ? 0u : in_cache);
             }
             RItem it;
             it.image = image_offsets[i];
-            it.src = !tagged    ? (uint64_t)(uintptr_t)d_images + image_offsets[i] + lthip_block_index_size(r->bcnt[b])
+            it.src = !tagged    ? (uint64_t)(uintptr_t)d_images + image_offsets[i] + lthip_block_index_size(blk.st.bcnt[b])
                      : in_cache ? in_cache
-                                : (uint64_t)(uintptr_t)d_scratch + slot;
+                                : (uint64_t)(uintptr_t)d_scratch + q->slots;
             it.size = image_sizes[i];
             it.block = b;
-            it.raw = r->braw[b];
-            it.efirst = (uint32_t)entries;
-            it.ebase = r->firsts[b];
-            it.vfirst = (uint32_t)ranges;
-            r->items.push_back(it);
-            r->outsz.push_back(tagged ? NONE : it.raw); // (a decoder overwrites its blocks' words; a raw block has nothing to decode)
-            if (tagged && !in_cache)
-                slot += round64(it.raw);
-            entries += r->firsts[b + 1] - r->firsts[b];
-            ranges += r->bcnt[b];
-            leaves += r->bleaves[b];
+            it.raw = blk.st.braw[b];
+            it.efirst = (uint32_t)q->entries;
+            it.ebase = blk.firsts[b];
+            it.vfirst = (uint32_t)q->ranges;
+            t.items.push_back(it);
+            t.outsz.push_back(tagged ? NONE : it.raw); // (a decoder overwrites its blocks' words; a raw block has nothing to decode)
+            if (!in_cache)
+                q->slots += blk.slot_bytes(b);
+            q->entries += blk.firsts[b + 1] - blk.firsts[b];
+            q->ranges += blk.st.bcnt[b];
+            q->leaves += blk.st.bleaves[b];
         }
-    LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    q->k = t.items.size();
+}
+
+// Stage 2: every image against the StoreIndex; behind it, with a cache, the raw blocks that have a slot into their slots
+static int queue_check(lthip_restore* r, const void* d_images, const Queued& q, bool any_position)
+{
+    lthip_ctx* ctx = r->ctx;
+    const size_t k = q.k, undecoded = r->call.c.group[0].size();
     int err;
-    if ((err = upload(ctx, r->d_items, r->items.data(), k * sizeof(RItem))) || (err = upload(ctx, r->d_outsz, r->outsz.data(), k * 4)))
+    if ((err = upload(ctx, r->d_items, r->call.items.data(), k * sizeof(RItem))) || (err = upload(ctx, r->d_outsz, r->call.outsz.data(), k * 4)) ||
+        (err = launch(ctx, LTHIP_K_OTHER, any_position ? k_restore_check_images_any : k_restore_check_images, dim3((uint32_t)k), dim3(64),
+                      (const RItem*)r->d_items, (uint32_t)k, (const uint8_t*)d_images, r->sv, r->hash_identifier, r->d_status)))
         return err;
-    {
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(any_position ? k_restore_check_images_any : k_restore_check_images, dim3((uint32_t)k), dim3(64), 0, s,
-                           (const RItem*)r->d_items, (uint32_t)k, (const uint8_t*)d_images, r->sv, r->hash_identifier, r->d_status);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    if (copy_raw)
-    {
-        if ((err = upload(ctx, r->d_slot_of, r->slot_of.data(), r->group[0].size() * 8)))
-            return err;
-        LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_cache_copy, dim3((uint32_t)r->group[0].size(), (copy_raw + CACHE_PIECE - 1u) / CACHE_PIECE), dim3(RT), 0, s,
-                           (const RItem*)r->d_items, (const uint64_t*)r->d_slot_of, (const uint32_t*)r->d_status);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    // ---- decode: one call per codec; sizes and places from the StoreIndex and image_sizes alone ----
-    size_t at = r->group[0].size();
+    if (!q.copy_raw)
+        return 0;
+    if ((err = upload(ctx, r->cl.d_slot_of, r->cl.slot_of.data(), undecoded * 8)))
+        return err;
+    return launch(ctx, LTHIP_K_GATHER, k_restore_cache_copy, dim3((uint32_t)undecoded, (q.copy_raw + CACHE_PIECE - 1u) / CACHE_PIECE), dim3(RT),
+                  (const RItem*)r->d_items, (const uint64_t*)r->cl.d_slot_of, (const uint32_t*)r->d_status);
+}
+
+// Stage 3: one call per codec; sizes and places from the StoreIndex and the items alone.  dbase: what the destinations are relative to
+static int queue_decode(lthip_restore* r, const void* d_images, uint64_t dbase)
+{
+    CallTables& t = r->call;
+    size_t at = t.c.group[0].size();
     for (int g = 1; g < 3; ++g)
     {
-        const size_t cnt = r->group[g].size();
+        const size_t cnt = t.c.group[g].size();
         if (!cnt)
             continue;
-        r->c_src.clear(), r->c_size.clear(), r->c_dst.clear(), r->c_cap.clear();
+        t.c_src.clear(), t.c_size.clear(), t.c_dst.clear(), t.c_cap.clear();
         for (size_t j = 0; j < cnt; ++j)
         {
-            const RItem& it = r->items[at + j];
-            const uint64_t hdr = lthip_stored_block_header_size(r->bcnt[it.block]);
-            r->c_src.push_back(it.image + hdr);
-            r->c_size.push_back((uint32_t)(it.size - hdr));
-            r->c_dst.push_back(it.src - dbase);
-            r->c_cap.push_back(it.raw); // (a slot holds at least the raw size of the block that reserved it)
+            const RItem& it = t.items[at + j];
+            const uint64_t hdr = lthip_stored_block_header_size(r->blk.st.bcnt[it.block]);
+            t.c_src.push_back(it.image + hdr);
+            t.c_size.push_back((uint32_t)(it.size - hdr));
+            t.c_dst.push_back(it.src - dbase);
+            t.c_cap.push_back(it.raw); // (a slot holds at least the raw size of the block that reserved it)
         }
-        void* const d_dst = (void*)(uintptr_t)dbase;
-        err = g == 1 ? lthip_lz4_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_dst, r->c_dst.data(),
-                                                   r->c_cap.data(), r->d_outsz + at)
-                     : lthip_zstd_decompress_blocks(ctx, d_images, (uint32_t)cnt, r->c_src.data(), r->c_size.data(), d_dst, r->c_dst.data(),
-                                                    r->c_cap.data(), r->d_outsz + at);
+        const int err = (g == 1 ? lthip_lz4_decompress_blocks : lthip_zstd_decompress_blocks)(
+            r->ctx, d_images, (uint32_t)cnt, t.c_src.data(), t.c_size.data(), (void*)(uintptr_t)dbase, t.c_dst.data(), t.c_cap.data(), r->d_outsz + at);
         if (err)
             return err;
         at += cnt;
     }
-    // ---- the decoders' verdict, then verify, both before the scatter ----
-    const uint64_t base = cache  ? std::min((uint64_t)(uintptr_t)d_images, dbase)
-                          : slot ? std::min((uint64_t)(uintptr_t)d_images, (uint64_t)(uintptr_t)d_scratch)
-                                 : (uint64_t)(uintptr_t)d_images;
-    {
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_ranges, dim3((uint32_t)k), dim3(64), 0, s, (const RItem*)r->d_items, (uint32_t)k, (const uint32_t*)r->d_outsz,
-                           r->sv, r->d_status, r->verify, base, r->ranges);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    if (r->verify && ranges)
-    {
-        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, (const void*)(uintptr_t)base, ranges, r->ranges.off, r->ranges.len, r->max_chunk,
-                                           leaves, r->ranges.hash)))
-            return err;
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_compare, dim3((uint32_t)((ranges + 255u) / 256u)), dim3(256), 0, s, (uint32_t)ranges, r->ranges,
-                           (const uint64_t*)r->sv.chash, r->d_status, r->d_counters);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    LaunchTimer tm(ctx, LTHIP_K_GATHER);
-    constexpr uint64_t LAUNCH_ENTRIES = 1u << 23; // (a launch holds fewer than 2^32 threads)
-    for (uint64_t e0 = 0; e0 < entries; e0 += LAUNCH_ENTRIES)
-        hipLaunchKernelGGL(k_restore_scatter, dim3((uint32_t)std::min(LAUNCH_ENTRIES, entries - e0)), dim3(RT), 0, s, (const RItem*)r->d_items,
-                           (uint32_t)k, (const uint4*)r->d_entries, (const uint32_t*)r->d_status, (const uint32_t*)r->d_outsz, (uint32_t)e0,
-                           (uint8_t*)d_out);
-    LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }
 
-// lthip_restore_blocks (any_position false: an image offset that is not 8-byte aligned is refused) and lthip_restore_archive_blocks
-static int restore_deliver(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const void* d_images, const uint64_t* image_offsets,
-                           const uint32_t* image_sizes, void* d_scratch, uint64_t scratch_bytes, void* d_out, bool any_position, const char* who)
+// Stage 4: the decoders' verdict, then verify, both before anything is copied out.  base: what the ranges verify hashes are relative to
+static int queue_judge(lthip_restore* r, uint64_t base, const Queued& q)
 {
     lthip_ctx* ctx = r->ctx;
-    // ---- the refusals, before anything is queued or changed ----
-    int refused = 0;
-    const char* why = "";
-    uint64_t scratch = 0;
-    bool any_needed = false;
-    uint32_t marked = 0;
-    for (; marked < block_count && !refused; ++marked)
-    {
-        const auto it = r->block_of_hash.find(block_hashes[marked]);
-        if (it == r->block_of_hash.end())
-        {
-            refused = ENOENT, why = "a block hash the store index does not hold";
-            break;
-        }
-        const uint32_t b = it->second;
-        if (r->delivered[b] || r->in_call[b])
-        {
-            refused = EEXIST, why = "a block was delivered before, or twice in this call";
-            break;
-        }
-        r->in_call[b] = 1;
-        if (!any_position && (image_offsets[marked] & 7u))
-            refused = EINVAL, why = "image offsets must be 8-byte aligned";
-        else if (r->is_needed(b))
-        {
-            any_needed = true;
-            if (codec_of_tag(r->btag[b]) < 0)
-                refused = ENOTSUP, why = "a needed block's tag names no codec of this library";
-            else if (r->btag[b] != 0u)
-                scratch += round64(r->braw[b]);
-        }
-    }
-    for (uint32_t i = 0; i < block_count && i <= marked; ++i) // (the marks of this call, the refused block's included)
-    {
-        const auto it = r->block_of_hash.find(block_hashes[i]);
-        if (it != r->block_of_hash.end() && !r->delivered[it->second])
-            r->in_call[it->second] = 0;
-    }
-    if (!refused && scratch > scratch_bytes)
-        refused = ENOMEM, why = "scratch below lthip_restore_scratch_bound";
-    if (!refused && ((scratch && !d_scratch) || (any_needed && !d_out)))
-        refused = EINVAL, why = "null scratch or output";
-    if (!refused && any_needed && r->in_place_buf && d_out != r->in_place_buf)
-        refused = EINVAL, why = "the base was carried in place: the output is that buffer";
-    if (refused)
-        return lthip_fail(ctx, refused, who, why);
+    int err = launch(ctx, LTHIP_K_OTHER, k_restore_ranges, dim3((uint32_t)q.k), dim3(64), (const RItem*)r->d_items, (uint32_t)q.k,
+                     (const uint32_t*)r->d_outsz, r->sv, r->d_status, r->verify, base, r->ranges);
+    if (err || !r->verify || !q.ranges)
+        return err;
+    if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, (const void*)(uintptr_t)base, q.ranges, r->ranges.off, r->ranges.len, r->max_chunk,
+                                       q.leaves, r->ranges.hash)))
+        return err;
+    return launch(ctx, LTHIP_K_OTHER, k_restore_compare, dim3((uint32_t)((q.ranges + 255u) / 256u)), dim3(256), (uint32_t)q.ranges, r->ranges,
+                  (const uint64_t*)r->sv.chash, r->d_status, r->d_counters);
+}
+
+// The accepted call r->call.c.  any_position: the images lie at any byte positions (an archive's body), k_restore_check_images_any checks them
+static int restore_queue(lthip_restore* r, const void* d_images, const uint64_t* image_offsets, const uint32_t* image_sizes, void* d_scratch,
+                         void* d_out, bool any_position)
+{
+    restore_call::commit(&r->blk, &r->call.c, image_sizes);
+    r->finished = false;
+    Queued q;
+    queue_items(r, d_images, image_offsets, image_sizes, d_scratch, &q);
+    if (!q.k)
+        return 0;
+    r->blocks_queued = true;
+    LTHIP_CHECK(r->ctx, hipSetDevice(r->ctx->device));
+    // the decoders take one destination base: the scratch, with a cache the lower of the scratch and the arena; verify reads the raw
+    // blocks where they lie in the images as well
+    const uint64_t dbase = lowest((uint64_t)(uintptr_t)d_scratch, r->cl.cache ? (uint64_t)(uintptr_t)r->cl.cache->arena : 0u);
+    const uint64_t base = lowest((uint64_t)(uintptr_t)d_images, r->cl.cache || q.slots ? dbase : 0u);
     int err;
-    try
-    {
-        err = restore_queue(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, d_out, any_position);
-    }
-    catch (const std::bad_alloc&)
-    {
-        err = lthip_fail(ctx, ENOMEM, who, "host tables");
-    }
+    if ((err = queue_check(r, d_images, q, any_position)) || (err = queue_decode(r, d_images, dbase)) || (err = queue_judge(r, base, q)))
+        return err;
+    return launch_scatter(r, r->d_items, (uint32_t)q.k, q.entries, r->d_outsz, d_out);
+}
+
+// lthip_restore_blocks (its hashes; any_position false: an image offset that is not 8-byte aligned is refused) and
+// lthip_restore_archive_blocks (the block indices its pick gave): the refusals, before anything is queued or changed, then the call
+static int restore_deliver(lthip_restore* r, uint32_t block_count, const uint64_t* block_hashes, const uint32_t* blocks, const void* d_images,
+                           const uint64_t* image_offsets, const uint32_t* image_sizes, void* d_scratch, uint64_t scratch_bytes, void* d_out,
+                           bool any_position, const char* who)
+{
+    int refused = 0;
+    const int err = lthip_guarded(r->ctx, who, [&] {
+        const restore_call::Where w{d_scratch, d_out, r->bs.in_place_buf, scratch_bytes, any_position};
+        refused = restore_call::resolve(r->blk, block_count, block_hashes, blocks, image_offsets, w, &r->call.c);
+        return refused ? 0 : restore_queue(r, d_images, image_offsets, image_sizes, d_scratch, d_out, any_position);
+    });
+    if (refused)
+        return lthip_fail(r->ctx, refused, who, r->call.c.why);
     if (err) // (a call that did not queue all of its work commits nothing: no status word of it can be trusted)
-        r->release_cache(false);
+        r->cl.release_cache(false);
     return err;
 }
 
@@ -1222,63 +1168,18 @@ extern "C" int lthip_restore_blocks(lthip_restore* r, uint32_t block_count, cons
 {
     if (!r || (block_count && (!block_hashes || !d_images || !image_offsets || !image_sizes)))
         return EINVAL;
-    return restore_deliver(r, block_count, block_hashes, d_images, image_offsets, image_sizes, d_scratch, scratch_bytes, d_out, false,
+    return restore_deliver(r, block_count, block_hashes, nullptr, d_images, image_offsets, image_sizes, d_scratch, scratch_bytes, d_out, false,
                            "lthip_restore_blocks");
 }
 
-// ---- fed from an archive's body (archive_layout.h): the needed, not yet delivered blocks that lie wholly inside body bytes
-// [first, first + bytes), in the archive's block order.  A block of the archive that the session's StoreIndex does not hold, or holds
-// twice in the archive, is passed over. ----
-struct ArchivePick
-{
-    std::vector<uint64_t> hashes, offsets;
-    std::vector<uint32_t> sizes;
-    uint64_t scratch = 0, next_byte = 0;
-};
-static void archive_pick(lthip_restore* r, const archive_layout::Archive& a, uint64_t first, uint64_t bytes, ArchivePick* p)
-{
-    const uint64_t end = first + bytes < first ? ~0ull : first + bytes;
-    const size_t nb = a.bhash.size();
-    p->next_byte = a.body_bytes;
-    p->hashes.reserve(nb), p->offsets.reserve(nb), p->sizes.reserve(nb); // (nothing below throws: the marks are always taken back)
-    for (size_t i = 0; i < nb; ++i)
-    {
-        const auto it = r->block_of_hash.find(a.bhash[i]);
-        if (it == r->block_of_hash.end())
-            continue;
-        const uint32_t b = it->second;
-        if (!r->is_needed(b) || r->delivered[b] || r->in_call[b])
-            continue;
-        const uint64_t off = a.offsets[i], size = a.sizes[i];
-        if (off < first || off + size > end) // (off + size does not wrap: archive_layout::open)
-        {
-            p->next_byte = std::min(p->next_byte, off);
-            continue;
-        }
-        r->in_call[b] = 1; // (a hash the archive lists twice is picked once)
-        p->hashes.push_back(a.bhash[i]), p->offsets.push_back(off - first), p->sizes.push_back((uint32_t)size);
-        if (r->btag[b] != 0u)
-            p->scratch += round64(r->braw[b]);
-    }
-    for (const uint64_t h : p->hashes)
-        r->in_call[r->block_of_hash.find(h)->second] = 0;
-}
-
+// ---- fed from an archive's body (archive_layout.h; the pick: restore_call.h) ----
 extern "C" size_t lthip_restore_archive_scratch_bound(const lthip_restore* r, const lthip_archive* archive, uint64_t window_first_byte,
                                                       uint64_t window_bytes)
 {
-    if (!r || !archive)
+    restore_call::Pick p;
+    if (!r || !archive || lthip_guarded(nullptr, nullptr, [&] { return restore_call::pick(r->blk, archive->a, window_first_byte, window_bytes, &p), 0; }))
         return 0;
-    try
-    {
-        ArchivePick p;
-        archive_pick(const_cast<lthip_restore*>(r), archive->a, window_first_byte, window_bytes, &p); // (the marks are taken back)
-        return (size_t)p.scratch;
-    }
-    catch (const std::bad_alloc&)
-    {
-        return 0;
-    }
+    return (size_t)p.scratch;
 }
 
 extern "C" int lthip_restore_archive_blocks(lthip_restore* r, const lthip_archive* archive, const void* d_window, uint64_t window_first_byte,
@@ -1288,18 +1189,17 @@ extern "C" int lthip_restore_archive_blocks(lthip_restore* r, const lthip_archiv
     if (!r || !archive || !delivered || !next_byte)
         return EINVAL;
     *delivered = 0;
-    try
-    {
-        ArchivePick p;
-        archive_pick(r, archive->a, window_first_byte, window_bytes, &p);
+    return lthip_guarded(r->ctx, "lthip_restore_archive_blocks", [&] {
+        restore_call::Pick p;
+        restore_call::pick(r->blk, archive->a, window_first_byte, window_bytes, &p);
         *next_byte = p.next_byte;
-        const uint32_t k = (uint32_t)p.hashes.size();
+        const uint32_t k = (uint32_t)p.blocks.size();
         if (!k)
             return 0;
         if (!d_window)
             return lthip_fail(r->ctx, EINVAL, "lthip_restore_archive_blocks", "null window");
-        const int err = restore_deliver(r, k, p.hashes.data(), d_window, p.offsets.data(), p.sizes.data(), d_scratch, scratch_bytes, d_out, true,
-                                        "lthip_restore_archive_blocks");
+        const int err = restore_deliver(r, k, nullptr, p.blocks.data(), d_window, p.offsets.data(), p.sizes.data(), d_scratch, scratch_bytes, d_out,
+                                        true, "lthip_restore_archive_blocks");
         if (err) // (refused, or not all queued: the lowest outstanding block may be one of this window's)
         {
             for (const uint64_t o : p.offsets)
@@ -1308,11 +1208,7 @@ extern "C" int lthip_restore_archive_blocks(lthip_restore* r, const lthip_archiv
         }
         *delivered = k;
         return 0;
-    }
-    catch (const std::bad_alloc&)
-    {
-        return lthip_fail(r->ctx, ENOMEM, "lthip_restore_archive_blocks", "host tables");
-    }
+    });
 }
 
 extern "C" int lthip_restore_archive_ranges(const lthip_restore* r, const lthip_archive* archive, uint64_t max_gap, uint64_t* ranges, uint64_t capacity,
@@ -1320,12 +1216,11 @@ extern "C" int lthip_restore_archive_ranges(const lthip_restore* r, const lthip_
 {
     if (!r || !archive || !count)
         return EINVAL;
-    try
-    {
-        ArchivePick p;
-        archive_pick(const_cast<lthip_restore*>(r), archive->a, 0, ~0ull, &p); // every needed, outstanding block
+    return lthip_guarded(nullptr, nullptr, [&] {
+        restore_call::Pick p;
+        restore_call::pick(r->blk, archive->a, 0, ~0ull, &p); // every needed, outstanding block
         std::vector<std::pair<uint64_t, uint64_t>> v;
-        for (size_t i = 0; i < p.hashes.size(); ++i)
+        for (size_t i = 0; i < p.blocks.size(); ++i)
             v.emplace_back(p.offsets[i], (uint64_t)p.sizes[i]);
         archive_layout::merge_ranges(&v, max_gap);
         *count = v.size();
@@ -1334,11 +1229,7 @@ extern "C" int lthip_restore_archive_ranges(const lthip_restore* r, const lthip_
         for (size_t i = 0; i < v.size(); ++i)
             ranges[2 * i] = v[i].first, ranges[2 * i + 1] = v[i].second;
         return 0;
-    }
-    catch (const std::bad_alloc&)
-    {
-        return ENOMEM;
-    }
+    });
 }
 
 // d_scratch == null: out of place, d_base -> d_out.  Otherwise in place: d_base == d_out is the one buffer, and the moved runs go through
@@ -1347,24 +1238,22 @@ static int carry_queue(lthip_restore* r, const void* d_base, void* d_out, void* 
 {
     lthip_ctx* ctx = r->ctx;
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const uint32_t n = r->ncarry;
-    const bool in_place = r->in_place;
+    const uint32_t n = r->bs.ncarry;
+    const bool in_place = r->bs.in_place;
     int err;
     // ---- verify: the base chunks that feed something, hashed where they lie, before anything of them is copied ----
     const uint32_t* bbad = nullptr;
-    if (r->verify && r->nmarked)
+    if (r->verify && r->bs.nmarked)
     {
-        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, d_base, r->nmarked, r->base_ranges.off, r->base_ranges.len, r->base_max_chunk,
-                                           r->carry_leaves, r->base_ranges.hash)))
+        const BaseState& bs = r->bs;
+        if ((err = lthip_hash_ranges_by_id(ctx, r->hash_identifier, d_base, bs.nmarked, bs.base_ranges.off, bs.base_ranges.len, bs.base_max_chunk,
+                                           bs.carry_leaves, bs.base_ranges.hash)) ||
+            (err = launch(ctx, LTHIP_K_OTHER, k_restore_carry_compare, dim3((bs.nmarked + 255u) / 256u), dim3(256), bs.nmarked, bs.base_ranges, bs.base,
+                          r->d_counters)))
             return err;
-        LaunchTimer tm(ctx, LTHIP_K_OTHER);
-        hipLaunchKernelGGL(k_restore_carry_compare, dim3((r->nmarked + 255u) / 256u), dim3(256), 0, s, r->nmarked, r->base_ranges, r->base,
-                           r->d_counters);
-        LTHIP_LAUNCH_CHECK(ctx);
-        bbad = r->base.bad;
+        bbad = r->bs.base.bad;
     }
-    if (in_place && !r->moved_occ) // everything the base feeds lies where it belongs: no copy is queued
+    if (in_place && !r->bs.moved_occ) // everything the base feeds lies where it belongs: no copy is queued
         return 0;
     RunTables runs;
     void* tab = nullptr;
@@ -1372,41 +1261,26 @@ static int carry_queue(lthip_restore* r, const void* d_base, void* d_out, void* 
         return err;
     runs.carve(Carver(tab), n, in_place);
     // ---- runs: boundaries, their scan, a slot per entry that starts a run, the pieces' scan, the copy ----
-    {
-        LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_carry_bounds, dim3((n + 255u) / 256u), dim3(256), 0, s, n, r->carry, bbad, runs);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    if ((err = lthip_exclusive_scan_u32(ctx, runs.bound, runs.rank, n, nullptr, LTHIP_K_GATHER)))
+    const dim3 grid((n + 255u) / 256u), block(256);
+    if ((err = launch(ctx, LTHIP_K_GATHER, k_restore_carry_bounds, grid, block, n, r->bs.carry, bbad, runs)) ||
+        (err = lthip_exclusive_scan_u32(ctx, runs.bound, runs.rank, n, nullptr, LTHIP_K_GATHER)) ||
+        (err = launch(ctx, LTHIP_K_GATHER, k_restore_carry_runs, grid, block, n, r->bs.carry, bbad, runs)))
         return err;
-    {
-        LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_carry_runs, dim3((n + 255u) / 256u), dim3(256), 0, s, n, r->carry, bbad, runs);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
     if (!in_place)
     {
         if ((err = lthip_exclusive_scan_u32(ctx, runs.pieces, runs.first_piece, n, nullptr, LTHIP_K_GATHER)))
             return err;
         return lthip_raw_copy_runs(ctx, runs.first_piece, n, runs.src, runs.dst, runs.len, d_base, d_out,
-                                   r->carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
+                                   r->bs.carry_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + n);
     }
     // ---- in place: kept runs drop out, moved runs get a slot; pass 1 buffer -> scratch, pass 2 scratch -> buffer ----
-    {
-        LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_in_place_classify, dim3((n + 255u) / 256u), dim3(256), 0, s, n, runs);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    if ((err = lthip_exclusive_scan_u32(ctx, runs.units, runs.first_unit, n, nullptr, LTHIP_K_GATHER)) ||
+    if ((err = launch(ctx, LTHIP_K_GATHER, k_restore_in_place_classify, grid, block, n, runs)) ||
+        (err = lthip_exclusive_scan_u32(ctx, runs.units, runs.first_unit, n, nullptr, LTHIP_K_GATHER)) ||
         (err = lthip_exclusive_scan_u32(ctx, runs.pieces_in, runs.first_piece_in, n, nullptr, LTHIP_K_GATHER)) ||
-        (err = lthip_exclusive_scan_u32(ctx, runs.pieces, runs.first_piece, n, nullptr, LTHIP_K_GATHER)))
+        (err = lthip_exclusive_scan_u32(ctx, runs.pieces, runs.first_piece, n, nullptr, LTHIP_K_GATHER)) ||
+        (err = launch(ctx, LTHIP_K_GATHER, k_restore_in_place_slots, grid, block, n, runs)))
         return err;
-    {
-        LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        hipLaunchKernelGGL(k_restore_in_place_slots, dim3((n + 255u) / 256u), dim3(256), 0, s, n, runs);
-        LTHIP_LAUNCH_CHECK(ctx);
-    }
-    const uint64_t pieces_bound = r->moved_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + r->moved_occ;
+    const uint64_t pieces_bound = r->bs.moved_bytes / (LTHIP_RAW_PIECE_VEC * 16u) + r->bs.moved_occ;
     if ((err = lthip_raw_copy_runs(ctx, runs.first_piece_in, n, runs.src, runs.slot, runs.len, d_base, d_scratch, pieces_bound)))
         return err;
     return lthip_raw_copy_runs(ctx, runs.first_piece, n, runs.slot, runs.dst, runs.len, d_scratch, d_out, pieces_bound);
@@ -1418,40 +1292,40 @@ extern "C" int lthip_restore_carry(lthip_restore* r, const void* d_base, void* d
         return EINVAL;
     lthip_ctx* ctx = r->ctx;
     // ---- the refusals, before anything is queued or changed ----
-    if (!r->has_base)
+    if (!r->bs.has_base)
         return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "the session was created without a base");
-    if (r->carried)
+    if (r->bs.carried)
         return lthip_fail(ctx, EEXIST, "lthip_restore_carry", "the base was carried before");
-    if (r->ncarry)
+    if (r->bs.ncarry)
     {
         if (!d_base || !d_out)
             return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "null base or output");
         const uint64_t b0 = (uint64_t)(uintptr_t)d_base, o0 = (uint64_t)(uintptr_t)d_out;
-        if (b0 < o0 + r->out_bytes && o0 < b0 + r->base_window)
+        if (b0 < o0 + r->out_bytes && o0 < b0 + r->bs.base_window)
             return lthip_fail(ctx, EINVAL, "lthip_restore_carry", "the base and the output overlap: the update is out of place");
         const int err = carry_queue(r, d_base, d_out, nullptr);
         if (err)
             return err;
     }
-    r->carried = true;
+    r->bs.carried = true;
     r->finished = false;
     return 0;
 }
 
 // what the moved runs need in the caller's scratch: their bytes, every run's slot rounded up to 16 bytes (a run holds at least one moved
 // occurrence), and room to start the first slot on a 16-byte boundary
-static uint64_t in_place_bound(const lthip_restore* r) { return r->moved_occ ? r->moved_bytes + 16u * r->moved_occ + 64u : 0u; }
+static uint64_t in_place_bound(const lthip_restore* r) { return r->bs.moved_occ ? r->bs.moved_bytes + 16u * r->bs.moved_occ + 64u : 0u; }
 
-extern "C" size_t lthip_restore_in_place_scratch_bound(const lthip_restore* r) { return r && r->has_base ? (size_t)in_place_bound(r) : 0; }
+extern "C" size_t lthip_restore_in_place_scratch_bound(const lthip_restore* r) { return r && r->bs.has_base ? (size_t)in_place_bound(r) : 0; }
 
 extern "C" int lthip_restore_in_place_stats(const lthip_restore* r, uint64_t out[4])
 {
     if (!r || !out)
         return EINVAL;
-    out[0] = r->has_base ? r->ncarry - r->moved_occ : 0u;
-    out[1] = r->has_base ? r->carry_bytes - r->moved_bytes : 0u;
-    out[2] = r->has_base ? r->moved_occ : 0u;
-    out[3] = r->has_base ? r->moved_bytes : 0u;
+    out[0] = r->bs.has_base ? r->bs.ncarry - r->bs.moved_occ : 0u;
+    out[1] = r->bs.has_base ? r->bs.carry_bytes - r->bs.moved_bytes : 0u;
+    out[2] = r->bs.has_base ? r->bs.moved_occ : 0u;
+    out[3] = r->bs.has_base ? r->bs.moved_bytes : 0u;
     return 0;
 }
 
@@ -1461,16 +1335,16 @@ extern "C" int lthip_restore_carry_in_place(lthip_restore* r, void* d_buf, void*
         return EINVAL;
     lthip_ctx* ctx = r->ctx;
     // ---- the refusals, before anything is queued or changed ----
-    if (!r->has_base)
+    if (!r->bs.has_base)
         return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "the session was created without a base");
-    if (r->carried)
+    if (r->bs.carried)
         return lthip_fail(ctx, EEXIST, "lthip_restore_carry_in_place", "the base was carried before");
     if (r->blocks_queued)
         return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "a blocks call has queued work: the carry in place comes first");
-    if (r->ncarry && !d_buf)
+    if (r->bs.ncarry && !d_buf)
         return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "null buffer");
     void* scratch = nullptr;
-    if (r->moved_occ)
+    if (r->bs.moved_occ)
     {
         const uint64_t bound = in_place_bound(r);
         if (bound >> 36) // (the slots are placed by a 32-bit scan of 16-byte units)
@@ -1478,21 +1352,21 @@ extern "C" int lthip_restore_carry_in_place(lthip_restore* r, void* d_buf, void*
         if (!d_scratch)
             return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "null scratch");
         const uint64_t b0 = (uint64_t)(uintptr_t)d_buf, s0 = (uint64_t)(uintptr_t)d_scratch;
-        if (s0 < b0 + std::max(r->base_window, r->out_bytes) && b0 < s0 + std::max(bound, scratch_bytes))
+        if (s0 < b0 + std::max(r->bs.base_window, r->out_bytes) && b0 < s0 + std::max(bound, scratch_bytes))
             return lthip_fail(ctx, EINVAL, "lthip_restore_carry_in_place", "the scratch overlaps the buffer");
         if (scratch_bytes < bound)
             return lthip_fail(ctx, ENOMEM, "lthip_restore_carry_in_place", "scratch below lthip_restore_in_place_scratch_bound");
         scratch = (void*)(uintptr_t)((s0 + 15u) & ~(uint64_t)15u);
     }
-    r->in_place = true;
-    const int err = r->ncarry ? carry_queue(r, d_buf, d_buf, scratch) : 0;
+    r->bs.in_place = true;
+    const int err = r->bs.ncarry ? carry_queue(r, d_buf, d_buf, scratch) : 0;
     if (err)
     {
-        r->in_place = false;
+        r->bs.in_place = false;
         return err;
     }
-    r->in_place_buf = d_buf;
-    r->carried = true;
+    r->bs.in_place_buf = d_buf;
+    r->bs.carried = true;
     r->finished = false;
     return 0;
 }
@@ -1501,15 +1375,10 @@ extern "C" int lthip_restore_layout_in_place(const void* base_vi, size_t base_vi
                                              const void* target_vi, size_t target_vi_size, uint64_t align, uint64_t* target_offsets,
                                              uint32_t* asset_count, uint64_t* total_bytes, uint32_t* kept_assets)
 {
-    try
-    {
+    return lthip_guarded(nullptr, nullptr, [&] {
         return restore_layout::in_place(base_vi, base_vi_size, base_offsets, base_bytes, target_vi, target_vi_size, align, target_offsets, asset_count,
                                         total_bytes, kept_assets);
-    }
-    catch (const std::bad_alloc&)
-    {
-        return ENOMEM;
-    }
+    });
 }
 
 extern "C" int lthip_version_diff(const void* source_vi, size_t source_size, const void* target_vi, size_t target_size, uint32_t* source_removed,
@@ -1518,8 +1387,7 @@ extern "C" int lthip_version_diff(const void* source_vi, size_t source_size, con
 {
     if (!source_vi || !target_vi || !counts)
         return EINVAL;
-    try
-    {
+    return lthip_guarded(nullptr, nullptr, [&] {
         version_diff::Lists d;
         const int err = version_diff::diff(source_vi, source_size, target_vi, target_size, &d);
         if (err)
@@ -1534,11 +1402,7 @@ extern "C" int lthip_version_diff(const void* source_vi, size_t source_size, con
         counts[0] = (uint32_t)d.source_removed.size(), counts[1] = (uint32_t)d.target_added.size();
         counts[2] = (uint32_t)d.source_content.size(), counts[3] = (uint32_t)d.source_permissions.size();
         return 0;
-    }
-    catch (const std::bad_alloc&)
-    {
-        return ENOMEM;
-    }
+    });
 }
 
 extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
@@ -1557,58 +1421,53 @@ extern "C" int lthip_restore_finish(lthip_restore* r, lthip_restore_result* out)
     memset(&res, 0, sizeof res);
     res.assets_selected = r->assets_selected;
     res.occurrences = r->nocc;
-    res.blocks_needed = r->needed;
-    res.blocks_delivered = r->delivered_all;
-    res.blocks_unneeded = r->unneeded;
+    res.blocks_needed = r->blk.needed;
+    res.blocks_delivered = r->blk.delivered_all;
+    res.blocks_unneeded = r->blk.unneeded;
     res.chunks_mismatched = counters.block_chunks_bad;
-    res.base_occurrences = r->ncarry;
-    res.base_bytes = r->carry_bytes;
+    res.base_occurrences = r->bs.ncarry;
+    res.base_bytes = r->bs.carry_bytes;
     res.base_chunks_mismatched = counters.base_chunks_bad;
-    if (r->carried) // (what a mismatched base chunk would have fed was left out of the runs)
+    if (r->bs.carried) // (what a mismatched base chunk would have fed was left out of the runs)
     {
-        res.occurrences_written = r->ncarry - counters.base_bad_occ;
-        res.bytes_written = r->carry_bytes - counters.base_bad_bytes;
+        res.occurrences_written = r->bs.ncarry - counters.base_bad_occ;
+        res.bytes_written = r->bs.carry_bytes - counters.base_bad_bytes;
     }
+    const auto wrote = [&](uint32_t b) { res.occurrences_written += r->blk.firsts[b + 1] - r->blk.firsts[b], res.bytes_written += r->bbytes[b]; };
     for (uint32_t b = 0; b < r->nb; ++b)
     {
-        if (!r->delivered[b] || !r->is_needed(b))
+        if (!r->blk.delivered[b] || !r->blk.is_needed(b))
             continue;
         if (r->status[b])
             ++res.blocks_bad;
         else
-        {
-            res.occurrences_written += r->firsts[b + 1] - r->firsts[b];
-            res.bytes_written += r->bbytes[b];
-        }
-        if (r->btag[b] != 0u && !(r->status[b] & (LTHIP_RESTORE_BAD_HEADER | LTHIP_RESTORE_BAD_PAYLOAD)))
-            res.decoded_bytes += r->braw[b];
+            wrote(b);
+        if (r->blk.st.btag[b] != 0u && !(r->status[b] & (LTHIP_RESTORE_BAD_HEADER | LTHIP_RESTORE_BAD_PAYLOAD)))
+            res.decoded_bytes += r->blk.st.braw[b];
     }
-    if (r->cache)
+    if (r->cl.cache)
     {
         // the status words are final: a good block's reserved slot becomes an entry, every other one is given back
-        block_cache::Table& table = r->cache->table;
-        for (const uint32_t b : r->reserved)
+        block_cache::Table& table = r->cl.cache->table;
+        for (const uint32_t b : r->cl.reserved)
         {
             if (r->status[b])
-                table.abort(r->cslot[b], true), ++r->c_dropped;
-            else if (table.commit(r->cslot[b], r->verify != 0u))
-                ++r->c_inserted;
+                table.abort(r->cl.cslot[b], true), ++r->cl.c_dropped;
+            else if (table.commit(r->cl.cslot[b], r->verify != 0u))
+                ++r->cl.c_inserted;
             else
-                ++r->c_bypassed;
+                ++r->cl.c_bypassed;
         }
-        r->reserved.clear();
-        if (r->from_cache_done)
-            for (const uint32_t b : r->fed_blocks)
-            {
-                res.occurrences_written += r->firsts[b + 1] - r->firsts[b];
-                res.bytes_written += r->bbytes[b];
-            }
+        r->cl.reserved.clear();
+        if (r->cl.from_cache_done)
+            for (const uint32_t b : r->cl.fed_blocks)
+                wrote(b);
     }
     const bool outstanding =
-        r->needed_delivered < r->needed || (r->ncarry && !r->carried) || (!r->fed_blocks.empty() && !r->from_cache_done);
+        r->blk.needed_delivered < r->blk.needed || (r->bs.ncarry && !r->bs.carried) || (!r->cl.fed_blocks.empty() && !r->cl.from_cache_done);
     const int code = res.blocks_bad || res.base_chunks_mismatched ? EBADF : outstanding ? ENOENT : 0;
     if (!code)
-        r->release_cache(true); // (the session is complete: its pins go)
+        r->cl.release_cache(true); // (the session is complete: its pins go)
     if (out)
     {
         const uint64_t have = out->struct_size;
@@ -1629,18 +1488,11 @@ extern "C" int lthip_block_cache_create(lthip_ctx* ctx, uint32_t slot_count, uin
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     void* arena = nullptr;
     LTHIP_CHECK(ctx, lthip_hip_malloc(&arena, (size_t)(bytes * slot_count)));
-    lthip_block_cache* c = nullptr;
-    try
-    {
-        c = new lthip_block_cache{ctx, arena, block_cache::Table(slot_count, bytes)};
-    }
-    catch (const std::bad_alloc&)
-    {
+    const int err = lthip_guarded(ctx, "lthip_block_cache_create",
+                                  [&] { return *out = new lthip_block_cache{ctx, arena, block_cache::Table(slot_count, bytes)}, 0; });
+    if (err)
         (void)hipFree(arena);
-        return lthip_fail(ctx, ENOMEM, "lthip_block_cache_create", "host tables");
-    }
-    *out = c;
-    return 0;
+    return err;
 }
 
 extern "C" void lthip_block_cache_destroy(lthip_block_cache* c)
@@ -1685,67 +1537,67 @@ static int set_cache(lthip_restore* r, lthip_block_cache* c)
 {
     lthip_ctx* ctx = r->ctx;
     const uint32_t nb = r->nb;
+    const restore_plan::StoreTables& st = r->blk.st;
     // ---- which needed blocks the cache feeds: a visible entry with the same chunk count, raw size and chunk table (verify: verified) ----
-    r->bdigest.assign(nb, 0u), r->cslot.assign(nb, block_cache::NO_SLOT);
+    r->cl.bdigest.assign(nb, 0u), r->cl.cslot.assign(nb, block_cache::NO_SLOT);
     for (uint32_t b = 0; b < nb; ++b)
-        if (r->is_needed(b)) // (only a needed block is looked up, now or when it is delivered)
-            r->bdigest[b] = block_cache::table_digest(r->h_chash.data() + r->h_bcoff[b], r->h_csize.data() + r->h_bcoff[b], r->bcnt[b]);
+        if (r->blk.is_needed(b)) // (only a needed block is looked up, now or when it is delivered)
+            r->cl.bdigest[b] = block_cache::table_digest(st.chash.data() + st.bcoff[b], st.csize.data() + st.bcoff[b], st.bcnt[b]);
     std::vector<RItem> items;
     std::vector<uint32_t> outsz;
     uint64_t entries = 0, bytes = 0;
     for (uint32_t b = 0; b < nb; ++b)
     {
-        if (!r->is_needed(b))
+        if (!r->blk.is_needed(b))
             continue;
-        const uint32_t s = c->table.lookup(r->cache_key(b));
-        if (s == block_cache::NO_SLOT || !c->table.matches(s, r->cache_meta(b), r->verify != 0u))
+        const uint32_t s = c->table.lookup(r->cl.cache_key(r->hash_identifier, st, b));
+        if (s == block_cache::NO_SLOT || !c->table.matches(s, r->cl.cache_meta(st, b), r->verify != 0u))
             continue;
-        r->cslot[b] = s;
-        r->fed_blocks.push_back(b);
+        r->cl.cslot[b] = s;
+        r->cl.fed_blocks.push_back(b);
         RItem it = {};
         it.src = c->slot_address(s);
         it.block = b;
-        it.raw = r->braw[b];
+        it.raw = st.braw[b];
         it.efirst = (uint32_t)entries;
-        it.ebase = r->firsts[b];
+        it.ebase = r->blk.firsts[b];
         items.push_back(it);
         outsz.push_back(it.raw);
-        entries += r->firsts[b + 1] - r->firsts[b];
+        entries += r->blk.firsts[b + 1] - r->blk.firsts[b];
         bytes += it.raw;
     }
     // ---- the session's device tables for the cache; on an error the session stays as it was ----
     int err = 0;
     if (hipSetDevice(ctx->device) != hipSuccess)
         err = lthip_fail(ctx, EIO, "lthip_restore_set_cache", "hipSetDevice");
-    else if (lthip_hip_malloc(&r->d_cmem, r->carve_cache(Carver()) + 256) != hipSuccess)
+    else if (lthip_hip_malloc(&r->cl.d_cmem, r->cl.carve_cache(Carver(), nb) + 256) != hipSuccess)
         err = lthip_fail(ctx, ENOMEM, "lthip_restore_set_cache", "device tables");
     if (!err)
     {
-        r->carve_cache(Carver(r->d_cmem));
-        if (!items.empty() && !(err = upload(ctx, r->d_fed_items, items)))
-            err = upload(ctx, r->d_fed_outsz, outsz);
+        r->cl.carve_cache(Carver(r->cl.d_cmem), nb);
+        if (!items.empty() && !(err = upload(ctx, r->cl.d_fed_items, items)))
+            err = upload(ctx, r->cl.d_fed_outsz, outsz);
     }
     if (err)
     {
-        if (r->d_cmem)
+        if (r->cl.d_cmem)
         {
             (void)hipStreamSynchronize(ctx->stream);
-            (void)hipFree(r->d_cmem);
+            (void)hipFree(r->cl.d_cmem);
         }
-        r->d_cmem = nullptr;
-        r->fed_blocks.clear();
+        r->cl.d_cmem = nullptr;
         return err;
     }
-    for (const uint32_t b : r->fed_blocks)
+    for (const uint32_t b : r->cl.fed_blocks)
     {
-        c->table.pin(r->cslot[b]);
-        r->fed[b] = 1;
+        c->table.pin(r->cl.cslot[b]);
+        r->blk.fed[b] = 1;
     }
-    r->pins_held = true;
-    r->needed -= r->fed_blocks.size();
-    r->fed_entries = entries;
-    r->fed_bytes = bytes;
-    r->cache = c;
+    r->cl.pins_held = true;
+    r->blk.needed -= r->cl.fed_blocks.size();
+    r->cl.fed_entries = entries;
+    r->cl.fed_bytes = bytes;
+    r->cl.cache = c;
     return 0;
 }
 
@@ -1755,19 +1607,14 @@ extern "C" int lthip_restore_set_cache(lthip_restore* r, lthip_block_cache* c)
         return EINVAL;
     if (c->ctx != r->ctx)
         return lthip_fail(r->ctx, EINVAL, "lthip_restore_set_cache", "the cache belongs to another context");
-    if (r->cache)
+    if (r->cl.cache)
         return lthip_fail(r->ctx, EEXIST, "lthip_restore_set_cache", "the session has a cache");
     if (r->blocks_queued)
         return lthip_fail(r->ctx, EINVAL, "lthip_restore_set_cache", "a blocks call has queued work: the cache is attached before the first one");
-    try
-    {
-        return set_cache(r, c);
-    }
-    catch (const std::bad_alloc&)
-    {
-        r->fed_blocks.clear();
-        return lthip_fail(r->ctx, ENOMEM, "lthip_restore_set_cache", "host tables");
-    }
+    const int err = lthip_guarded(r->ctx, "lthip_restore_set_cache", [&] { return set_cache(r, c); });
+    if (err) // (the session stays as it was)
+        r->cl.fed_blocks.clear();
+    return err;
 }
 
 extern "C" int lthip_restore_from_cache(lthip_restore* r, void* d_out)
@@ -1775,30 +1622,25 @@ extern "C" int lthip_restore_from_cache(lthip_restore* r, void* d_out)
     if (!r)
         return EINVAL;
     lthip_ctx* ctx = r->ctx;
-    if (!r->cache)
+    if (!r->cl.cache)
         return lthip_fail(ctx, EINVAL, "lthip_restore_from_cache", "the session has no cache");
-    if (r->from_cache_done)
+    if (r->cl.from_cache_done)
         return lthip_fail(ctx, EEXIST, "lthip_restore_from_cache", "the cache-fed blocks were queued before");
-    const uint32_t k = (uint32_t)r->fed_blocks.size();
+    const uint32_t k = (uint32_t)r->cl.fed_blocks.size();
     if (k)
     {
         if (!d_out)
             return lthip_fail(ctx, EINVAL, "lthip_restore_from_cache", "null output");
-        if (r->in_place_buf && d_out != r->in_place_buf)
+        if (r->bs.in_place_buf && d_out != r->bs.in_place_buf)
             return lthip_fail(ctx, EINVAL, "lthip_restore_from_cache", "the base was carried in place: the output is that buffer");
         LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
-        LaunchTimer tm(ctx, LTHIP_K_GATHER);
-        constexpr uint64_t LAUNCH_ENTRIES = 1u << 23;
         // (a cache-fed block is never delivered as needed: its status word stays 0)
-        for (uint64_t e0 = 0; e0 < r->fed_entries; e0 += LAUNCH_ENTRIES)
-            hipLaunchKernelGGL(k_restore_scatter, dim3((uint32_t)std::min(LAUNCH_ENTRIES, r->fed_entries - e0)), dim3(RT), 0, ctx->stream,
-                               (const RItem*)r->d_fed_items, k, (const uint4*)r->d_entries, (const uint32_t*)r->d_status,
-                               (const uint32_t*)r->d_fed_outsz, (uint32_t)e0, (uint8_t*)d_out);
-        LTHIP_LAUNCH_CHECK(ctx);
+        if (const int err = launch_scatter(r, r->cl.d_fed_items, k, r->cl.fed_entries, r->cl.d_fed_outsz, d_out))
+            return err;
         r->blocks_queued = true;
         r->finished = false;
     }
-    r->from_cache_done = true;
+    r->cl.from_cache_done = true;
     return 0;
 }
 
@@ -1806,12 +1648,12 @@ extern "C" int lthip_restore_cache_stats(const lthip_restore* r, uint64_t out[6]
 {
     if (!r || !out)
         return EINVAL;
-    out[0] = r->fed_blocks.size();
-    out[1] = r->fed_bytes;
-    out[2] = r->c_inserted;
-    out[3] = r->c_bypassed;
-    out[4] = r->c_dropped;
-    out[5] = r->from_cache_done ? r->fed_entries : 0u;
+    out[0] = r->cl.fed_blocks.size();
+    out[1] = r->cl.fed_bytes;
+    out[2] = r->cl.c_inserted;
+    out[3] = r->cl.c_bypassed;
+    out[4] = r->cl.c_dropped;
+    out[5] = r->cl.from_cache_done ? r->cl.fed_entries : 0u;
     return 0;
 }
 
@@ -1823,11 +1665,10 @@ extern "C" int lthip_restore_block_status(const lthip_restore* r, uint32_t count
         return lthip_fail(r->ctx, EINVAL, "lthip_restore_block_status", "valid after lthip_restore_finish");
     for (uint32_t i = 0; i < count; ++i)
     {
-        const auto it = r->block_of_hash.find(block_hashes[i]);
-        if (it == r->block_of_hash.end())
+        const uint32_t b = r->blk.find(block_hashes[i]);
+        if (b == NONE)
             return lthip_fail(r->ctx, ENOENT, "lthip_restore_block_status", "a block hash the store index does not hold");
-        const uint32_t b = it->second;
-        status[i] = !r->is_needed(b) ? 0u : !r->delivered[b] ? LTHIP_RESTORE_NOT_DELIVERED : r->status[b];
+        status[i] = !r->blk.is_needed(b) ? 0u : !r->blk.delivered[b] ? LTHIP_RESTORE_NOT_DELIVERED : r->status[b];
     }
     return 0;
 }

@@ -5,7 +5,7 @@
 //                        block (hash, first chunk position, chunk count, tag, raw size, 1 KiB leaves)
 //   whole_asset_windows  asset_offsets -> one window per selected asset, for restore_windows::expand
 // A refusal is an errno with *why set to its reason.  May throw std::bad_alloc.
-// Included by restore.hip and by the stand-alone driver tests/san/restore_plan_driver.cpp.
+// Included by restore.hip (through restore_call.h) and by the stand-alone driver tests/san/restore_plan_driver.cpp.
 #pragma once
 #include "restore_parse.h"
 #include "restore_windows.h"

@@ -1,6 +1,6 @@
 // store_layout.h -- what a store looks like, on the host and without a line of HIP: Longtail_CreateStoreIndex's greedy packing rule, the
 // tables a block-hash launch takes, the serialized StoreIndex, the caller's lthip_ingest_result and which tags a session's codec mode
-// takes.  Shared by the ingest sessions (ingest.hip, ingest_stream.hip) and the bulk calls (version_index.hip, k_gather.hip).
+// takes.  Shared by the ingest sessions (ingest.hip, ingest_stream.hip), the bulk calls (version_index.hip, k_gather.hip) and restore_call.h.
 #pragma once
 #include <errno.h>
 #include <stdint.h>
