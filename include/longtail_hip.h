@@ -1228,6 +1228,107 @@ LTHIP_EXPORT int lthip_store_index_merge(const void* local, size_t local_size, c
 LTHIP_EXPORT int lthip_version_chunk_hashes(const void* version_index, size_t version_index_size, uint64_t* out /*host, may be NULL*/,
                                             uint64_t capacity, uint64_t* count);
 
+/* ---- the repack session: the live chunks of under-used blocks into new blocks (repack.hip, repack_plan.h) -----------------------------
+ * Acting on min_block_usage_percent.  A store that has seen many versions fills with blocks of which a fifth is still wanted; this
+ * session takes the store's StoreIndex, the LIVE set (a device array of chunk hashes, typically the concatenated
+ * lthip_version_chunk_hashes of the versions that are kept; duplicates allowed) and a threshold, decides which blocks stay, rewrites the
+ * live chunks of the others into new stored-block images on the device, from the blocks themselves, and returns the indexes that
+ * describe the store afterwards.  No file is read, no chunk is cut or hashed again but to verify.  With `live` = the distinct hashes of
+ * the live list in first-occurrence order:
+ *   kept     exactly the blocks of lthip_get_existing_store_index(store_index, live list, min_block_usage_percent), and
+ *            lthip_repack_kept_index is byte for byte that call's output.  A block below the threshold, a block with no live chunk and a
+ *            block whose live chunks an earlier block of that call's walk already holds are all not kept.
+ *   moved    the hashes of `live` that no kept block holds, in live's order.  A moved chunk's size is the StoreIndex's, its tag the tag
+ *            of its SOURCE block: the first block in StoreIndex order that holds it.  A chunk two non-kept blocks hold is moved once,
+ *            from the first; a chunk a kept block also holds is not moved.
+ *   source   the blocks that are the source of at least one moved chunk, in StoreIndex order.  Only these have to be delivered.
+ *   dropped  every block that is not kept, in StoreIndex order.
+ *   new      byte for byte lthip_create_missing_content(existing = the kept blocks' chunk hashes, chunks = live with the sizes and tags
+ *            above, the StoreIndex's hash identifier, cfg.max_block_size, cfg.max_chunks_per_block) -- also when nothing is missing.
+ *   after    lthip_repack_store_index: lthip_store_index_merge(local = kept, remote = new), with ONE correction.  The reference takes a
+ *            found block's tag from m_BlockTags[first chunk index] (src/longtail.c:7307) and lthip_get_existing_store_index mirrors it;
+ *            in a store of mixed tags that word is not the block's tag, and no restore session accepts an image against it.  The
+ *            index handed out here carries every kept block's OWN tag, as the store's index records it; where the two agree it is
+ *            the plain merge of lthip_repack_kept_index and the new index.
+ * THE SAFETY CONTRACT: delete dropped blocks only after lthip_repack_finish returned 0 and the new images are stored.
+ *   create       builds the whole plan; the stream is waited for here and nowhere else before finish (the two index calls wait as they
+ *                always do, the plan reads back once, the restore plan once).  EINVAL: cfg NULL, a struct_size that does not reach
+ *                max_chunks_per_block, a percent above 100, a zero max_block_size or max_chunks_per_block.  EBADF: a malformed index.
+ *                ENOENT: the live list names a hash the StoreIndex does not hold.  ENOTSUP: a SOURCE block's tag is not 0, 'lz42' or
+ *                'ztd1'..'ztd5' (such a tag on a kept block, or on a dropped block that is no source, is fine).  On any error nothing
+ *                stays allocated and the context stays usable.
+ *   plan_info    what the plan came to (struct_size honoured); host only, as are the three block lists (hashes NULL or capacity too
+ *                small: the count alone) and lthip_repack_kept_index (ENOMEM with *size set: out NULL or too small).
+ *   the work buffer   ONE caller buffer of info.work_bytes (device memory, 8-byte aligned), laid out by the session: a staging region
+ *                of info.staging_bytes, then the images at 8-byte aligned offsets, each with room for
+ *                lthip_stored_block_header_size(n) + the codec's bound, or lthip_block_index_size(n) + raw size for tag 0.  A tagged
+ *                new block's chunks are staged back to back in the new index's chunk order: its raw payload is one byte range the
+ *                codec reads where it lies.  A tag-0 new block's chunks are scattered straight to their final positions inside its
+ *                image and never pass through staging.
+ *   scratch_bound, blocks, block_status   lthip_restore_scratch_bound / _blocks / _block_status over the source blocks, d_work in the
+ *                place of d_out, with every refusal and property of those calls: ENOENT unknown hash, EEXIST delivered before or twice,
+ *                EINVAL misaligned offset, ENOMEM scratch below the bound; a block that is no source is accepted, counted and not
+ *                touched; nothing is waited for; sources may come in any number of calls, in any order; scratch and images may be
+ *                reused once a call's work has run.  THE GUARANTEE of the restore session holds: no byte of a bad block reaches d_work.
+ *                With cfg.verify every chunk of a delivered source block is hashed and compared.  Every call names the same d_work;
+ *                EINVAL, the session unchanged, for another one or one that is not 8-byte aligned (write refuses the same).
+ *   write        queues the block writer of the ingest sessions for all new blocks: the codec by tag from staging into the images,
+ *                BlockIndex and [raw][compressed] words; the block hashes are the new index's.  ENOENT, nothing queued, while source
+ *                blocks are outstanding: deliver and call again.  EEXIST on a second successful call.  ENOMEM: work_bytes below
+ *                info.work_bytes.
+ *   finish       the session's one full synchronisation.  0 only if every source block was delivered and good and the images were
+ *                written; then the new index goes to h_new_index (NULL: *size alone; ENOMEM when capacity is too small -- call again).
+ *                ENOENT: source blocks, or write, are outstanding.  EBADF: a delivered block was bad -- it takes precedence; NO IMAGE
+ *                TABLE IS HANDED OUT, lthip_repack_images and lthip_repack_store_index return EBADF from then on, the caller must
+ *                delete nothing and the session is over.  The result is filled either way (struct_size honoured).
+ *   images       host tables, valid after finish returned 0 and until destroy: image i of the new index lies at d_work + offsets[i]
+ *                and is sizes[i] bytes long.
+ * Re-tagging moved chunks, a repack whose moved bytes do not fit one work buffer, and every file operation are not part of it.  One
+ * session belongs to one context (and its thread) and must be destroyed before it. */
+typedef struct lthip_repack lthip_repack;
+typedef struct lthip_repack_config
+{
+    uint64_t struct_size;             /* IN: sizeof(lthip_repack_config) of the caller's header; the library reads at most that */
+    uint32_t min_block_usage_percent; /* 0 .. 100; 0 keeps every block that holds a live chunk no earlier block of the walk holds */
+    uint32_t max_block_size;          /* of the new blocks, as lthip_create_missing_content takes them */
+    uint32_t max_chunks_per_block;
+    uint32_t verify;                  /* 0 or 1 */
+} lthip_repack_config;
+typedef struct lthip_repack_info
+{
+    uint64_t struct_size; /* IN: sizeof(lthip_repack_info) of the caller's header; the library fills at most that */
+    uint64_t blocks_total, blocks_kept, blocks_dropped, blocks_source;
+    uint64_t live_chunks /* distinct */, moved_chunks, moved_bytes;
+    uint64_t new_blocks;
+    uint64_t staging_bytes, work_bytes;
+    uint64_t kept_index_size, new_index_size, store_index_size;
+} lthip_repack_info;
+typedef struct lthip_repack_result
+{
+    uint64_t struct_size; /* IN: sizeof(lthip_repack_result) of the caller's header; the library fills at most that */
+    uint64_t blocks_source, blocks_delivered /* all accepted blocks */, blocks_bad;
+    uint64_t chunks_mismatched;                           /* verify: chunks whose hash differed */
+    uint64_t raw_bytes_written, compressed_bytes_written; /* of the new blocks: chunk bytes, payload bytes (0 unless finish returned 0) */
+    uint64_t decoded_bytes;                               /* raw bytes of the tagged source blocks whose decoder returned the raw size */
+} lthip_repack_result;
+LTHIP_EXPORT int lthip_repack_create(lthip_ctx* ctx, const lthip_repack_config* config, const void* store_index, size_t store_index_size,
+                                     uint64_t live_count, const uint64_t* d_live_hashes, lthip_repack** out);
+LTHIP_EXPORT void lthip_repack_destroy(lthip_repack* repack);
+LTHIP_EXPORT int lthip_repack_plan_info(const lthip_repack* repack, lthip_repack_info* out_info);
+LTHIP_EXPORT int lthip_repack_kept_blocks(const lthip_repack* repack, uint64_t* block_hashes, uint64_t capacity, uint64_t* count);
+LTHIP_EXPORT int lthip_repack_dropped_blocks(const lthip_repack* repack, uint64_t* block_hashes, uint64_t capacity, uint64_t* count);
+LTHIP_EXPORT int lthip_repack_source_blocks(const lthip_repack* repack, uint64_t* block_hashes, uint64_t capacity, uint64_t* count);
+LTHIP_EXPORT int lthip_repack_kept_index(const lthip_repack* repack, void* out, size_t capacity, size_t* size);
+LTHIP_EXPORT size_t lthip_repack_scratch_bound(const lthip_repack* repack, uint32_t block_count, const uint64_t* block_hashes);
+LTHIP_EXPORT int lthip_repack_blocks(lthip_repack* repack, uint32_t block_count, const uint64_t* block_hashes /*host*/, const void* d_images,
+                                     const uint64_t* image_offsets /*host, 8-byte aligned*/, const uint32_t* image_sizes /*host*/,
+                                     void* d_scratch, uint64_t scratch_bytes, void* d_work);
+LTHIP_EXPORT int lthip_repack_write(lthip_repack* repack, void* d_work, uint64_t work_bytes);
+LTHIP_EXPORT int lthip_repack_finish(lthip_repack* repack, void* h_new_index, size_t capacity, size_t* size, lthip_repack_result* out_result);
+LTHIP_EXPORT int lthip_repack_images(const lthip_repack* repack, uint64_t* count, const uint64_t** offsets, const uint32_t** sizes);
+LTHIP_EXPORT int lthip_repack_store_index(const lthip_repack* repack, void* out, size_t capacity, size_t* size);
+LTHIP_EXPORT int lthip_repack_block_status(const lthip_repack* repack, uint32_t count, const uint64_t* block_hashes, uint32_t* status);
+
 /* ---- multi-GPU work division, host functions -----------------------------------------------------------
  * The unit of independence is the reference's own job: one (asset, target_chunk_size*1024-byte part) of ChunkAssets
  * (src/longtail.c:2396-2458).  lthip_job_count / lthip_make_jobs list the jobs of a tree exactly as :2399-2404 / :2432-2457 do

@@ -28,5 +28,5 @@ def build(verbose: bool = False) -> Path:
     return LIB_PATH
 
 
-from .lib import (Archive, ArchiveWriter, BlockCache, HipLib, Context, LongtailHipError, Restore, RestoreWindow, load, restore_asset_sizes, restore_layout_in_place,  # noqa: E402,F401
+from .lib import (Archive, ArchiveWriter, BlockCache, HipLib, Context, LongtailHipError, Repack, Restore, RestoreWindow, load, restore_asset_sizes, restore_layout_in_place,  # noqa: E402,F401
                   restore_rank_windows, store_index_merge, store_index_prune, version_chunk_hashes, version_diff)

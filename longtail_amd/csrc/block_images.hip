@@ -107,7 +107,7 @@ int lthip_block_payloads(lthip_ctx* ctx, BlockImageBufs& w, BlockBatch& bt, cons
     bt.r_first.clear(), bt.r_count.clear(), bt.r_payload.clear();
     uint64_t raw_bytes = 0;
     for (size_t i = 0; i < cnt; ++i)
-        if (bt.codec[i].codec == LTHIP_CODEC_NONE)
+        if (bt.codec[i].codec == LTHIP_CODEC_NONE && bt.place[i] != PLACE_IN_IMAGE)
         {
             const uint32_t nchunks = bt.first[i + 1] - bt.first[i];
             bt.r_first.push_back(dev.chunk_base + bt.first[i]);

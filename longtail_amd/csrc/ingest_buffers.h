@@ -93,6 +93,7 @@ inline size_t block_codec_bound(uint32_t codec, size_t n) { return codec == LTHI
 inline size_t block_header_bytes(uint32_t codec, uint32_t chunks) { return codec == LTHIP_CODEC_NONE ? lthip_block_index_size(chunks) : lthip_stored_block_header_size(chunks); }
 
 constexpr uint32_t PLACE_RAW = ~0u; // BlockBatch::place of a block that is copied straight from where its chunks lie
+constexpr uint32_t PLACE_IN_IMAGE = ~0u - 1u; // ... of a raw block whose chunks lie in its image already (the repack session): nothing is copied
 
 // One batch of stored-block images, as the session describes it block after block (add) and the writer lays it out: a slot of the arena
 // per block -- BlockIndex, the [raw][compressed] words unless the block is stored raw, the bound of the block's own codec, rounded to

@@ -413,4 +413,19 @@ int lthip_launch_lz_sequences(lthip_ctx* ctx, const void* d_src, uint32_t block_
                               const uint32_t* src_sizes, void* d_dst, const uint64_t* dst_offsets, const uint32_t* dst_caps,
                               uint8_t** d_lits, uint64_t** d_recs, void** d_meta, uint32_t* unit_base, uint64_t* total_units, int quality);
 
+// A restore session over occurrences that lie on the device (restore.hip): `count` whole chunks, chunk d_hash[i] of d_len[i] bytes to
+// byte d_dst[i] of the output.  The session behaves as one lthip_restore_create made, with no asset selected; the list is copied on the
+// context's stream and may be freed once that has run.  who: the name refusals carry.
+struct lthip_occurrence_list
+{
+    uint32_t hash_identifier;
+    uint64_t count;
+    const uint64_t* d_hash;
+    const uint32_t* d_len;
+    const uint64_t* d_dst;
+};
+int lthip_restore_create_occurrences(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_occurrence_list* list, const void* store_index,
+                                     size_t si_size, uint64_t out_bytes, const char* who, lthip_restore** out);
+uint64_t lthip_restore_outstanding(const lthip_restore* r); // needed blocks that were not delivered yet
+
 static inline uint64_t div_up_u64(uint64_t a, uint64_t b) { return (a + b - 1) / b; }

@@ -14,6 +14,9 @@
 //            still compares the full length with the StoreIndex's size and counts `clip` bytes; k_restore_fill places (offset in block +
 //            skip, clip, destination).  A clipped occurrence is an ordinary entry: check, decode, verify and scatter do not know of it.
 //            The sessions of whole assets are the same routine with one window per selected asset and no skip / clip tables at all.
+//   list     (lthip_restore_create_occurrences, lthip_internal.h) the occurrences lie on the device already -- the repack session's moved
+//            chunks, each a whole chunk with a destination in its work buffer: no VersionIndex is read and nothing is expanded, the
+//            list is copied device to device into the plan's tables and everything behind that is the same plan.
 //   blocks   k_restore_check_images (a wave per image, against the device copy of the StoreIndex) -> the decoders into 64-byte slots of
 //            the caller's scratch -> k_restore_ranges (the decoders' verdict into the block's status word; with verify the (offset,
 //            length) of every chunk) -> lthip_hash_ranges_by_id -> k_restore_compare -> k_restore_scatter over the call's entries
@@ -745,7 +748,8 @@ extern "C" void lthip_restore_destroy(lthip_restore* r)
 }
 
 // What a session writes: byte windows of assets (lthip_restore_create_windows), or whole assets at asset_offsets -- which become one
-// window per selected asset once the VersionIndex has been read.
+// window per selected asset once the VersionIndex has been read --, or (list) occurrences that lie on the device already: no
+// VersionIndex is read, and every occurrence is its whole chunk (lthip_restore_create_occurrences, the repack session).
 struct Wanted
 {
     const char* who;
@@ -753,6 +757,7 @@ struct Wanted
     bool by_window;
     uint64_t window_count;
     const restore_windows::Window* windows;
+    const lthip_occurrence_list* list = nullptr;
 };
 
 // `base` is optional: lthip_restore_create passes none, and then every step that serves it is skipped
@@ -762,8 +767,10 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     lthip_ctx* ctx = r->ctx;
     restore_parse::VersionIndex vi, bvi;
     restore_parse::StoreIndex si;
-    if (restore_parse::parse_version_index(version_index, vi_size, &vi))
+    if (!wanted.list && restore_parse::parse_version_index(version_index, vi_size, &vi))
         return lthip_fail(ctx, EBADF, "lthip_restore_create", "malformed version index");
+    if (wanted.list)
+        vi.hash_identifier = wanted.list->hash_identifier;
     if (restore_parse::parse_store_index(store_index, si_size, &si))
         return lthip_fail(ctx, EBADF, "lthip_restore_create", "malformed store index");
     if (si.chunk_count && si.hash_identifier != vi.hash_identifier)
@@ -808,7 +815,9 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     r->block_chunks = st.block_chunks;
     // ---- occurrences: per window and chunk it touches (hash, full length, skip, clip, destination) ----
     restore_windows::Occurrences occ;
-    if (wanted.by_window)
+    if (wanted.list)
+        refused = wanted.list->count > 0x7FFFFFFFull ? (why = "more than 2^31 - 1 occurrences", EINVAL) : 0;
+    else if (wanted.by_window)
         refused = restore_windows::expand(vi, wanted.window_count, wanted.windows, out_bytes, &occ, &why);
     else
     {
@@ -818,7 +827,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     if (refused)
         return lthip_fail(ctx, refused, wanted.who, why);
     r->assets_selected = occ.assets_selected;
-    const uint32_t nocc = r->nocc = (uint32_t)occ.hash.size();
+    const uint32_t nocc = r->nocc = wanted.list ? (uint32_t)wanted.list->count : (uint32_t)occ.hash.size();
     const bool clipped = !occ.clip.empty();
     // ---- device memory: the session's, and the plan's temporaries ----
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -833,9 +842,16 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
     int err;
     if ((err = upload(ctx, sv.chash, st.chash)) || (err = upload(ctx, sv.csize, st.csize)) || (err = upload(ctx, sv.cblock, st.cblock)) ||
         (err = upload(ctx, sv.coff, st.coff)) || (err = upload(ctx, sv.bhash, st.bhash)) || (err = upload(ctx, sv.bcoff, st.bcoff)) ||
-        (err = upload(ctx, sv.bcnt, st.bcnt)) || (err = upload(ctx, sv.btag, st.btag)) || (err = upload(ctx, sv.braw, st.braw)) ||
-        (err = upload(ctx, t.ohash, occ.hash)) || (err = upload(ctx, t.occ.dst, occ.dst)) || (err = upload(ctx, t.occ.len, occ.len)))
+        (err = upload(ctx, sv.bcnt, st.bcnt)) || (err = upload(ctx, sv.btag, st.btag)) || (err = upload(ctx, sv.braw, st.braw)))
         return err;
+    if (!wanted.list && ((err = upload(ctx, t.ohash, occ.hash)) || (err = upload(ctx, t.occ.dst, occ.dst)) || (err = upload(ctx, t.occ.len, occ.len))))
+        return err;
+    if (wanted.list && nocc) // (the list lies on the device: queued on the stream that wrote it)
+    {
+        LTHIP_CHECK(ctx, hipMemcpyAsync(t.ohash, wanted.list->d_hash, (size_t)nocc * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(t.occ.dst, wanted.list->d_dst, (size_t)nocc * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        LTHIP_CHECK(ctx, hipMemcpyAsync(t.occ.len, wanted.list->d_len, (size_t)nocc * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
     if (clipped && ((err = upload(ctx, t.occ.skip, occ.skip)) || (err = upload(ctx, t.occ.clip, occ.clip))))
         return err;
     if (base && ((err = upload(ctx, r->bs.base.hash, bt.hash)) || (err = upload(ctx, r->bs.base.off, bt.off)) ||
@@ -916,7 +932,7 @@ static int restore_build(lthip_restore* r, const lthip_restore_config* cfg, cons
 static int restore_create(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_restore_base* base, const void* version_index,
                           size_t vi_size, const void* store_index, size_t si_size, const Wanted& wanted, uint64_t out_bytes, lthip_restore** out)
 {
-    if (!ctx || !out || !version_index || !store_index)
+    if (!ctx || !out || (!version_index && !wanted.list) || !store_index)
         return EINVAL;
     *out = nullptr;
     lthip_restore* r = new (std::nothrow) lthip_restore();
@@ -940,6 +956,19 @@ extern "C" int lthip_restore_create(lthip_ctx* ctx, const lthip_restore_config* 
     return restore_create(ctx, cfg, nullptr, version_index, vi_size, store_index, si_size,
                           Wanted{"lthip_restore_create", asset_offsets, false, 0, nullptr}, out_bytes, out);
 }
+
+// (lthip_internal.h) the session the repack session owns: its occurrences are the moved chunks, its output the work buffer
+int lthip_restore_create_occurrences(lthip_ctx* ctx, const lthip_restore_config* cfg, const lthip_occurrence_list* list, const void* store_index,
+                                     size_t si_size, uint64_t out_bytes, const char* who, lthip_restore** out)
+{
+    if (!list || (list->count && (!list->d_hash || !list->d_len || !list->d_dst)))
+        return EINVAL;
+    Wanted wanted{who, nullptr, false, 0, nullptr};
+    wanted.list = list;
+    return restore_create(ctx, cfg, nullptr, nullptr, 0, store_index, si_size, wanted, out_bytes, out);
+}
+
+uint64_t lthip_restore_outstanding(const lthip_restore* r) { return r->blk.needed - r->blk.needed_delivered; }
 
 static_assert(sizeof(lthip_restore_window) == sizeof(restore_windows::Window) &&
                   offsetof(lthip_restore_window, dst) == offsetof(restore_windows::Window, dst),

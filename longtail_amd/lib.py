@@ -210,6 +210,19 @@ class HipLib:
         sig("lthip_store_index_prune", i32, [vp, sz, u32, vp, vp, sz, P(sz)])
         sig("lthip_store_index_merge", i32, [vp, sz, vp, sz, vp, sz, P(sz)])
         sig("lthip_version_chunk_hashes", i32, [vp, sz, vp, u64, P(u64)])
+        sig("lthip_repack_create", i32, [vp, vp, vp, sz, u64, vp, P(vp)])
+        sig("lthip_repack_destroy", None, [vp])
+        sig("lthip_repack_plan_info", i32, [vp, vp])
+        for name in ("kept", "dropped", "source"):
+            sig(f"lthip_repack_{name}_blocks", i32, [vp, vp, u64, P(u64)])
+        sig("lthip_repack_kept_index", i32, [vp, vp, sz, P(sz)])
+        sig("lthip_repack_scratch_bound", sz, [vp, u32, vp])
+        sig("lthip_repack_blocks", i32, [vp, u32, vp, vp, vp, vp, vp, u64, vp])
+        sig("lthip_repack_write", i32, [vp, vp, u64])
+        sig("lthip_repack_finish", i32, [vp, vp, sz, P(sz), vp])
+        sig("lthip_repack_images", i32, [vp, P(u64), P(vp), P(vp)])
+        sig("lthip_repack_store_index", i32, [vp, vp, sz, P(sz)])
+        sig("lthip_repack_block_status", i32, [vp, u32, vp, vp])
         sig("lthip_store_create", i32, [vp, u64, P(vp)])
         sig("lthip_store_destroy", None, [vp])
         sig("lthip_store_add", i32, [vp, u64, vp])
@@ -1350,6 +1363,144 @@ class Restore:
         out = np.zeros(len(h), np.uint32)
         self.ctx._check(self.ctx.lib.dll.lthip_restore_block_status(self.h, len(h), h.ctypes.data if len(h) else None,
                                                                     out.ctypes.data if len(h) else None), "lthip_restore_block_status")
+        return out
+
+
+class RepackConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64), ("min_block_usage_percent", C.c_uint32), ("max_block_size", C.c_uint32),
+                ("max_chunks_per_block", C.c_uint32), ("verify", C.c_uint32)]
+
+
+class RepackInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_uint64) for n in (
+        "blocks_total", "blocks_kept", "blocks_dropped", "blocks_source", "live_chunks", "moved_chunks", "moved_bytes", "new_blocks",
+        "staging_bytes", "work_bytes", "kept_index_size", "new_index_size", "store_index_size")]
+
+
+class RepackResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_uint64) for n in (
+        "blocks_source", "blocks_delivered", "blocks_bad", "chunks_mismatched", "raw_bytes_written", "compressed_bytes_written",
+        "decoded_bytes")]
+
+
+class Repack:
+    """lthip_repack: the live chunks of a store's under-used blocks into new stored-block images (include/longtail_hip.h, "the repack
+    session").  live_hashes: a device uint64 tensor (or None for an empty live set).  info() -> the plan; source_blocks() -> which blocks
+    to fetch; blocks() per batch of images, all with the same `work` tensor of info().work_bytes; write(work); finish() -> (code, new
+    index or None, RepackResult); then images() and store_index().  Delete dropped_blocks() only after finish() returned 0 and the new
+    images are stored."""
+
+    def __init__(self, ctx: "Context", store_index: bytes, live_hashes, min_block_usage_percent: int, max_block_size: int,
+                 max_chunks_per_block: int, verify: bool = True):
+        self.ctx = ctx
+        self.h = None
+        si = np.frombuffer(store_index, np.uint8)
+        n = _numel(live_hashes) if live_hashes is not None else 0
+        cfg = RepackConfig(C.sizeof(RepackConfig), min_block_usage_percent, max_block_size, max_chunks_per_block, 1 if verify else 0)
+        h = C.c_void_p()
+        ctx._check(ctx.lib.dll.lthip_repack_create(ctx.h, C.byref(cfg), si.ctypes.data if len(si) else None, len(si), n,
+                                                   _ptr(live_hashes) if n else None, C.byref(h)), "lthip_repack_create")
+        self.h = h
+        self._keep = []
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.dll.lthip_repack_destroy(self.h)
+        self.h = None
+        self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> RepackInfo:
+        out = RepackInfo()
+        out.struct_size = C.sizeof(RepackInfo)
+        self.ctx._check(self.ctx.lib.dll.lthip_repack_plan_info(self.h, C.byref(out)), "lthip_repack_plan_info")
+        return out
+
+    def _hashes(self, which: str) -> np.ndarray:
+        fn, n = getattr(self.ctx.lib.dll, f"lthip_repack_{which}_blocks"), C.c_uint64(0)
+        self.ctx._check(fn(self.h, None, 0, C.byref(n)), f"lthip_repack_{which}_blocks")
+        out = np.zeros(n.value, np.uint64)
+        self.ctx._check(fn(self.h, out.ctypes.data if len(out) else None, len(out), C.byref(n)), f"lthip_repack_{which}_blocks")
+        return out
+
+    def kept_blocks(self) -> np.ndarray:
+        """The hashes of the blocks that stay, in the order lthip_get_existing_store_index lists them."""
+        return self._hashes("kept")
+
+    def dropped_blocks(self) -> np.ndarray:
+        """The hashes of the blocks that do not stay, in StoreIndex order."""
+        return self._hashes("dropped")
+
+    def source_blocks(self) -> np.ndarray:
+        """The hashes of the blocks a moved chunk comes from, in StoreIndex order: the ones to deliver."""
+        return self._hashes("source")
+
+    def kept_index(self) -> bytes:
+        """The serialized StoreIndex of the kept blocks: byte for byte lthip_get_existing_store_index's."""
+        return _sized_blob_call(self.ctx.lib.dll.lthip_repack_kept_index, "lthip_repack_kept_index", self.h)
+
+    def scratch_bound(self, block_hashes) -> int:
+        h = _u64arr(block_hashes)
+        return int(self.ctx.lib.dll.lthip_repack_scratch_bound(self.h, len(h), h.ctypes.data if len(h) else None))
+
+    def blocks(self, block_hashes, images, image_offsets, image_sizes, scratch, work):
+        """Delivers the images of these blocks, as Restore.blocks does, with the work buffer as the output.  Asynchronous on the
+        context's stream: the tensors are kept until finish() or close()."""
+        h, o, z = _u64arr(block_hashes), _u64arr(image_offsets), _u32arr(image_sizes)
+        assert len(h) == len(o) == len(z)
+        self.ctx._check(self.ctx.lib.dll.lthip_repack_blocks(self.h, len(h), h.ctypes.data if len(h) else None, _ptr(images),
+                                                             o.ctypes.data if len(o) else None, z.ctypes.data if len(z) else None,
+                                                             _ptr(scratch), _numel(scratch), _ptr(work)), "lthip_repack_blocks")
+        self._keep.append((images, scratch, work))
+
+    def write(self, work):
+        """Queues the block writer for all new blocks; ENOENT (raised) while source blocks are outstanding."""
+        self.ctx._check(self.ctx.lib.dll.lthip_repack_write(self.h, _ptr(work) or None, _numel(work)), "lthip_repack_write")
+        self._keep.append((work,))
+
+    def finish(self):
+        """-> (code, the new index's bytes or None, RepackResult): 0, errno.ENOENT (source blocks or write() are outstanding) or
+        errno.EBADF (a delivered block was bad: delete nothing).  The session's one full synchronisation."""
+        res = RepackResult()
+        res.struct_size = C.sizeof(RepackResult)
+        n = C.c_size_t(self.info().new_index_size)
+        out = np.zeros(max(n.value, 1), np.uint8)
+        code = self.ctx.lib.dll.lthip_repack_finish(self.h, out.ctypes.data, n.value, C.byref(n), C.byref(res))
+        if code not in (0, errno.ENOENT, errno.EBADF):
+            self.ctx._check(code, "lthip_repack_finish")
+        self._keep = []
+        return code, (out[: n.value].tobytes() if code == 0 else None), res
+
+    def images(self):
+        """After finish() returned 0 -> (offsets: uint64 array, sizes: uint32 array): image i of the new index lies at work[offsets[i]:]."""
+        n, po, pz = C.c_uint64(0), C.c_void_p(), C.c_void_p()
+        self.ctx._check(self.ctx.lib.dll.lthip_repack_images(self.h, C.byref(n), C.byref(po), C.byref(pz)), "lthip_repack_images")
+        k = n.value
+        offs = np.frombuffer(C.string_at(po.value, 8 * k), np.uint64).copy() if k else np.zeros(0, np.uint64)
+        sizes = np.frombuffer(C.string_at(pz.value, 4 * k), np.uint32).copy() if k else np.zeros(0, np.uint32)
+        return offs, sizes
+
+    def store_index(self) -> bytes:
+        """After finish() returned 0: the store's index afterwards -- the kept blocks (under their own tags), then the new blocks."""
+        n = C.c_size_t(0)
+        err = self.ctx.lib.dll.lthip_repack_store_index(self.h, None, 0, C.byref(n))
+        if err != errno.ENOMEM:
+            self.ctx._check(err or errno.EIO, "lthip_repack_store_index")
+        out = np.zeros(n.value, np.uint8)
+        self.ctx._check(self.ctx.lib.dll.lthip_repack_store_index(self.h, out.ctypes.data, len(out), C.byref(n)), "lthip_repack_store_index")
+        return out.tobytes()
+
+    def block_status(self, block_hashes) -> np.ndarray:
+        """After finish(): per block 0 or RESTORE_* flag bits."""
+        h = _u64arr(block_hashes)
+        out = np.zeros(len(h), np.uint32)
+        self.ctx._check(self.ctx.lib.dll.lthip_repack_block_status(self.h, len(h), h.ctypes.data if len(h) else None,
+                                                                   out.ctypes.data if len(h) else None), "lthip_repack_block_status")
         return out
 
 
