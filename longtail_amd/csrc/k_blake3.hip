@@ -11,9 +11,12 @@
 //                 at arbitrary byte offsets, so message words are rebuilt from 4-byte aligned dwords with one
 //                 v_alignbit each.  Leaf -> range mapping is a binary search over the exclusive scan of leaf
 //                 counts (no per-leaf descriptor traffic).
-//   parent kernel in-place left-heavy reduction of each range's chaining values (level by level, stride
-//                 doubling == blake3's compress_parents_parallel with the odd node carried up), ROOT on the
-//                 last merge; writes output words 0,1 as the u64 digest.
+//   parent kernel left-heavy reduction of each range's chaining values (level by level, stride doubling ==
+//                 blake3's compress_parents_parallel with the odd node carried up), ROOT on the last merge;
+//                 writes output words 0,1 as the u64 digest.  Small trees (<= 256 leaves): a workgroup per
+//                 window of 2048 leaf slots, the two lowest levels in registers (a thread per aligned block
+//                 of four leaves, read straight from global memory), the others lane-dense in LDS from a
+//                 merge list that each level filters for the next.  Big trees: one launch per level, in place.
 #include "lthip_internal.h"
 
 #include <stdlib.h>
@@ -105,21 +108,56 @@ __global__ void k_leaf_counts(const uint32_t* __restrict__ lens, uint64_t bound,
 }
 
 // ---------------------------------------------------------------------------------------------------
+// small trees: windows and blocks (parents kernel; the leaf kernel notes each window's first range)
+// ---------------------------------------------------------------------------------------------------
+// The small-tree parents kernel (k_blake3_parents_window, below) and the one line of the leaf kernel that notes a window's first
+// range share these.  A range of n leaves is cut into blocks of B = 2^J leaf slots, block b holding leaves [b B, min(b B + B, n)):
+// the node over a block is a node of the range's left-heavy tree (the stride doubling of the level reducers, restricted to the
+// block), so a block is merged in one thread's registers and only its node goes on to the levels in LDS.
+// The functions between the two marks are all the shape arithmetic of that kernel; a host compiler takes them as they are
+// (tests/test_blake3_parents_shapes.py cuts them out and walks them for every n).
+// [b3-parents-shapes
+constexpr uint32_t b3s_blocks(uint32_t n, uint32_t B) { return (n + B - 1u) / B; } // blocks of a range of n leaves
+constexpr uint32_t b3s_block_leaves(uint32_t n, uint32_t b, uint32_t B) { return n - b * B < B ? n - b * B : B; } // leaves of block b
+// register stage, a block of m leaves: for st = 1, 2, .. < B, for k = 0, 2 st, .. < B in that order, leaf k takes leaf k + st
+constexpr bool b3s_reg_merge(uint32_t m, uint32_t k, uint32_t st) { return k + st < m; }
+// ROOT is on the merge at stride st (in leaves) whose left child is leaf K of a range of n leaves
+constexpr bool b3s_root(uint32_t n, uint32_t K, uint32_t st) { return K == 0u && 2u * st >= n; }
+// a range of more than one block sends every block's node to LDS; the node of a one-block range is its digest
+constexpr bool b3s_to_lds(uint32_t n, uint32_t B) { return b3s_blocks(n, B) > 1u; }
+// LDS levels, st = 1, 2, .. in BLOCKS: block k of a range of nb blocks takes block k + st.  The list of level 2 st is the part of
+// level st's list for which this holds again (a left child at 2 st was one at st)
+constexpr bool b3s_lds_merge(uint32_t nb, uint32_t k, uint32_t st) { return (k & (2u * st - 1u)) == 0u && k + st < nb; }
+constexpr bool b3s_lds_root(uint32_t nb, uint32_t st) { return 2u * st >= nb; } // (then k = 0: it is b3s_root in blocks)
+// most nodes in LDS for S leaf slots of ranges: ceil(n / B) <= 2 n / (B + 1) for every n > B, with equality at n = B + 1
+constexpr uint32_t b3s_max_nodes(uint32_t S, uint32_t B) { return 2u * S / (B + 1u); }
+// LDS bytes of a window of S leaf slots: a range has three 16-bit table entries and 32 bytes per node, which is at most 6 bytes per
+// slot for a range of one block (n >= 1) and (6 + 64) / (B + 1) for the others (n = B + 1 again); tables and nodes share one
+// array, because the window with the most ranges (all of one leaf) has no node and the one with the most nodes has few ranges
+constexpr uint32_t b3s_range_bytes(uint32_t n, uint32_t B) { return 6u + (b3s_to_lds(n, B) ? 32u * b3s_blocks(n, B) : 0u); }
+constexpr uint32_t b3s_max_bytes(uint32_t S, uint32_t B) { return (6u * (B + 1u) > 70u ? 6u * (B + 1u) : 70u) * S / (B + 1u) + 6u + 16u; }
+// b3-parents-shapes]
+
+constexpr uint32_t PJ = 2;
+constexpr uint32_t PB = 1u << PJ; // leaf slots of a block
+constexpr int PW = 2048;          // parents kernel: window of leaf slots per workgroup (a power of two)
+constexpr int PW_MAXN = 256;      // leaves of the largest range (small trees: <= 256 KiB)
+constexpr int PW_THREADS = 512;   // threads of a parents workgroup (a multiple of 64)
+constexpr int PW_WAVES = 8;       // waves per SIMD the kernel is compiled for: FOUR workgroups per CU (32 waves; 4 x 36 KiB of LDS)
+// Measured on the 64 GiB tree (same box, builds side by side through LTHIP_LIB_PATH; the kernel before this one, every level in LDS
+// with a window of 1024, 2.80 ms): J = 1 / 2 / 3 with windows of 1024 / 2048 / 2048 slots and 512 / 512 / 256 threads 2.20 / 1.85 /
+// 1.91 ms (J = 3 needs 92 registers: five workgroups of four waves).  Workgroups per CU decide more than anything else: J = 2 with
+// tables and nodes in arrays of their own (45 KiB, three per CU) 2.03; 576 / 640 threads (one trip through the register stage, but
+// 9 / 10 waves a workgroup) 2.57 / 2.43; J = 3 with 320 / 384 threads 2.61 / 3.07, with a window of 4096 and two per CU 2.32; J = 2
+// with 1024 slots and 256 threads 2.13.  (profiles/b3_parents_ab.txt)
+constexpr uint32_t PW_NODES = b3s_max_nodes(PW + PW_MAXN - 1, PB) + 1u;          // a window's slots: PW - 1 + 256 at the most
+constexpr uint32_t PW_MEM16 = (b3s_max_bytes(PW + PW_MAXN - 1, PB) + 15u) / 16u; // uint4s of tables and nodes
+constexpr uint32_t PW_LEVELS = 8u - PJ;                                          // 2^PW_LEVELS blocks in the largest range
+static_assert(PW <= 4096 && (PW & (PW - 1)) == 0 && PW_THREADS % 64 == 0 && PW_MAXN >> PJ <= 255, "window tables are 16 bits, list entries 16 + 8 + 8");
+
+// ---------------------------------------------------------------------------------------------------
 // leaves
 // ---------------------------------------------------------------------------------------------------
-#ifndef LTHIP_B3_PW
-#define LTHIP_B3_PW 1024
-#endif
-constexpr int PW = LTHIP_B3_PW; // parents kernel: window of leaf slots per workgroup (a power of two)
-constexpr int PW_MAXN = 256; // leaves of the largest range (small trees: <= 256 KiB)
-constexpr int PW_SLOTS = PW + PW_MAXN;
-#ifndef LTHIP_B3_PW_THREADS
-#define LTHIP_B3_PW_THREADS 512
-#endif
-constexpr int PW_THREADS = LTHIP_B3_PW_THREADS; // threads of a parents workgroup (a power of two).  Measured on the 64 GiB tree (same box,
-// builds side by side through LTHIP_LIB_PATH): windows of 256 / 512 / 1024 / 2048 slots with 256 threads 4.19 / 3.54 / 3.12 / 5.55 ms
-// (2048: two workgroups per CU); 1024 slots with 256 / 512 / 1024 threads 3.12 / 2.80 / 3.19 ms -- 512 threads have one merge each
-// on the first level and three workgroups of them are 24 waves per CU.
 
 // The message dwords of one 64-byte block as they lie in memory: 16 dwords from the 4-byte aligned address at or below the block's
 // first byte, and the dword behind them, which holds the block's last 1..3 bytes when the leaf starts off a dword boundary.
@@ -562,26 +600,61 @@ __global__ __launch_bounds__(B3S_LEAVES) void k_blake3_stream_final(const uint8_
     *out = (uint64_t)cur[0] | ((uint64_t)cur[1] << 32);
 }
 
-// small trees, lane-dense: a workgroup owns the ranges whose first leaf slot lies in its window of PW slots, keeps their
-// chaining values in LDS and reduces ALL of them level by level -- the merges of one level (any range, any position) are
-// compacted into a list so that every lane of every wave has one, instead of one thread walking one tree serially with
-// its 2 x 32-byte loads uncoalesced (k_blake3_parents_small).  Left-heavy tree as above: the node of leaves [k, k + 2 st)
-// lives at slot k; a level's merges read slots (k, k + st) and write slot k, so they are independent.
-__global__ __launch_bounds__(PW_THREADS) void k_blake3_parents_window(const uint32_t* __restrict__ leaf_prefix, uint64_t count_bound,
-                                                               const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ cvs,
-                                                               const uint32_t* __restrict__ win_first, uint64_t* __restrict__ hashes)
+// left <- parent(left, right), both in registers
+__device__ __forceinline__ void b3_merge_regs(uint32_t (&left)[8], const uint32_t (&right)[8], uint32_t flags)
 {
-    __shared__ uint4 s_cv[PW_SLOTS * 2];
-    __shared__ uint32_t s_info[PW_SLOTS]; // leaf index inside its range | leaves of the range << 16
-    __shared__ uint16_t s_list[PW_SLOTS / 2 + 64];
-    __shared__ uint32_t s_cnt, s_maxn;
+    const uint32_t m[16] = {left[0], left[1], left[2], left[3], left[4], left[5], left[6], left[7],
+                            right[0], right[1], right[2], right[3], right[4], right[5], right[6], right[7]};
+    uint32_t cv[8] = {B3_IV0, B3_IV1, B3_IV2, B3_IV3, B3_IV4, B3_IV5, B3_IV6, B3_IV7};
+    b3_compress(cv, m, 0u, 64u, flags);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        left[i] = cv[i];
+}
+
+// the lanes of a wave with `is` put their entry on a list in LDS (all lanes of the wave call it together)
+__device__ __forceinline__ void pw_append(bool is, uint32_t entry, uint32_t* list, uint32_t* cnt, int lane)
+{
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(is);
+    if (mask == 0)
+        return;
+    uint32_t base = 0;
+    if (lane == 0)
+        base = atomicAdd(cnt, (uint32_t)__builtin_popcountll(mask));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (is)
+        list[base + (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull))] = entry;
+}
+
+// small trees: a workgroup owns the ranges whose first leaf slot lies in its window of PW slots (at most PW - 1 + 256 slots, at
+// most PW ranges) and reduces ALL of them, in two stages (shapes: b3s_* above).
+//   tables    one scan over the window's ranges gives each its first leaf slot, first block and first node, 16 bits each
+//   registers thread t takes the window's t-th block (a search of the block table finds its range), loads the block's chaining
+//             values from global memory -- 32 B contiguous bytes, the blocks of a range follow each other -- and merges them in tree
+//             order: every lane has B - 1 compressions, no LDS, no barrier.  A range of one block is finished here (one leaf: no
+//             merge, the leaf's value already carries ROOT); of the others each block's node goes to LDS and the left children of
+//             the first level onto a list
+//   levels    strides of 1, 2, 4 .. blocks: lane i takes the list's i-th merge, and its node goes onto the next level's list if
+//             it is a left child there too, so no level looks at more than the level before it produced.  One barrier per level.
+// LDS: the tables (6 bytes a range) and behind them the nodes (32 bytes each) in one array of b3s_max_bytes, two lists of PW_NODES / 2
+// entries: 36 KiB, and 60 registers, so FOUR workgroups are resident per CU, 32 waves, all a CU holds.  The kernel is bound by the
+// latency of its own chain (five dependent loads before the first compression, then one compression per level with ever fewer
+// lanes), which only other workgroups on the same SIMDs cover: with three per CU it takes 2.03 ms on the 64 GiB tree, with four 1.85.
+__global__ __launch_bounds__(PW_THREADS, PW_WAVES) void k_blake3_parents_window(const uint32_t* __restrict__ leaf_prefix, uint64_t count_bound,
+                                                                         const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ cvs,
+                                                                         const uint32_t* __restrict__ win_first, uint64_t* __restrict__ hashes)
+{
+    __shared__ uint4 s_mem[PW_MEM16]; // the tables, behind them the nodes
+    __shared__ uint32_t s_list[2][PW_NODES / 2 + 1];                   // node | block inside the range << 16 | blocks of the range << 24
+    __shared__ uint32_t s_cnt[PW_LEVELS + 1];
+    __shared__ uint32_t s_wsum[PW_THREADS / 64];
     const uint32_t count = (uint32_t)(n_dev ? (*n_dev < count_bound ? *n_dev : count_bound) : count_bound);
     const uint32_t total = leaf_prefix[count];
     const uint64_t w0 = (uint64_t)blockIdx.x * PW;
     if (w0 >= total)
         return;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
+    const uint32_t tid = threadIdx.x;
+    const int lane = (int)(tid & 63u);
     // first range that starts at or after the window / the next window: noted by the leaf kernel's thread of that slot (a
     // binary search here would be ~40 dependent loads before the workgroup can start)
     const uint32_t c_lo = win_first[blockIdx.x];
@@ -590,83 +663,156 @@ __global__ __launch_bounds__(PW_THREADS) void k_blake3_parents_window(const uint
     if (nch == 0)
         return;
     const uint32_t wbase = leaf_prefix[c_lo];
-    const uint32_t nslots = leaf_prefix[c_hi] - wbase;
-    if (tid == 0)
+    if (nch > (uint32_t)PW || leaf_prefix[c_hi] - wbase > (uint32_t)(PW + PW_MAXN - 1))
+        return; // not a window of ranges of at most 256 leaves: the tables are not made for it
+    if (tid <= PW_LEVELS)
+        s_cnt[tid] = 0;
+    uint16_t* s_leaf = reinterpret_cast<uint16_t*>(s_mem); // of the window's j-th range: first leaf slot, ..
+    uint16_t* s_blk = s_leaf + (nch + 1u);                 // .. first block ..
+    uint16_t* s_node = s_blk + (nch + 1u);                 // .. and first node (j = nch: the totals)
+    uint4* s_cv = s_mem + (6u * (nch + 1u) + 15u) / 16u;
+
+    // tables: thread t has ranges t R .. t R + R - 1; blocks and nodes are summed in one word (blocks < 2^16)
+    constexpr uint32_t R = (PW + PW_THREADS - 1) / PW_THREADS;
     {
-        s_cnt = 0;
-        s_maxn = 0;
-    }
-    {
-        const uint4* g = reinterpret_cast<const uint4*>(cvs) + (uint64_t)wbase * 2u;
-        for (uint32_t v = tid; v < nslots * 2u; v += PW_THREADS)
-            s_cv[v] = g[v];
-    }
-    __syncthreads();
-    if (nch * 8u < nslots)
-    {
-        // few large ranges: a wave per range
-        for (uint32_t j = tid >> 6; j < nch; j += PW_THREADS / 64)
+        const uint32_t j0 = tid * R;
+        uint32_t lp[R + 1], sum = 0;
+#pragma unroll
+        for (uint32_t i = 0; i <= R; ++i)
+            lp[i] = leaf_prefix[c_lo + (j0 + i < nch ? j0 + i : nch)] - wbase;
+#pragma unroll
+        for (uint32_t i = 0; i < R; ++i)
         {
-            const uint32_t p0 = leaf_prefix[c_lo + j], n = leaf_prefix[c_lo + j + 1] - p0;
-            for (uint32_t k = lane; k < n; k += 64)
-                s_info[p0 - wbase + k] = k | (n << 16);
-            if (lane == 0)
-                atomicMax(&s_maxn, n);
+            const uint32_t n = lp[i + 1] - lp[i], nb = b3s_blocks(n, PB); // (0 behind the window's last range)
+            sum += nb | (b3s_to_lds(n, PB) ? nb << 16 : 0u);
+        }
+        uint32_t incl = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1)
+        {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d)
+                incl += up;
+        }
+        if (lane == 63)
+            s_wsum[tid >> 6] = incl;
+        __syncthreads();
+        uint32_t run = incl - sum;
+        for (uint32_t w = 0; w < (tid >> 6); ++w)
+            run += s_wsum[w];
+#pragma unroll
+        for (uint32_t i = 0; i <= R; ++i)
+        {
+            const uint32_t j = j0 + i;
+            if (j <= nch && (i < R || j == nch)) // (the entry behind the last range: by whoever reaches it)
+            {
+                s_leaf[j] = (uint16_t)lp[i];
+                s_blk[j] = (uint16_t)(run & 0xFFFFu);
+                s_node[j] = (uint16_t)(run >> 16);
+            }
+            if (i < R)
+            {
+                const uint32_t n = lp[i + 1] - lp[i], nb = b3s_blocks(n, PB);
+                run += nb | (b3s_to_lds(n, PB) ? nb << 16 : 0u);
+            }
         }
     }
-    else
-    {
-        for (uint32_t j = tid; j < nch; j += PW_THREADS)
-        {
-            const uint32_t p0 = leaf_prefix[c_lo + j], n = leaf_prefix[c_lo + j + 1] - p0;
-            for (uint32_t k = 0; k < n; ++k)
-                s_info[p0 - wbase + k] = k | (n << 16);
-            atomicMax(&s_maxn, n);
-        }
-    }
     __syncthreads();
-    const uint32_t maxn = s_maxn;
+
+    if ((6u * (nch + 1u) + 15u) / 16u + 2u * s_node[nch] > PW_MEM16)
+        return; // (cannot be: b3s_max_bytes)
+
+    // registers
+    const uint32_t nblk = s_blk[nch];
+    const uint4* cvs4 = reinterpret_cast<const uint4*>(cvs) + (uint64_t)wbase * 2u;
+    for (uint32_t b0 = 0; b0 < nblk; b0 += PW_THREADS)
+    {
+        const uint32_t blk = b0 + tid;
+        bool left = false;
+        uint32_t entry = 0;
+        if (blk < nblk)
+        {
+            uint32_t lo = 0, hi = nch; // range j with s_blk[j] <= blk < s_blk[j + 1] (every range has a block)
+            while (hi - lo > 1)
+            {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (s_blk[mid] <= blk)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const uint32_t j = lo, b = blk - s_blk[j];
+            const uint32_t p = s_leaf[j], n = s_leaf[j + 1] - p, nb = b3s_blocks(n, PB);
+            const uint32_t m = b3s_block_leaves(n, b, PB);
+            const uint4* g = cvs4 + (p + b * PB) * 2u;
+            uint32_t cv[PB][8];
+#pragma unroll
+            for (uint32_t i = 0; i < PB; ++i)
+            {
+                const uint32_t ii = i < m ? i : m - 1u; // (a short block reads its last leaf again: no load is conditional)
+                const uint4 x = g[2u * ii], y = g[2u * ii + 1u];
+                cv[i][0] = x.x; cv[i][1] = x.y; cv[i][2] = x.z; cv[i][3] = x.w;
+                cv[i][4] = y.x; cv[i][5] = y.y; cv[i][6] = y.z; cv[i][7] = y.w;
+            }
+#pragma unroll
+            for (uint32_t st = 1; st < PB; st <<= 1)
+            {
+#pragma unroll
+                for (uint32_t k = 0; k + st < PB; k += 2u * st)
+                    if (b3s_reg_merge(m, k, st))
+                        b3_merge_regs(cv[k], cv[k + st], (uint32_t)F_PARENT | (b3s_root(n, b * PB + k, st) ? (uint32_t)F_ROOT : 0u));
+            }
+            if (!b3s_to_lds(n, PB))
+                hashes[c_lo + j] = (uint64_t)cv[0][0] | ((uint64_t)cv[0][1] << 32);
+            else
+            {
+                const uint32_t node = (uint32_t)s_node[j] + b;
+                s_cv[2u * node] = make_uint4(cv[0][0], cv[0][1], cv[0][2], cv[0][3]);
+                s_cv[2u * node + 1u] = make_uint4(cv[0][4], cv[0][5], cv[0][6], cv[0][7]);
+                left = b3s_lds_merge(nb, b, 1u);
+                entry = node | (b << 16) | (nb << 24);
+            }
+        }
+        pw_append(left, entry, s_list[0], &s_cnt[0], lane);
+    }
+
+    // levels
     uint32_t rot = blockIdx.x; // which wave takes the first 64 merges of a level: rotates, or the SIMD of wave 0 does all the thin levels
-    for (uint32_t st = 1; st < maxn; st <<= 1, ++rot)
+    for (uint32_t lvl = 0, st = 1;; ++lvl, st <<= 1, ++rot)
     {
-        for (uint32_t s0 = 0; s0 < nslots; s0 += PW_THREADS)
+        __syncthreads();
+        const uint32_t nm = lvl < PW_LEVELS ? s_cnt[lvl] : 0u;
+        if (nm == 0)
+            break;
+        const uint32_t* cur = s_list[lvl & 1u];
+        uint32_t* nxt = s_list[(lvl + 1u) & 1u];
+        for (uint32_t m0 = 0; m0 < nm; m0 += PW_THREADS)
         {
-            const uint32_t sl = s0 + (uint32_t)tid;
-            const uint32_t info = sl < nslots ? s_info[sl] : 0u;
-            const uint32_t k = info & 0xFFFFu, n = info >> 16;
-            const bool is = (k & ((st << 1) - 1u)) == 0u && k + st < n;
-            const uint64_t mask = __builtin_amdgcn_ballot_w64(is);
-            uint32_t base = 0;
-            if (lane == 0 && mask)
-                base = atomicAdd(&s_cnt, (uint32_t)__builtin_popcountll(mask));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (is)
-                s_list[base + (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull))] = (uint16_t)sl;
+            const uint32_t mi = m0 + (tid + 64u * rot) % (uint32_t)PW_THREADS;
+            bool keep = false;
+            uint32_t entry = 0;
+            if (mi < nm)
+            {
+                entry = cur[mi];
+                const uint32_t node = entry & 0xFFFFu, k = (entry >> 16) & 0xFFu, nb = entry >> 24;
+                const uint4 a0 = s_cv[2u * node], a1 = s_cv[2u * node + 1u];
+                const uint4 b0 = s_cv[2u * (node + st)], b1 = s_cv[2u * (node + st) + 1u];
+                uint32_t m[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+                uint32_t cv[8] = {B3_IV0, B3_IV1, B3_IV2, B3_IV3, B3_IV4, B3_IV5, B3_IV6, B3_IV7};
+                b3_compress(cv, m, 0u, 64u, (uint32_t)F_PARENT | (b3s_lds_root(nb, st) ? (uint32_t)F_ROOT : 0u));
+                s_cv[2u * node] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+                s_cv[2u * node + 1u] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+                keep = b3s_lds_merge(nb, k, 2u * st);
+            }
+            pw_append(keep, entry, nxt, &s_cnt[lvl + 1u], lane);
         }
-        __syncthreads();
-        const uint32_t nm = s_cnt;
-        for (uint32_t mi = ((uint32_t)tid + 64u * rot) & (uint32_t)(PW_THREADS - 1); mi < nm; mi += PW_THREADS)
-        {
-            const uint32_t sl = s_list[mi];
-            const uint32_t n = s_info[sl] >> 16;
-            const uint4 a0 = s_cv[2u * sl], a1 = s_cv[2u * sl + 1u];
-            const uint4 b0 = s_cv[2u * (sl + st)], b1 = s_cv[2u * (sl + st) + 1u];
-            uint32_t m[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            uint32_t cv[8] = {B3_IV0, B3_IV1, B3_IV2, B3_IV3, B3_IV4, B3_IV5, B3_IV6, B3_IV7};
-            b3_compress(cv, m, 0u, 64u, (uint32_t)F_PARENT | ((st << 1) >= n ? (uint32_t)F_ROOT : 0u));
-            s_cv[2u * sl] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-            s_cv[2u * sl + 1u] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
-        }
-        __syncthreads();
-        if (tid == 0)
-            s_cnt = 0;
-        __syncthreads();
     }
     for (uint32_t j = tid; j < nch; j += PW_THREADS)
-    {
-        const uint4 r = s_cv[2u * (leaf_prefix[c_lo + j] - wbase)];
-        hashes[c_lo + j] = (uint64_t)r.x | ((uint64_t)r.y << 32);
-    }
+        if (b3s_to_lds((uint32_t)s_leaf[j + 1] - s_leaf[j], PB))
+        {
+            const uint4 r = s_cv[2u * s_node[j]];
+            hashes[c_lo + j] = (uint64_t)r.x | ((uint64_t)r.y << 32);
+        }
 }
 
 // big trees: one launch per level, one thread per leaf slot
