@@ -1506,8 +1506,8 @@ static int lz4_decompress_parallel(lthip_ctx* ctx, const void* d_src, const std:
         uint32_t h[8] = {0};
         LTHIP_CHECK(ctx, hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-        fprintf(stderr, "lz4 parallel decode: %u blocks, %llu tiles (%u walked again by the link pass), %llu units\n", nb,
-                (unsigned long long)ntiles, h[4], (unsigned long long)nunits);
+        fprintf(stderr, "lz4 parallel decode: %u blocks, %llu tiles (%u walked again by the link pass), %llu units (%u given up to the origin pass)\n", nb,
+                (unsigned long long)ntiles, h[4], (unsigned long long)nunits, h[2]);
         fprintf(stderr, "   link pass: %u Kcycles in all, %u Kcycles walking tiles again (summed over the blocks)\n", h[7], h[6]);
     }
     return 0;
