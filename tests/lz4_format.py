@@ -280,3 +280,52 @@ def window_phases(payload: bytes) -> set:
                     w0 = q
         ip = nxt
     return seen
+
+
+# ---- what an encoder owes -------------------------------------------------------------------------------------------------------------
+
+def lz4_len_bytes(length: int) -> int:
+    """the bytes that follow a nibble for this length (k_lz4.hip's lz4_len_bytes): none below 15, then one per 255 and the rest"""
+    return (length - 15) // 255 + 1 if length >= 15 else 0
+
+
+def encoder_rules(payload: bytes, raw_len: int):
+    """The fields of the payload (loose()) and the list of what it does against the rules an LZ4 ENCODER has to keep (the block format's
+    "end of block restrictions", lz4.c:242-246) -- rules no decoder checks in full: the walk ends "final" at raw_len; 1 <= offset <=
+    min(output position, 65535); every match starts at or before raw_len - MFLIMIT and ends at or before raw_len - LASTLITERALS; after
+    a match the final literals are LASTLITERALS and more; a source below MFLIMIT + 1 bytes is one literal run; a length has exactly the
+    length bytes its value asks for.  -> (fields, [violation, ...]); an empty list is a block every LZ4 decoder has to take."""
+    fields, end = loose(payload)
+    bad = []
+    if end != "final":
+        bad.append(f"the walk ends '{end}', not with a final literal run")
+    matches = 0
+    for k, e in enumerate(fields):
+        if "ll" not in e:
+            continue  # (truncated inside the literal length: reported above)
+        if len(e["lit_len_at"]) != lz4_len_bytes(e["ll"]):
+            bad.append(f"sequence {k}: a literal length of {e['ll']} in {len(e['lit_len_at'])} length bytes")
+        if e["off"] is None:
+            continue
+        matches += 1
+        start = e["op"] + e["ll"]
+        if e["ml"] is None:
+            bad.append(f"sequence {k}: the match length is cut off")
+            continue
+        if len(e["ml_len_at"]) != lz4_len_bytes(e["ml"] - MINMATCH):
+            bad.append(f"sequence {k}: a match length of {e['ml']} in {len(e['ml_len_at'])} length bytes")
+        if not 1 <= e["off"] <= min(start, 65535):
+            bad.append(f"sequence {k}: offset {e['off']} at output position {start}")
+        if start > raw_len - MFLIMIT:
+            bad.append(f"sequence {k}: a match starts at {start}, {raw_len - start} bytes before the end (at least {MFLIMIT})")
+        if start + e["ml"] > raw_len - LASTLITERALS:
+            bad.append(f"sequence {k}: a match ends at {start + e['ml']}, {raw_len - start - e['ml']} bytes before the end (at least {LASTLITERALS})")
+    if end == "final":
+        last = fields[-1]
+        if last["op"] + last["ll"] != raw_len:
+            bad.append(f"the payload describes {last['op'] + last['ll']} bytes, the source has {raw_len}")
+        if matches and last["ll"] < LASTLITERALS:
+            bad.append(f"{last['ll']} final literals after a match (at least {LASTLITERALS})")
+    if raw_len < MFLIMIT + 1 and matches:
+        bad.append(f"a source of {raw_len} bytes with a match (below {MFLIMIT + 1} bytes it is one literal run)")
+    return fields, bad
