@@ -31,6 +31,8 @@ void ltz_model_debug(uint32_t flags) { g_ltz_dbg = flags; }
 static int g_ltz_sub; /* 1: pieces are written as runs of sub-blocks (zb_encode_piece_sub) */
 static uint32_t g_ltz_flags = 0; /* ZbInput.flags of the next encodes (the kernel's default: plain offsets; ZB_F_REPCODES = LTHIP_ZSTD_REP=1) */
 void ltz_model_flags(uint32_t flags) { g_ltz_flags = flags; }
+int g_ltz_fill = 0xA5; /* what the output buffer holds before an encode (both instantiations; the result must not depend on it) */
+void ltz_model_fill(int byte) { g_ltz_fill = byte & 255; }
 static uint16_t g_ltz_last_sub[ZB_MAX_UNITS];
 void ltz_model_sub_blocks(int on) { g_ltz_sub = on; }
 const uint16_t* ltz_model_last_sub(void) { return g_ltz_last_sub; }
@@ -69,7 +71,7 @@ uint32_t ltz_model_encode_block_src(const void* meta, const uint8_t* unit_lits, 
     sc.seqs = (uint64_t*)malloc(sizeof(uint64_t) * ZB_SEQ_MAX);
     sc.sbits = (uint16_t*)malloc(sizeof(uint16_t) * 4 * ZB_SEQ_MAX);
     sc.out = (uint32_t*)malloc(ZB_OUT_BYTES);
-    memset(sc.out, 0xA5, ZB_OUT_BYTES); /* the encoders must not rely on a cleared output (the kernel's work area is reused) */
+    memset(sc.out, g_ltz_fill, ZB_OUT_BYTES); /* the encoders must not rely on a cleared output (the kernel's work area is reused) */
     n = g_ltz_sub ? zb_encode_piece_sub(&in, &sc, sh, 0, g_ltz_last_sub) : zb_encode_block(&in, &sc, sh, 0);
     if (n)
         memcpy(out, sc.out, n);

@@ -146,6 +146,7 @@ static void lane_main(void)
 
 /* zb_encode_piece_sub by 64 lanes: same arguments and result as ltz_model_encode_block_src with the sub-block layout; `sub` receives
  * the directory entries (ZB_MAX_UNITS).  0xFFFFFFFF: the lanes did not keep step (see the header of this file). */
+extern int g_ltz_fill; /* zstd_model.c */
 uint32_t ltz_lanes_encode_piece_sub(const void* meta, const uint8_t* unit_lits, const uint64_t* unit_recs, uint32_t nunits, uint32_t raw_size,
                                     const uint8_t* src, uint32_t flags, uint8_t* out, uint16_t* sub)
 {
@@ -164,7 +165,7 @@ uint32_t ltz_lanes_encode_piece_sub(const void* meta, const uint8_t* unit_lits, 
     sc.seqs = (uint64_t*)malloc(sizeof(uint64_t) * ZB_SEQ_MAX);
     sc.sbits = (uint16_t*)malloc(sizeof(uint16_t) * 4 * ZB_SEQ_MAX);
     sc.out = (uint32_t*)malloc(ZB_OUT_BYTES);
-    memset(sc.out, 0xA5, ZB_OUT_BYTES); /* the encoders must not rely on a cleared output */
+    memset(sc.out, g_ltz_fill, ZB_OUT_BYTES); /* the encoders must not rely on a cleared output (ltz_model_fill) */
     g_sh = (ZbShared*)calloc(1, sizeof(ZbShared));
     g_in = &in;
     g_sc = &sc;

@@ -7,6 +7,7 @@ import torch
 
 from tests._libs import have_ref, ref as get_ref
 from tests.gpu_util import layout, to_device, u32
+from tests.zstd_gpu_util import check_against_model as _check_against_model, model_src as _model_src, zstd_pieces
 
 pytestmark = pytest.mark.gpu
 
@@ -160,55 +161,6 @@ def gpu_zstd(gpu, blocks, quality=0):
     return [host[o : o + int(s)].copy() for o, s in zip(d_offs, sizes)]
 
 
-def zstd_pieces(frame: np.ndarray):
-    """[(type, payload bytes)] per 128 KiB piece of a single-segment frame with an 8-byte content size (the layouts k_zstd.hip
-    writes).  A piece is one block -- or, in frames that end with the "LTP\\2" directory, a run of sub-blocks (one per 4 KiB unit):
-    then type 2 and the payload is the run WITH its block headers, Last_Block cleared (what zb_encode_piece_sub returns)."""
-    assert bytes(frame[:5]) == bytes([0x28, 0xB5, 0x2F, 0xFD, 0xE0])
-    content = int.from_bytes(bytes(frame[5:13]), "little")
-    nunits = (content + 4095) // 4096
-    pos, blocks = 13, []
-    while True:
-        h = int(frame[pos]) | int(frame[pos + 1]) << 8 | int(frame[pos + 2]) << 16
-        last, typ, size = h & 1, (h >> 1) & 3, h >> 3
-        n = 1 if typ == 1 else size
-        blocks.append((typ, pos, 3 + n))
-        pos += 3 + n
-        if last:
-            break
-    tail = bytes(frame[pos:])
-    magic = bytes([0x5D, 0x2A, 0x4D, 0x18])
-    if tail[:4] == magic and tail[8:12] in (b"LTP\x02", b"LTP\x03"):
-        # sub-block frames: skippable frame with the directory, one u16 per unit
-        assert len(tail) == 12 + 2 * nunits and int.from_bytes(tail[4:8], "little") == 4 + 2 * nunits
-        d = np.frombuffer(tail[12:], dtype="<u2")
-        out, k = [], 0
-        for u0 in range(0, nunits, 32):
-            nu = min(32, nunits - u0)
-            if d[u0] >= 0xFFFE:
-                assert (d[u0 : u0 + nu] == d[u0]).all()
-                typ, p0, n = blocks[k]
-                assert typ == (0 if d[u0] == 0xFFFF else 1)
-                out.append((typ, frame[p0 + 3 : p0 + n]))
-                k += 1
-            else:
-                p0 = blocks[k][1]
-                for u in range(nu):
-                    typ, _, n = blocks[k + u]
-                    assert n == 3 + (int(d[u0 + u]) & 0x7FFF) and typ == (0 if d[u0 + u] & 0x8000 else 2)
-                end = blocks[k + nu - 1][1] + blocks[k + nu - 1][2]
-                run = frame[p0:end].copy()
-                run[blocks[k + nu - 1][1] - p0] &= 0xFE
-                out.append((2, run))
-                k += nu
-        assert k == len(blocks)
-        return out
-    # frames of two or more pieces end with the independence marker: a skippable frame (k_zstd.hip z_write_trailer)
-    if tail:
-        assert len(blocks) >= 2 and tail == magic + bytes([4, 0, 0, 0]) + b"LTP\x01"
-    return [(typ, frame[p0 + 3 : p0 + n]) for typ, p0, n in blocks]
-
-
 def test_zstd_frames_decode_with_reference(zgpu, oracle, ref, zmode):
     gpu = zgpu
     blocks = [oracle.synth(n, 40 + n, k) for k in (0, 1, 2, 11, 12, 13) for n in (0, 1, 100, 5000, 131071, 131072, 131073, 400000)]
@@ -236,40 +188,6 @@ def test_zstd_compresses(zgpu, oracle, zmode):
         kinds = [t for t, _ in zstd_pieces(f)]
         assert kinds.count(2) >= len(kinds) // 2
         assert len(f) < len(l)
-
-
-def _model_src(oracle):
-    import ctypes as C
-
-    d = oracle.dll
-    d.ltz_model_encode_block_src.restype = C.c_uint32
-    d.ltz_model_encode_block_src.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    return d
-
-
-def _check_against_model(gpu, d, blocks, frames):
-    """every Compressed_Block of `frames` == the host model run on the GPU match finder's units; Raw where the model says so"""
-    unit0 = 0
-    checked = 0
-    for b, f in zip(blocks, frames):
-        b = np.ascontiguousarray(b)
-        nunits = (len(b) + 4095) // 4096
-        meta, lits, recs = gpu.zstd_debug_units(unit0, nunits)
-        for i, (typ, payload) in enumerate(zstd_pieces(f)):
-            raw = min(131072, len(b) - i * 131072)
-            nu = (raw + 4095) // 4096
-            out = np.zeros(140000, np.uint8)
-            m, l, r = (np.ascontiguousarray(a[i * 32 : i * 32 + nu]) for a in (meta, lits, recs))
-            l[m[:, 0] == 0] = 0x5A  # units without a sequence have no literal buffer: their literals are the source bytes
-            piece = b[i * 131072 : i * 131072 + raw]
-            n = d.ltz_model_encode_block_src(m.ctypes.data, l.ctypes.data, r.ctypes.data, nu, raw, piece.ctypes.data, out.ctypes.data)
-            if typ == 2:
-                assert n == len(payload) and (out[:n] == payload).all()
-                checked += 1
-            elif typ == 0:
-                assert n == 0
-        unit0 += nunits
-    return checked
 
 
 def test_zstd_entropy_stage_is_bit_exact_with_host_model(zgpu, oracle, zmode):

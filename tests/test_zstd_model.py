@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from tests._libs import digest, have_ref, oracle as get_oracle, ref as get_ref
+from tests.zstd_encoder_units import execute_units
+from tests.zstd_gpu_util import model_compress
 
 needs_ref_build = pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built: the test decodes frames the reference encoded")
 
@@ -61,12 +63,7 @@ def layout(request, model):
 
 
 def compress(o, b: np.ndarray) -> np.ndarray:
-    b = np.ascontiguousarray(b, dtype=np.uint8)
-    cap = o.dll.ltz_model_bound(len(b))
-    out = np.zeros(cap + 8, np.uint8)
-    n = C.c_size_t(0)
-    assert o.dll.ltz_model_compress(b.ctypes.data, len(b), out.ctypes.data, cap, C.byref(n)) == 0
-    return out[: n.value].copy()
+    return model_compress(o, b)
 
 
 def roundtrip(o, b: np.ndarray) -> int:
@@ -258,25 +255,20 @@ def test_cooperative_fse_table_builder_equals_serial(model):
 
 def _rep_piece(seed, nunits=8):
     """Sequences whose offsets repeat in every way the format has a code for -- the last, the one before, the third, the last minus
-    one, with and without literals in front -- executed into the raw bytes they describe; per 4 KiB unit as the match finder delivers
-    them (records {literals | match length << 16 | offset << 32}, the unit's literal bytes, meta {nseq, nlit, tail, 0})."""
+    one, with and without literals in front -- executed into the raw bytes they describe (tests/zstd_encoder_units.py:
+    execute_units); per 4 KiB unit as the match finder delivers them (records {literals | match length << 16 | offset << 32}, the
+    unit's literal bytes, meta {nseq, nlit, tail, 0})."""
     rng = np.random.default_rng(seed)
-    raw = np.zeros(nunits * 4096, np.uint8)
-    meta = np.zeros((nunits, 4), np.uint32)
-    lits = np.zeros((nunits, 4096), np.uint8)
-    recs = np.zeros((nunits, 1024), np.uint64)
-    pos = 0
+    units, pos = [], 0
     for u in range(nunits):
-        end, nlit, nseq, hist = (u + 1) * 4096, 0, 0, []
+        end, seqs, hist, pending = (u + 1) * 4096, [], [], b""
         while True:
             lit = int(rng.choice([0, 0, 0, 1, 2, 5, 17]))
             ml = int(rng.integers(3, 40))
-            if pos + lit + ml > end - 8 or nseq == 1024:
+            if pos + lit + ml > end - 8 or len(seqs) == 1024:
                 break
-            raw[pos : pos + lit] = rng.integers(0, 256, lit)
-            lits[u, nlit : nlit + lit] = raw[pos : pos + lit]
+            pending += rng.integers(0, 256, lit).astype(np.uint8).tobytes()
             pos += lit
-            nlit += lit
             pick = int(rng.integers(0, 6))
             off = None
             if hist and pick < 5:
@@ -284,25 +276,17 @@ def _rep_piece(seed, nunits=8):
             if not off or off < 1 or off > pos:
                 off = int(rng.integers(1, pos + 1)) if pos else None
             if off is None:  # nothing to copy from yet: literals only
-                raw[pos : pos + ml] = rng.integers(0, 256, ml)
-                lits[u, nlit : nlit + ml] = raw[pos : pos + ml]
+                pending += rng.integers(0, 256, ml).astype(np.uint8).tobytes()
                 pos += ml
-                nlit += ml
                 continue
-            for k in range(ml):
-                raw[pos + k] = raw[pos + k - off]
+            seqs.append((pending, ml, off))  # the literals in front of this match are all the literal bytes since the last match
+            pending = b""
             pos += ml
-            # the literals in front of this match are all the literal bytes since the last match
-            recs[u, nseq] = (nlit - int(sum(int(r & 0xFFFF) for r in recs[u, :nseq]))) | (ml << 16) | (off << 32)
-            nseq += 1
             hist.append(off)
-        tail = end - pos
-        raw[pos:end] = rng.integers(0, 256, tail)
-        lits[u, nlit : nlit + tail] = raw[pos:end]
-        nlit += tail
+        assert not pending
+        units.append((seqs, rng.integers(0, 256, end - pos).astype(np.uint8).tobytes()))
         pos = end
-        meta[u] = (nseq, nlit, tail, 0)
-    return raw, meta, lits, recs
+    return execute_units(units)
 
 
 @pytest.mark.parametrize("seed", range(6))

@@ -33,6 +33,7 @@ OF_DEFAULT = [1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 
 ML_DEFAULT = [1, 4, 3, 2, 2, 2, 2, 2, 2] + [1] * 37 + [-1] * 7
 LL, OF, ML = 0, 1, 2
 NAMES = ("ll", "of", "ml")
+LIT_COUNTS = (0, 1, 31, 32, 255, 256, 257, 258, 259, 260, 1023, 1024, 4092, 4095, 4096)  # the literal counts the census names (lit_n*)
 DEFAULTS = ((LL_DEFAULT, 6), (OF_DEFAULT, 5), (ML_DEFAULT, 6))
 MAX_LOG = (9, 8, 9)
 MAX_SYM = (35, 31, 52)
@@ -658,7 +659,8 @@ def build(spec):
 # ---- the census -----------------------------------------------------------------------------------------------------------------------
 def census(data: bytes, seq_limit: int | None = None) -> Counter:
     """Counts of the format features in a frame or a concatenation of frames (the keys are listed in FEATURES of
-    tests/zstd_format_frames.py).  Headers of every frame, block, literals and sequences section are read; the sequence bit-streams
+    tests/zstd_format_frames.py; the ones an ENCODER's frames are asked for -- literal counts lit_n*, stream starts and ends mod 4 / 32,
+    where a Raw_Block stands, accuracy logs -- in REACHABLE of tests/test_zstd_encoder_units_cases.py).  Headers of every frame, block, literals and sequences section are read; the sequence bit-streams
     are decoded (tables built, read backwards) for the codes, the offset forms and the positions.  seq_limit: after that many
     sequences of a frame the remaining blocks' bit-streams are not decoded (counted as seq_blocks_skipped) and the features that
     need positions stop for that frame.  Raises FormatError on what it cannot walk."""
@@ -748,6 +750,15 @@ def _census_frame(data, ip, c, seq_limit):
         if bsize > block_max:
             raise FormatError("block above Block_Maximum_Size")
         start = pos
+        c[f"block_start_mod4_{(p - 3 - ip) & 3}"] += 1  # (of the Block_Header, from the frame's first byte)
+        if btype == 0 and bsize:
+            c["raw_block_first" if bi == 0 else "raw_block_last" if last else "raw_block_mid"] += 1
+            if types and types[-1] == "raw":
+                c["raw_block_after_raw_block"] += 1
+            if any(t is not None for t in tables) or huf_age is not None:
+                c["raw_block_after_compressed"] += 1
+        if btype == 2 and types and types[-1] == "raw":
+            c["compressed_after_raw_block"] += 1
         if btype < 2:
             if btype == 0 and bsize == 0:
                 c["raw_block_empty_mid" if not last else "raw_block_empty_last"] += 1
@@ -778,6 +789,8 @@ def _census_frame(data, ip, c, seq_limit):
                 c[f"lit_{'raw' if lmode == 0 else 'rle'}_hdr{lh}"] += 1
                 if nlit in (31, 32, 4095, 4096):
                     c[f"lit_{'raw' if lmode == 0 else 'rle'}_n{nlit}"] += 1
+                if nlit in LIT_COUNTS:
+                    c[f"lit_n{nlit}"] += 1
                 if huf_age is not None:
                     huf_age.add("raw_lits")
             else:
@@ -790,6 +803,9 @@ def _census_frame(data, ip, c, seq_limit):
                 c[f"lit_huf_hdr{lh}"] += 1
                 if nlit in (6, 1023, 1024, 16383, 16384):
                     c[f"lit_huf_{streams}stream_n{nlit}"] += 1
+                if nlit in LIT_COUNTS:
+                    c[f"lit_n{nlit}"] += 1
+                    c[f"lit_huf_n{nlit}"] += 1
                 tree = 0
                 if lmode == 2:
                     c["lit_huf_tree"] += 1
@@ -831,12 +847,20 @@ def _census_frame(data, ip, c, seq_limit):
                         raise FormatError("four streams need six literals")
                     if nlit - 3 * ((nlit + 3) // 4) == 0:
                         c["lit_huf_last_stream_empty"] += 1
+                    seg = (nlit + 3) // 4
+                    c[f"lit_huf_4stream_seg_mod16_{seg & 15}"] += 1  # (a 16-byte literal quad straddles stream ends unless 0)
+                    if nlit - 3 * seg == seg - 3:
+                        c["lit_huf_4stream_last_shortest"] += 1  # n = 4 k + 1: the last stream is three literals short
                 else:
                     sizes = [body]
                 at = lh + tree + (6 if streams == 4 else 0)
                 for s in sizes:  # (the streams are not decoded; a zero last byte is seen without)
                     if s < 1 or blk[at + s - 1] == 0:
                         raise FormatError("a literal stream ends in a zero byte")
+                    # where the stream starts (byte, from the frame's first byte) and where its end mark stands (bit, likewise)
+                    first = p - bsize + at - ip
+                    c[f"lit_stream_start_mod4_{first & 3}"] += 1
+                    c[f"lit_stream_endbit_mod32_{(8 * (first + s - 1) + blk[at + s - 1].bit_length() - 1) & 31}"] += 1
                     at += s
                 c["huf_stream_short"] += sum(1 for s in sizes if s < 8)
                 c["huf_stream_long"] += sum(1 for s in sizes if s >= 64)
@@ -856,6 +880,10 @@ def _census_frame(data, ip, c, seq_limit):
             c[f"nbseq_{form}byte"] += 1
             if nseq in (0, 1, 127, 128, 0x7EFF):
                 c[f"nbseq_{nseq}"] += 1
+            if nseq in (255, 256, 1023, 1024):
+                c[f"nbseq_{nseq}"] += 1
+            if nseq == 0 and lmode >= 2:
+                c["huf_block_without_sequences"] += 1
             if nseq >= 0x7F00:
                 c["nbseq_ge_0x7F00"] += 1
             if nseq == 0:
@@ -874,6 +902,8 @@ def _census_frame(data, ip, c, seq_limit):
                     m = (modes >> (6 - 2 * t)) & 3
                     c[f"{NAMES[t]}_{MODES[m]}"] += 1
                     if m == 0:
+                        if tables[t] is not None and tables[t].source == "predefined":
+                            c["predefined_again"] += 1
                         tables[t] = default_table(t)
                     elif m == 1:
                         if blk[q] > MAX_SYM[t]:
@@ -884,6 +914,11 @@ def _census_frame(data, ip, c, seq_limit):
                         norm, log, used = read_ncount(blk[q:], MAX_SYM[t], MAX_LOG[t])
                         tables[t] = FseTable(norm, log)
                         q += used
+                        c[f"{NAMES[t]}_fse_log_{log}"] += 1
+                        if sum(1 for x in norm if x == -1) >= 2:
+                            c[f"{NAMES[t]}_fse_several_low_probability"] += 1
+                        if sum(1 for x in norm if x == 1) >= 2:
+                            c[f"{NAMES[t]}_fse_several_count_1"] += 1
                     else:
                         if tables[t] is None:
                             raise FormatError("Repeat_Mode without a table")
@@ -897,6 +932,10 @@ def _census_frame(data, ip, c, seq_limit):
                     table_age[t] = set()
                 if q >= bsize:
                     raise FormatError("no sequence bit-stream")
+                if blk[bsize - 1]:
+                    first = p - bsize + q - ip
+                    c[f"seq_stream_start_mod4_{first & 3}"] += 1
+                    c[f"seq_stream_endbit_mod32_{(8 * (p - 1 - ip) + blk[bsize - 1].bit_length() - 1) & 31}"] += 1
                 if any(s > 23 for s in tables[OF].symbols()):
                     c["of_table_holds_codes_above_23"] += 1
                 if seq_limit is not None and nseq_frame >= seq_limit:
