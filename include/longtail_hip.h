@@ -426,7 +426,7 @@ LTHIP_EXPORT int lthip_zstd_decompress_blocks(lthip_ctx* ctx, const void* d_src,
  * other encoders' frames that were listed for the block-parallel decoder, out[2] payloads a lane-parallel decoder gave back to the
  * serial one, out[3] where the first of those was sent back (a source line of k_zstd.hip).  Waits for the context's stream. */
 LTHIP_EXPORT int lthip_zstd_last_decode_stats(lthip_ctx* ctx, uint32_t out[4]);
-/* Tests only: the library caches its environment switches (LTHIP_ZSTD_DBG, LTHIP_LZ4_SERIAL_DECODER, LTHIP_LZ4_SHARED, ...) per process; after
+/* Tests only: the library caches its environment switches (LTHIP_ZSTD_DBG, LTHIP_LZ4_SERIAL_DECODER, LTHIP_LZ4_DBG, ...) per process; after
  * this call they are read again, so that one process can run a path and its ablation. */
 LTHIP_EXPORT void lthip_debug_reload_env(void);
 /* Tests only, ABLATION build only (the product library answers ENOTSUP / -1 and has no counter in its allocation path): make the

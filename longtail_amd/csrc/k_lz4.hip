@@ -11,9 +11,10 @@
 //                      1. classification, batch geometry (8 units / 32 KiB, 1280-entry tables, 24 waves per CU): four probe
 //                         batches of 64 positions decide whether the group holds redundancy.  If not -- incompressible
 //                         data -- the same workgroup skims it (probe stride grows with the misses, lz4.c:1044-1053; units
-//                         without a match put their bytes where an all-literal block wants them); if so the 16-unit group is
-//                         put on a list and left alone.
-//                      2. lane parser (16 units / 64 KiB, 2560-entry tables, one persistent workgroup per CU) over the list:
+//                         without a match put their bytes where an all-literal block wants them); if so the half is noted
+//                         in its 16-unit group's word and left alone.
+//                      2. lane parser (16 units / 64 KiB, 1536-entry private tables and the group's shared one, one persistent
+//                         workgroup per CU) over the noted halves, two to an item:
 //                         every LANE owns a 64-byte sub-unit and runs the reference's greedy loop on it (probe; on a hit extend
 //                         forwards 36 bytes on its own -- longer ones with the whole wave -- and 8 backwards, record, jump;
 //                         else step 1 + misses / 4): 64 parsers in lock step, no selection among hits.  History enters the
@@ -21,7 +22,7 @@
 //                         sub-units in reverse so that the lowest position survives a write conflict; matches may cross
 //                         sub-units, what they cover is dropped from the later lanes' records (prefix maximum); three wave
 //                         scans place the sequences and every lane writes its own bytes.
-//                    LTHIP_LZ4_PARSER=batch keeps the round-1 batch parser for everything (64 consecutive positions per step,
+//                    Unit sizes other than 4 KiB keep the round-1 batch parser for everything (64 consecutive positions per step,
 //                    scalar selection among the hits).  Sequences go to a per-unit stream.
 //   K6 lz4_stitch    per block: three wave scans over the units' results (literal carry, output position, run count) turn
 //                    trailing literals of one unit into leading literals of the next sequence and assign exact output offsets,
@@ -99,7 +100,7 @@ __device__ __forceinline__ uint32_t lds_read32(const uint32_t* sdata, uint32_t b
     return __builtin_amdgcn_alignbyte(sdata[w + 1], sdata[w], byte_idx & 3u);
 }
 
-// PADDED window (the second formulation of the lane parser, PV 2).  Lanes own consecutive 64-byte sub-units, so whatever the lanes of a
+// PADDED window (the lane parser's).  Lanes own consecutive 64-byte sub-units, so whatever the lanes of a
 // wave read "at their own position" lies 16 dwords apart: two of the 32 LDS banks serve a 32-lane group, a 16-way conflict on every
 // such read while the lanes run in phase (any data made of aligned structures; SQ_LDS_BANK_CONFLICT was 62 % of the LDS-array cycles on
 // "tokens", and half of that went away with an odd sub-unit pitch -- which costs ratio and lanes).  Here the window keeps its 64-byte
@@ -109,47 +110,41 @@ __device__ __forceinline__ uint32_t lds_read32(const uint32_t* sdata, uint32_t b
 // contiguous in LDS: one address computation (x + 12 (x >> 7): two instructions) and ds_read2_b32 with constant offsets, no matter
 // where the row ends.
 constexpr uint32_t LZ4_ROW_DUP = 3; // repeated dwords per 32-dword row
-template <bool PAD>
+// the place of window dword D
 __device__ __forceinline__ uint32_t lds_pidx(uint32_t D)
 {
-    return PAD ? D + LZ4_ROW_DUP * (D >> 5) : D;
+    return D + LZ4_ROW_DUP * (D >> 5);
 }
 // the dword that holds window byte x, as a pointer: x + 12 (x >> 7) in bytes -- a shift and one v_mad_u32_u24 (a 32-bit multiply is
 // a quarter-rate instruction), the runs then use the LDS instructions' immediate offsets
-template <bool PAD>
-__device__ __forceinline__ const uint32_t* lds_ptr(const uint32_t* sdata, uint32_t x)
+__device__ __forceinline__ const uint32_t* lds_ptr(uint32_t x)
 {
     const uint32_t xa = x & ~3u;
-    const uint32_t a = PAD ? __umul24(xa >> 7, 4u * LZ4_ROW_DUP) + xa : xa;
-    if constexpr (PAD)
-    {
-        // The padded window is the lane parser's, and there it is the kernel's dynamic LDS, which starts at LDS address 0 (k_lz4_lanes2
-        // has no static LDS and checks this once): the byte offset IS the address.  Through `sdata` the compiler adds the window's base
-        // to every address -- a constant it learns too late to fold --, one more vector instruction per address in a kernel that is
-        // bound by their number.
-        typedef __attribute__((address_space(3))) const uint32_t* lds_cptr_t;
-        return (const uint32_t*)(lds_cptr_t)(uintptr_t)a;
-    }
-    return reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(sdata) + a);
+    const uint32_t a = __umul24(xa >> 7, 4u * LZ4_ROW_DUP) + xa;
+    // The padded window is the lane parser's, and there it is the kernel's dynamic LDS, which starts at LDS address 0 (k_lz4_lanes2
+    // has no static LDS and checks this once): the byte offset IS the address.  Through the window's pointer the compiler adds its base
+    // to every address -- a constant it learns too late to fold --, one more vector instruction per address in a kernel that is
+    // bound by their number.
+    typedef __attribute__((address_space(3))) const uint32_t* lds_cptr_t;
+    return (const uint32_t*)(lds_cptr_t)(uintptr_t)a;
 }
-// (what lds_ptr<true> relies on; a kernel with a padded window calls this first)
+// (what lds_ptr relies on; a kernel with a padded window calls this first)
 __device__ __forceinline__ void lds_window_must_start_at_zero(const uint32_t* sdata)
 {
     typedef __attribute__((address_space(3))) const uint32_t* lds_cptr_t;
     if ((uint32_t)(uintptr_t)(lds_cptr_t)sdata != 0u)
         __builtin_trap();
 }
-template <bool PAD>
-__device__ __forceinline__ uint32_t lds_dw(const uint32_t* sdata, uint32_t D)
+__device__ __forceinline__ uint32_t lds_dw(uint32_t D)
 {
-    return *lds_ptr<PAD>(sdata, D << 2);
+    return *lds_ptr(D << 2);
 }
 // N <= 4 consecutive dwords of the window from dword D
-template <bool PAD, int N>
-__device__ __forceinline__ void lds_run(const uint32_t* sdata, uint32_t D, uint32_t* out)
+template <int N>
+__device__ __forceinline__ void lds_run(uint32_t D, uint32_t* out)
 {
     static_assert(N >= 1 && N <= 1 + (int)LZ4_ROW_DUP, "a run is contiguous up to 1 + LZ4_ROW_DUP dwords");
-    const uint32_t* q = lds_ptr<PAD>(sdata, D << 2);
+    const uint32_t* q = lds_ptr(D << 2);
 #pragma unroll
     for (int k = 0; k < N; ++k)
         out[k] = q[k];
@@ -170,7 +165,7 @@ __device__ __forceinline__ uint32_t lds_read32x(const uint32_t* sdata, uint32_t 
     if constexpr (!PAD)
         return lds_read32(sdata, byte_idx);
     uint32_t d[2];
-    lds_run<true, 2>(sdata, byte_idx >> 2, d);
+    lds_run<2>(byte_idx >> 2, d);
     return __builtin_amdgcn_alignbyte(d[1], d[0], byte_idx); // (v_alignbyte_b32 shifts by the selector's two low bits: no mask)
 }
 // bytes of LDS a window of n data bytes occupies
@@ -201,8 +196,8 @@ __device__ __forceinline__ void wave_copy_lds_to_global(uint8_t* __restrict__ ds
         {
             const uint32_t w = b >> 2, sh = b & 3u;
             uint32_t d[4];
-            lds_run<true, 4>(sdata, w, d);
-            const uint32_t d4 = lds_dw<true>(sdata, w + 4u);
+            lds_run<4>(w, d);
+            const uint32_t d4 = lds_dw(w + 4u);
             o.x = __builtin_amdgcn_alignbyte(d[1], d[0], sh);
             o.y = __builtin_amdgcn_alignbyte(d[2], d[1], sh);
             o.z = __builtin_amdgcn_alignbyte(d[3], d[2], sh);
@@ -220,14 +215,6 @@ __device__ __forceinline__ void wave_copy_lds_to_global(uint8_t* __restrict__ ds
     const uint32_t done = nvec << 4;
     if ((uint32_t)lane < n - done)
         dst[done + (uint32_t)lane] = (uint8_t)lds_byte<PAD>(sdata, sbyte + done + (uint32_t)lane);
-}
-
-// wave-cooperative emission of a length (already reduced by 15) as 255,255,...,rem
-__device__ __forceinline__ void emit_len(uint8_t* out, uint32_t len, int lane)
-{
-    const uint32_t n = len / 255u + 1u;
-    for (uint32_t j = lane; j < n; j += 64)
-        out[j] = j + 1 == n ? (uint8_t)(len % 255u) : (uint8_t)255;
 }
 
 // Parser state shared by the cooperative and the lane-parallel paths (all wave-uniform).
@@ -371,17 +358,16 @@ __device__ __forceinline__ void lz4_coop_sequence(const uint8_t* __restrict__ sb
 // the history lazily: every wave first parses PROBE batches with an empty table; if any wave of the group finds a
 // match the data is taken to be compressible and each wave inserts the positions before its unit (newer entries
 // kept), otherwise (incompressible data) nobody pays for it.  24 waves per CU instead of 4 at the same window.
-constexpr int LZ4_G_BATCH = 8;   // MODE 0 (batch parser): 8 x 4 KiB units per 32 KiB window group
-constexpr int LZ4_G_LANES = 16;  // MODE 1 (lane parser): 16 x 4 KiB units per 64 KiB window group, one workgroup per CU
+constexpr int LZ4_G_BATCH = 8;   // batch parser: 8 x 4 KiB units per 32 KiB window group
+constexpr int LZ4_G_LANES = 16;  // lane parser: 16 x 4 KiB units per 64 KiB window group, one workgroup per CU
 constexpr int LZ4_PROBE_BATCHES = 4;
 constexpr uint32_t LZ4_Z_CHAIN = LTHIP_ZSTD_CHAIN;
 constexpr uint32_t Z_PIECE = 128u << 10; // zstd Block_Maximum_Size (ZB_BLOCK_MAX of zstd_block_core.h, asserted in k_zstd.hip)
-// table entries per wave.  MODE 0: 32 KiB window + 8 x 2.5 KiB tables = 52 KiB: THREE workgroups (24 waves) per CU.
-// MODE 1: 64 KiB window + 16 x 5 KiB tables = 144 KiB: one workgroup of 16 waves per CU (the lane parser is not issue bound, it
-// wants history: tools/lz4_lane_model.c -- mixed 1.72 at 8 x 1280, 1.85 at 16 x 2048, 1.89 at 16 x 2560; reference 1.92)
+// table entries per wave.  Batch parser: 32 KiB window + 8 x 2.5 KiB tables = 52 KiB: THREE workgroups (24 waves) per CU.
+// Lane parser: one workgroup of 16 waves per CU (it is not issue bound, it wants history: tools/lz4_lane_model.c -- mixed 1.72 at
+// 8 x 1280 private entries, 1.85 at 16 x 2048, 1.89 at 16 x 2560; reference 1.92 -- and takes it from the group's shared table)
 constexpr int LZ4_TAB_LZ4 = 1024 + 256;
 constexpr int LZ4_TAB_ZSTD = 1024 + 256;
-[[maybe_unused]] constexpr int LZ4_TAB_LANES = 2560; // (round 2's lane kernel: ablations/)
 constexpr int LZ4_TAB_SHARED = 1536, LZ4_SH_LOG2 = 13; // lane parser with the group's shared table: 64 + 48 + 32 KiB of LDS
 
 #include "lz4/lz4_lane_parse.inc"
@@ -439,9 +425,6 @@ static int upload_blocks(lthip_ctx* ctx, uint32_t block_count, const uint64_t* s
     return 0;
 }
 
-// The parser of the match finder: "lanes" (default, MODE 1: 16 x 4 KiB units share a 64 KiB window, every lane parses its own
-// 64-byte sub-unit; 144 KiB of LDS, one workgroup of 16 waves per CU) or "batch" (LTHIP_LZ4_PARSER=batch, MODE 0: the round-1
-// parser, 8 x 4 KiB units per 32 KiB window, 52 KiB of LDS, 24 waves per CU).
 #ifdef LTHIP_K5_PROF
 extern "C" __attribute__((visibility("default"))) int lthip_k5_prof_dump(int reset)
 {
@@ -464,24 +447,10 @@ extern "C" __attribute__((visibility("default"))) int lthip_k5_prof_dump(int res
 }
 #endif
 
-static bool lz4_lane_parser()
-{
-#ifdef LTHIP_ABLATIONS
-    static const bool v = [] {
-        const char* e = getenv("LTHIP_LZ4_PARSER"); // "batch": the round-1 batch parser for everything
-        return !(e && strcmp(e, "batch") == 0);
-    }();
-    return v;
-#else
-    return true;
-#endif
-}
-
 // the batch parser's geometry: classification pass (CLS 1) or the parser for everything (CLS 0)
 template <int FMT, int CLS>
 static int launch_segments(lthip_ctx* ctx, uint32_t groups, uint32_t SEG, const void* d_src, const Lz4Block* d_blocks, uint32_t block_count,
-                           uint32_t g0, uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg, uint32_t ngroups,
-                           uint32_t* worklist)
+                           uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg, uint32_t ngroups, uint32_t* worklist)
 {
     constexpr int TAB = FMT == 1 ? LZ4_TAB_ZSTD : LZ4_TAB_LZ4;
     const size_t lds = (size_t)lz4_window_lds_bytes(LZ4_G_BATCH * SEG + 64u, false) + 16 + (size_t)LZ4_G_BATCH * TAB * 2;
@@ -492,111 +461,37 @@ static int launch_segments(lthip_ctx* ctx, uint32_t groups, uint32_t SEG, const 
         ctx->k5_lds_enabled[FMT][CLS] = true;
     }
     hipLaunchKernelGGL((k_lz4_segments<LZ4_G_BATCH, TAB, FMT, CLS>), dim3(groups), dim3(64 * LZ4_G_BATCH), lds, ctx->stream, (const uint8_t*)d_src,
-                       d_blocks, block_count, g0, SEG, streams, meta, zrecs, spec_dst, dbg, nullptr, ngroups, worklist);
+                       d_blocks, block_count, 0u, SEG, streams, meta, zrecs, spec_dst, dbg, nullptr, ngroups, worklist);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }
-
-#ifdef LTHIP_ABLATIONS
-// the lane parser inside the segments kernel (rounds 2-4: ablations/k_lz4_segments_modes.inc), persistent, one workgroup per CU
-template <int TAB, int FMT, int SH = 0, int PV = 0>
-static int launch_segments_lane_mode(lthip_ctx* ctx, uint32_t groups, uint32_t SEG, const void* d_src, const Lz4Block* d_blocks, uint32_t block_count,
-                                     uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg, uint64_t* lane_recs,
-                                     uint32_t ngroups, uint32_t* worklist)
-{
-    constexpr int G = LZ4_G_LANES;
-    const size_t lds = (size_t)lz4_window_lds_bytes(G * SEG + 64u + (PV == 2 ? LZ4_LPAD : 0u), PV == 2) + 16 + (size_t)G * TAB * 2 + (SH ? (size_t)4 << SH : 0);
-    static bool granted[64] = {}; // per device and instance: more than 64 KiB of dynamic LDS has to be granted explicitly
-    if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device])
-    {
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lz4_segments_modes<G, TAB, FMT, 1, 0, SH, PV>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (ctx->device >= 0 && ctx->device < 64)
-            granted[ctx->device] = true;
-    }
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const uint32_t grid = groups < (uint32_t)ncu ? groups : (uint32_t)ncu;
-    hipLaunchKernelGGL((k_lz4_segments_modes<G, TAB, FMT, 1, 0, SH, PV>), dim3(grid), dim3(64 * G), lds, ctx->stream, (const uint8_t*)d_src, d_blocks,
-                       block_count, 0u, SEG, streams, meta, zrecs, spec_dst, dbg, lane_recs, ngroups, worklist);
-    LTHIP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-#endif
 
 // The match finder of one batch (FMT 0: LZ4 streams, FMT 1: zstd sequences), two passes: the batch parser's geometry (8 units per group,
 // 24 waves per CU) classifies every 32 KiB half-group with its four probe batches and skims the ones without redundancy on the spot
-// (incompressible data never sees the slower one-workgroup-per-CU geometry); the 16-unit groups that hold redundancy are listed, the
-// list becomes items of two half-groups (k_lz4_pair_halves), and the lane kernel (k_lz4_lanes2) is persistent over the items.
+// (incompressible data never sees the slower one-workgroup-per-CU geometry); the halves that hold redundancy are noted, a bit each in
+// their 16-unit group's word, the words become items of two half-groups (k_lz4_pair_halves), and the lane kernel (k_lz4_lanes2) is
+// persistent over the items.
 // `lanes` false (unit sizes other than 4 KiB): the batch parser for everything.
 template <int FMT>
 static int launch_match_finder(lthip_ctx* ctx, bool lanes, uint32_t SEG, const void* d_src, const Lz4Block* d_blocks, uint32_t block_count,
-                               uint32_t g0, uint32_t g1, uint64_t ngrp, uint64_t ncgrp, uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs,
-                               uint8_t* spec_dst, uint32_t dbg, [[maybe_unused]] uint64_t* lane_recs)
+                               uint64_t ngrp, uint64_t ncgrp, uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg)
 {
     if (!lanes)
-        return launch_segments<FMT, 0>(ctx, g1 - g0, SEG, d_src, d_blocks, block_count, g0, streams, meta, zrecs, spec_dst, dbg, 0, nullptr);
-#ifdef LTHIP_ABLATIONS
-    // LTHIP_LZ4_SHARED=0: round 2/3a's history (prefix maximum over the waves' 2560-entry tables) instead of the shared table
-    LTHIP_ABLATION_ENV(env_shared, "LTHIP_LZ4_SHARED");
-    const bool shared = env_shared.get() != 0;
-    LTHIP_ABLATION_ENV(env_pv, "LTHIP_LZ4_PV"); // 0: the round-3 formulation of the lane parse (lz4_lane_parse), default: the round-4 one
-    const bool pv2 = shared && env_pv.get() != 0;
-    if (dbg & 16384u) // the lane kernel alone, with its own probe
-        return pv2      ? launch_segments_lane_mode<LZ4_TAB_SHARED, FMT, LZ4_SH_LOG2, 2>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs,
-                                                                                        spec_dst, dbg, lane_recs, (uint32_t)ngrp, nullptr)
-               : shared ? launch_segments_lane_mode<LZ4_TAB_SHARED, FMT, LZ4_SH_LOG2>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs,
-                                                                                     spec_dst, dbg, lane_recs, (uint32_t)ngrp, nullptr)
-                        : launch_segments_lane_mode<LZ4_TAB_LANES, FMT>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst,
-                                                                        dbg, lane_recs, (uint32_t)ngrp, nullptr);
-#endif
+        return launch_segments<FMT, 0>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst, dbg, 0, nullptr);
     void* wl;
     int err = lthip_scratch(ctx, S_LZ4_CLASSIFY, 4 * (11 * (size_t)ngrp + 16), &wl);
     if (err)
         return err;
     LTHIP_CHECK(ctx, hipMemsetAsync(wl, 0, 4 * (2 * (size_t)ngrp + 4), ctx->stream));
-    if ((err = launch_segments<FMT, 1>(ctx, (uint32_t)ncgrp, SEG, d_src, d_blocks, block_count, 0, streams, meta, zrecs, spec_dst, dbg, (uint32_t)ngrp,
+    if ((err = launch_segments<FMT, 1>(ctx, (uint32_t)ncgrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst, dbg, (uint32_t)ngrp,
                                        (uint32_t*)wl)))
         return err;
-#ifdef LTHIP_ABLATIONS
-    LTHIP_ABLATION_ENV(env_halves, "LTHIP_LZ4_HALVES"); // 0: whole groups as the unit of work (a group's incompressible half idles eight waves)
-    if (!pv2 || env_halves.get() == 0)
-        return pv2      ? launch_segments_lane_mode<LZ4_TAB_SHARED, FMT, LZ4_SH_LOG2, 2>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs,
-                                                                                        spec_dst, dbg, lane_recs, (uint32_t)ngrp, (uint32_t*)wl)
-               : shared ? launch_segments_lane_mode<LZ4_TAB_SHARED, FMT, LZ4_SH_LOG2>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs,
-                                                                                     spec_dst, dbg, lane_recs, (uint32_t)ngrp, (uint32_t*)wl)
-                        : launch_segments_lane_mode<LZ4_TAB_LANES, FMT>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst,
-                                                                        dbg, lane_recs, (uint32_t)ngrp, (uint32_t*)wl);
-#endif
-    // the list of groups -> items of two half-groups (k_lz4_pair_halves), then the lane kernel over the items
+    // the groups' half bits -> items of two half-groups (k_lz4_pair_halves), then the lane kernel over the items
     const uint32_t nthreads = 256, ng = (uint32_t)ngrp;
     // history halves: the zstd flavour at its "high" and "max" settings
-    uint32_t hist = (FMT == 1 && (dbg & LZ4_DBG_Q_MAX)) ? 3u : (FMT == 1 && (dbg & LZ4_DBG_Q_HIGH)) ? 1u : 0u;
+    const uint32_t hist = (FMT == 1 && (dbg & LZ4_DBG_Q_MAX)) ? 3u : (FMT == 1 && (dbg & LZ4_DBG_Q_HIGH)) ? 1u : 0u;
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    LTHIP_ABLATION_ENV(env_far, "LTHIP_LZ4_FAR");
-    const uint32_t farlog = env_far.get() >= 0 ? (uint32_t)env_far.get() : (10u | (12u << 8) | (8u << 16));
-#ifdef LTHIP_ABLATIONS
-    LTHIP_ABLATION_ENV(env_split, "LTHIP_LZ4_SPLITWG"); // experiment (round 5): half-items on two 8-wave workgroups per CU
-    if (env_split.get() > 0 && hist == 0u)
-    {
-        hist = 2u;
-        hipLaunchKernelGGL(k_lz4_pair_halves, dim3((ng + nthreads - 1) / nthreads), dim3(nthreads), 0, ctx->stream, (uint32_t*)wl, ng, 0u, d_blocks, block_count, hist);
-        hipLaunchKernelGGL(k_lz4_pair_halves, dim3((2u * ng + nthreads) / nthreads), dim3(nthreads), 0, ctx->stream, (uint32_t*)wl, ng, 1u, d_blocks, block_count, hist);
-        LTHIP_LAUNCH_CHECK(ctx);
-        const size_t lds8 = (size_t)lz4_window_lds_bytes(8u * SEG + 64u + LZ4_LPAD + 32u, true) + 16 + (size_t)8 * LZ4_TAB_SHARED * 2 + ((size_t)2 << LZ4_SH_LOG2);
-        static bool granted8[2] = {false, false};
-        if (!granted8[FMT])
-        {
-            LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lz4_lanes2<FMT, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            granted8[FMT] = true;
-        }
-        hipLaunchKernelGGL((k_lz4_lanes2<FMT, 8>), dim3(2u * (uint32_t)ncu), dim3(64 * 8), lds8, ctx->stream, (const uint8_t*)d_src, d_blocks, block_count, SEG,
-                           streams, meta, zrecs, spec_dst, dbg, ng, (uint32_t*)wl, farlog);
-        LTHIP_LAUNCH_CHECK(ctx);
-        return 0;
-    }
-#endif
     hipLaunchKernelGGL(k_lz4_pair_halves, dim3((ng + nthreads - 1) / nthreads), dim3(nthreads), 0, ctx->stream, (uint32_t*)wl, ng, 0u, d_blocks, block_count, hist);
     hipLaunchKernelGGL(k_lz4_pair_halves, dim3((ng / 2 + nthreads) / nthreads), dim3(nthreads), 0, ctx->stream, (uint32_t*)wl, ng, 1u, d_blocks, block_count, hist);
     LTHIP_LAUNCH_CHECK(ctx);
@@ -607,12 +502,26 @@ static int launch_match_finder(lthip_ctx* ctx, bool lanes, uint32_t SEG, const v
         LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lz4_lanes2<FMT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ctx->k5h_lds_enabled[FMT] = true;
     }
-    // zstd flavour (farlog above): a match must be one byte longer from 2^a bytes away and two from 2^b, and c bytes long when it reaches
-    // into a history half (a + 256 b + 65536 c = 10, 12, 8; a = b = 31 and c = 4: no rule; the ablation build reads LTHIP_LZ4_FAR)
+    // zstd flavour: a match must be one byte longer from 2^a bytes away and two from 2^b, and c bytes long when it reaches into a history
+    // half (a + 256 b + 65536 c = 10, 12, 8; a = b = 31 and c = 4: no rule; the ablation build reads LTHIP_LZ4_FAR)
+    LTHIP_ABLATION_ENV(env_far, "LTHIP_LZ4_FAR");
+    const uint32_t farlog = env_far.get() >= 0 ? (uint32_t)env_far.get() : (10u | (12u << 8) | (8u << 16));
     hipLaunchKernelGGL((k_lz4_lanes2<FMT>), dim3((uint32_t)ncu), dim3(64 * LZ4_G_LANES), lds, ctx->stream, (const uint8_t*)d_src, d_blocks,
                        block_count, SEG, streams, meta, zrecs, spec_dst, dbg, ng, (uint32_t*)wl, farlog);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
+}
+
+// LTHIP_LZ4_DBG (ablation build; 0 in the product): bits that switch parts of the match finder off or over.
+//    0  no pre-seed of the private tables          1  no in-batch candidates          2  every hit handled cooperatively
+//    3  no twin probe                              4  no stride jump after a group's probe batches missed
+//    6  no speculative placement of units without a match
+//   26  the shared table's group tag runs out every third group (tests)
+// Bits 15 and 31 are not settings: lthip_launch_lz_sequences puts the zstd quality there (LZ4_DBG_Q_HIGH, LZ4_DBG_Q_MAX).  No other bit is read.
+static uint32_t lz4_dbg()
+{
+    LTHIP_ABLATION_ENV(env_dbg, "LTHIP_LZ4_DBG");
+    return env_dbg.get() > 0 ? (uint32_t)env_dbg.get() : 0u;
 }
 
 static int lz4_compress_batch(lthip_ctx* ctx, const void* d_src, uint32_t block_count, const uint64_t* src_offsets,
@@ -686,16 +595,14 @@ static int lz4_compress_batch(lthip_ctx* ctx, const void* d_src, uint32_t block_
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     Lz4Block* d_blocks = nullptr;
     uint64_t nseg64 = 0, ngrp64 = 0;
-    const bool lanes = lz4_lane_parser() && SEG == 4096u; // other unit sizes (tests, ablations) keep the batch parser's geometry
+    const bool lanes = SEG == 4096u; // other unit sizes (tests, ablations) keep the batch parser's geometry
     const uint32_t GU = lanes ? LZ4_G_LANES : LZ4_G_BATCH;
     uint64_t ncgrp64 = 0;
     int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, GU, &d_blocks, &nseg64, &ngrp64, &ncgrp64);
     if (err)
         return err;
-    const uint32_t nseg = (uint32_t)nseg64;
-    void *meta, *plan, *bout, *streams, *runs, *lrecs = nullptr;
-    if (lanes && (err = lthip_scratch(ctx, S_LZ4_LANE_RECS, (size_t)64 * LZ4_LANE_MAXREC * 8 * ((size_t)nseg + 1), &lrecs)))
-        return err;
+    const uint32_t nseg = (uint32_t)nseg64, ngrp = (uint32_t)ngrp64;
+    void *meta, *plan, *bout, *streams, *runs, *worklist;
     if ((err = lthip_scratch(ctx, S_TABLES2, 4 * ((size_t)nseg + block_count + 1), &runs)))
         return err;
     if ((err = lthip_scratch(ctx, S_LZ4_META, sizeof(Lz4Meta) * ((size_t)nseg + 1), &meta)))
@@ -706,35 +613,9 @@ static int lz4_compress_batch(lthip_ctx* ctx, const void* d_src, uint32_t block_
         return err;
     if ((err = lthip_scratch(ctx, S_LZ4_STREAM, (size_t)lz4_stream_stride(SEG) * ((size_t)nseg + 1), &streams)))
         return err;
-    // Optional (LTHIP_LZ4_DBG bit 5): the match finder is latency / LDS bound, the stitch copy HBM bound, so the batch can
-    // be cut into up to four slices by bytes with slice i's stitch on the context's second stream while slice i+1 is
-    // parsed on the main one.  MEASURED SLOWER on MI355X (64 GiB random: 151.6 vs 137.6 ms per step: the copy's traffic
-    // lengthens every probe's LDS-fill latency and both kernels lose more than the overlap wins), hence off by default.
-    LTHIP_ABLATION_ENV(env_dbg, "LTHIP_LZ4_DBG"); // (ablation build: bits that switch parts of the match finder off or over; 0 in the product)
-    const uint32_t dbg = env_dbg.get() > 0 ? (uint32_t)env_dbg.get() : 0u;
-    uint64_t total_bytes = 0;
-    for (uint32_t b = 0; b < block_count; ++b)
-        total_bytes += src_sizes[b];
-    const uint32_t want = (!(dbg & 32u) || lanes) ? 1u : (total_bytes >= (1ull << 30) ? 4u : (total_bytes >= (256ull << 20) ? 2u : 1u));
-    std::vector<uint32_t> cut{0};
-    {
-        uint64_t acc = 0;
-        for (uint32_t b = 0; b < block_count; ++b)
-        {
-            acc += src_sizes[b];
-            if (cut.size() < want && acc * want >= total_bytes * cut.size() && b + 1 < block_count)
-                cut.push_back(b + 1);
-        }
-        cut.push_back(block_count);
-    }
-    // per-block first segment / group (same arithmetic as upload_blocks)
-    std::vector<uint32_t> grp_first(block_count + 1, 0);
-    for (uint32_t b = 0; b < block_count; ++b)
-        grp_first[b + 1] = grp_first[b] + (uint32_t)(((((uint64_t)src_sizes[b] + SEG - 1) / SEG) + GU - 1) / GU);
-    const bool overlap = cut.size() > 2;
-    void* worklist;
-    if ((err = lthip_scratch(ctx, S_LZ4_WORKLIST, 4 * (2 * (size_t)ngrp64 + 1) * (cut.size() - 1), &worklist)))
+    if ((err = lthip_scratch(ctx, S_LZ4_WORKLIST, 4 * (2 * (size_t)ngrp + 1), &worklist))) // count, group ids, their blocks
         return err;
+    const uint32_t dbg = lz4_dbg();
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
     // The stitch copy is persistent over the work list with a fixed stride, so its grid has to be RESIDENT at once: a multiple of what
@@ -746,53 +627,28 @@ static int lz4_compress_batch(lthip_ctx* ctx, const void* d_src, uint32_t block_
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&stitch_wgs, k_lz4_stitch_copy, K6_THREADS, 0) != hipSuccess || stitch_wgs < 1)
         stitch_wgs = 7;
     const uint32_t copy_grid = (uint32_t)ncu * (env_swg.get() > 0 ? (uint32_t)env_swg.get() : 2u * (uint32_t)stitch_wgs);
-    hipStream_t s2 = ctx->stream;
-    if (overlap)
+    // (Match finder and stitch run one after the other on the context's stream.  The stitch of one slice of the batch beside the match
+    // finder of the next, on a second stream, was MEASURED SLOWER on MI355X -- 64 GiB random: 151.6 vs 137.6 ms per step: the copy's
+    // traffic lengthens every probe's LDS-fill latency and both kernels lose more than the overlap wins.)
+    if (ngrp)
     {
-        if ((err = lthip_second_stream(ctx, &s2)))
+        LaunchTimer t(ctx, LTHIP_K_LZ4_SEG);
+        uint8_t* spec = (dbg & 64u) ? (uint8_t*)nullptr : (uint8_t*)d_dst;
+        if ((err = launch_match_finder<0>(ctx, lanes, SEG, d_src, d_blocks, block_count, ngrp64, ncgrp64, (uint8_t*)streams, (Lz4Meta*)meta, nullptr, spec,
+                                          dbg)))
             return err;
     }
-    for (size_t i = 0; i + 1 < cut.size(); ++i)
-    {
-        const uint32_t b0 = cut[i], b1 = cut[i + 1];
-        const uint32_t g0 = grp_first[b0], g1 = grp_first[b1];
-        if (g1 > g0)
-        {
-            LaunchTimer t(ctx, LTHIP_K_LZ4_SEG);
-            uint8_t* spec = (dbg & 64u) ? (uint8_t*)nullptr : (uint8_t*)d_dst;
-            if ((err = launch_match_finder<0>(ctx, lanes, SEG, d_src, d_blocks, block_count, g0, g1, ngrp64, ncgrp64, (uint8_t*)streams, (Lz4Meta*)meta,
-                                              nullptr, spec, dbg, (uint64_t*)lrecs)))
-                return err;
-        }
-        if (overlap)
-        {
-            hipEvent_t e = lthip_sync_event(ctx);
-            LTHIP_CHECK(ctx, hipEventRecord(e, ctx->stream));
-            LTHIP_CHECK(ctx, hipStreamWaitEvent(s2, e, 0));
-        }
-        {
-            LaunchTimer t(ctx, LTHIP_K_LZ4_STITCH, s2);
-            uint32_t* wl = (uint32_t*)worklist + (size_t)i * (2 * (size_t)ngrp64 + 1); // one list per slice: count, group ids, their blocks
-            LTHIP_CHECK(ctx, hipMemsetAsync(wl, 0, 4, s2));
-            hipLaunchKernelGGL(k_lz4_stitch_scan, dim3(b1 - b0), dim3(64), 0, s2, d_blocks, b0, b1, SEG, (const Lz4Meta*)meta,
-                               (Lz4Plan*)plan, (uint32_t*)runs, (Lz4BlockOut*)bout, d_out_sizes, (uint8_t*)d_dst, (dbg & 64u) ? 0u : 1u, wl, (uint32_t)ngrp64);
-            if (g1 > g0)
-                hipLaunchKernelGGL(k_lz4_stitch_copy, dim3(g1 - g0 < copy_grid ? g1 - g0 : copy_grid), dim3(K6_THREADS), 0, s2,
-                                   (const uint8_t*)d_src, d_blocks, block_count, SEG, (const uint8_t*)streams, (const Lz4Meta*)meta,
-                                   (const Lz4Plan*)plan, (const uint32_t*)runs, (const Lz4BlockOut*)bout, (uint8_t*)d_dst,
-                                   (const uint32_t*)wl, GU, (uint32_t)ngrp64);
-            if (i + 2 == cut.size())
-                hipLaunchKernelGGL(k_lz4_empty_blocks, dim3((block_count + 255) / 256), dim3(256), 0, s2, d_blocks, block_count,
-                                   (const Lz4BlockOut*)bout, (uint8_t*)d_dst);
-            LTHIP_LAUNCH_CHECK(ctx);
-        }
-    }
-    if (overlap)
-    {
-        hipEvent_t e = lthip_sync_event(ctx);
-        LTHIP_CHECK(ctx, hipEventRecord(e, s2));
-        LTHIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, e, 0));
-    }
+    LaunchTimer t(ctx, LTHIP_K_LZ4_STITCH);
+    LTHIP_CHECK(ctx, hipMemsetAsync(worklist, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(k_lz4_stitch_scan, dim3(block_count), dim3(64), 0, ctx->stream, d_blocks, 0u, block_count, SEG, (const Lz4Meta*)meta,
+                       (Lz4Plan*)plan, (uint32_t*)runs, (Lz4BlockOut*)bout, d_out_sizes, (uint8_t*)d_dst, (dbg & 64u) ? 0u : 1u, (uint32_t*)worklist, ngrp);
+    if (ngrp)
+        hipLaunchKernelGGL(k_lz4_stitch_copy, dim3(ngrp < copy_grid ? ngrp : copy_grid), dim3(K6_THREADS), 0, ctx->stream, (const uint8_t*)d_src,
+                           d_blocks, block_count, SEG, (const uint8_t*)streams, (const Lz4Meta*)meta, (const Lz4Plan*)plan, (const uint32_t*)runs,
+                           (const Lz4BlockOut*)bout, (uint8_t*)d_dst, (const uint32_t*)worklist, GU, ngrp);
+    hipLaunchKernelGGL(k_lz4_empty_blocks, dim3((block_count + 255) / 256), dim3(256), 0, ctx->stream, d_blocks, block_count,
+                       (const Lz4BlockOut*)bout, (uint8_t*)d_dst);
+    LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }
 
@@ -803,10 +659,8 @@ int lthip_launch_lz_sequences(lthip_ctx* ctx, const void* d_src, uint32_t block_
     const uint32_t SEG = 4096u; // ZB_UNIT
     Lz4Block* d_blocks = nullptr;
     uint64_t nseg64 = 0, ngrp64 = 0;
-    const bool lanes = lz4_lane_parser();
     uint64_t ncgrp64 = 0;
-    int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, lanes ? LZ4_G_LANES : LZ4_G_BATCH, &d_blocks,
-                            &nseg64, &ngrp64, &ncgrp64);
+    int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, LZ4_G_LANES, &d_blocks, &nseg64, &ngrp64, &ncgrp64);
     if (err)
         return err;
     uint64_t nseg = 0;
@@ -823,22 +677,18 @@ int lthip_launch_lz_sequences(lthip_ctx* ctx, const void* d_src, uint32_t block_
         return err;
     if ((err = lthip_scratch(ctx, S_LZ4_META, sizeof(Lz4Meta) * ((size_t)nseg + 1), &meta)))
         return err;
-    void* lrecs = nullptr;
-    if (lanes && (err = lthip_scratch(ctx, S_LZ4_LANE_RECS, (size_t)64 * LZ4_LANE_MAXREC * 8 * ((size_t)nseg + 1), &lrecs)))
-        return err;
     if (nseg)
     {
         LaunchTimer t(ctx, LTHIP_K_LZ4_SEG);
-        LTHIP_ABLATION_ENV(env_dbg, "LTHIP_LZ4_DBG");
-        uint32_t dbg = env_dbg.get() > 0 ? (uint32_t)env_dbg.get() : 0u;
+        uint32_t dbg = lz4_dbg();
         // the parse the zstd setting asks for (LTHIP_ZSTD_Q_*): bit 15 = "high" (history halves: k_lz4_pair_halves), bit 31 = "max" (high +
         // the private table read again after the step's inserts); launch_match_finder and lz4_lane_parse2 read them
         if (quality >= 1)
             dbg |= LZ4_DBG_Q_HIGH;
         if (quality >= 2)
             dbg |= LZ4_DBG_Q_MAX;
-        if ((err = launch_match_finder<1>(ctx, lanes, SEG, d_src, d_blocks, block_count, 0u, (uint32_t)ngrp64, ngrp64, ncgrp64, (uint8_t*)lits,
-                                          (Lz4Meta*)meta, (uint64_t*)recs, (uint8_t*)d_dst, dbg, (uint64_t*)lrecs)))
+        if ((err = launch_match_finder<1>(ctx, true, SEG, d_src, d_blocks, block_count, ngrp64, ncgrp64, (uint8_t*)lits, (Lz4Meta*)meta, (uint64_t*)recs,
+                                          (uint8_t*)d_dst, dbg)))
             return err;
     }
     *d_lits = (uint8_t*)lits;

@@ -5,7 +5,6 @@
 // CLS = classification pass of the two-pass scheme: groups without redundancy are skimmed here and now (the fast geometry: 24 waves
 // per CU), groups with redundancy are only NOTED -- the 16-unit group they belong to goes onto `worklist` -- and left to the lane
 // parser (k_lz4_lanes2), which then runs over that list.  CLS 0 = the batch parser for everything: unit sizes other than 4 KiB.
-// (The lane parser used to be MODE 1 of this template: ablations/k_lz4_segments_modes.inc.)
 template <int G, int TAB, int FMT, int CLS = 0>
 __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __restrict__ src, const Lz4Block* __restrict__ blocks,
                                                              uint32_t nblocks, uint32_t grp0, uint32_t sub_bytes,
@@ -44,8 +43,7 @@ __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __res
 
     // ---- stage the whole group with every wave (16-byte loads from the aligned-down address), clear my table ----
     const uint32_t head_src = (uint32_t)((uintptr_t)g & 15u);
-    // LDS byte address of position 0 of the group: the source's misalignment (the window is staged in aligned 16-byte lines) and, for
-    // the second formulation of the lane parser, one line of padding in front (its extension reads 8 bytes below a position)
+    // LDS byte address of position 0 of the group: the source's misalignment (the window is staged in aligned 16-byte lines)
     const uint32_t head = head_src;
     {
         const uint4* gv = reinterpret_cast<const uint4*>(g - head_src);
@@ -130,16 +128,10 @@ __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __res
                         const uint32_t g16 = blk.grp_base + gi / (uint32_t)(LZ4_G_LANES / LZ4_G_BATCH);
                         // (bit h of the group's word: its half h holds redundancy; a half WITHOUT it is skimmed by this pass, and the
                         // lane kernel only takes its bytes as history)
-#ifdef LTHIP_ABLATIONS
-                        // (the whole-group experiments, LTHIP_LZ4_HALVES=0, run over a LIST of the noted groups)
-                        if (atomicOr(&worklist[1u + ngroups + g16], 1u << (gi & 1u)) == 0u)
-                            worklist[1u + atomicAdd(&worklist[0], 1u)] = g16;
-#else
                         // one atomic nobody waits for: k_lz4_pair_halves reads the groups' words.  (Round 5: the list of noted groups
                         // that this thread used to build -- an atomic OR whose answer decides about an atomic add whose answer is the
                         // slot -- kept a workgroup that had nothing left to do on its CU for two round trips to memory.)
                         (void)__hip_atomic_fetch_or(&worklist[1u + ngroups + g16], 1u << (gi & 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
                     }
                     return;
                 }
@@ -528,7 +520,3 @@ __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __res
     K5P(9);
     } // the group
 }
-
-#ifdef LTHIP_ABLATIONS
-#include "../ablations/k_lz4_segments_modes.inc"
-#endif

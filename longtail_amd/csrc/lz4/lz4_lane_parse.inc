@@ -11,9 +11,9 @@
 //   * a match may run past its lane's sub-unit (up to the unit's end); what it covers is dropped from the later lanes'
 //     records afterwards (exclusive prefix maximum of the lanes' match ends) and lanes that are covered while a long match
 //     is being extended stop parsing
-//   * records {start, length, offset} go to a per-unit scratch area (8 per lane); after the parse three wave scans (cover,
-//     previous kept end, output offset) place every lane's sequences and each lane writes its own bytes; literal runs longer
-//     than 16 bytes are copied by the whole wave
+//   * records {start, length, offset} stay in registers (8 per lane); after the parse three wave scans (cover, previous kept
+//     end, output offset) place every lane's sequences and each lane writes its own bytes; literal runs longer than 16 bytes
+//     are copied by the whole wave
 // Results are a function of the data only (the table is private, the wave runs in lock step).
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t LZ4_LANE_MAXREC = 8; // sequences a lane may record (tools/lz4_lane_model.c: 8 costs nothing, 6 does)
@@ -37,18 +37,6 @@ struct K5Prof
 #define K5P(i) do { } while (0)
 #define K5P_COUNT(i, n) do { } while (0)
 #define K5P_FLUSH do { } while (0)
-#endif
-
-// value held by the lane that owns sub-unit `s` (s outside 0..63: `ident`)
-__device__ __forceinline__ uint32_t sub_shfl(uint32_t x, int s, bool rev, uint32_t ident)
-{
-    const int src = rev ? 63 - s : s;
-    const uint32_t v = __shfl(x, src & 63, 64);
-    return (s < 0 || s > 63) ? ident : v;
-}
-
-#ifdef LTHIP_ABLATIONS
-#include "../ablations/k_lz4_lane_parse_r3.inc" // lz4_lane_parse: the round-3 formulation of the parse below (same payloads)
 #endif
 
 // Scans in SUB-UNIT order with the reverse mapping (sub-unit 63 - lane): a prefix over the sub-units is a SUFFIX over the lanes.  Round 5:
@@ -77,8 +65,8 @@ __device__ __forceinline__ uint32_t lane_from_sub_before(uint32_t v)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K5, lane-sequential parse, second formulation (round 4; PV = 2 of k_lz4_segments).  The parse is the one above -- same probe rule,
-// same candidates, same extension limits, same cover rule: the payloads are byte-identical -- restated around what the per-phase
+// K5, lane-sequential parse, second formulation (round 4).  The parse is the one described above -- the probe rule, candidates,
+// extension limits and cover rule of round 3's formulation: the payloads are byte-identical -- restated around what the per-phase
 // cycle counters said it costs (profiles/r04_k5_prof.txt: a probe step took 1500 cycles for ~100 instructions):
 //   * PROBE in three LDS round trips instead of four: the private and the shared candidate's bytes are read by ONE pair of
 //     unconditional reads (an invalid candidate reads the lane's own position and is masked) -- the compiler had serialised the two
@@ -96,22 +84,19 @@ __device__ __forceinline__ uint32_t lane_from_sub_before(uint32_t v)
 // compile-time zeros in the product; code that every wave walks anyway wants | and & and selects instead of || / && / else-if (an
 // exec-mask region is three scalar instructions), code that whole waves usually skip wants the branch.
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t LZ4_LPAD = 16; // PV 2: LDS byte offset of the staged window
+constexpr uint32_t LZ4_LPAD = 16; // LDS byte offset of the staged window
 constexpr uint32_t LZ4_QUIET = 3;  // lane parser: probe rounds without a hit at an unaligned position before the one-byte steps stop
                                    // (profiles/r05_adaptive_stepping.txt: 6 / 4 / 3 / 2 / 1 rounds: match finder 161.6 / 160.3 / 159.0 / 158.1 /
                                    // 156.4 ms per 64 GiB of "mixed", word-soup text 2.0284 / 2.0284 / 2.0283 / 2.0282 / 2.0249; fixed rule 169.9, 2.0284)
 constexpr uint32_t LZ4_DBG_Q_HIGH = 1u << 15, LZ4_DBG_Q_MAX = 1u << 31; // quality bits of `dbg` (zstd settings, lthip_launch_lz_sequences)
 
-// slot of a private table of TAB entries for the (multiplied) hash `prod`.  PV 0: mulhi(prod, TAB), a quarter-rate 32-bit multiply;
-// PV 2: the upper 16 bits of prod times TAB, a 24-bit multiply and a shift (TAB < 2^16) -- another function of the same bits, so the two
-// formulations fill their tables differently (ratios agree to the fourth digit)
-template <int TAB, int PV>
+// slot of a private table of TAB entries for the (multiplied) hash `prod`: the upper 16 bits of prod times TAB, a 24-bit multiply and a
+// shift (TAB < 2^16).  (mulhi(prod, TAB), what the batch parser takes, is a quarter-rate 32-bit multiply -- another function of the same
+// bits: the tables fill differently, ratios agree to the fourth digit.)
+template <int TAB>
 __device__ __forceinline__ uint32_t lz4_tab_slot(uint32_t prod)
 {
-    if constexpr (PV == 2)
-        return __umul24(prod >> 16, (uint32_t)TAB) >> 16;
-    else
-        return __umulhi(prod, (uint32_t)TAB);
+    return __umul24(prod >> 16, (uint32_t)TAB) >> 16;
 }
 
 // the first nonzero byte of four XOR words (16: none) without a branch: as an if / else-if chain every level is an exec-mask region
@@ -123,15 +108,14 @@ __device__ __forceinline__ uint32_t lz4_first_diff16(uint32_t x0, uint32_t x1, u
     return lo ? nlo : (hi ? nhi : 16u);
 }
 // equal leading bytes (0..16) of the 16 bytes at LDS byte addresses qa and qb (any alignment): five aligned dwords per side
-template <bool PAD>
-__device__ __forceinline__ uint32_t lds_cmp16(const uint32_t* sdata, uint32_t qa, uint32_t qb)
+__device__ __forceinline__ uint32_t lds_cmp16(uint32_t qa, uint32_t qb)
 {
     const uint32_t wa = qa >> 2, wb = qb >> 2, da = qa, db = qb; // (v_alignbyte_b32 takes the two low bits)
     uint32_t ra[4], rb[4];
-    lds_run<PAD, 4>(sdata, wa, ra);
-    lds_run<PAD, 4>(sdata, wb, rb);
-    const uint32_t a0 = ra[0], a1 = ra[1], a2 = ra[2], a3 = ra[3], a4 = lds_dw<PAD>(sdata, wa + 4u);
-    const uint32_t b0 = rb[0], b1 = rb[1], b2 = rb[2], b3 = rb[3], b4 = lds_dw<PAD>(sdata, wb + 4u);
+    lds_run<4>(wa, ra);
+    lds_run<4>(wb, rb);
+    const uint32_t a0 = ra[0], a1 = ra[1], a2 = ra[2], a3 = ra[3], a4 = lds_dw(wa + 4u);
+    const uint32_t b0 = rb[0], b1 = rb[1], b2 = rb[2], b3 = rb[3], b4 = lds_dw(wb + 4u);
     const uint32_t x0 = __builtin_amdgcn_alignbyte(a1, a0, da) ^ __builtin_amdgcn_alignbyte(b1, b0, db);
     const uint32_t x1 = __builtin_amdgcn_alignbyte(a2, a1, da) ^ __builtin_amdgcn_alignbyte(b2, b1, db);
     const uint32_t x2 = __builtin_amdgcn_alignbyte(a3, a2, da) ^ __builtin_amdgcn_alignbyte(b3, b2, db);
@@ -165,17 +149,10 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
     const uint32_t s0 = my_start + (uint32_t)sidx * sub;
     const uint32_t lend = s0 + sub < unit_end ? s0 + sub : unit_end;
     uint32_t p = s0, anchor = s0, nrec = 0, last_end = 0, nmiss = 0;
-    // LTHIP_LZ4_DBG bit 13, "deep": every byte position is probed and, where both tables' candidates verify, the longer match wins --
-    // round 4's first "high" setting; with the history halves it measures WORSE than without on every synthetic kind (and a third slower)
-    // the experiments' switches (LTHIP_LZ4_DBG) exist in the ablation build; in the product they are compile-time zeros, not
-    // wave-uniform branches and selects in the probe loop
-#ifdef LTHIP_ABLATIONS
-    const uint32_t xdbg = dbg;
-#else
-    constexpr uint32_t xdbg = 0u;
-#endif
-    const bool q_high = (xdbg & 8192u) != 0u, q_max = FMT == 1 && (dbg & LZ4_DBG_Q_MAX) != 0u;
-    const uint32_t dense = q_high ? 0xFFFFu : 4u >> ((xdbg >> 29) & 3u);
+    // ("deep" -- every byte position probed and, where both tables' candidates verify, the longer match taken, round 4's first "high"
+    // setting -- measured WORSE with the history halves than without on every synthetic kind, and a third slower: DESIGN_HISTORY.md)
+    const bool q_max = FMT == 1 && (dbg & LZ4_DBG_Q_MAX) != 0u;
+    constexpr uint32_t dense = 4u;
     // Round 5, ADAPTIVE miss stepping.  After a hit (and at a sub-unit's start) a lane steps `dense` single bytes before it probes
     // aligned dwords only -- history enters the tables at aligned dwords, so a probe at an unaligned position is what finds a repeat
     // whose distance is not a multiple of four.  Data made of aligned structures (records, tables, tokens: what compresses in an asset
@@ -184,19 +161,17 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
     // text none of them costs 5 % of the ratio, tools/text_ratio_probe.py).  So the WAVE
     // keeps count: after LZ4_QUIET probe rounds without a single hit at an unaligned position the one-byte steps stop; the first such
     // hit -- the probe behind a match's end stands wherever the match ended -- brings them back.  Wave-uniform, from ballots: a function
-    // of the unit's data alone.  (LTHIP_LZ4_DBG bit 16, or an explicit step count in bits 29-30: the fixed rule.)
-    const bool adaptive = !q_high && !(xdbg & 65536u) && ((xdbg >> 29) & 3u) == 0u;
-    const uint32_t quiet_rounds = (xdbg >> 17) & 7u ? (xdbg >> 17) & 7u : LZ4_QUIET; // (bits 17-19: the sweep of profiles/r05_adaptive_stepping.txt)
+    // of the unit's data alone.
+    constexpr uint32_t quiet_rounds = LZ4_QUIET; // (the sweep: profiles/r05_adaptive_stepping.txt)
     // (the state: bit k of qhist = an unaligned hit k probe rounds ago; bit 0 also stands for the unit's start)
     uint32_t qhist = 1u;
     bool dense_now = true;
     // lanes that must hold a hit before the wave turns to the extension: 4 (round 4, VALU bound: 2 GiB mixed 4.25 ms at 8, 4.12 at 4,
     // 4.16 / 4.37 / 4.76 at 16 / 32 / 48; tokens 5.97 / 5.93 / 6.03 / 6.80 / 7.78 -- waiting lanes are idle lanes)
     // (round 5, with the probe round at half its instructions: mixed 147.2 / 146.2 / 145.6 / 145.0 / 145.4 / 148.4 ms of match finder per
-    // 64 GiB at 4 / 6 / 8 / 12 / 16 / 24, tokens 165.8 / 163.4 / 162.0 / 160.5 / 161.3 / 169.5 -- tools/ablations/wait_for_sweep.sh: 12)
-    const uint32_t wait_for = (xdbg >> 20) & 63u ? (xdbg >> 20) & 63u : 12u;
+    // 64 GiB at 4 / 6 / 8 / 12 / 16 / 24, tokens 165.8 / 163.4 / 162.0 / 160.5 / 161.3 / 169.5: 12)
+    constexpr uint32_t wait_for = 12u;
     uint32_t rsl[8], roff[8]; // records: start | length << 16, offset
-    uint32_t cand2 = 0xFFFFFFFFu; // "high": the other verified candidate of the probe (0xFFFFFFFF: none)
 #pragma unroll
     for (int k = 0; k < 8; ++k)
         rsl[k] = roff[k] = 0u;
@@ -208,7 +183,7 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
     constexpr uint32_t PEND = 0x80000000u;
     const uint32_t headm1 = head - 1u;
     const uint32_t stop0 = start_limit < 0 ? 0u : ((uint32_t)start_limit + 1u < lend ? (uint32_t)start_limit + 1u : lend);
-    uint32_t plim = (xdbg & 2048u) ? 0u : stop0;
+    uint32_t plim = stop0;
     for (;;)
     {
         // ---- probe rounds, until enough hits wait (or nobody can probe any more) ----
@@ -230,14 +205,14 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
                     // window's bookkeeping -- reload after every jump, shift at every crossing, and the copies the three versions of
                     // every register cost at the loop's joins -- was 20 of a probe round's 110 instructions, the round trip is hidden)
                     uint32_t d2[2];
-                    lds_run<PAD, 2>(sdata, x >> 2, d2);
+                    lds_run<2>(x >> 2, d2);
                     const uint32_t v = __builtin_amdgcn_alignbyte(d2[1], d2[0], x);
                     const uint32_t prod = v * 2654435761u;
-                    const uint32_t h = lz4_tab_slot<TAB, 2>(prod);
+                    const uint32_t h = lz4_tab_slot<TAB>(prod);
                     uint32_t c = tab[h];
                     const uint32_t c2 = shr[(prod >> sh_shift) + sh_off] - sh_base; // (another group's entry: far above any position)
                     tab[h] = (uint16_t)p;
-                    if ((xdbg & (1u << 28)) || q_max) // "max": the slot is read again after the step's inserts (entries of lanes in phase)
+                    if (q_max) // "max": the slot is read again after the step's inserts (entries of lanes in phase)
                     {
                         uint32_t hr = h;
                         asm volatile("" : "+v"(hr));
@@ -263,7 +238,6 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
                     {
                         p |= PEND;
                         cand = h1 ? c : (h2 ? c2 : c3); // the private table's (the nearest one) first, the history's last
-                        cand2 = (q_high && h1 && h2 && c != c2) ? c2 : 0xFFFFFFFFu;
                     }
                     else
                     {
@@ -275,8 +249,8 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
             K5P(3);
             K5P_COUNT(10, 1);
             pm = __builtin_amdgcn_ballot_w64((int32_t)p < 0);
-            if (adaptive) // (scalar: the hits of this round are the waiting lanes that probed)
             {
+                // (scalar: the hits of this round are the waiting lanes that probed)
                 const uint64_t t = unm & pm & am;
                 uint32_t bit; // t != 0 as 0 / 1 (written out: the compiler takes the truth value through a vector register)
                 asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, 1, 0" : "=s"(bit) : "s"(t) : "scc");
@@ -302,10 +276,10 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
             const uint32_t qo = p + head - 8u, qc = cand + head - 8u;
             const uint32_t bo = qo >> 2, bc = qc >> 2, dlo = qo, dlc = qc; // (v_alignbyte_b32 takes the two low bits)
             uint32_t Do[8], Dc[8];
-            lds_run<PAD, 4>(sdata, bo, Do);
-            lds_run<PAD, 4>(sdata, bo + 4u, Do + 4);
-            lds_run<PAD, 4>(sdata, bc, Dc);
-            lds_run<PAD, 4>(sdata, bc + 4u, Dc + 4);
+            lds_run<4>(bo, Do);
+            lds_run<4>(bo + 4u, Do + 4);
+            lds_run<4>(bc, Dc);
+            lds_run<4>(bc + 4u, Dc + 4);
             uint32_t X[7];
 #pragma unroll
             for (int k = 0; k < 7; ++k)
@@ -328,40 +302,10 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
                 nbk = cand >= lo_bound + 8u ? nbk : 0u;
             }
         }
-        // ---- "high": where the probe verified BOTH candidates, the other one's first 16 bytes too; the longer match wins (the nearer on a
-        // tie).  One more round trip for the lanes concerned. ----
-        if (q_high && __builtin_amdgcn_ballot_w64(ok && cand2 != 0xFFFFFFFFu))
-        {
-            if (ok && cand2 != 0xFFFFFFFFu)
-            {
-                uint32_t a2 = 4u + lds_cmp16<PAD>(sdata, p + 4u + head, cand2 + 4u + head);
-                bool g2 = a2 == 20u;
-                if (a2 >= maxlen)
-                {
-                    a2 = maxlen;
-                    g2 = false;
-                }
-                if (a2 > mlen)
-                {
-                    // the backward count belongs to the candidate: redo it for the new one
-                    nbk = 0;
-                    if (cand2 >= lo_bound + 8u && p - anchor != 0u)
-                    {
-                        const uint32_t x1 = lds_read32x<PAD>(sdata, p - 4u + head) ^ lds_read32x<PAD>(sdata, cand2 - 4u + head);
-                        const uint32_t x0 = lds_read32x<PAD>(sdata, p - 8u + head) ^ lds_read32x<PAD>(sdata, cand2 - 8u + head);
-                        nbk = x1 ? (uint32_t)__builtin_clz(x1) >> 3 : (x0 ? 4u + ((uint32_t)__builtin_clz(x0) >> 3) : 8u);
-                        nbk = nbk < p - anchor ? nbk : p - anchor;
-                    }
-                    cand = cand2;
-                    mlen = a2;
-                    grow = g2;
-                }
-            }
-        }
         // ---- matches of 20 bytes and more: one more 16-byte round of their own (at most 36 bytes), then the whole wave ----
         if (grow)
         {
-            const uint32_t add = lds_cmp16<PAD>(sdata, p + mlen + head, cand + mlen + head);
+            const uint32_t add = lds_cmp16(p + mlen + head, cand + mlen + head);
             mlen += add;
             if (add != 16u)
                 grow = false;
@@ -491,7 +435,6 @@ __device__ __forceinline__ void lz4_lane_parse2(const uint32_t* sdata, uint32_t 
 
     K5P(6);
     // ---- emission: every lane writes its own sequences; literal runs above 16 bytes are copied by the whole wave ----
-    if (!(xdbg & 1024u))
     {
         uint32_t prev = prev0;
         const uint64_t anyrec = __builtin_amdgcn_ballot_w64(cnt != 0u);

@@ -12,8 +12,8 @@
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t LZ4_HALF_NONE = 0xFFFFFFFFu;
 constexpr uint32_t LZ4_HALF_HIST = 0x40000000u; // on an item's first half: staged as HISTORY of the second, not parsed (k_lz4_pair_halves, hist)
-// worklist layout behind the classification pass (ngroups = groups of the batch): [0] listed groups, [1 .. ngroups] their ids (ablation build only: the product notes the half bits and nothing else),
-// [1 + ngroups ..) per-group half bits, [2 ngroups + 1] ticket, [2 ngroups + 2] items, [2 ngroups + 3] lone halves,
+// worklist layout behind the classification pass (ngroups = groups of the batch): [0 .. ngroups] unused (round 4's list of the noted
+// groups; nobody writes or reads them, the offsets behind them are kept), [1 + ngroups ..) per-group half bits, [2 ngroups + 1] ticket, [2 ngroups + 2] items, [2 ngroups + 3] lone halves,
 // [2 ngroups + 4 ..) items of four words {half a, half b, block of a, block of b} (up to two per group), [10 ngroups + 4 ..) lone halves
 __host__ __device__ constexpr uint32_t lz4_items_off(uint32_t ngroups) { return (2u * ngroups + 4u + 3u) & ~3u; } // (16-byte aligned: items are read as uint4)
 __device__ __forceinline__ uint32_t lz4_block_of_group(const Lz4Block* __restrict__ blocks, uint32_t nblocks, uint32_t grp)
@@ -48,13 +48,7 @@ __global__ void k_lz4_pair_halves(uint32_t* __restrict__ wl, uint32_t ngroups, u
         const uint32_t g = i, bits = wl[1u + ngroups + g] & 3u;
         if (bits == 0u)
             return;
-        if (hist == 2u) // (LTHIP_LZ4_SPLITWG: every flagged half an item of its own)
-        {
-            for (uint32_t hh = 0; hh < 2u; ++hh)
-                if ((bits >> hh) & 1u)
-                    lone[atomicAdd(&wl[2u * ngroups + 3u], 1u)] = 2u * g + hh;
-        }
-        else if (hist)
+        if (hist)
         {
             const uint32_t b = lz4_block_of_group(blocks, nblocks, g);
             // (a piece = two groups; hist 3 -- the "max" setting -- lets a piece's first half see the piece before, except every
@@ -91,17 +85,6 @@ __global__ void k_lz4_pair_halves(uint32_t* __restrict__ wl, uint32_t ngroups, u
     else
     {
         const uint32_t nl = wl[2u * ngroups + 3u];
-        if (hist == 2u)
-        {
-            if (i >= nl)
-                return;
-            const uint32_t k = atomicAdd(&wl[2u * ngroups + 2u], 1u);
-            items[4u * k] = lone[i];
-            items[4u * k + 1u] = LZ4_HALF_NONE;
-            items[4u * k + 2u] = lz4_block_of_group(blocks, nblocks, lone[i] >> 1);
-            items[4u * k + 3u] = 0u;
-            return;
-        }
         if (2u * i >= nl)
             return;
         const uint32_t k = atomicAdd(&wl[2u * ngroups + 2u], 1u);
@@ -113,12 +96,9 @@ __global__ void k_lz4_pair_halves(uint32_t* __restrict__ wl, uint32_t ngroups, u
     }
 }
 
-// WG = waves per workgroup: 16 (the product: an item of two halves per workgroup, one workgroup per CU), or 8 (experiment of round 5,
-// ablation build, LTHIP_LZ4_SPLITWG=1: every flagged half an item of its own, TWO independent workgroups of eight waves per CU with
-// half the window and half the shared table each -- no half ever waits for another at a barrier, and one workgroup's staging runs beside
-// the other's parse; the price: no half sees the half before it).
-template <int FMT, int WG = 16>
-__global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __restrict__ src, const Lz4Block* __restrict__ blocks, uint32_t nblocks,
+// Sixteen waves per workgroup: an item of two halves per workgroup, one workgroup per CU.
+template <int FMT>
+__global__ __launch_bounds__(64 * LZ4_G_LANES, 4) void k_lz4_lanes2(const uint8_t* __restrict__ src, const Lz4Block* __restrict__ blocks, uint32_t nblocks,
                                                        uint32_t sub_bytes, uint8_t* __restrict__ streams, Lz4Meta* __restrict__ meta,
                                                        uint64_t* __restrict__ zrecs, uint8_t* __restrict__ spec_dst, uint32_t dbg,
                                                        uint32_t ngroups, uint32_t* __restrict__ worklist, uint32_t farlog)
@@ -128,8 +108,7 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
     constexpr bool PAD = true;
     constexpr uint32_t GAP = 32u; // LDS bytes between the windows of two unlinked halves
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    static_assert(WG == 16 || WG == 8, "two halves per workgroup, or one");
-    const uint32_t data_bytes = lz4_window_lds_bytes((uint32_t)WG * sub_bytes + 64u + LZ4_LPAD + GAP, true);
+    const uint32_t data_bytes = lz4_window_lds_bytes((uint32_t)G * sub_bytes + 64u + LZ4_LPAD + GAP, true);
     uint32_t* sdata = smem;
     lds_window_must_start_at_zero(sdata);
     uint32_t* flag = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(smem) + data_bytes); // 16 bytes
@@ -138,8 +117,8 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t hsel = (uint32_t)wave >> 3, wih = (uint32_t)wave & 7u; // my half of the item, my unit in the half
     uint16_t* tab = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(smem) + data_bytes + 16u) + (size_t)wave * TAB;
-    uint32_t* shr = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(smem) + data_bytes + 16u + (size_t)WG * TAB * 2);
-    constexpr uint32_t SH_BYTES = WG == 16 ? (4u << SH) : (2u << SH); // (a lone half uses the lower half of the table)
+    uint32_t* shr = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(smem) + data_bytes + 16u + (size_t)G * TAB * 2);
+    constexpr uint32_t SH_BYTES = 4u << SH;
     const uint32_t* items = worklist + lz4_items_off(ngroups);
     const uint32_t nitems = worklist[2u * ngroups + 2u];
     const uint32_t half_bytes = (uint32_t)(G / 2) * sub_bytes;
@@ -155,7 +134,7 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
         {
             uint4* hv = reinterpret_cast<uint4*>(shr);
             const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-            for (uint32_t v = tid; v < SH_BYTES / 16u; v += 64 * WG)
+            for (uint32_t v = tid; v < SH_BYTES / 16u; v += 64 * G)
                 hv[v] = none;
             __syncthreads();
             sh_gen = (dbg & (1u << 26)) ? 3u : 0xFFFFu;
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
             const uint4* gv = reinterpret_cast<const uint4*>(g - head_src);
             const uint32_t nvec = hlen ? (head_src + hlen + 15u) >> 4 : 0u;
             const uint32_t line0 = (wbase + extra + LZ4_LPAD) >> 4; // LDS line (unpadded numbering) of my half's source line 0
-            const uint32_t th = (uint32_t)tid & 511u;
+            const uint32_t th = (uint32_t)tid & 511u; // (my thread among the eight waves of my half)
             for (uint32_t v0 = 0; v0 < nvec; v0 += 512u * 4u)
             {
                 uint4 q[4];
@@ -207,7 +186,7 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
                     if (v < nvec)
                     {
                         const uint32_t D = 4u * (line0 + v);
-                        uint32_t* w = sdata + lds_pidx<true>(D);
+                        uint32_t* w = sdata + lds_pidx(D);
                         w[0] = q[u].x;
                         w[1] = q[u].y;
                         w[2] = q[u].z;
@@ -291,7 +270,7 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
                 for (int u = 0; u < 4; ++u)
                 {
                     const uint32_t j = j0 + (uint32_t)u * 64u + (uint32_t)lane;
-                    const uint32_t* q = sdata + lds_pidx<true>(4u * j);
+                    const uint32_t* q = sdata + lds_pidx(4u * j);
                     w[u] = j < l1 ? make_uint4(q[0], q[1], q[2], q[3]) : make_uint4(0, 0, 0, 0);
                 }
 #pragma unroll
@@ -305,7 +284,7 @@ __global__ __launch_bounds__(64 * WG, 4) void k_lz4_lanes2(const uint8_t* __rest
                     {
                         const uint32_t pk = q + 4u * (uint32_t)k;
                         if (j < l1 && pk >= p0 && pk < my_start)
-                            tab[lz4_tab_slot<TAB, 2>(g4[k] * 2654435761u)] = (uint16_t)pk;
+                            tab[lz4_tab_slot<TAB>(g4[k] * 2654435761u)] = (uint16_t)pk;
                     }
                 }
             }

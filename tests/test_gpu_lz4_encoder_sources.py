@@ -9,7 +9,7 @@ and ends 5 bytes before the end, offsets within 1 .. 65535, one coding per lengt
 every boundary the table is built for (S.Coverage; tests/test_lz4_encoder_sources_cases.py holds the oracle's payloads to the same).
 Further: a block's payload does not depend on the order of the call's blocks or on its company (k_lz4.hip: "results do not depend on
 timing"); the same sources through zstd_compress_blocks at qualities 0, 1, 2 decode with the reference and with this library; sources
-of a period of 8 and less compress to under a quarter."""
+of a period of 8 and less compress to under a quarter; the ablation library, with no switch set, writes the product's bytes."""
 import numpy as np
 import pytest
 
@@ -77,6 +77,12 @@ def product_payloads(gpu):
     return _product["p"]
 
 
+def product_frames(gpu, quality):
+    if ("z", quality) not in _product:
+        _product["z", quality] = encode(lambda *a: gpu.zstd_compress_blocks(*a, quality=quality), [s.data for s in S.sources()], W.zstd_bound)
+    return _product["z", quality]
+
+
 def test_product_library_default_unit(gpu, oracle):
     """(a); run before the tests below, which read its payloads"""
     srcs = S.sources()
@@ -137,7 +143,7 @@ def test_zstd_front_end(gpu, ref, quality):
     """the same sources through the match finder's zstd flavour (qualities 1 and 2: the history halves reach a group further back, where
     the periods of 2 G and the repeat exactly G back lie): the frames decode with the reference and with this library"""
     srcs = S.sources()
-    frames = encode(lambda *a: gpu.zstd_compress_blocks(*a, quality=quality), [s.data for s in srcs], W.zstd_bound)
+    frames = product_frames(gpu, quality)
     bad = []
     for s, f in zip(srcs, frames):
         err, out = ref.decompress(1, f, len(s.data))
@@ -154,3 +160,20 @@ def test_zstd_front_end(gpu, ref, quality):
     assert not bad, f"quality {quality}: zstd_decompress_blocks does not decode {len(bad)} frames to their sources, the first: " + "; ".join(bad[:12])
     g = sum(len(f) for f in frames)
     print(f"lz4 encoder sources, zstd quality {quality}: {g} bytes of frames for {sum(len(s.data) for s in srcs)}")
+
+
+def test_ablation_library_without_a_switch_writes_the_products_bytes(gpu, gpu_abl):
+    """The premise of every gpu_abl differential test: with no LTHIP_* switch set the ablation build runs the product's match finder --
+    the same kernels launched the same way, its switches at their defaults.  Every LZ4 payload at the default unit and every zstd frame
+    at qualities 0, 1 and 2 is byte for byte the product library's."""
+    gpu_abl.lib.dll.lthip_debug_reload_env()  # (a value an earlier test's switch left cached in that library)
+    srcs = S.sources()
+    datas = [s.data for s in srcs]
+    runs = [("lz4", product_payloads(gpu), encode(gpu_abl.lz4_compress_blocks, datas, W.lz4_bound))]
+    for q in (0, 1, 2):
+        runs.append((f"zstd quality {q}", product_frames(gpu, q), encode(lambda *a: gpu_abl.zstd_compress_blocks(*a, quality=q), datas, W.zstd_bound)))
+    bad = []
+    for way, prod, abl in runs:
+        assert len(prod) == len(abl) == len(srcs)
+        bad += [f"{way}, '{s.name}': {len(a)} bytes against the product's {len(p)}" for s, p, a in zip(srcs, prod, abl) if len(p) != len(a) or not (p == a).all()]
+    assert not bad, f"{len(bad)} outputs of the ablation library are not the product's, the first: " + "; ".join(bad[:12])

@@ -2,7 +2,7 @@
 """Compare the device code of two builds kernel by kernel (refactorings that must not change a shipped kernel).
 usage: isa_diff.py <before.s> <after.s> [old_name_substring=new_name_substring ...]
 Both files come from `hipcc --offload-arch=gfx950 -O3 ... --cuda-device-only -S`.  Kernels are matched by demangled-ish name (the
-mangled symbol with the given substitutions applied to the BEFORE side); instruction streams are compared with local labels
+mangled symbol with the given substitutions applied to the BEFORE side, its text included); instruction streams are compared with local labels
 renumbered in order of appearance and comments stripped."""
 import re
 import sys
@@ -43,6 +43,8 @@ def main():
         k2 = k
         for a, b in subs:
             k2 = k2.replace(a, b)
+        for a, b in subs:  # (the kernel descriptor behind the code names the symbol)
+            v = [t.replace(a, b) for t in v]
         renamed[k2] = (k, v)
     same = diff = 0
     for k in sorted(after):

@@ -1,9 +1,7 @@
 #!/usr/bin/env python3
 """Is the LZ4 / zstd payload of a block a function of the block alone?  Compresses the same blocks several times (alone, in another
-order of the call's block list, with tickets and with the fixed stride) and compares the payload bytes.
+order of the call's block list, a part of the list) and compares the payload bytes.  Sets no switch: runs on the product library.
 python tools/k5_determinism.py [gib] [codec] [ragged|-] [zstd quality 0..2]"""
-import _ablations  # noqa: F401  (first: the LTHIP_* switches used here exist in the ablation build only)
-import os
 import sys
 from pathlib import Path
 
@@ -35,9 +33,7 @@ quality = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 fn = ctx.lz4_compress_blocks if codec == "lz4" else (lambda *a: ctx.zstd_compress_blocks(*a, quality=quality))
 
 
-def run(order, dbg):
-    os.environ["LTHIP_LZ4_DBG"] = str(dbg)
-    ctx.lib.dll.lthip_debug_reload_env()
+def run(order):
     arena = torch.zeros(int(bound.sum()) + nb * 64 + 64, dtype=torch.uint8, device="cuda")
     b_off = np.asarray(order, np.int64) * BLOCK
     sizes = fn(data, b_off, b_size[np.asarray(order)], arena, d_offs[: len(order)], bound[: len(order)])
@@ -48,9 +44,8 @@ def run(order, dbg):
 
 
 ident = list(range(nb))
-base = run(ident, 0)
-for name, order, dbg in [("again", ident, 0), ("reversed block list", ident[::-1], 0), ("fixed stride", ident, 1 << 27),
-                         ("fixed stride, reversed", ident[::-1], 1 << 27), ("first half only", ident[: nb // 2], 0)]:
-    other = run(order, dbg)
+base = run(ident)
+for name, order in [("again", ident), ("reversed block list", ident[::-1]), ("first half only", ident[: nb // 2])]:
+    other = run(order)
     diff = [b for b in other if other[b] != base[b]]
     print(f"{codec}{' q' + str(quality) if quality else ''}{' ragged' if ragged else ''} {name}: {len(diff)} of {len(other)} payloads differ" + (f" (first: block {diff[0]}, {len(base[diff[0]])} vs {len(other[diff[0]])} bytes)" if diff else ""))

@@ -29,7 +29,7 @@ bound = b_size + b_size // 255 + 16 if codec == "lz4" else b_size + (b_size >> 8
 d_offs = np.concatenate([[0], np.cumsum((bound + 63) // 64 * 64)[:-1]])
 arena = torch.empty(int(bound.sum()) + nb * 64 + 64, dtype=torch.uint8, device="cuda")
 back = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
-print(f"parser={os.environ.get('LTHIP_LZ4_PARSER', 'lanes')} {gib} GiB, {codec}")
+print(f"{gib} GiB, {codec}")
 for kind in kinds:
     nfiles = (n + BLOCK) // (1 << 20)
     ctx.synth_fill(data, np.arange(nfiles, dtype=np.uint64) * np.uint64(1 << 20), np.full(nfiles, 1 << 20, np.uint64), asset_seeds(0xBEEF, 0, nfiles), KINDS[kind])

@@ -1,6 +1,9 @@
+"""LZ4 and zstd ratio on word-soup text (repeats at every distance, none of them aligned) for a list of LTHIP_LZ4_DBG settings.
+python tools/text_ratio_probe.py [dbg,dbg,...]"""
 import _ablations  # noqa: F401  (first: the LTHIP_* switches used here exist in the ablation build only)
 import sys
-sys.path.insert(0,'/root/repo')
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import os, numpy as np, torch
 from tests.gpu_util import to_device, layout, u32
 from longtail_amd.lib import Context
@@ -19,7 +22,7 @@ blocks = [text(4 << 20) for _ in range(8)]
 dev, offs = to_device(blocks)
 sizes = [len(b) for b in blocks]
 for codec in ("lz4", "zstd"):
-    for dbg in (1 << 16, 0, 3 << 17, 2 << 17, 1 << 17, 3 << 29):  # fixed four one-byte steps; adaptive with 6 (default), 3, 2, 1 quiet rounds; no one-byte steps
+    for dbg in [int(x, 0) for x in (sys.argv[1] if len(sys.argv) > 1 else "0").split(",")]:
         os.environ["LTHIP_LZ4_DBG"] = str(dbg)
         ctx.lib.dll.lthip_debug_reload_env()
         caps = [s + s // 255 + 16 if codec == "lz4" else s + (s >> 8) + 64 for s in sizes]
