@@ -24,79 +24,11 @@
 namespace
 {
 
-enum
-{
-    F_CHUNK_START = 1, // blake3_impl.h:14-22
-    F_CHUNK_END = 2,
-    F_PARENT = 4,
-    F_ROOT = 8
-};
-
-#define B3_IV0 0x6A09E667u
-#define B3_IV1 0xBB67AE85u
-#define B3_IV2 0x3C6EF372u
-#define B3_IV3 0xA54FF53Au
-#define B3_IV4 0x510E527Fu
-#define B3_IV5 0x9B05688Cu
-#define B3_IV6 0x1F83D9ABu
-#define B3_IV7 0x5BE0CD19u
-
-__device__ __forceinline__ uint32_t rotr32(uint32_t x, uint32_t r) { return __builtin_amdgcn_alignbit(x, x, r); }
-
-__device__ __forceinline__ void b3_g(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t mx, uint32_t my)
-{
-    a = a + b + mx;
-    d = rotr32(d ^ a, 16);
-    c = c + d;
-    b = rotr32(b ^ c, 12);
-    a = a + b + my;
-    d = rotr32(d ^ a, 8);
-    c = c + d;
-    b = rotr32(b ^ c, 7);
-}
-
-// one round with message words named explicitly (the schedule is applied by the caller's argument order)
-#define B3_ROUND(m0, m1, m2, m3, m4, m5, m6, m7, m8, m9, m10, m11, m12, m13, m14, m15) \
-    b3_g(s0, s4, s8, s12, m0, m1);                                                      \
-    b3_g(s1, s5, s9, s13, m2, m3);                                                      \
-    b3_g(s2, s6, s10, s14, m4, m5);                                                     \
-    b3_g(s3, s7, s11, s15, m6, m7);                                                     \
-    b3_g(s0, s5, s10, s15, m8, m9);                                                     \
-    b3_g(s1, s6, s11, s12, m10, m11);                                                   \
-    b3_g(s2, s7, s8, s13, m12, m13);                                                    \
-    b3_g(s3, s4, s9, s14, m14, m15);
-
-// cv <- first 8 output words of compress(cv, m, counter, block_len, flags)
-__device__ __forceinline__ void b3_compress(uint32_t (&cv)[8], const uint32_t (&m)[16], uint32_t counter_lo,
-                                            uint32_t block_len, uint32_t flags)
-{
-    uint32_t s0 = cv[0], s1 = cv[1], s2 = cv[2], s3 = cv[3], s4 = cv[4], s5 = cv[5], s6 = cv[6], s7 = cv[7];
-    uint32_t s8 = B3_IV0, s9 = B3_IV1, s10 = B3_IV2, s11 = B3_IV3;
-    uint32_t s12 = counter_lo, s13 = 0u, s14 = block_len, s15 = flags;
-    // rows of MSG_SCHEDULE (blake3_impl.h:89-97): row r+1 = row r permuted by {2,6,3,10,7,0,4,13,1,11,12,5,9,14,15,8}
-    B3_ROUND(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11], m[12], m[13], m[14], m[15])
-    B3_ROUND(m[2], m[6], m[3], m[10], m[7], m[0], m[4], m[13], m[1], m[11], m[12], m[5], m[9], m[14], m[15], m[8])
-    B3_ROUND(m[3], m[4], m[10], m[12], m[13], m[2], m[7], m[14], m[6], m[5], m[9], m[0], m[11], m[15], m[8], m[1])
-    B3_ROUND(m[10], m[7], m[12], m[9], m[14], m[3], m[13], m[15], m[4], m[0], m[11], m[2], m[5], m[8], m[1], m[6])
-    B3_ROUND(m[12], m[13], m[9], m[11], m[15], m[10], m[14], m[8], m[7], m[2], m[5], m[3], m[0], m[1], m[6], m[4])
-    B3_ROUND(m[9], m[14], m[11], m[5], m[8], m[12], m[15], m[1], m[13], m[3], m[0], m[10], m[2], m[6], m[4], m[7])
-    B3_ROUND(m[11], m[15], m[5], m[0], m[1], m[9], m[8], m[6], m[14], m[10], m[2], m[12], m[3], m[4], m[7], m[13])
-    cv[0] = s0 ^ s8;
-    cv[1] = s1 ^ s9;
-    cv[2] = s2 ^ s10;
-    cv[3] = s3 ^ s11;
-    cv[4] = s4 ^ s12;
-    cv[5] = s5 ^ s13;
-    cv[6] = s6 ^ s14;
-    cv[7] = s7 ^ s15;
-}
-
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+#include "k_blake3_leaf.h" // the compression function and the hashing of one leaf
 
 // ---------------------------------------------------------------------------------------------------
 // leaf counts
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t leaves_of(uint32_t len) { return len ? (len + 1023u) >> 10 : 1u; }
 
 __global__ void k_leaf_counts(const uint32_t* __restrict__ lens, uint64_t bound, const uint32_t* __restrict__ n_dev,
                               uint32_t* __restrict__ counts)
@@ -159,70 +91,6 @@ static_assert(PW <= 4096 && (PW & (PW - 1)) == 0 && PW_THREADS % 64 == 0 && PW_M
 // leaves
 // ---------------------------------------------------------------------------------------------------
 
-// The message dwords of one 64-byte block as they lie in memory: 16 dwords from the 4-byte aligned address at or below the block's
-// first byte, and the dword behind them, which holds the block's last 1..3 bytes when the leaf starts off a dword boundary.
-__device__ __forceinline__ void b3_load_interior(uint32_t (&w)[17], const uint32_t* __restrict__ src)
-{
-    const u32x4_a4 v0 = *reinterpret_cast<const u32x4_a4*>(src);
-    const u32x4_a4 v1 = *reinterpret_cast<const u32x4_a4*>(src + 4);
-    const u32x4_a4 v2 = *reinterpret_cast<const u32x4_a4*>(src + 8);
-    const u32x4_a4 v3 = *reinterpret_cast<const u32x4_a4*>(src + 12);
-    w[0] = v0.x; w[1] = v0.y; w[2] = v0.z; w[3] = v0.w;
-    w[4] = v1.x; w[5] = v1.y; w[6] = v1.z; w[7] = v1.w;
-    w[8] = v2.x; w[9] = v2.y; w[10] = v2.z; w[11] = v2.w;
-    w[12] = v3.x; w[13] = v3.y; w[14] = v3.z; w[15] = v3.w;
-    // an interior block has a block of the same leaf behind it, and this is that block's first dword: it holds a byte of the leaf
-    // whatever the alignment, so it is loaded without a test (v_alignbit with a shift of 0 does not look at it)
-    w[16] = src[16];
-}
-
-// the leaf's last block, `nd` dwords of which hold at least one of its bytes: only those are touched
-__device__ __forceinline__ void b3_load_last(uint32_t (&w)[17], const uint32_t* __restrict__ src, uint32_t nd)
-{
-#pragma unroll
-    for (int i = 0; i < 17; ++i)
-        w[i] = (uint32_t)i < nd ? src[i] : 0u;
-}
-
-// w[0 .. 15] <- the block's message words, each in the register of the dword it starts in (the dword is dead behind it): written with
-// the destination tied, because left to itself the allocator puts the sixteen words into registers of their own and two sets of
-// loaded dwords beside message and state then do not fit in 64
-__device__ __forceinline__ void b3_interior_block(uint32_t (&cv)[8], uint32_t (&w)[17], uint32_t sh, uint32_t k, uint32_t flags)
-{
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        asm("v_alignbit_b32 %0, %1, %0, %2" : "+v"(w[i]) : "v"(w[i + 1]), "v"(sh));
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        m[i] = w[i];
-    b3_compress(cv, m, k, 64u, flags);
-}
-
-__device__ __forceinline__ void b3_last_block(uint32_t (&cv)[8], const uint32_t (&w)[17], uint32_t sh, uint32_t k, uint32_t bl, uint32_t flags)
-{
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-    {
-        uint32_t v = __builtin_amdgcn_alignbit(w[i + 1], w[i], sh);
-        const int rem = (int)bl - 4 * i; // valid bytes in this word
-        if (rem <= 0)
-            v = 0u;
-        else if (rem < 4)
-            v &= (1u << (8 * rem)) - 1u;
-        m[i] = v;
-    }
-    b3_compress(cv, m, k, bl, flags);
-}
-
-// Fixes a point of the program order: the chaining value is complete in front of it, and no load moves across it.  It emits nothing.
-// (Without it the compiler sinks a whole compression below the loads that follow it, and those then need a third set of registers.)
-__device__ __forceinline__ void b3_pin(uint32_t (&cv)[8])
-{
-    asm volatile("" : "+v"(cv[0]), "+v"(cv[1]), "+v"(cv[2]), "+v"(cv[3]), "+v"(cv[4]), "+v"(cv[5]), "+v"(cv[6]), "+v"(cv[7])::"memory");
-}
-
 // PIPE: the message dwords of block b + 1 are loaded while block b is compressed (two register sets that swap roles by name, the
 // loop unrolled by two).  A lane's loads are 64-line gathers, one 16-byte piece per lane and the lanes 1 KiB apart; without the
 // second set every block waits for all of its own in front of its compression and only the SIMD's other waves cover them.  The
@@ -275,53 +143,7 @@ __global__ __launch_bounds__(256, 8) void k_blake3_leaves(const uint8_t* __restr
 
     if constexpr (PIPE)
     {
-        const uint32_t last = nblocks - 1u;
-        const uint32_t bl = llen - last * 64u;                  // 0..64 bytes in the last block
-        const uint32_t nd = bl ? (mis + bl + 3u) >> 2 : 0u;    // its dwords that intersect [p, p + bl)
-        // Blocks 0 .. last - 2 (the block behind each is interior too) go through a loop of two halves: the first compresses wa while
-        // wb is in flight, the second wb while wa is.  A lane with an odd number of them sits out the first half of the first trip,
-        // so every lane leaves at the bottom with block last - 1 in wa, and a wave makes no more trips than its longest lane needs.
-        uint32_t wa[17], wb[17];
-        uint32_t b = 0;
-        bool first_half = last > 1u && ((last - 1u) & 1u) == 0u;
-        if (last > 1u && !first_half)
-            b3_load_interior(wb, q);
-        else if (last)
-            b3_load_interior(wa, q);
-        if (last > 1u)
-        {
-#pragma unroll 1
-            for (;;)
-            {
-                if (first_half)
-                {
-                    b3_load_interior(wb, q + (b + 1u) * 16u);
-                    b3_pin(cv);
-                    b3_interior_block(cv, wa, sh, k, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
-                    b3_pin(cv);
-                    ++b;
-                }
-                first_half = true;
-                b3_load_interior(wa, q + (b + 1u) * 16u);
-                b3_pin(cv);
-                b3_interior_block(cv, wb, sh, k, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
-                b3_pin(cv);
-                ++b;
-                if (b + 1u >= last)
-                    break;
-            }
-        }
-        // block last - 1 is loaded, the last interior one: the last block's dwords are asked for before it is compressed
-        if (last)
-        {
-            b3_load_last(wb, q + last * 16u, nd);
-            b3_pin(cv);
-            b3_interior_block(cv, wa, sh, k, b == 0 ? (uint32_t)F_CHUNK_START : 0u);
-            b3_pin(cv);
-        }
-        else
-            b3_load_last(wb, q, nd);
-        b3_last_block(cv, wb, sh, k, bl, (uint32_t)F_CHUNK_END | root | (last == 0 ? (uint32_t)F_CHUNK_START : 0u));
+#include "k_blake3_leaf_body.inc" // (the text of b3_leaf, k_blake3_leaf.h, which the walking scan that hashes calls)
     }
     else
     {
@@ -640,9 +462,13 @@ __device__ __forceinline__ void pw_append(bool is, uint32_t entry, uint32_t* lis
 // entries: 36 KiB, and 60 registers, so FOUR workgroups are resident per CU, 32 waves, all a CU holds.  The kernel is bound by the
 // latency of its own chain (five dependent loads before the first compression, then one compression per level with ever fewer
 // lanes), which only other workgroups on the same SIMDs cover: with three per CU it takes 2.03 ms on the 64 GiB tree, with four 1.85.
+// run_slot != null: the leaves' chaining values are not in the dense leaf order but where the walking scan that hashes left them, range
+// c's at slot run_slot[c] of cvs and following (k_blake3_run_slots): one more dependent load per block, and no pass that moves 32 bytes
+// a leaf.  (One kernel for both, told apart by the pointer: tests/test_k3_parents_budget.py holds the product to one reducer.)
 __global__ __launch_bounds__(PW_THREADS, PW_WAVES) void k_blake3_parents_window(const uint32_t* __restrict__ leaf_prefix, uint64_t count_bound,
                                                                          const uint32_t* __restrict__ n_dev, const uint32_t* __restrict__ cvs,
-                                                                         const uint32_t* __restrict__ win_first, uint64_t* __restrict__ hashes)
+                                                                         const uint32_t* __restrict__ win_first, uint64_t* __restrict__ hashes,
+                                                                         const uint32_t* __restrict__ run_slot)
 {
     __shared__ uint4 s_mem[PW_MEM16]; // the tables, behind them the nodes
     __shared__ uint32_t s_list[2][PW_NODES / 2 + 1];                   // node | block inside the range << 16 | blocks of the range << 24
@@ -744,7 +570,7 @@ __global__ __launch_bounds__(PW_THREADS, PW_WAVES) void k_blake3_parents_window(
             const uint32_t j = lo, b = blk - s_blk[j];
             const uint32_t p = s_leaf[j], n = s_leaf[j + 1] - p, nb = b3s_blocks(n, PB);
             const uint32_t m = b3s_block_leaves(n, b, PB);
-            const uint4* g = cvs4 + (p + b * PB) * 2u;
+            const uint4* g = run_slot ? reinterpret_cast<const uint4*>(cvs) + ((uint64_t)run_slot[c_lo + j] + b * PB) * 2u : cvs4 + (p + b * PB) * 2u;
             uint32_t cv[PB][8];
 #pragma unroll
             for (uint32_t i = 0; i < PB; ++i)
@@ -852,11 +678,80 @@ __global__ void k_blake3_emit(const uint32_t* __restrict__ leaf_prefix, uint32_t
     hashes[c] = (uint64_t)base[0] | ((uint64_t)base[1] << 32);
 }
 
+// The chaining values that the walking scan hashed itself (k_buzhash.hip) lie in runs, one per part, each filled densely from its
+// start in the part's chunk order.  A workgroup per part, behind compaction (which yields leaf_prefix):
+//   MOVE   moves the run to the part's place in the dense leaf order -- leaf_prefix of the part's first chunk -- for the reducers that
+//          work in place on the dense order (big trees);
+//   !MOVE  notes for every chunk of the part the slot of its first leaf in the runs, which k_blake3_parents_window<true> reads them from;
+// and both note the windows that start inside the part, as the leaf kernel does.
+template <bool MOVE>
+__global__ __launch_bounds__(256) void k_blake3_run_slots(const PartDev* __restrict__ parts, uint32_t nparts,
+                                                           const uint32_t* __restrict__ part_first,
+                                                           const uint32_t* __restrict__ leaf_prefix, const uint4* __restrict__ runs,
+                                                           uint4* __restrict__ cvs, uint32_t* __restrict__ run_slot,
+                                                           uint32_t* __restrict__ win_first)
+{
+    const uint32_t p = blockIdx.x;
+    if (p >= nparts)
+        return;
+    const uint32_t c0 = part_first[p], c1 = part_first[p + 1];
+    const uint32_t g0 = leaf_prefix[c0], g1 = leaf_prefix[c1];
+    if constexpr (MOVE)
+    {
+        const uint4* src = runs + lthip_part_run_base(parts[p]) * 2u;
+        uint4* dst = cvs + (uint64_t)g0 * 2u;
+        const uint32_t n = (g1 - g0) * 2u; // (a part is below 4 GiB: its leaves and chunks are below 2^23)
+        for (uint32_t i = threadIdx.x; i < n; i += 256u)
+            dst[i] = src[i];
+    }
+    else
+    {
+        const uint32_t base = (uint32_t)lthip_part_run_base(parts[p]) - g0; // (slots are below 2^32: lthip_launch_buzhash_walk)
+        for (uint32_t c = c0 + threadIdx.x; c < c1; c += 256u)
+            run_slot[c] = base + leaf_prefix[c];
+    }
+    if (!win_first)
+        return;
+    for (uint64_t g = (((uint64_t)g0 + (uint32_t)(PW - 1)) & ~(uint64_t)(PW - 1)) + (uint64_t)threadIdx.x * PW; g < g1; g += 256u * (uint64_t)PW)
+    {
+        uint32_t lo = c0, hi = c1; // range c of the part with leaf_prefix[c] <= g < leaf_prefix[c + 1]
+        while (hi - lo > 1)
+        {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (leaf_prefix[mid] <= g)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        win_first[g / (uint32_t)PW] = leaf_prefix[lo] == g ? lo : lo + 1u;
+    }
+}
+
+#ifndef B3_RUNS_IN_PLACE
+#define B3_RUNS_IN_PLACE 1 // 1: small trees are reduced from the runs of a scan that hashes where they lie; 0: the runs are moved first (profiles/walk_hash_ab.txt)
+#endif
+
 } // namespace
+
+static int launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
+                         uint64_t count_bound, uint64_t leaf_bound, uint64_t max_len, uint64_t* d_hashes, const lthip_b3_runs* runs);
 
 int lthip_launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens,
                         const uint32_t* d_count, uint64_t count_bound, uint64_t leaf_bound, uint64_t max_len,
                         uint64_t* d_hashes)
+{
+    return launch_blake3(ctx, d_data, d_offsets, d_lens, d_count, count_bound, leaf_bound, max_len, d_hashes, nullptr);
+}
+
+int lthip_launch_blake3_parents(lthip_ctx* ctx, const lthip_b3_runs& runs, const uint32_t* d_lens, const uint32_t* d_count,
+                                uint64_t count_bound, uint64_t leaf_bound, uint64_t max_len, uint64_t* d_hashes)
+{
+    return launch_blake3(ctx, nullptr, nullptr, d_lens, d_count, count_bound, leaf_bound, max_len, d_hashes, &runs);
+}
+
+// runs: the leaves are hashed already and lie in per-part runs; they are moved into place where the leaf kernel would have written them
+static int launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens, const uint32_t* d_count,
+                         uint64_t count_bound, uint64_t leaf_bound, uint64_t max_len, uint64_t* d_hashes, const lthip_b3_runs* runs)
 {
     if (count_bound == 0)
         return 0;
@@ -905,6 +800,23 @@ int lthip_launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d
     void* wf = nullptr;
     if (small_trees && (err = lthip_scratch(ctx, S_B3_WINDOWS, (leaf_bound / PW + 2) * 4, &wf)))
         return err;
+    LTHIP_ABLATION_ENV(env_serial, "LTHIP_B3_SERIAL_PARENTS"); // one thread per tree (dense order)
+    void* slots = nullptr; // small trees are reduced from the runs where they lie
+    if (runs && small_trees && B3_RUNS_IN_PLACE && env_serial.get() < 0 &&
+        (err = lthip_scratch(ctx, S_CV_SLOTS, (count_bound + 1) * 4, &slots)))
+        return err;
+    if (runs)
+    {
+        LaunchTimer t(ctx, LTHIP_K_B3_LEAF);
+        if (slots)
+            hipLaunchKernelGGL(k_blake3_run_slots<false>, dim3(runs->nparts), dim3(256), 0, ctx->stream, runs->d_parts, runs->nparts,
+                               runs->d_part_first, (const uint32_t*)lp, (const uint4*)runs->d_cvs, (uint4*)nullptr, (uint32_t*)slots, (uint32_t*)wf);
+        else
+            hipLaunchKernelGGL(k_blake3_run_slots<true>, dim3(runs->nparts), dim3(256), 0, ctx->stream, runs->d_parts, runs->nparts,
+                               runs->d_part_first, (const uint32_t*)lp, (const uint4*)runs->d_cvs, (uint4*)cv, (uint32_t*)nullptr, (uint32_t*)wf);
+        LTHIP_LAUNCH_CHECK(ctx);
+    }
+    else
     {
         LaunchTimer t(ctx, LTHIP_K_B3_LEAF);
         LTHIP_ABLATION_ENV(env_pad, "LTHIP_B3_PAD_LDS"); // experiment: unused LDS limits the waves per CU
@@ -924,14 +836,14 @@ int lthip_launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d
     {
         LaunchTimer t(ctx, LTHIP_K_B3_PARENT);
 #ifdef LTHIP_ABLATIONS
-        LTHIP_ABLATION_ENV(env_serial, "LTHIP_B3_SERIAL_PARENTS"); // one thread per tree
         if (env_serial.get() >= 0)
             hipLaunchKernelGGL(k_blake3_parents_small, dim3((uint32_t)div_up_u64(count_bound, 256)), dim3(256), 0, ctx->stream,
                                d_lens, (const uint32_t*)lp, count_bound, d_count, (uint32_t*)cv, d_hashes);
         else
 #endif
             hipLaunchKernelGGL(k_blake3_parents_window, dim3((uint32_t)div_up_u64(leaf_bound, PW)), dim3(PW_THREADS), 0, ctx->stream,
-                               (const uint32_t*)lp, count_bound, d_count, (const uint32_t*)cv, (const uint32_t*)wf, d_hashes);
+                               (const uint32_t*)lp, count_bound, d_count, slots ? runs->d_cvs : (const uint32_t*)cv, (const uint32_t*)wf, d_hashes,
+                               (const uint32_t*)slots);
         LTHIP_LAUNCH_CHECK(ctx);
     }
     else

@@ -30,6 +30,8 @@ __constant__ uint32_t c_buztab[256] = {
 #include "buzhash_table.inc"
 };
 
+#include "k_blake3_leaf.h" // the hashing of one BLAKE3 leaf in a lane's registers (k_buzhash_hash_walk)
+
 constexpr int RUN = 64;                      // bytes per thread
 constexpr int TILE = 256 * RUN;              // 16 KiB: the plan's tile (four wave-tiles)
 constexpr int ROW_DW = 17;                   // 16 data dwords + 1 pad: thread-strided ds_read_b32 hits 32 distinct banks
@@ -829,6 +831,269 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
 }
 
 // ---------------------------------------------------------------------------------------------------
+// K1 + K2 + K3's leaf pass in one: the walking scan whose waves HASH the chunks they cut.
+//
+// The scan leaves a SIMD's issue slots about a quarter idle (LDS round trips of the table look-ups) and the leaf pass is pure vector
+// issue, so waves that scan and waves that hash fill each other's holes when they share a SIMD.  Here they are the same waves: a wave
+// that emits a chunk holds its (s, len) in scalars, so it appends it to a pending list of its own in LDS -- {byte offset in data, len,
+// chaining-value slot of its first leaf} -- and whenever 64 leaves are pending it runs one round of b3_leaf (k_blake3_leaf.h: the body
+// of k_blake3_leaves), a leaf per lane.  A lane finds its (chunk, leaf) by a wave scan over the pending chunks' leaf counts.  The list
+// is the only hand-off (no lane reads region[] back), it carries across parts, so only a wave's last round is short, and a chunk of
+// more than 64 leaves spans rounds.  Nothing waits for another wave.
+// The walk is k_buzhash_walk's, written as ONE loop so that the round stands at one place in the code (it is three compressions long)
+// and every emission is followed by the test for a round before the next one: a part is drawn, a chunk that needs no scan is emitted,
+// a tile is hashed, or a round is run, one of them per trip.  At most 63 leaves are pending in front of an emission, so the list never
+// holds more than 64 chunks, and behind a round of 64 only (the rest of) the last chunk is left.  Rounds run between tiles, where the
+// walk's state is scalar and the tile's registers are dead; a guessed tile may be on its way into the buffer meanwhile (the list has
+// LDS of its own).  A tile with several cuts (min < 4 KiB) is left when the list fills up and hashed again behind the round.
+// Chaining values go to the part's run of cv_runs (lthip_part_run_base), densely from its start in chunk order: leaf k of a chunk at
+// slot + k.  Flags and counter are the leaf kernel's.  region[] and part_count[] are written exactly as by k_buzhash_walk.
+// ---------------------------------------------------------------------------------------------------
+constexpr int PEND_CAP = 64; // chunks of a wave's pending list (uint4 each)
+
+template <int MODE, int WAVES, bool GUESS>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts,
+                                                                      uint32_t nparts, DivTest dv, uint32_t min_chunk, uint32_t max_chunk,
+                                                                      uint2* __restrict__ region, uint32_t* __restrict__ part_count,
+                                                                      uint32_t* __restrict__ ticket, uint32_t* __restrict__ cv_runs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t* buf = smem + 256 * TAB_REP + wave * ((DMA_BUF_B >> 2) + HALO_DW);
+    uint32_t* halo = buf + (DMA_BUF_B >> 2);
+    uint4* pend = reinterpret_cast<uint4*>(smem + 256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW)) + wave * PEND_CAP;
+    prefix_table_init(smem, tid, 64 * WAVES);
+
+    const TileDma dma(data, buf, lane);
+    const PrefixConsts pc = dma.consts<MODE>(dv);
+    const int lane_base = lane * RUN;
+
+    auto jump = [](uint64_t q) __attribute__((always_inline)) { return q >= 64 ? ((q - 64) & ~(uint64_t)15) + 64 : (uint64_t)0; };
+
+    bool inflight = false; // a guessed tile is on its way into the buffer
+    uint64_t inflight_tb = 0;
+#ifdef LTHIP_ABLATIONS
+    uint32_t tiles = 0;
+#endif
+    // the pending list: pn chunks with pl leaves still to hash, phead of them of chunk 0 hashed already; last_nl = leaves of the newest chunk
+    uint32_t pn = 0, pl = 0, phead = 0, last_nl = 0;
+    // the walk (all wave-uniform): a part in hand, a chunk of it that needs a scan over the candidates [qlo, qhi], the tile at tb
+    bool have = false, scanning = false, drained = false;
+    PartDev pd = {};
+    uint32_t t = 0, n = 0, end = 0, slot = 0;
+    uint64_t size = 0, s = 0, qlo = 0, qhi = 0, tb = 0;
+    uint2* out = region;
+
+    auto emit = [&](uint32_t len) __attribute__((always_inline))
+    {
+        if (lane == 0)
+        {
+            const uint64_t at = pd.off + s;
+            out[n] = make_uint2((uint32_t)s, len);
+            pend[pn] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), len, slot);
+        }
+        last_nl = leaves_of(len);
+        ++n;
+        ++pn;
+        pl += last_nl;
+        slot += last_nl;
+        s += len;
+    };
+    // the chunk at s < size: true = it needs a scan (end, qlo, qhi set), false = it is `len` bytes without one (hpcdcchunker.c:257-264, and min == end)
+    auto classify = [&](uint32_t& len) __attribute__((always_inline)) -> bool
+    {
+        const uint64_t left = size - s;
+        len = left <= min_chunk ? (uint32_t)left : left > max_chunk ? max_chunk : (uint32_t)left; // :284
+        if (!(left > min_chunk && len > min_chunk))
+            return false;
+        end = len;
+        qlo = s + min_chunk; // a cut of length L needs candidate bit q = s + L - 1, L in [min + 1, end]
+        qhi = s + end - 1;
+        return true;
+    };
+
+    for (;;)
+    {
+        if (pl >= 64u || (drained && pl != 0u))
+        {
+            // ---- one round: lane L hashes pending leaf L ----
+            asm volatile("" ::: "memory"); // lane 0's list entries are in LDS in front of the lanes' reads (one wave: LDS is in order)
+            __builtin_amdgcn_wave_barrier();
+            const bool has = (uint32_t)lane < pn;
+            const uint4 e = pend[has ? lane : 0];
+            const uint32_t cnt = has ? leaves_of(e.z) - (lane == 0 ? phead : 0u) : 0u;
+            uint32_t incl = cnt; // inclusive scan over the lanes
+            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false); // row_shr:1
+            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false); // row_shr:2
+            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false); // row_shr:4
+            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false); // row_shr:8
+            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false); // row_bcast:15
+            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false); // row_bcast:31
+            const uint32_t excl = incl - cnt;
+            if (!has)
+                incl = 0xFFFFFFFFu;
+            const uint32_t take = pl < 64u ? pl : 64u;
+            // chunk j of the list holds leaf L: j = the chunks whose leaves end at or below L (incl is ascending; L < take <= incl[pn - 1])
+            uint32_t j = 0;
+#pragma unroll
+            for (uint32_t step = 32u; step; step >>= 1)
+                if ((uint32_t)__builtin_amdgcn_ds_bpermute((int)((j + step - 1u) * 4u), (int)incl) <= (uint32_t)lane)
+                    j += step;
+            const bool on = (uint32_t)lane < take;
+            if (!on)
+                j = 0;
+            const uint32_t k = (uint32_t)lane - (uint32_t)__builtin_amdgcn_ds_bpermute((int)(j * 4u), (int)excl) + (j == 0u ? phead : 0u);
+            const uint4 c = pend[j];
+            if (on)
+            {
+                uint32_t cv[8];
+                b3_leaf(cv, data + (((uint64_t)c.y << 32) | c.x) + ((uint64_t)k << 10), c.z, k);
+                uint4* o = reinterpret_cast<uint4*>(cv_runs + (uint64_t)(c.w + k) * 8u);
+                o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+                o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+            }
+            pl -= take;
+            if (pl != 0u) // (the rest of) the newest chunk
+            {
+                const uint32_t li = pn - 1u;
+                const uint4 l = make_uint4(__builtin_amdgcn_readlane(e.x, li), __builtin_amdgcn_readlane(e.y, li),
+                                           __builtin_amdgcn_readlane(e.z, li), __builtin_amdgcn_readlane(e.w, li));
+                if (lane == 0)
+                    pend[0] = l;
+                phead = last_nl - pl;
+                pn = 1;
+            }
+            else
+                pn = 0, phead = 0;
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            continue;
+        }
+        if (drained)
+            break;
+        if (!have)
+        {
+            // Every lane takes part in the draw (lane 0 adds one, the others zero): no lane-dependent branch around the loop-carried
+            // ticket (the compiler hazard)
+            __builtin_amdgcn_wave_barrier();
+            t = atomicAdd(ticket, lane == 0 ? 1u : 0u);
+            t = __builtin_amdgcn_readfirstlane(t);
+            if (t >= nparts)
+            {
+                drained = true;
+                continue;
+            }
+            pd = parts[t];
+            size = pd.size;
+            out = region + pd.region_base;
+            slot = (uint32_t)lthip_part_run_base(pd);
+            s = 0;
+            n = 0;
+            have = true;
+            scanning = false;
+        }
+        if (!scanning)
+        {
+            if (s >= size) // the part is done
+            {
+                if (inflight)
+                {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // nothing may land in the buffer behind the next part's first tile
+                    inflight = false;
+                }
+                if (lane == 0)
+                    part_count[t] = n;
+                have = false;
+                continue;
+            }
+            uint32_t len;
+            if (!classify(len))
+            {
+                emit(len);
+                continue;
+            }
+            tb = jump(qlo); // part-relative start of the tile's data
+            scanning = true;
+        }
+
+        // ---- one tile (k_buzhash_walk's, see there) ----
+        auto ends_here = [&]() __attribute__((always_inline)) { return (uint32_t)(qhi - tb) < (uint32_t)WTILE; };
+        if (!(inflight && inflight_tb == tb))
+        {
+            if (inflight)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the wrong guess has to land before the buffer is aimed at again
+            dma.issue(pd, tb);
+        }
+        inflight = false;
+        uint32_t win[16], hb;
+        dma.take(win, hb, pc);
+        if (GUESS)
+        {
+            uint64_t g = tb + (uint64_t)WTILE; // no cut in this tile: the chunk goes on ...
+            bool aim = true;
+            if (ends_here()) // ... or ends at `end`, and the walk jumps
+            {
+                const uint64_t s2 = s + end;
+                aim = size - s2 > min_chunk && max_chunk > min_chunk;
+                g = jump(s2 + min_chunk);
+            }
+            if (aim)
+            {
+                dma.issue(pd, g);
+                inflight = true;
+                inflight_tb = g;
+            }
+        }
+        const uint64_t raw = prefix_tile<MODE>(win, hb, pc, dv, lane, halo); // bit k <=> candidate tb + lane_base + k
+#ifdef LTHIP_ABLATIONS
+        ++tiles;
+#endif
+        for (;;) // the chunks that end in this tile
+        {
+            const int lo = (int)(qlo > tb ? qlo - tb : 0) - lane_base;
+            const int hi = (int)(ends_here() ? (uint32_t)(qhi - tb) : (uint32_t)WTILE - 1u) - lane_base;
+            uint64_t m = raw;
+            if (lo > 0)
+                m = lo > 63 ? 0ull : m & (~0ull << lo);
+            if (hi < 63)
+                m = hi < 0 ? 0ull : m & ((2ull << hi) - 1ull);
+            const uint64_t any = __builtin_amdgcn_ballot_w64(m != 0ull);
+            uint32_t len;
+            if (any != 0ull)
+            {
+                const int f = __builtin_ctzll(any);
+                const uint64_t q = tb + (uint64_t)(f * RUN + __builtin_ctzll(bcast64(m, f)));
+                len = (uint32_t)(q - s) + 1u;
+            }
+            else if (ends_here())
+                len = end; // no candidate up to the last legal one
+            else
+            {
+                tb += (uint64_t)WTILE; // the chunk goes on in the next tile, whose halo row is this tile's last 64 bytes
+                break;
+            }
+            emit(len);
+            uint32_t plain;
+            if (s >= size || !classify(plain)) // the part's end, or a chunk without a scan: the head of the loop deals with both
+            {
+                scanning = false;
+                break;
+            }
+            if ((uint32_t)(qlo - tb) < (uint32_t)WTILE && pl < 64u) // (tb < s <= qlo < size: the chunk before ended in this tile)
+                continue; // (min < 4 KiB) the next chunk's first candidate lies in this tile as well
+            tb = jump(qlo); // (a full list: this very tile again, behind the round)
+            break;
+        }
+    }
+#ifdef LTHIP_ABLATIONS
+    if (lane == 0 && tiles)
+        atomicAdd(&g_walk_tiles, (unsigned long long)tiles);
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------------
 // scans + compaction
 // ---------------------------------------------------------------------------------------------------
 constexpr int SCAN_THREADS = 256;
@@ -1162,18 +1427,27 @@ uint32_t lthip_k1_resident_waves(int device)
                         // whole test file ran on; the other is LTHIP_K1_WALK_GUESS=0 in the ablation build.
 #endif
 
-template <bool GUESS>
-static int launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count)
+// HASH: the scan that hashes the chunks it cuts (cv_runs), with the waves' pending lists behind the tile buffers
+template <bool GUESS, bool HASH>
+static int launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count,
+                               uint32_t* cv_runs)
 {
     constexpr int WAVES = 16;
-    const size_t lds = sizeof(uint32_t) * (256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW)); // (the budget of k_buzhash_prefix_dma)
+    constexpr size_t lds = sizeof(uint32_t) * (256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW)) // (the budget of k_buzhash_prefix_dma)
+                           + (HASH ? sizeof(uint4) * WAVES * PEND_CAP : 0);
+    static_assert(lds <= 160 * 1024 && (sizeof(uint32_t) * (256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW))) % 16 == 0,
+                  "LDS budget: one workgroup per CU; the lists are 16-byte aligned");
     auto k0 = &k_buzhash_walk<0, WAVES, GUESS>;
     auto k1 = &k_buzhash_walk<1, WAVES, GUESS>;
+    auto h0 = &k_buzhash_hash_walk<0, WAVES, GUESS>;
+    auto h1 = &k_buzhash_hash_walk<1, WAVES, GUESS>;
     static bool granted[64] = {}; // per device: more than 64 KiB of dynamic LDS has to be granted explicitly
     if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device])
     {
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        LTHIP_CHECK(ctx, hipFuncSetAttribute(HASH ? reinterpret_cast<const void*>(h0) : reinterpret_cast<const void*>(k0),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        LTHIP_CHECK(ctx, hipFuncSetAttribute(HASH ? reinterpret_cast<const void*>(h1) : reinterpret_cast<const void*>(k1),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (ctx->device >= 0 && ctx->device < 64)
             granted[ctx->device] = true;
     }
@@ -1186,23 +1460,30 @@ static int launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uin
         grid = (uint32_t)div_up_u64(plan->nparts, WAVES);
     LaunchTimer t(ctx, LTHIP_K_BUZHASH);
     LTHIP_CHECK(ctx, hipMemsetAsync(ticket, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(plan->div.pow2 ? k1 : k0, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts,
-                       plan->div, plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket);
+    if (HASH)
+        hipLaunchKernelGGL(plan->div.pow2 ? h1 : h0, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts,
+                           plan->div, plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket, cv_runs);
+    else
+        hipLaunchKernelGGL(plan->div.pow2 ? k1 : k0, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts,
+                           plan->div, plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }
 
 // the walking scan: candidate scan and cut selection of every part in one launch (region / part_count as lthip_launch_select leaves them)
-int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count)
+int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count,
+                              uint32_t* cv_runs)
 {
     if (plan->nparts == 0)
         return 0;
 #ifdef LTHIP_ABLATIONS
     LTHIP_ABLATION_ENV(env_guess, "LTHIP_K1_WALK_GUESS"); // 0 / 1: the other form of the prefetch
     if (env_guess.get() >= 0 && (env_guess.get() != 0) != (K1_WALK_GUESS != 0))
-        return launch_buzhash_walk<!K1_WALK_GUESS>(ctx, plan, d_data, region, part_count);
+        return cv_runs ? launch_buzhash_walk<!K1_WALK_GUESS, true>(ctx, plan, d_data, region, part_count, cv_runs)
+                       : launch_buzhash_walk<!K1_WALK_GUESS, false>(ctx, plan, d_data, region, part_count, nullptr);
 #endif
-    return launch_buzhash_walk<K1_WALK_GUESS != 0>(ctx, plan, d_data, region, part_count);
+    return cv_runs ? launch_buzhash_walk<K1_WALK_GUESS != 0, true>(ctx, plan, d_data, region, part_count, cv_runs)
+                   : launch_buzhash_walk<K1_WALK_GUESS != 0, false>(ctx, plan, d_data, region, part_count, nullptr);
 }
 
 // (ablation build) wave-tiles the walking scans of this process have hashed since the last call; waits for the device

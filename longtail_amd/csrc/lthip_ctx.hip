@@ -923,21 +923,42 @@ extern "C" uint32_t lthip_plan_walked_scans(const lthip_plan* plan)
     return n;
 }
 
+#ifndef LTHIP_WALK_HASH
+#define LTHIP_WALK_HASH 1 // 1: a scan that walks hashes the leaves of the chunks it cuts (k_buzhash_hash_walk); 0: the leaf pass of its own behind it
+#endif
+// whether the scan of (this slice of) a plan hashes the leaves of its chunks as well: a scan that walks, when hashes are asked for
+// (ablation build: LTHIP_WALK_HASH = 0 / 1 forces either form)
+static bool plan_walk_hashes(const lthip_plan* plan, bool hashes)
+{
+    LTHIP_ABLATION_ENV(env_fused, "LTHIP_WALK_HASH");
+    const bool on = env_fused.get() >= 0 ? env_fused.get() != 0 : LTHIP_WALK_HASH != 0;
+    return on && hashes && plan_walks(plan) && lthip_plan_run_slots(plan) <= 0xFFFFFFF0ull; // (a run's slot is a 32-bit number; the leaf pass has the same limit)
+}
+uint64_t lthip_plan_run_slots(const lthip_plan* plan) { return plan->chunk_cap + 16u * plan->ntiles; }
+
 // ---------------------------------------------------------------------------------------------------
 // phase 1
 // ---------------------------------------------------------------------------------------------------
 // What the scans of a whole plan leave for cut selection and compaction (the slices' lie back to back in them): the candidate bitmaps
-// of the tile scan -- a plan whose scans all walk needs none -- and the bounded chunk region with the per-part counts.
+// of the tile scan -- a plan whose scans all walk needs none -- and the bounded chunk region with the per-part counts; with hashes, the
+// runs of leaf chaining values of the scans that hash.
 struct ScanBuffers
 {
     uint64_t *bm0, *bm1;
     uint2* region;
     uint32_t* part_count;
+    uint32_t* cv_runs;
 };
-static int chunk_scan_buffers(lthip_ctx* ctx, const lthip_plan* plan, bool bitmaps, ScanBuffers* b)
+static int chunk_scan_buffers(lthip_ctx* ctx, const lthip_plan* plan, bool bitmaps, bool hashes, ScanBuffers* b)
 {
     b->bm0 = b->bm1 = nullptr;
+    b->cv_runs = nullptr;
     int err;
+    bool runs = !plan->sliced && plan_walk_hashes(plan, hashes);
+    for (uint32_t k = 0; plan->sliced && k < plan->nslices; ++k)
+        runs |= plan_walk_hashes(plan->slice[k], hashes);
+    if (runs && (err = lthip_scratch(ctx, S_CV_RUNS, lthip_plan_run_slots(plan) * 32, (void**)&b->cv_runs)))
+        return err;
     if (bitmaps && ((err = lthip_scratch(ctx, S_BM0, plan->bm0_words * 8, (void**)&b->bm0)) ||
                     (err = lthip_scratch(ctx, S_BM1, plan->bm1_words * 8, (void**)&b->bm1))))
         return err;
@@ -952,7 +973,8 @@ static int chunk_scan(lthip_ctx* ctx, const lthip_plan* plan, const void* d_data
 {
     if (!plan->nparts)
         return 0;
-    return plan_walks(plan) ? lthip_launch_buzhash_walk(ctx, plan, (const uint8_t*)d_data, b.region, b.part_count)
+    return plan_walks(plan) ? lthip_launch_buzhash_walk(ctx, plan, (const uint8_t*)d_data, b.region, b.part_count,
+                                                        plan_walk_hashes(plan, b.cv_runs != nullptr) ? b.cv_runs : nullptr)
                             : lthip_launch_buzhash(ctx, plan, (const uint8_t*)d_data, b.bm0, b.bm1);
 }
 
@@ -965,9 +987,13 @@ static int chunk_cut_hash(lthip_ctx* ctx, const lthip_plan* plan, const void* d_
         return err;
     if ((err = lthip_launch_compact(ctx, plan, b.region, b.part_count, d_part_first, d_offsets, d_lens)))
         return err;
-    return d_hashes ? lthip_launch_blake3(ctx, (const uint8_t*)d_data, d_offsets, d_lens, d_part_first + plan->nparts, plan->chunk_cap,
-                                          plan->leaf_cap, plan->max_chunk, d_hashes)
-                    : 0;
+    if (!d_hashes)
+        return 0;
+    if (plan_walk_hashes(plan, b.cv_runs != nullptr)) // the scan has hashed the leaves
+        return lthip_launch_blake3_parents(ctx, lthip_b3_runs{b.cv_runs, plan->d_parts, plan->nparts, d_part_first}, d_lens,
+                                           d_part_first + plan->nparts, plan->chunk_cap, plan->leaf_cap, plan->max_chunk, d_hashes);
+    return lthip_launch_blake3(ctx, (const uint8_t*)d_data, d_offsets, d_lens, d_part_first + plan->nparts, plan->chunk_cap, plan->leaf_cap,
+                               plan->max_chunk, d_hashes);
 }
 
 // a slice's lists behind the slices before it: base = part_first[0] (= the chunk count of everything before the slice, final by now),
@@ -1019,7 +1045,7 @@ static int chunk_hash_sliced(lthip_ctx* ctx, const lthip_plan* plan, const void*
     const bool bitmaps = lthip_plan_walked_scans(plan) != S;
     if (lthip_scratch(ctx, S_SLICE_OFFS, cap_rest * 8, &x_off) || lthip_scratch(ctx, S_SLICE_LENS, cap_rest * 4, &x_len) ||
         lthip_scratch(ctx, S_SLICE_HASH, cap_rest * 8, &x_hash) || lthip_scratch(ctx, S_SLICE_FIRST, parts_rest * 4, &x_first) ||
-        chunk_scan_buffers(ctx, plan, bitmaps, &sb))
+        chunk_scan_buffers(ctx, plan, bitmaps, true, &sb))
     {
         ctx->err[0] = 0;
         return 0;
@@ -1057,6 +1083,8 @@ static int chunk_hash_sliced(lthip_ctx* ctx, const lthip_plan* plan, const void*
         }
         sb.region += pk->chunk_cap;
         sb.part_count += pk->nparts;
+        if (sb.cv_runs)
+            sb.cv_runs += lthip_plan_run_slots(pk) * 8;
     }
     // the join (also after a failure: the context's stream never runs ahead of the second one)
     hipEvent_t hashed = lthip_sync_event(ctx);
@@ -1096,7 +1124,7 @@ extern "C" int lthip_chunk_hash(lthip_ctx* ctx, const lthip_plan* plan, const vo
     bool sliced;
     int err = chunk_hash_sliced(ctx, plan, d_data, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first, &sliced);
     ScanBuffers sb;
-    if (!sliced && !(err = chunk_scan_buffers(ctx, plan, !plan_walks(plan), &sb)) && !(err = chunk_scan(ctx, plan, d_data, sb)))
+    if (!sliced && !(err = chunk_scan_buffers(ctx, plan, !plan_walks(plan), d_chunk_hashes != nullptr, &sb)) && !(err = chunk_scan(ctx, plan, d_data, sb)))
         err = chunk_cut_hash(ctx, plan, d_data, sb, d_chunk_offsets, d_chunk_lens, d_chunk_hashes, d_part_first);
     if (err)
         return err;

@@ -29,6 +29,11 @@ struct PartDev
     uint32_t region_cap;  // slots in the region
 };
 
+// The walking scan that hashes (k_buzhash_hash_walk) gives every part a run of slots for the chaining values of its leaves, sized by a
+// bound of them: a leaf per chunk beyond ceil(size / 1024) at the most, and ceil(size / 1024) <= 16 tiles of 16 KiB.  So the runs need no
+// field of their own: part p's starts at region_base + 16 tile_base, and a plan's take chunk_cap + 16 ntiles slots.
+__host__ __device__ inline uint64_t lthip_part_run_base(const PartDev& p) { return p.region_base + 16ull * p.tile_base; }
+
 // exact "H % d == d-1" test without a division:  d = dodd << k2 ;  inv = dodd^-1 mod 2^32
 //   t = ror32(h*inv + addc, k2) <= qlim            (lthip_plan.cpp explains the derivation)
 struct DivTest
@@ -55,6 +60,8 @@ struct PlanExtents
     uint64_t max_part_bytes;
 };
 
+struct lthip_plan;
+uint64_t lthip_plan_run_slots(const lthip_plan* plan); // slots of the plan's runs of leaf chaining values (lthip_part_run_base)
 struct lthip_plan : PlanExtents
 {
     int device;
@@ -131,6 +138,8 @@ enum ScratchSlot
     S_RAW_TABLES,      // ... and the hash / BlockIndex tables of lthip_write_raw_block_images
     S_CARRY_RUNS,      // restore session, lthip_restore_carry: boundary flags and their scan, the runs, their piece counts and the scan of those
     S_ARCHIVE_ITEMS,   // archive writer, lthip_archive_writer_append: {source, destination, size} of the call's images
+    S_CV_RUNS,         // 8 x u32 per leaf slot of the parts' runs (the walking scan that hashes)
+    S_CV_SLOTS,        // ... and per dense chunk the slot of its first leaf in them (u32)
     S_COUNT
 };
 
@@ -292,8 +301,11 @@ struct LaunchTimer
 // ---------------------------------------------------------------------------------------------------
 int lthip_launch_tile_table(lthip_ctx* ctx, lthip_plan* plan);
 int lthip_launch_buzhash(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint64_t* bm0, uint64_t* bm1);
-// K1 + K2 in one launch, a wave per part (k_buzhash.hip: the walking scan); needs neither bitmap
-int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count);
+// K1 + K2 in one launch, a wave per part (k_buzhash.hip: the walking scan); needs neither bitmap.  cv_runs != null: K3's leaf pass as
+// well -- the wave that cuts a chunk hashes its leaves, chaining values to the part's run of cv_runs (8 words a slot, lthip_plan_run_slots
+// of them, below 2^32) -- and lthip_launch_blake3_parents finishes the hashes behind compaction
+int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count,
+                              uint32_t* cv_runs);
 uint32_t lthip_k1_resident_waves(int device); // waves of a K1 launch that the device holds at a time
 int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* bm0, const uint64_t* bm1, uint2* region,
                         uint32_t* part_count);
@@ -364,6 +376,17 @@ int lthip_exclusive_scan_u32(lthip_ctx* ctx, const uint32_t* d_in, uint32_t* d_o
 int lthip_launch_blake3(lthip_ctx* ctx, const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_lens,
                         const uint32_t* d_count, uint64_t count_bound, uint64_t leaf_bound, uint64_t max_len,
                         uint64_t* d_hashes);
+
+// The same for the chunks of a plan whose leaves the walking scan has hashed: the runs are moved to the dense leaf order, then the parents
+struct lthip_b3_runs
+{
+    const uint32_t* d_cvs;        // the runs (lthip_part_run_base)
+    const PartDev* d_parts;
+    uint32_t nparts;              // > 0
+    const uint32_t* d_part_first; // nparts + 1: the parts' first chunks in the dense lists (d_count = its last entry)
+};
+int lthip_launch_blake3_parents(lthip_ctx* ctx, const lthip_b3_runs& runs, const uint32_t* d_lens, const uint32_t* d_count,
+                                uint64_t count_bound, uint64_t leaf_bound, uint64_t max_len, uint64_t* d_hashes);
 
 int lthip_hash_ranges_known(lthip_ctx* ctx, const void* d_data, uint64_t range_count, const uint64_t* d_offsets, const uint32_t* d_lens,
                             uint32_t max_len, uint64_t leaf_total, uint64_t* d_hashes); // lthip_hash_ranges without its read-back
