@@ -871,13 +871,9 @@ int lthip_launch_blake3_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64
     const size_t lds = 64 * 8 * 4 + (size_t)(len ? (len + 1023u) >> 10 : 1u) * B3_ONE_PITCH;
     if (lds > 64u * 1024u)
     {
-        static bool granted[64] = {}; // per device: more than 64 KiB of dynamic LDS has to be granted explicitly
-        if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device])
-        {
-            LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_blake3_one), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            if (ctx->device >= 0 && ctx->device < 64)
-                granted[ctx->device] = true;
-        }
+        static std::atomic<bool> granted[64] = {};
+        if (int err = lthip_grant_lds(ctx, granted, {reinterpret_cast<const void*>(&k_blake3_one)}, 80 * 1024))
+            return err;
     }
     hipLaunchKernelGGL(k_blake3_one, dim3(1), dim3(64), lds, ctx->stream, (const uint8_t*)in, len, out);
     LTHIP_LAUNCH_CHECK(ctx);

@@ -353,6 +353,28 @@ __device__ __forceinline__ void prefix_table_init(uint32_t* tab, int tid, int nt
 // in front of that issue, so that the vmcnt(0) which retires the DMA never waits for a store just issued.
 constexpr int DMA_BUF_B = WROWS * 64; // 4160 bytes, linear
 
+// The dynamic LDS of the kernels fed by LDS-DMA, in dwords: the table, then per wave its tile buffer and its halo[]; behind them, in the
+// walking scan that hashes, per wave a pending list of PEND_CAP chunks (uint4 each).  Kernels and launchers read the layout from here.
+constexpr int TAB_DW = 256 * TAB_REP;
+constexpr int DMA_WAVE_DW = (DMA_BUF_B >> 2) + HALO_DW;
+constexpr int PEND_CAP = 64;
+constexpr size_t lds_tiles_dw(int waves) { return TAB_DW + (size_t)waves * DMA_WAVE_DW; }
+constexpr size_t lds_pend_dw(int waves) { return lds_tiles_dw(waves); } // where the lists start
+constexpr size_t lds_bytes(int waves, bool lists) { return sizeof(uint32_t) * lds_pend_dw(waves) + (lists ? sizeof(uint4) * waves * PEND_CAP : 0); }
+
+struct WaveLds
+{
+    uint32_t* buf;  // the wave's tile buffer (TileDma)
+    uint32_t* halo; // HALO_DW dwords behind it
+    uint4* pend;    // the wave's pending list: there only if the launch asked for lds_bytes(WAVES, true)
+};
+template <int WAVES>
+__device__ __forceinline__ WaveLds wave_lds(uint32_t* smem, int wave)
+{
+    uint32_t* buf = smem + TAB_DW + wave * DMA_WAVE_DW;
+    return {buf, buf + (DMA_BUF_B >> 2), reinterpret_cast<uint4*>(smem + lds_pend_dw(WAVES)) + wave * PEND_CAP};
+}
+
 // The LDS-DMA staging of one wave: its buffer, the lane's place in a DMA instruction and in the buffer, and the issue of a wave-tile.
 struct TileDma
 {
@@ -500,11 +522,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix_dma(const uint
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    uint32_t* buf = smem + 256 * TAB_REP + wave * ((DMA_BUF_B >> 2) + HALO_DW);
-    uint32_t* halo = buf + (DMA_BUF_B >> 2);
+    const WaveLds lds = wave_lds<WAVES>(smem, wave);
+    uint32_t* const halo = lds.halo;
     prefix_table_init(smem, tid, 64 * WAVES);
 
-    const TileDma dma(data, buf, lane);
+    const TileDma dma(data, lds.buf, lane);
     const PrefixConsts pc = dma.consts<MODE>(dv);
 
     const uint64_t nwt = (uint64_t)ntiles * 4u;
@@ -655,7 +677,7 @@ __global__ __launch_bounds__(64) void k_select_cuts(const PartDev* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K1 + K2 in one, the WALKING scan: a wave owns a whole part and walks it chunk by chunk.
+// K1 + K2 in one, the WALKING scan: a wave owns a whole part and walks it chunk by chunk.  HASH: K3's leaf pass as well.
 //
 // k_select_cuts reads only the candidate bits q in [s + min, s + end - 1] of a chunk that starts at s, and a candidate at q depends on
 // the bytes [q - 47, q] alone: the first min - 47 bytes of every chunk are hashed for nothing by a scan that does not know where the
@@ -668,26 +690,42 @@ __global__ __launch_bounds__(64) void k_select_cuts(const PartDev* __restrict__ 
 // holds no cut (the next 4 KiB, or the jump target behind a chunk that ends at `end`); a cut makes the guess wrong, and the tile is
 // issued again.  Without it a tile's DMA is issued when the walk knows where it goes (ablation build: the measured alternative).
 // Needs many more parts than resident waves (the host decides: plan_walk_rule, lthip_ctx.hip).
+// The walk is ONE loop: a part is drawn, a chunk that needs no scan is emitted, a tile is hashed, or (HASH) a round is run, one of them
+// per trip.  So the round stands at one place in the code (it is three compressions long), and every emission is followed by the test
+// for a round before the next one.
+//
+// HASH: the waves hash the chunks they cut.  The scan leaves a SIMD's issue slots about a quarter idle (LDS round trips of the table
+// look-ups) and the leaf pass is pure vector issue, so waves that scan and waves that hash fill each other's holes when they share a
+// SIMD.  Here they are the same waves: a wave that emits a chunk holds its (s, len) in scalars, so it appends it to a pending list of
+// its own in LDS -- {byte offset in data, len, chaining-value slot of its first leaf} -- and whenever 64 leaves are pending it runs one
+// round of b3_leaf (k_blake3_leaf.h: the body of k_blake3_leaves), a leaf per lane.  A lane finds its (chunk, leaf) by a wave scan over
+// the pending chunks' leaf counts.  The list is the only hand-off (no lane reads region[] back), it carries across parts, so only a
+// wave's last round is short, and a chunk of more than 64 leaves spans rounds.  Nothing waits for another wave.
+// At most 63 leaves are pending in front of an emission, so the list never holds more than 64 chunks, and behind a round of 64 only
+// (the rest of) the last chunk is left.  Rounds run between tiles, where the walk's state is scalar and the tile's registers are dead; a
+// guessed tile may be on its way into the buffer meanwhile (the list has LDS of its own).  A tile with several cuts (min < 4 KiB) is
+// left when the list fills up and hashed again behind the round.
+// Chaining values go to the part's run of cv_runs (lthip_part_run_base), densely from its start in chunk order: leaf k of a chunk at
+// slot + k.  Flags and counter are the leaf kernel's.  region[] and part_count[] are the same with and without HASH.
 // ---------------------------------------------------------------------------------------------------
 #ifdef LTHIP_ABLATIONS
 __device__ unsigned long long g_walk_tiles; // wave-tiles hashed by the walking scans of this process (lthip_debug_walk_tiles)
 #endif
 
-template <int MODE, int WAVES, bool GUESS>
-__global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts,
-                                                                 uint32_t nparts, DivTest dv, uint32_t min_chunk, uint32_t max_chunk,
-                                                                 uint2* __restrict__ region, uint32_t* __restrict__ part_count,
-                                                                 uint32_t* __restrict__ ticket)
+template <int MODE, int WAVES, bool GUESS, bool HASH>
+__device__ __forceinline__ void walk_body(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts, uint32_t nparts, DivTest dv,
+                                          uint32_t min_chunk, uint32_t max_chunk, uint2* __restrict__ region,
+                                          uint32_t* __restrict__ part_count, uint32_t* __restrict__ ticket, uint32_t* __restrict__ cv_runs)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    uint32_t* buf = smem + 256 * TAB_REP + wave * ((DMA_BUF_B >> 2) + HALO_DW);
-    uint32_t* halo = buf + (DMA_BUF_B >> 2);
+    const WaveLds lds = wave_lds<WAVES>(smem, __builtin_amdgcn_readfirstlane(tid >> 6));
+    uint32_t* const halo = lds.halo;
+    [[maybe_unused]] uint4* const pend = lds.pend;
     prefix_table_init(smem, tid, 64 * WAVES);
 
-    const TileDma dma(data, buf, lane);
+    const TileDma dma(data, lds.buf, lane);
     const PrefixConsts pc = dma.consts<MODE>(dv);
     const int lane_base = lane * RUN;
 
@@ -699,190 +737,13 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* _
 #ifdef LTHIP_ABLATIONS
     uint32_t tiles = 0;
 #endif
-    for (;;)
-    {
-        // Every lane takes part in the draw (lane 0 adds one, the others zero): no lane-dependent branch around the loop-carried
-        // ticket (the compiler hazard)
-        __builtin_amdgcn_wave_barrier();
-        uint32_t t = atomicAdd(ticket, lane == 0 ? 1u : 0u);
-        t = __builtin_amdgcn_readfirstlane(t);
-        if (t >= nparts)
-            break;
-        const PartDev pd = parts[t];
-        const uint64_t size = pd.size;
-        uint2* out = region + pd.region_base;
-        uint64_t s = 0, qlo = 0, qhi = 0;
-        uint32_t n = 0, end = 0;
-
-        // the chunks at s that need no scan (hpcdcchunker.c:257-264, and min == end); true: a scan over the candidates [qlo, qhi]
-        auto next_chunk = [&]() __attribute__((always_inline)) -> bool
-        {
-            for (;;)
-            {
-                if (s >= size)
-                    return false;
-                const uint64_t left = size - s;
-                const uint32_t len = left <= min_chunk ? (uint32_t)left : left > max_chunk ? max_chunk : (uint32_t)left; // :284
-                if (left > min_chunk && len > min_chunk)
-                {
-                    end = len;
-                    qlo = s + min_chunk; // a cut of length L needs candidate bit q = s + L - 1, L in [min + 1, end]
-                    qhi = s + end - 1;
-                    return true;
-                }
-                if (lane == 0)
-                    out[n] = make_uint2((uint32_t)s, len);
-                ++n;
-                s += len;
-            }
-        };
-
-        if (next_chunk())
-        {
-            uint64_t tb = jump(qlo); // part-relative start of the tile's data
-            // whether the chunk's last legal candidate lies in the tile at tb.  tb <= qlo <= qhi < size < 2^32 whenever a tile is hashed
-            // (tb = jump(qlo), or moved on by a tile because qhi lay behind it), so the distance is a 32-bit scalar
-            auto ends_here = [&]() __attribute__((always_inline)) { return (uint32_t)(qhi - tb) < (uint32_t)WTILE; };
-            for (bool walking = true; walking;)
-            {
-                if (!(inflight && inflight_tb == tb))
-                {
-                    if (inflight)
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the wrong guess has to land before the buffer is aimed at again
-                    dma.issue(pd, tb);
-                }
-                inflight = false;
-                uint32_t win[16], hb;
-                dma.take(win, hb, pc);
-                if (GUESS)
-                {
-                    uint64_t g = tb + (uint64_t)WTILE; // no cut in this tile: the chunk goes on ...
-                    bool aim = true;
-                    if (ends_here()) // ... or ends at `end`, and the walk jumps
-                    {
-                        const uint64_t s2 = s + end;
-                        aim = size - s2 > min_chunk && max_chunk > min_chunk;
-                        g = jump(s2 + min_chunk);
-                    }
-                    if (aim)
-                    {
-                        dma.issue(pd, g);
-                        inflight = true;
-                        inflight_tb = g;
-                    }
-                }
-                const uint64_t raw = prefix_tile<MODE>(win, hb, pc, dv, lane, halo); // bit k <=> candidate tb + lane_base + k
-#ifdef LTHIP_ABLATIONS
-                ++tiles;
-#endif
-                for (;;) // the chunks that end in this tile
-                {
-                    // the legal bits of the run: [qlo, qhi] relative to the tile, then to the run (beyond the part: qhi < size)
-                    const int lo = (int)(qlo > tb ? qlo - tb : 0) - lane_base;
-                    const int hi = (int)(ends_here() ? (uint32_t)(qhi - tb) : (uint32_t)WTILE - 1u) - lane_base;
-                    uint64_t m = raw;
-                    if (lo > 0)
-                        m = lo > 63 ? 0ull : m & (~0ull << lo);
-                    if (hi < 63)
-                        m = hi < 0 ? 0ull : m & ((2ull << hi) - 1ull);
-                    const uint64_t any = __builtin_amdgcn_ballot_w64(m != 0ull);
-                    uint32_t len;
-                    if (any != 0ull)
-                    {
-                        const int f = __builtin_ctzll(any);
-                        const uint64_t q = tb + (uint64_t)(f * RUN + __builtin_ctzll(bcast64(m, f)));
-                        len = (uint32_t)(q - s) + 1u;
-                    }
-                    else if (ends_here())
-                        len = end; // no candidate up to the last legal one
-                    else
-                    {
-                        tb += (uint64_t)WTILE; // the chunk goes on in the next tile, whose halo row is this tile's last 64 bytes
-                        break;
-                    }
-                    if (lane == 0)
-                        out[n] = make_uint2((uint32_t)s, len);
-                    ++n;
-                    s += len;
-                    if (!next_chunk())
-                    {
-                        walking = false;
-                        break;
-                    }
-                    if ((uint32_t)(qlo - tb) < (uint32_t)WTILE) // (tb < s <= qlo < size: the chunk before ended in this tile)
-                        continue; // (min < 4 KiB) the next chunk's first candidate lies in this tile as well
-                    tb = jump(qlo);
-                    break;
-                }
-            }
-        }
-        if (inflight)
-        {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // nothing may land in the buffer behind the next part's first tile
-            inflight = false;
-        }
-        if (lane == 0)
-            part_count[t] = n;
-    }
-#ifdef LTHIP_ABLATIONS
-    if (lane == 0 && tiles)
-        atomicAdd(&g_walk_tiles, (unsigned long long)tiles);
-#endif
-}
-
-// ---------------------------------------------------------------------------------------------------
-// K1 + K2 + K3's leaf pass in one: the walking scan whose waves HASH the chunks they cut.
-//
-// The scan leaves a SIMD's issue slots about a quarter idle (LDS round trips of the table look-ups) and the leaf pass is pure vector
-// issue, so waves that scan and waves that hash fill each other's holes when they share a SIMD.  Here they are the same waves: a wave
-// that emits a chunk holds its (s, len) in scalars, so it appends it to a pending list of its own in LDS -- {byte offset in data, len,
-// chaining-value slot of its first leaf} -- and whenever 64 leaves are pending it runs one round of b3_leaf (k_blake3_leaf.h: the body
-// of k_blake3_leaves), a leaf per lane.  A lane finds its (chunk, leaf) by a wave scan over the pending chunks' leaf counts.  The list
-// is the only hand-off (no lane reads region[] back), it carries across parts, so only a wave's last round is short, and a chunk of
-// more than 64 leaves spans rounds.  Nothing waits for another wave.
-// The walk is k_buzhash_walk's, written as ONE loop so that the round stands at one place in the code (it is three compressions long)
-// and every emission is followed by the test for a round before the next one: a part is drawn, a chunk that needs no scan is emitted,
-// a tile is hashed, or a round is run, one of them per trip.  At most 63 leaves are pending in front of an emission, so the list never
-// holds more than 64 chunks, and behind a round of 64 only (the rest of) the last chunk is left.  Rounds run between tiles, where the
-// walk's state is scalar and the tile's registers are dead; a guessed tile may be on its way into the buffer meanwhile (the list has
-// LDS of its own).  A tile with several cuts (min < 4 KiB) is left when the list fills up and hashed again behind the round.
-// Chaining values go to the part's run of cv_runs (lthip_part_run_base), densely from its start in chunk order: leaf k of a chunk at
-// slot + k.  Flags and counter are the leaf kernel's.  region[] and part_count[] are written exactly as by k_buzhash_walk.
-// ---------------------------------------------------------------------------------------------------
-constexpr int PEND_CAP = 64; // chunks of a wave's pending list (uint4 each)
-
-template <int MODE, int WAVES, bool GUESS>
-__global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts,
-                                                                      uint32_t nparts, DivTest dv, uint32_t min_chunk, uint32_t max_chunk,
-                                                                      uint2* __restrict__ region, uint32_t* __restrict__ part_count,
-                                                                      uint32_t* __restrict__ ticket, uint32_t* __restrict__ cv_runs)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    uint32_t* buf = smem + 256 * TAB_REP + wave * ((DMA_BUF_B >> 2) + HALO_DW);
-    uint32_t* halo = buf + (DMA_BUF_B >> 2);
-    uint4* pend = reinterpret_cast<uint4*>(smem + 256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW)) + wave * PEND_CAP;
-    prefix_table_init(smem, tid, 64 * WAVES);
-
-    const TileDma dma(data, buf, lane);
-    const PrefixConsts pc = dma.consts<MODE>(dv);
-    const int lane_base = lane * RUN;
-
-    auto jump = [](uint64_t q) __attribute__((always_inline)) { return q >= 64 ? ((q - 64) & ~(uint64_t)15) + 64 : (uint64_t)0; };
-
-    bool inflight = false; // a guessed tile is on its way into the buffer
-    uint64_t inflight_tb = 0;
-#ifdef LTHIP_ABLATIONS
-    uint32_t tiles = 0;
-#endif
-    // the pending list: pn chunks with pl leaves still to hash, phead of them of chunk 0 hashed already; last_nl = leaves of the newest chunk
-    uint32_t pn = 0, pl = 0, phead = 0, last_nl = 0;
+    // (HASH) the pending list: pn chunks with pl leaves still to hash, phead of them of chunk 0 hashed already; last_nl = leaves of the
+    // newest chunk; slot = the chaining-value slot of the next chunk's first leaf
+    [[maybe_unused]] uint32_t pn = 0, pl = 0, phead = 0, last_nl = 0, slot = 0;
     // the walk (all wave-uniform): a part in hand, a chunk of it that needs a scan over the candidates [qlo, qhi], the tile at tb
     bool have = false, scanning = false, drained = false;
     PartDev pd = {};
-    uint32_t t = 0, n = 0, end = 0, slot = 0;
+    uint32_t t = 0, n = 0, end = 0;
     uint64_t size = 0, s = 0, qlo = 0, qhi = 0, tb = 0;
     uint2* out = region;
 
@@ -890,15 +751,20 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
     {
         if (lane == 0)
         {
-            const uint64_t at = pd.off + s;
+            [[maybe_unused]] const uint64_t at = pd.off + s;
             out[n] = make_uint2((uint32_t)s, len);
-            pend[pn] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), len, slot);
+            if constexpr (HASH)
+                pend[pn] = make_uint4((uint32_t)at, (uint32_t)(at >> 32), len, slot);
         }
-        last_nl = leaves_of(len);
+        if constexpr (HASH)
+            last_nl = leaves_of(len);
         ++n;
-        ++pn;
-        pl += last_nl;
-        slot += last_nl;
+        if constexpr (HASH)
+        {
+            ++pn;
+            pl += last_nl;
+            slot += last_nl;
+        }
         s += len;
     };
     // the chunk at s < size: true = it needs a scan (end, qlo, qhi set), false = it is `len` bytes without one (hpcdcchunker.c:257-264, and min == end)
@@ -916,61 +782,62 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
 
     for (;;)
     {
-        if (pl >= 64u || (drained && pl != 0u))
-        {
-            // ---- one round: lane L hashes pending leaf L ----
-            asm volatile("" ::: "memory"); // lane 0's list entries are in LDS in front of the lanes' reads (one wave: LDS is in order)
-            __builtin_amdgcn_wave_barrier();
-            const bool has = (uint32_t)lane < pn;
-            const uint4 e = pend[has ? lane : 0];
-            const uint32_t cnt = has ? leaves_of(e.z) - (lane == 0 ? phead : 0u) : 0u;
-            uint32_t incl = cnt; // inclusive scan over the lanes
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false); // row_shr:1
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false); // row_shr:2
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false); // row_shr:4
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false); // row_shr:8
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false); // row_bcast:15
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false); // row_bcast:31
-            const uint32_t excl = incl - cnt;
-            if (!has)
-                incl = 0xFFFFFFFFu;
-            const uint32_t take = pl < 64u ? pl : 64u;
-            // chunk j of the list holds leaf L: j = the chunks whose leaves end at or below L (incl is ascending; L < take <= incl[pn - 1])
-            uint32_t j = 0;
+        if constexpr (HASH)
+            if (pl >= 64u || (drained && pl != 0u))
+            {
+                // ---- one round: lane L hashes pending leaf L ----
+                asm volatile("" ::: "memory"); // lane 0's list entries are in LDS in front of the lanes' reads (one wave: LDS is in order)
+                __builtin_amdgcn_wave_barrier();
+                const bool has = (uint32_t)lane < pn;
+                const uint4 e = pend[has ? lane : 0];
+                const uint32_t cnt = has ? leaves_of(e.z) - (lane == 0 ? phead : 0u) : 0u;
+                uint32_t incl = cnt; // inclusive scan over the lanes
+                incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, false); // row_shr:1
+                incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, false); // row_shr:2
+                incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, false); // row_shr:4
+                incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xf, 0xf, false); // row_shr:8
+                incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xa, 0xf, false); // row_bcast:15
+                incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xc, 0xf, false); // row_bcast:31
+                const uint32_t excl = incl - cnt;
+                if (!has)
+                    incl = 0xFFFFFFFFu;
+                const uint32_t take = pl < 64u ? pl : 64u;
+                // chunk j of the list holds leaf L: j = the chunks whose leaves end at or below L (incl is ascending; L < take <= incl[pn - 1])
+                uint32_t j = 0;
 #pragma unroll
-            for (uint32_t step = 32u; step; step >>= 1)
-                if ((uint32_t)__builtin_amdgcn_ds_bpermute((int)((j + step - 1u) * 4u), (int)incl) <= (uint32_t)lane)
-                    j += step;
-            const bool on = (uint32_t)lane < take;
-            if (!on)
-                j = 0;
-            const uint32_t k = (uint32_t)lane - (uint32_t)__builtin_amdgcn_ds_bpermute((int)(j * 4u), (int)excl) + (j == 0u ? phead : 0u);
-            const uint4 c = pend[j];
-            if (on)
-            {
-                uint32_t cv[8];
-                b3_leaf(cv, data + (((uint64_t)c.y << 32) | c.x) + ((uint64_t)k << 10), c.z, k);
-                uint4* o = reinterpret_cast<uint4*>(cv_runs + (uint64_t)(c.w + k) * 8u);
-                o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-                o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+                for (uint32_t step = 32u; step; step >>= 1)
+                    if ((uint32_t)__builtin_amdgcn_ds_bpermute((int)((j + step - 1u) * 4u), (int)incl) <= (uint32_t)lane)
+                        j += step;
+                const bool on = (uint32_t)lane < take;
+                if (!on)
+                    j = 0;
+                const uint32_t k = (uint32_t)lane - (uint32_t)__builtin_amdgcn_ds_bpermute((int)(j * 4u), (int)excl) + (j == 0u ? phead : 0u);
+                const uint4 c = pend[j];
+                if (on)
+                {
+                    uint32_t cv[8];
+                    b3_leaf(cv, data + (((uint64_t)c.y << 32) | c.x) + ((uint64_t)k << 10), c.z, k);
+                    uint4* o = reinterpret_cast<uint4*>(cv_runs + (uint64_t)(c.w + k) * 8u);
+                    o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+                    o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+                }
+                pl -= take;
+                if (pl != 0u) // (the rest of) the newest chunk
+                {
+                    const uint32_t li = pn - 1u;
+                    const uint4 l = make_uint4(__builtin_amdgcn_readlane(e.x, li), __builtin_amdgcn_readlane(e.y, li),
+                                               __builtin_amdgcn_readlane(e.z, li), __builtin_amdgcn_readlane(e.w, li));
+                    if (lane == 0)
+                        pend[0] = l;
+                    phead = last_nl - pl;
+                    pn = 1;
+                }
+                else
+                    pn = 0, phead = 0;
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                continue;
             }
-            pl -= take;
-            if (pl != 0u) // (the rest of) the newest chunk
-            {
-                const uint32_t li = pn - 1u;
-                const uint4 l = make_uint4(__builtin_amdgcn_readlane(e.x, li), __builtin_amdgcn_readlane(e.y, li),
-                                           __builtin_amdgcn_readlane(e.z, li), __builtin_amdgcn_readlane(e.w, li));
-                if (lane == 0)
-                    pend[0] = l;
-                phead = last_nl - pl;
-                pn = 1;
-            }
-            else
-                pn = 0, phead = 0;
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            continue;
-        }
         if (drained)
             break;
         if (!have)
@@ -988,7 +855,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
             pd = parts[t];
             size = pd.size;
             out = region + pd.region_base;
-            slot = (uint32_t)lthip_part_run_base(pd);
+            if constexpr (HASH)
+                slot = (uint32_t)lthip_part_run_base(pd);
             s = 0;
             n = 0;
             have = true;
@@ -1018,7 +886,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
             scanning = true;
         }
 
-        // ---- one tile (k_buzhash_walk's, see there) ----
+        // ---- one tile ----
+        // whether the chunk's last legal candidate lies in the tile at tb.  tb <= qlo <= qhi < size < 2^32 whenever a tile is hashed
+        // (tb = jump(qlo), or moved on by a tile because qhi lay behind it), so the distance is a 32-bit scalar
         auto ends_here = [&]() __attribute__((always_inline)) { return (uint32_t)(qhi - tb) < (uint32_t)WTILE; };
         if (!(inflight && inflight_tb == tb))
         {
@@ -1052,6 +922,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
 #endif
         for (;;) // the chunks that end in this tile
         {
+            // the legal bits of the run: [qlo, qhi] relative to the tile, then to the run (beyond the part: qhi < size)
             const int lo = (int)(qlo > tb ? qlo - tb : 0) - lane_base;
             const int hi = (int)(ends_here() ? (uint32_t)(qhi - tb) : (uint32_t)WTILE - 1u) - lane_base;
             uint64_t m = raw;
@@ -1081,9 +952,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
                 scanning = false;
                 break;
             }
-            if ((uint32_t)(qlo - tb) < (uint32_t)WTILE && pl < 64u) // (tb < s <= qlo < size: the chunk before ended in this tile)
+            // (tb < s <= qlo < size: the chunk before ended in this tile)
+            if ((uint32_t)(qlo - tb) < (uint32_t)WTILE && (!HASH || pl < 64u))
                 continue; // (min < 4 KiB) the next chunk's first candidate lies in this tile as well
-            tb = jump(qlo); // (a full list: this very tile again, behind the round)
+            tb = jump(qlo); // (HASH, a full list: this very tile again, behind the round)
             break;
         }
     }
@@ -1091,6 +963,24 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8
     if (lane == 0 && tiles)
         atomicAdd(&g_walk_tiles, (unsigned long long)tiles);
 #endif
+}
+
+template <int MODE, int WAVES, bool GUESS>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_walk(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts,
+                                                                 uint32_t nparts, DivTest dv, uint32_t min_chunk, uint32_t max_chunk,
+                                                                 uint2* __restrict__ region, uint32_t* __restrict__ part_count,
+                                                                 uint32_t* __restrict__ ticket)
+{
+    walk_body<MODE, WAVES, GUESS, false>(data, parts, nparts, dv, min_chunk, max_chunk, region, part_count, ticket, nullptr);
+}
+
+template <int MODE, int WAVES, bool GUESS>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_hash_walk(const uint8_t* __restrict__ data, const PartDev* __restrict__ parts,
+                                                                      uint32_t nparts, DivTest dv, uint32_t min_chunk, uint32_t max_chunk,
+                                                                      uint2* __restrict__ region, uint32_t* __restrict__ part_count,
+                                                                      uint32_t* __restrict__ ticket, uint32_t* __restrict__ cv_runs)
+{
+    walk_body<MODE, WAVES, GUESS, true>(data, parts, nparts, dv, min_chunk, max_chunk, region, part_count, ticket, cv_runs);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1311,9 +1201,9 @@ template <int WAVES, bool DMA>
 static int launch_buzhash_prefix(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint64_t* bm0, uint64_t* bm1)
 {
     static_assert(DMA || K1_HAS_REG_FLAVOUR, "the register-staged flavour is compiled by the ablation build only");
-    constexpr size_t per_wave = DMA ? (DMA_BUF_B >> 2) + HALO_DW : WROWS * ROW_DW + HALO_DW;
-    static_assert(sizeof(uint32_t) * (256 * TAB_REP + WAVES * per_wave) <= 160 * 1024, "LDS budget: one workgroup per CU");
-    const size_t lds = sizeof(uint32_t) * (256 * TAB_REP + WAVES * per_wave);
+    // (the register-staged flavour: padded rows in place of the linear buffer, ablations/k_buzhash_prefix_regs.inc)
+    constexpr size_t lds = DMA ? lds_bytes(WAVES, false) : sizeof(uint32_t) * (256 * TAB_REP + WAVES * (WROWS * ROW_DW + HALO_DW));
+    static_assert(lds <= 160 * 1024, "LDS budget: one workgroup per CU");
 #ifdef LTHIP_ABLATIONS
     auto k0 = DMA ? &k_buzhash_prefix_dma<0, WAVES> : &k_buzhash_prefix<0, WAVES>;
     auto k1 = DMA ? &k_buzhash_prefix_dma<1, WAVES> : &k_buzhash_prefix<1, WAVES>;
@@ -1321,17 +1211,10 @@ static int launch_buzhash_prefix(lthip_ctx* ctx, const lthip_plan* plan, const u
     auto k0 = &k_buzhash_prefix_dma<0, WAVES>;
     auto k1 = &k_buzhash_prefix_dma<1, WAVES>;
 #endif
-    static bool granted[64] = {}; // per device: more than 64 KiB of dynamic LDS has to be granted explicitly
-    if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device])
-    {
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (ctx->device >= 0 && ctx->device < 64)
-            granted[ctx->device] = true;
-    }
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    uint32_t grid = (uint32_t)ncu;
+    static std::atomic<bool> granted[64] = {};
+    if (int err = lthip_grant_lds(ctx, granted, {reinterpret_cast<const void*>(k0), reinterpret_cast<const void*>(k1)}, lds))
+        return err;
+    uint32_t grid = lthip_cu_count(ctx->device);
     if ((uint64_t)grid * WAVES > plan->ntiles * 4u)
         grid = (uint32_t)div_up_u64(plan->ntiles * 4u, WAVES);
     LaunchTimer t(ctx, LTHIP_K_BUZHASH);
@@ -1364,16 +1247,11 @@ static int launch_buzhash_roll(lthip_ctx* ctx, const lthip_plan* plan, const uin
 {
     static_assert(sizeof(uint32_t) * (256 * TAB_REP + K1_WAVES * WROWS * ROW_DW) <= 160 * 1024, "LDS budget: one workgroup per CU");
     const size_t lds = sizeof(uint32_t) * (256 * TAB_REP + K1_WAVES * WROWS * ROW_DW);
-    if (!ctx->k1_lds_enabled) // per context = per device: more than 64 KiB of dynamic LDS has to be granted explicitly
-    {
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_buzhash_candidates<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_buzhash_candidates<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->k1_lds_enabled = true;
-    }
+    static std::atomic<bool> granted[64] = {};
+    if (int err = lthip_grant_lds(ctx, granted, {reinterpret_cast<const void*>(&k_buzhash_candidates<0>), reinterpret_cast<const void*>(&k_buzhash_candidates<1>)}, lds))
+        return err;
     // one persistent workgroup of 12 waves per CU (64 KiB table + 12 wave row buffers = 117 KiB of LDS)
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    uint32_t grid = (uint32_t)ncu;
+    uint32_t grid = lthip_cu_count(ctx->device);
     if ((uint64_t)grid * K1_WAVES > plan->ntiles * 4u)
         grid = (uint32_t)div_up_u64(plan->ntiles * 4u, K1_WAVES);
     LaunchTimer t(ctx, LTHIP_K_BUZHASH);
@@ -1406,18 +1284,18 @@ int lthip_launch_buzhash(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* 
     return launch_buzhash_prefix<16, true>(ctx, plan, d_data, bm0, bm1);
 }
 
-// waves of K1 that are resident on the device at a time: one 16-wave workgroup per CU
-uint32_t lthip_k1_resident_waves(int device)
+// the device's compute units (256 where the runtime does not say)
+uint32_t lthip_cu_count(int device)
 {
     static std::atomic<uint32_t> cached[64] = {};
     if (device >= 0 && device < 64 && cached[device].load(std::memory_order_relaxed))
         return cached[device].load(std::memory_order_relaxed);
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-    const uint32_t w = (uint32_t)(ncu > 0 ? ncu : 256) * 16u;
+    const uint32_t n = (uint32_t)(ncu > 0 ? ncu : 256);
     if (device >= 0 && device < 64)
-        cached[device].store(w, std::memory_order_relaxed);
-    return w;
+        cached[device].store(n, std::memory_order_relaxed);
+    return n;
 }
 
 #ifndef K1_WALK_GUESS
@@ -1427,45 +1305,44 @@ uint32_t lthip_k1_resident_waves(int device)
                         // whole test file ran on; the other is LTHIP_K1_WALK_GUESS=0 in the ablation build.
 #endif
 
+template <int MODE, int WAVES, bool GUESS, bool HASH>
+static constexpr auto walk_kernel()
+{
+    if constexpr (HASH)
+        return &k_buzhash_hash_walk<MODE, WAVES, GUESS>;
+    else
+        return &k_buzhash_walk<MODE, WAVES, GUESS>;
+}
+
 // HASH: the scan that hashes the chunks it cuts (cv_runs), with the waves' pending lists behind the tile buffers
 template <bool GUESS, bool HASH>
 static int launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count,
                                uint32_t* cv_runs)
 {
     constexpr int WAVES = 16;
-    constexpr size_t lds = sizeof(uint32_t) * (256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW)) // (the budget of k_buzhash_prefix_dma)
-                           + (HASH ? sizeof(uint4) * WAVES * PEND_CAP : 0);
-    static_assert(lds <= 160 * 1024 && (sizeof(uint32_t) * (256 * TAB_REP + WAVES * ((DMA_BUF_B >> 2) + HALO_DW))) % 16 == 0,
+    constexpr size_t lds = lds_bytes(WAVES, HASH);
+    static_assert(lds <= 160 * 1024 && (sizeof(uint32_t) * lds_pend_dw(WAVES)) % 16 == 0,
                   "LDS budget: one workgroup per CU; the lists are 16-byte aligned");
-    auto k0 = &k_buzhash_walk<0, WAVES, GUESS>;
-    auto k1 = &k_buzhash_walk<1, WAVES, GUESS>;
-    auto h0 = &k_buzhash_hash_walk<0, WAVES, GUESS>;
-    auto h1 = &k_buzhash_hash_walk<1, WAVES, GUESS>;
-    static bool granted[64] = {}; // per device: more than 64 KiB of dynamic LDS has to be granted explicitly
-    if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device])
-    {
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(HASH ? reinterpret_cast<const void*>(h0) : reinterpret_cast<const void*>(k0),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        LTHIP_CHECK(ctx, hipFuncSetAttribute(HASH ? reinterpret_cast<const void*>(h1) : reinterpret_cast<const void*>(k1),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (ctx->device >= 0 && ctx->device < 64)
-            granted[ctx->device] = true;
-    }
-    void* ticket;
-    int err = lthip_scratch(ctx, S_WALK_TICKET, 64, &ticket);
+    const auto k0 = walk_kernel<0, WAVES, GUESS, HASH>(), k1 = walk_kernel<1, WAVES, GUESS, HASH>();
+    static std::atomic<bool> granted[64] = {};
+    int err = lthip_grant_lds(ctx, granted, {reinterpret_cast<const void*>(k0), reinterpret_cast<const void*>(k1)}, lds);
     if (err)
         return err;
-    uint32_t grid = lthip_k1_resident_waves(ctx->device) / WAVES;
+    void* ticket;
+    if ((err = lthip_scratch(ctx, S_WALK_TICKET, 64, &ticket)))
+        return err;
+    uint32_t grid = lthip_cu_count(ctx->device); // one 16-wave workgroup per CU (lthip_k1_resident_waves)
     if ((uint64_t)grid * WAVES > plan->nparts)
         grid = (uint32_t)div_up_u64(plan->nparts, WAVES);
     LaunchTimer t(ctx, LTHIP_K_BUZHASH);
     LTHIP_CHECK(ctx, hipMemsetAsync(ticket, 0, 4, ctx->stream));
-    if (HASH)
-        hipLaunchKernelGGL(plan->div.pow2 ? h1 : h0, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts,
-                           plan->div, plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket, cv_runs);
+    const auto k = plan->div.pow2 ? k1 : k0;
+    if constexpr (HASH)
+        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts, plan->div,
+                           plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket, cv_runs);
     else
-        hipLaunchKernelGGL(plan->div.pow2 ? k1 : k0, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts,
-                           plan->div, plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WAVES), lds, ctx->stream, d_data, plan->d_parts, plan->nparts, plan->div,
+                           plan->min_chunk, plan->max_chunk, region, part_count, (uint32_t*)ticket);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -123,15 +123,9 @@ int chain_launch_one(lthip_ctx* ctx, const void* in, uint32_t len, uint64_t* out
     const size_t lds = K::one_lds(len);
     if (lds > K::one_lds_grant)
     {
-        // per device and kind: more than 64 KiB of LDS has to be granted explicitly (plugin threads race here: the flag is atomic, and
-        // two threads that both set the attribute set the same value)
-        static std::atomic<bool> granted[64] = {};
-        if (ctx->device < 0 || ctx->device >= 64 || !granted[ctx->device].load(std::memory_order_acquire))
-        {
-            LTHIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(K::one), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            if (ctx->device >= 0 && ctx->device < 64)
-                granted[ctx->device].store(true, std::memory_order_release);
-        }
+        static std::atomic<bool> granted[64] = {}; // per device and kind (lthip_grant_lds)
+        if (int err = lthip_grant_lds(ctx, granted, {reinterpret_cast<const void*>(K::one)}, 80 * 1024))
+            return err;
     }
     hipLaunchKernelGGL(K::one, dim3(1), dim3(64), lds, ctx->stream, (const uint8_t*)in, len, out);
     LTHIP_LAUNCH_CHECK(ctx);

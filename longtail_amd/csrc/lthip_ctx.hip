@@ -141,7 +141,6 @@ extern "C" int lthip_ctx_create(int device, void* hip_stream, lthip_ctx** out_ct
     memset(ctx->stage, 0, sizeof ctx->stage);
     memset(ctx->stage_small, 0, sizeof ctx->stage_small);
     ctx->stage_next = ctx->stage_small_next = 0;
-    ctx->k1_lds_enabled = false;
     ctx->z_last_retry = nullptr;
     ctx->z_last_payloads = 0;
     ctx->z_last_foreign_blocks = 0;

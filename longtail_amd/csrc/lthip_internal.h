@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -172,8 +173,7 @@ struct lthip_ctx
     Stage stage[8], stage_small[64];
     size_t stage_small_next;
     size_t stage_next;
-    bool k1_lds_enabled; // hipFuncAttributeMaxDynamicSharedMemorySize set for K1 on this context's device
-    bool k5_lds_enabled[2][2]; // ... and for k_lz4_segments<.., FMT, CLS> with units above 4 KiB
+    bool k5_lds_enabled[2][2]; // hipFuncAttributeMaxDynamicSharedMemorySize set on this context's device for k_lz4_segments<.., FMT, CLS> with units above 4 KiB
     bool k5h_lds_enabled[2]; // ... and for k_lz4_lanes2<FMT>
     void* scratch[S_COUNT];
     size_t scratch_cap[S_COUNT];
@@ -277,6 +277,21 @@ int lthip_stage_upload(lthip_ctx* ctx, void* d_dst, const void* h_src, size_t by
             return lthip_fail((ctx), e__ == hipErrorOutOfMemory ? ENOMEM : EIO, #expr, hipGetErrorString(e__)); \
     } while (0)
 
+// More than 64 KiB of dynamic LDS has to be granted to a kernel explicitly, once per device.  `granted`: the call site's flags, one per
+// device (plugin threads race here: the flags are atomic, and two threads that both set the attribute set the same value); a device
+// outside the array is granted at every call.
+inline int lthip_grant_lds(lthip_ctx* ctx, std::atomic<bool> (&granted)[64], std::initializer_list<const void*> kernels, size_t bytes)
+{
+    const bool known = ctx->device >= 0 && ctx->device < 64;
+    if (known && granted[ctx->device].load(std::memory_order_acquire))
+        return 0;
+    for (const void* k : kernels)
+        LTHIP_CHECK(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (known)
+        granted[ctx->device].store(true, std::memory_order_release);
+    return 0;
+}
+
 // timing brackets around a launch on ctx->stream
 struct LaunchTimer
 {
@@ -306,7 +321,8 @@ int lthip_launch_buzhash(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* 
 // of them, below 2^32) -- and lthip_launch_blake3_parents finishes the hashes behind compaction
 int lthip_launch_buzhash_walk(lthip_ctx* ctx, const lthip_plan* plan, const uint8_t* d_data, uint2* region, uint32_t* part_count,
                               uint32_t* cv_runs);
-uint32_t lthip_k1_resident_waves(int device); // waves of a K1 launch that the device holds at a time
+uint32_t lthip_cu_count(int device);          // the device's compute units, asked for once per device
+inline uint32_t lthip_k1_resident_waves(int device) { return 16u * lthip_cu_count(device); } // waves of a K1 launch that the device holds at a time: one 16-wave workgroup per CU
 int lthip_launch_select(lthip_ctx* ctx, const lthip_plan* plan, const uint64_t* bm0, const uint64_t* bm1, uint2* region,
                         uint32_t* part_count);
 // The payloads of raw (tag 0) block images (k_gather.hip): for each of `count` blocks the chunks [h_first[i], h_first[i] + h_count[i]) of the

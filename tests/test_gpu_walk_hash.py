@@ -1,7 +1,8 @@
 """-m gpu: the walking scan that hashes the chunks it cuts (k_buzhash_hash_walk: the wave that emits a chunk puts it on a pending
 list and hashes 64 pending leaves at a time, a leaf per lane; the chaining values go to per-part runs that a kernel behind compaction
 moves into the dense leaf order) against the walking scan followed by the leaf pass of its own, and against the oracle (ablation build:
-LTHIP_WALK_HASH = 0 / 1 forces either form, LTHIP_K1_WALK = 1 the walking scan for any plan).
+LTHIP_WALK_HASH = 0 / 1 forces either form, LTHIP_K1_WALK = 1 the walking scan for any plan, LTHIP_K1_WALK_GUESS = 0 the other
+prefetch form: the two kernels are one walk body, and both forms of both meet the oracle here).
 
 Offsets, lengths, hashes and part_first must be bit-identical for the parameter sets of test_gpu_chunk_walk.py -- (48, 48, 48) and
 (48, 64, 64) have leaves of 48-64 bytes -- on part sizes at every edge of the leaf (0, 1, 47, 48, min, min + 1, 1023 .. 1025, 4095 ..
@@ -11,7 +12,7 @@ is a multiple of 16 (the plan's rule); the chunks inside start at every residue 
 import numpy as np
 import pytest
 
-from tests.gpu_util import check_part, to_device
+from tests.gpu_util import check_part, to_device, u32, u64
 from tests.test_gpu_chunk_walk import CFGS, assert_same, layout, lists, set_env
 
 pytestmark = pytest.mark.gpu
@@ -36,8 +37,22 @@ def edge_sizes(mn, mx):
     return sorted(s)
 
 
-@pytest.mark.parametrize("cfg", CFGS)
-def test_fused_against_separate_and_oracle(gpu_abl, oracle, monkeypatch, cfg):
+def prefetch_env(mp, guess):
+    """The walk's prefetch form: None = the product's (LTHIP_K1_WALK_GUESS unset), 0 = the other one.  With the fused and the separate
+    form of both_forms all four GUESS x HASH instantiations of the one walk body run."""
+    if guess is None:
+        mp.delenv("LTHIP_K1_WALK_GUESS", raising=False)
+        return {}
+    return {"LTHIP_K1_WALK_GUESS": guess}
+
+
+# every cfg on the product's prefetch form; several cuts per tile and the headline's parameters on the other form as well
+CFGS_GUESS = [pytest.param(c, None, id=f"cfg{i}") for i, c in enumerate(CFGS)]
+CFGS_GUESS += [pytest.param(c, 0, id=f"cfg{CFGS.index(c)}-guess0") for c in ((64, 128, 4096), (8192, 32768, 131072))]
+
+
+@pytest.mark.parametrize("cfg,guess", CFGS_GUESS)
+def test_fused_against_separate_and_oracle(gpu_abl, oracle, monkeypatch, cfg, guess):
     mn, av, mx = cfg
     sizes = edge_sizes(mn, mx)
     big = max(sizes)
@@ -57,8 +72,8 @@ def test_fused_against_separate_and_oracle(gpu_abl, oracle, monkeypatch, cfg):
         o = (i * 131) % 2048
         parts.append(rnd[o : o + s].copy() if i % 11 else np.zeros(s, np.uint8))
     dev, offs = to_device(parts)
-    got = both_forms(gpu_abl, monkeypatch, offs, [len(p) for p in parts], cfg, dev, LTHIP_K1_WALK=1)
-    assert_same(got[1], got[0], f"cfg={cfg}: fused against separate")
+    got = both_forms(gpu_abl, monkeypatch, offs, [len(p) for p in parts], cfg, dev, LTHIP_K1_WALK=1, **prefetch_env(monkeypatch, guess))
+    assert_same(got[1], got[0], f"cfg={cfg} guess={guess}: fused against separate")
     g, first = got[1], got[1]["part_first"]
     if mx > mn:  # (random data, chunks of varying length: they start everywhere)
         assert set((g["offsets"] % np.uint64(16)).tolist()) == set(range(16))
@@ -68,16 +83,19 @@ def test_fused_against_separate_and_oracle(gpu_abl, oracle, monkeypatch, cfg):
         check_part(oracle, parts[i], part, mn, av, mx, what=f"cfg={cfg} part {i} size={len(parts[i])}")
 
 
-@pytest.mark.parametrize("tail", [1, 63 * KIB, 64 * KIB, 64 * KIB + 1])
-@pytest.mark.parametrize("zeros", [True, False])
-def test_one_wave_last_round(gpu_abl, oracle, monkeypatch, tail, zeros):
+@pytest.mark.parametrize(
+    "zeros,tail,guess",
+    [pytest.param(z, t, g, id=f"{z}-{t}" + ("" if g is None else f"-guess{g}"))
+     for g in (None, 0) for z in (True, False) for t in (1, 63 * KIB, 64 * KIB, 64 * KIB + 1)],
+)
+def test_one_wave_last_round(gpu_abl, oracle, monkeypatch, tail, zeros, guess):
     """ONE part, so one wave: on zeros a chunk of max = 128 leaves (two full rounds), then a tail of 1, 63, 64 or 65 leaves."""
     cfg = (8192, 32768, 131072)
     size = cfg[2] + tail
     part = np.zeros(size, np.uint8) if zeros else np.random.default_rng(tail).integers(0, 256, size=size, dtype=np.uint8)
     dev, offs = to_device([part])
-    got = both_forms(gpu_abl, monkeypatch, offs, [size], cfg, dev, LTHIP_K1_WALK=1)
-    assert_same(got[1], got[0], f"tail={tail} zeros={zeros}")
+    got = both_forms(gpu_abl, monkeypatch, offs, [size], cfg, dev, LTHIP_K1_WALK=1, **prefetch_env(monkeypatch, guess))
+    assert_same(got[1], got[0], f"tail={tail} zeros={zeros} guess={guess}")
     if zeros:
         assert got[1]["lengths"].tolist() == [cfg[2], tail]
     check_part(oracle, part, (got[1]["offsets"], got[1]["lengths"], got[1]["hashes"]), *cfg, what=f"tail={tail} zeros={zeros}")
@@ -135,4 +153,16 @@ def test_reaim_walked_rejected_walked(gpu_abl, tree, monkeypatch):
     plan.reaim(layout(SIZES_WALK)[0], SIZES_WALK)
     assert plan.walked_scans == 1
     assert_same(lists(gpu_abl, plan, tree), ref["walk"], "re-aimed at the walked layout again")
+    plan.close()
+
+
+def test_product_walks_without_hashes(gpu, tree):
+    """The product library runs k_buzhash_walk only for a walked plan whose hashes nobody asks for: the cuts of the scan that hashes."""
+    plan = gpu.make_plan(layout(SIZES_WALK)[0], SIZES_WALK, *CFG)
+    assert plan.walked_scans == 1
+    hashed = lists(gpu, plan, tree)
+    total, off, ln, h, first = gpu.chunk_hash(plan, tree, want_hashes=False)
+    assert plan.walked_scans == 1 and h is None
+    plain = {"offsets": u64(off)[:total], "lengths": u32(ln)[:total], "part_first": u32(first)[: plan.nparts + 1]}
+    assert_same(plain, {k: hashed[k] for k in plain}, "the walk without hashes against the walk that hashes")
     plan.close()
