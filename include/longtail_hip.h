@@ -578,7 +578,9 @@ LTHIP_EXPORT int lthip_write_raw_block_images(lthip_ctx* ctx, uint32_t block_cou
  * Which of the version's chunks (unique list, version order: device hashes + sizes, host tags or NULL) does a store holding
  * d_existing_hashes lack, and how are they packed into blocks?  Output: the serialized StoreIndex of the missing content
  * (the bytes Longtail_WriteStoreIndexToBuffer produces: blocks with their block hashes -- of hash_identifier's type, see above --,
- * chunk lists, tags).
+ * chunk lists, tags).  A chunk list with repeats is outside the contract, here as in the reference; what the reference returns for one
+ * (it leaves out chunks that first occur among the list's last entries, src/longtail.c:6666 and :6731) is returned here too, byte for
+ * byte.
  * Returns ENOMEM with *out_size set when `out` is too small. */
 LTHIP_EXPORT int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_count, const uint64_t* d_existing_hashes,
                                               uint64_t chunk_count, const uint64_t* d_chunk_hashes, const uint32_t* d_chunk_lens,

@@ -261,8 +261,12 @@ extern "C" int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_co
     LTHIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t ne = (size_t)existing_count, n = (size_t)chunk_count;
     int err;
-    DBuf d_all, d_first, d_uniq;
-    if ((err = reserve_dev(ctx, d_all, (ne + n) * 8)) || (err = reserve_dev(ctx, d_first, (ne + n) * 4)) || (err = reserve_dev(ctx, d_uniq, 8)))
+    DBuf d_all, d_first, d_uniq, d_vuniq;
+    if ((err = reserve_dev(ctx, d_all, (ne + n) * 8)) || (err = reserve_dev(ctx, d_first, (ne + n) * 4)) || (err = reserve_dev(ctx, d_uniq, 8)) ||
+        (err = reserve_dev(ctx, d_vuniq, 8)))
+        return err;
+    // the distinct hashes of the version list alone: n for the unique list of the contract (see the repeats below)
+    if ((err = lthip_dedup_first_seen_range(ctx, n, d_chunk_hashes, 0, 0, nullptr, (uint64_t*)d_vuniq.p)))
         return err;
     if (ne)
         LTHIP_CHECK(ctx, hipMemcpyAsync(d_all.p, d_existing_hashes, ne * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -278,17 +282,47 @@ extern "C" int lthip_create_missing_content(lthip_ctx* ctx, uint64_t existing_co
         LTHIP_CHECK(ctx, hipMemcpyAsync(lens.data(), d_chunk_lens, n * 4, hipMemcpyDeviceToHost, ctx->stream));
         LTHIP_CHECK(ctx, hipMemcpyAsync(hashes.data(), d_chunk_hashes, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
+    uint64_t distinct = 0;
+    LTHIP_CHECK(ctx, hipMemcpyAsync(&distinct, d_vuniq.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     LTHIP_CHECK(ctx, lthip_stream_wait(ctx));
-    // the missing chunks, version order
-    std::vector<uint64_t> m_hash;
-    std::vector<uint32_t> m_size, m_tag;
+    // the missing chunks, version order: the first occurrences that the store lacks
+    std::vector<uint32_t> pick;
     for (size_t i = 0; i < n; ++i)
         if (first[i] == (uint32_t)(ne + i))
-        {
-            m_hash.push_back(hashes[i]);
-            m_size.push_back(lens[i]);
-            m_tag.push_back(chunk_tags ? chunk_tags[i] : 0u);
-        }
+            pick.push_back((uint32_t)i);
+    if (distinct != n)
+    {
+        // A list with repeats is outside the contract here and in the reference (a VersionIndex's chunk list is unique), and what the
+        // reference makes of one is mirrored, not fixed: DiffHashes puts the added hashes -- sorted until then -- back into version order by
+        // walking as many ENTRIES of the list as it has distinct hashes (:6666, :6731), so the last entries are never looked at, an
+        // entry met twice is written twice, and where the walk wrote fewer than there are added hashes the sorted ones stay behind it;
+        // Longtail_CreateStoreIndex then keeps the first of equal hashes (GetUniqueHashes, :6796), with the size and the tag of the
+        // hash's first entry in the version (the look-up of :6966-6977 finds that one).
+        const size_t added = pick.size();
+        std::vector<uint32_t> sorted(pick), walk;
+        std::sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return hashes[a] < hashes[b]; });
+        for (size_t i = 0; i < distinct && walk.size() < added; ++i)
+            if (first[i] >= ne)
+                walk.push_back(first[i] - (uint32_t)ne);
+        for (size_t j = walk.size(); j < added; ++j)
+            walk.push_back(sorted[j]);
+        std::vector<bool> taken(n, false);
+        pick.clear();
+        for (uint32_t i : walk)
+            if (!taken[i])
+            {
+                taken[i] = true;
+                pick.push_back(i);
+            }
+    }
+    std::vector<uint64_t> m_hash;
+    std::vector<uint32_t> m_size, m_tag;
+    for (uint32_t i : pick)
+    {
+        m_hash.push_back(hashes[i]);
+        m_size.push_back(lens[i]);
+        m_tag.push_back(chunk_tags ? chunk_tags[i] : 0u);
+    }
     const size_t m = m_hash.size();
     // greedy packing, :6801-6860
     std::vector<uint32_t> b_first(1, 0u), b_tag; // block b = chunks [b_first[b], b_first[b + 1])
