@@ -43,6 +43,7 @@ class Oracle:
         sig("lto_hpcdc_chunk_pure", u64, [vp, u64, u32, u32, u32, vp, u64])
         sig("lto_hpcdc_next_from_buffer", u64, [vp, u64, u32, u32, u32])
         sig("lto_buzhash_at", u32, [vp, u64])
+        sig("lto_hpcdc_candidates", None, [vp, u64, u32, vp])
         sig("lto_blake3_u64", u64, [vp, sz])
         sig("lto_blake3_u64_many", None, [vp, vp, vp, u64, vp])
         sig("lto_lz4_bound", sz, [sz])

@@ -114,7 +114,7 @@ def test_division_free_cut_test_is_exact(hiplib, oracle):
     f = hiplib.dll.lthip_divtest_eval
     rng = np.random.default_rng(0)
     ds = [oracle.dll.lto_hpcdc_discriminator(a) for a in (48, 64, 100, 2048, 16384, 32768, 65536, 131072, 1 << 20)]
-    ds += [1, 2, 3, 4, 5, 6, 7, 8, 12, 16, 96, 1024, 65536, 12345, 99991, 2**31, 2**31 + 1, 0xFFFFFFFF, 0xFFFFFFFE]
+    ds += [1, 2, 3, 4, 5, 6, 7, 8, 12, 16, 64, 96, 1024, 16384, 65536, 12345, 99991, 2**31, 2**31 + 1, 0xFFFFFFFF, 0xFFFFFFFE]
     ds += [int(x) for x in rng.integers(1, 2**32, size=40)]
     assert 24680 in ds and 49535 in ds  # target 65536 / 131072
     for d in ds:

@@ -75,7 +75,7 @@ def test_hash_ranges_fuzz(gpu, oracle):
 
 
 @pytest.mark.parametrize("cfg", [(8192, 32768, 131072), (48, 48, 48), (4096, 16384, 65536), (48, 100, 300), (16384, 65536, 262144),
-                                 (48, 64, 64), (64, 128, 4096), (2048, 2048, 8192)])
+                                 (48, 64, 64), (64, 128, 4096), (2048, 2048, 8192), (64, 86, 300)])
 def test_params_and_kinds(gpu, oracle, cfg):
     rng = np.random.default_rng(cfg[0] + cfg[2])
     parts = []

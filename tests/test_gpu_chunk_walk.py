@@ -14,7 +14,7 @@ from tests.gpu_util import check_part, to_device, u32, u64
 pytestmark = pytest.mark.gpu
 
 CFGS = [(8192, 32768, 131072), (48, 48, 48), (4096, 16384, 65536), (48, 100, 300), (16384, 65536, 262144), (48, 64, 64), (64, 128, 4096),
-        (2048, 2048, 8192)]  # test_gpu_chunk_hash.py::test_params_and_kinds
+        (2048, 2048, 8192), (64, 86, 300)]  # test_gpu_chunk_hash.py::test_params_and_kinds; (64, 86, 300): d = 64, the power-of-two kernels
 KIB, MIB = 1 << 10, 1 << 20
 
 
