@@ -29,10 +29,12 @@
 //                    honouring the end-of-block rules (last 5 bytes literal, last match starts >= 12 bytes before the end;
 //                    lz4.c:242-246, 2279-2329, 2421-2423); then one wave per unit, persistent over a work list, copies header,
 //                    literals (from the source) and sequence body (from the stream) into the single final block with 16-byte
-//                    stores.  Blocks without a single match were laid out by K5: only their header is written.
+//                    stores.  Blocks without a single match were laid out by K5: only their header is written, and -- K5 counts a
+//                    block's units with a sequence -- without a walk over their units.
 //   decode           k_lz4_decode.hip
 #include "k_copy.h"
 #include "lthip_internal.h"
+#include "lz4/lz4_grid_rule.h"
 
 #include <string>
 
@@ -370,6 +372,14 @@ constexpr int LZ4_TAB_LZ4 = 1024 + 256;
 constexpr int LZ4_TAB_ZSTD = 1024 + 256;
 constexpr int LZ4_TAB_SHARED = 1536, LZ4_SH_LOG2 = 13; // lane parser with the group's shared table: 64 + 48 + 32 KiB of LDS
 
+// The head of the classification pass's work area (`worklist` of k_lz4_segments<.., CLS 1>; the rest: lz4_lanes_kernel.inc), ngroups + 1
+// words that one fill clears with the groups' half bits behind them:
+//   [first group of a block]  how many of the block's units hold a sequence -- counted by whoever writes a unit's Lz4Meta, the
+//                             classification pass or the lane parser; k_lz4_stitch_scan walks only the blocks that have one
+//   [ngroups]                 the stitch's work count (groups on its list)
+// (a block without a unit has no group and no word; the stitch asks for none)
+__device__ __forceinline__ uint32_t* lz4_seq_units(uint32_t* worklist, uint32_t grp_base) { return worklist + grp_base; }
+
 #include "lz4/lz4_lane_parse.inc"
 #include "lz4/lz4_classify.inc"
 #include "lz4/lz4_lanes_kernel.inc"
@@ -386,10 +396,11 @@ extern "C" size_t lthip_lz4_bound(size_t size) { return size > 0x7E000000u ? 0 :
 
 static int upload_blocks(lthip_ctx* ctx, uint32_t block_count, const uint64_t* src_offsets, const uint32_t* src_sizes,
                          const uint64_t* dst_offsets, const uint32_t* dst_caps, uint32_t seg_bytes, uint32_t gunits, Lz4Block** d_blocks,
-                         uint64_t* out_nseg, uint64_t* out_ngrp = nullptr, uint64_t* out_ncgrp = nullptr)
+                         uint64_t* out_nseg, uint64_t* out_ngrp, uint64_t* out_ncgrp, uint32_t* out_max_ncgrp)
 {
     std::vector<Lz4Block> hb(block_count);
     uint64_t nseg = 0, ngrp = 0, ncgrp = 0;
+    uint32_t max_ncgrp = 0; // the longest block's classification groups (lz4_grid_rule)
     for (uint32_t b = 0; b < block_count; ++b)
     {
         if (src_sizes[b] > 0x7E000000u)
@@ -406,6 +417,7 @@ static int upload_blocks(lthip_ctx* ctx, uint32_t block_count, const uint64_t* s
         hb[b].cgrp_base = (uint32_t)ncgrp;
         hb[b].ncgrp = (hb[b].nseg + LZ4_G_BATCH - 1) / LZ4_G_BATCH;
         ncgrp += hb[b].ncgrp;
+        max_ncgrp = hb[b].ncgrp > max_ncgrp ? hb[b].ncgrp : max_ncgrp;
         nseg += hb[b].nseg;
     }
     if (nseg > 0x7FFFFFF0ull)
@@ -418,10 +430,9 @@ static int upload_blocks(lthip_ctx* ctx, uint32_t block_count, const uint64_t* s
         return err;
     *d_blocks = (Lz4Block*)p;
     *out_nseg = nseg;
-    if (out_ngrp)
-        *out_ngrp = ngrp;
-    if (out_ncgrp)
-        *out_ncgrp = ncgrp;
+    *out_ngrp = ngrp;
+    *out_ncgrp = ncgrp;
+    *out_max_ncgrp = max_ncgrp;
     return 0;
 }
 
@@ -447,9 +458,10 @@ extern "C" __attribute__((visibility("default"))) int lthip_k5_prof_dump(int res
 }
 #endif
 
-// the batch parser's geometry: classification pass (CLS 1) or the parser for everything (CLS 0)
+// the batch parser's geometry: classification pass (CLS 1) or the parser for everything (CLS 0).  groups = window groups of LZ4_G_BATCH
+// units in the batch, max_groups = in its longest block: they choose the grid (lz4_grid_rule.h)
 template <int FMT, int CLS>
-static int launch_segments(lthip_ctx* ctx, uint32_t groups, uint32_t SEG, const void* d_src, const Lz4Block* d_blocks, uint32_t block_count,
+static int launch_segments(lthip_ctx* ctx, uint32_t groups, uint32_t max_groups, uint32_t SEG, const void* d_src, const Lz4Block* d_blocks, uint32_t block_count,
                            uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg, uint32_t ngroups, uint32_t* worklist)
 {
     constexpr int TAB = FMT == 1 ? LZ4_TAB_ZSTD : LZ4_TAB_LZ4;
@@ -460,8 +472,9 @@ static int launch_segments(lthip_ctx* ctx, uint32_t groups, uint32_t SEG, const 
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ctx->k5_lds_enabled[FMT][CLS] = true;
     }
-    hipLaunchKernelGGL((k_lz4_segments<LZ4_G_BATCH, TAB, FMT, CLS>), dim3(groups), dim3(64 * LZ4_G_BATCH), lds, ctx->stream, (const uint8_t*)d_src,
-                       d_blocks, block_count, 0u, SEG, streams, meta, zrecs, spec_dst, dbg, nullptr, ngroups, worklist);
+    const Lz4Grid grid = lz4_grid_rule(groups, max_groups, block_count, 64 * LZ4_G_BATCH);
+    hipLaunchKernelGGL((k_lz4_segments<LZ4_G_BATCH, TAB, FMT, CLS>), dim3(grid.x, grid.y), dim3(64 * LZ4_G_BATCH), lds, ctx->stream, (const uint8_t*)d_src,
+                       d_blocks, block_count, grid.two_d ? 1u : 0u, SEG, streams, meta, zrecs, spec_dst, dbg, nullptr, ngroups, worklist);
     LTHIP_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -474,19 +487,25 @@ static int launch_segments(lthip_ctx* ctx, uint32_t groups, uint32_t SEG, const 
 // `lanes` false (unit sizes other than 4 KiB): the batch parser for everything.
 template <int FMT>
 static int launch_match_finder(lthip_ctx* ctx, bool lanes, uint32_t SEG, const void* d_src, const Lz4Block* d_blocks, uint32_t block_count,
-                               uint64_t ngrp, uint64_t ncgrp, uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg)
+                               uint64_t ngrp, uint64_t ncgrp, uint32_t max_ncgrp, uint8_t* streams, Lz4Meta* meta, uint64_t* zrecs, uint8_t* spec_dst, uint32_t dbg,
+                               uint32_t** out_wl /* the classification pass's work area (lz4_seq_units); null without one */)
 {
-    if (!lanes)
-        return launch_segments<FMT, 0>(ctx, (uint32_t)ngrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst, dbg, 0, nullptr);
+    *out_wl = nullptr;
+    if (!lanes) // (this geometry's groups ARE the classification groups)
+        return launch_segments<FMT, 0>(ctx, (uint32_t)ngrp, max_ncgrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst, dbg, 0, nullptr);
     void* wl;
     int err = lthip_scratch(ctx, S_LZ4_CLASSIFY, 4 * (11 * (size_t)ngrp + 16), &wl);
     if (err)
         return err;
+    // one fill: the blocks' counts and the stitch's work count (lz4_seq_units), the groups' half bits, the ticket and the two counters
     LTHIP_CHECK(ctx, hipMemsetAsync(wl, 0, 4 * (2 * (size_t)ngrp + 4), ctx->stream));
-    if ((err = launch_segments<FMT, 1>(ctx, (uint32_t)ncgrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst, dbg, (uint32_t)ngrp,
+    *out_wl = (uint32_t*)wl;
+    if ((err = launch_segments<FMT, 1>(ctx, (uint32_t)ncgrp, max_ncgrp, SEG, d_src, d_blocks, block_count, streams, meta, zrecs, spec_dst, dbg, (uint32_t)ngrp,
                                        (uint32_t*)wl)))
         return err;
-    // the groups' half bits -> items of two half-groups (k_lz4_pair_halves), then the lane kernel over the items
+    // the groups' half bits -> items of two half-groups (k_lz4_pair_halves), then the lane kernel over the items.  (Two launches: pairing
+    // the lone halves needs all of them counted, a device-wide order.  With nothing noted every thread of either leaves on its one load --
+    // its group's word, the count of lone halves --, and the lane kernel on the count of items.)
     const uint32_t nthreads = 256, ng = (uint32_t)ngrp;
     // history halves: the zstd flavour at its "high" and "max" settings
     const uint32_t hist = (FMT == 1 && (dbg & LZ4_DBG_Q_MAX)) ? 3u : (FMT == 1 && (dbg & LZ4_DBG_Q_HIGH)) ? 1u : 0u;
@@ -598,7 +617,8 @@ static int lz4_compress_batch(lthip_ctx* ctx, const void* d_src, uint32_t block_
     const bool lanes = SEG == 4096u; // other unit sizes (tests, ablations) keep the batch parser's geometry
     const uint32_t GU = lanes ? LZ4_G_LANES : LZ4_G_BATCH;
     uint64_t ncgrp64 = 0;
-    int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, GU, &d_blocks, &nseg64, &ngrp64, &ncgrp64);
+    uint32_t max_ncgrp = 0;
+    int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, GU, &d_blocks, &nseg64, &ngrp64, &ncgrp64, &max_ncgrp);
     if (err)
         return err;
     const uint32_t nseg = (uint32_t)nseg64, ngrp = (uint32_t)ngrp64;
@@ -630,22 +650,28 @@ static int lz4_compress_batch(lthip_ctx* ctx, const void* d_src, uint32_t block_
     // (Match finder and stitch run one after the other on the context's stream.  The stitch of one slice of the batch beside the match
     // finder of the next, on a second stream, was MEASURED SLOWER on MI355X -- 64 GiB random: 151.6 vs 137.6 ms per step: the copy's
     // traffic lengthens every probe's LDS-fill latency and both kernels lose more than the overlap wins.)
+    uint32_t* cls = nullptr; // the classification pass's work area
     if (ngrp)
     {
         LaunchTimer t(ctx, LTHIP_K_LZ4_SEG);
         uint8_t* spec = (dbg & 64u) ? (uint8_t*)nullptr : (uint8_t*)d_dst;
-        if ((err = launch_match_finder<0>(ctx, lanes, SEG, d_src, d_blocks, block_count, ngrp64, ncgrp64, (uint8_t*)streams, (Lz4Meta*)meta, nullptr, spec,
-                                          dbg)))
+        if ((err = launch_match_finder<0>(ctx, lanes, SEG, d_src, d_blocks, block_count, ngrp64, ncgrp64, max_ncgrp, (uint8_t*)streams, (Lz4Meta*)meta, nullptr,
+                                          spec, dbg, &cls)))
             return err;
     }
     LaunchTimer t(ctx, LTHIP_K_LZ4_STITCH);
-    LTHIP_CHECK(ctx, hipMemsetAsync(worklist, 0, 4, ctx->stream));
+    // The stitch's work count: behind a classification pass it is a word of that pass's work area, which the pass's one fill cleared
+    // (earlier on this stream; nothing in between writes it); else the list's own first word, cleared here.
+    uint32_t* wl_count = cls ? cls + ngrp : (uint32_t*)worklist;
+    if (!cls)
+        LTHIP_CHECK(ctx, hipMemsetAsync(worklist, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_lz4_stitch_scan, dim3(block_count), dim3(64), 0, ctx->stream, d_blocks, 0u, block_count, SEG, (const Lz4Meta*)meta,
-                       (Lz4Plan*)plan, (uint32_t*)runs, (Lz4BlockOut*)bout, d_out_sizes, (uint8_t*)d_dst, (dbg & 64u) ? 0u : 1u, (uint32_t*)worklist, ngrp);
+                       (Lz4Plan*)plan, (uint32_t*)runs, (Lz4BlockOut*)bout, d_out_sizes, (uint8_t*)d_dst, (dbg & 64u) ? 0u : 1u, (uint32_t*)worklist, ngrp, wl_count,
+                       (const uint32_t*)cls);
     if (ngrp)
         hipLaunchKernelGGL(k_lz4_stitch_copy, dim3(ngrp < copy_grid ? ngrp : copy_grid), dim3(K6_THREADS), 0, ctx->stream, (const uint8_t*)d_src,
                            d_blocks, block_count, SEG, (const uint8_t*)streams, (const Lz4Meta*)meta, (const Lz4Plan*)plan, (const uint32_t*)runs,
-                           (const Lz4BlockOut*)bout, (uint8_t*)d_dst, (const uint32_t*)worklist, GU, ngrp);
+                           (const Lz4BlockOut*)bout, (uint8_t*)d_dst, (const uint32_t*)worklist, GU, ngrp, (const uint32_t*)wl_count);
     hipLaunchKernelGGL(k_lz4_empty_blocks, dim3((block_count + 255) / 256), dim3(256), 0, ctx->stream, d_blocks, block_count,
                        (const Lz4BlockOut*)bout, (uint8_t*)d_dst);
     LTHIP_LAUNCH_CHECK(ctx);
@@ -660,7 +686,8 @@ int lthip_launch_lz_sequences(lthip_ctx* ctx, const void* d_src, uint32_t block_
     Lz4Block* d_blocks = nullptr;
     uint64_t nseg64 = 0, ngrp64 = 0;
     uint64_t ncgrp64 = 0;
-    int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, LZ4_G_LANES, &d_blocks, &nseg64, &ngrp64, &ncgrp64);
+    uint32_t max_ncgrp = 0;
+    int err = upload_blocks(ctx, block_count, src_offsets, src_sizes, dst_offsets, dst_caps, SEG, LZ4_G_LANES, &d_blocks, &nseg64, &ngrp64, &ncgrp64, &max_ncgrp);
     if (err)
         return err;
     uint64_t nseg = 0;
@@ -687,8 +714,9 @@ int lthip_launch_lz_sequences(lthip_ctx* ctx, const void* d_src, uint32_t block_
             dbg |= LZ4_DBG_Q_HIGH;
         if (quality >= 2)
             dbg |= LZ4_DBG_Q_MAX;
-        if ((err = launch_match_finder<1>(ctx, true, SEG, d_src, d_blocks, block_count, ngrp64, ncgrp64, (uint8_t*)lits, (Lz4Meta*)meta, (uint64_t*)recs,
-                                          (uint8_t*)d_dst, dbg)))
+        uint32_t* wl;
+        if ((err = launch_match_finder<1>(ctx, true, SEG, d_src, d_blocks, block_count, ngrp64, ncgrp64, max_ncgrp, (uint8_t*)lits, (Lz4Meta*)meta,
+                                          (uint64_t*)recs, (uint8_t*)d_dst, dbg, &wl)))
             return err;
     }
     *d_lits = (uint8_t*)lits;

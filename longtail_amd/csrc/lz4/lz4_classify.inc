@@ -7,7 +7,7 @@
 // parser (k_lz4_lanes2), which then runs over that list.  CLS 0 = the batch parser for everything: unit sizes other than 4 KiB.
 template <int G, int TAB, int FMT, int CLS = 0>
 __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __restrict__ src, const Lz4Block* __restrict__ blocks,
-                                                             uint32_t nblocks, uint32_t grp0, uint32_t sub_bytes,
+                                                             uint32_t nblocks, uint32_t grid2d, uint32_t sub_bytes,
                                                              uint8_t* __restrict__ streams, Lz4Meta* __restrict__ meta,
                                                              uint64_t* __restrict__ zrecs, uint8_t* __restrict__ spec_dst, uint32_t dbg,
                                                              uint64_t* __restrict__ lane_recs, uint32_t ngroups, uint32_t* __restrict__ worklist)
@@ -25,18 +25,30 @@ __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __res
     K5P_DECL
     // one window group per workgroup
     {
-    const uint32_t grp = grp0 + blockIdx.x;
-    uint32_t lo = 0, hi = nblocks;
-    while (hi - lo > 1)
+    // Which block, which of its groups?  Two grids (lz4_grid_rule.h): two-dimensional -- blockIdx.y is the block, blockIdx.x the group
+    // inside it, nothing to look up -- or one-dimensional over the batch's groups, the block found by bisection: ten dependent loads at
+    // 900 blocks before the first data load, in a workgroup that lives for one group.
+    uint32_t lo = blockIdx.y, gi = blockIdx.x;
+    if (!grid2d)
     {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((CLS ? blocks[mid].cgrp_base : blocks[mid].grp_base) <= grp)
-            lo = mid;
-        else
-            hi = mid;
+        uint32_t hi = nblocks;
+        lo = 0;
+        while (hi - lo > 1)
+        {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if ((CLS ? blocks[mid].cgrp_base : blocks[mid].grp_base) <= gi)
+                lo = mid;
+            else
+                hi = mid;
+        }
     }
     const Lz4Block blk = blocks[lo];
-    const uint32_t gi = grp - (CLS ? blk.cgrp_base : blk.grp_base);
+    if (!grid2d)
+        gi -= CLS ? blk.cgrp_base : blk.grp_base;
+    // (the two-dimensional grid is as wide as the longest block: beyond my block's groups there is nothing.  Wave-uniform, before any
+    // LDS access and any barrier.)
+    if (gi >= (CLS ? blk.ncgrp : blk.ngrp))
+        return;
     const uint32_t group_start = gi * G * sub_bytes;                                   // block relative
     const uint32_t glen = blk.size - group_start < G * sub_bytes ? blk.size - group_start : G * sub_bytes;
     const uint8_t* g = src + blk.src_off + group_start;
@@ -514,6 +526,10 @@ __global__ __launch_bounds__(64 * G, 6) void k_lz4_segments(const uint8_t* __res
         m.first_lit_len = st.first_lit;
         m.first_hdr_bytes = st.first_hdr;
         meta[unit] = m;
+        // the block's count of units with a sequence (lz4_seq_units): k_lz4_stitch_scan walks only blocks that have one.  One
+        // relaxed atomic nobody waits for, none on incompressible data.
+        if (CLS != 0 && st.op != 0u)
+            (void)__hip_atomic_fetch_add(lz4_seq_units(worklist, blk.grp_base), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     } // FMT 0
     K5P(8);

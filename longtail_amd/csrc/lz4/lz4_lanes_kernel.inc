@@ -12,8 +12,8 @@
 // ---------------------------------------------------------------------------------------------------
 constexpr uint32_t LZ4_HALF_NONE = 0xFFFFFFFFu;
 constexpr uint32_t LZ4_HALF_HIST = 0x40000000u; // on an item's first half: staged as HISTORY of the second, not parsed (k_lz4_pair_halves, hist)
-// worklist layout behind the classification pass (ngroups = groups of the batch): [0 .. ngroups] unused (round 4's list of the noted
-// groups; nobody writes or reads them, the offsets behind them are kept), [1 + ngroups ..) per-group half bits, [2 ngroups + 1] ticket, [2 ngroups + 2] items, [2 ngroups + 3] lone halves,
+// worklist layout behind the classification pass (ngroups = groups of the batch): [0 .. ngroups] the blocks' counts of units with a
+// sequence and the stitch's work count (k_lz4.hip, lz4_seq_units), [1 + ngroups ..) per-group half bits, [2 ngroups + 1] ticket, [2 ngroups + 2] items, [2 ngroups + 3] lone halves,
 // [2 ngroups + 4 ..) items of four words {half a, half b, block of a, block of b} (up to two per group), [10 ngroups + 4 ..) lone halves
 __host__ __device__ constexpr uint32_t lz4_items_off(uint32_t ngroups) { return (2u * ngroups + 4u + 3u) & ~3u; } // (16-byte aligned: items are read as uint4)
 __device__ __forceinline__ uint32_t lz4_block_of_group(const Lz4Block* __restrict__ blocks, uint32_t nblocks, uint32_t grp)
@@ -104,6 +104,10 @@ __global__ __launch_bounds__(64 * LZ4_G_LANES, 4) void k_lz4_lanes2(const uint8_
                                                        uint32_t ngroups, uint32_t* __restrict__ worklist, uint32_t farlog)
 {
     constexpr int G = LZ4_G_LANES, TAB = LZ4_TAB_SHARED, SH = LZ4_SH_LOG2;
+    // no item (incompressible data): every wave leaves on this one scalar load, before any LDS access and any barrier
+    const uint32_t nitems = worklist[2u * ngroups + 2u];
+    if (nitems == 0u)
+        return;
     const uint32_t far1 = 1u << (farlog & 31u), far2 = 1u << ((farlog >> 8) & 31u), far3 = (farlog >> 16) & 255u; // (zstd flavour: lz4_lane_parse2; far3 = bytes a match into the history half must have)
     constexpr bool PAD = true;
     constexpr uint32_t GAP = 32u; // LDS bytes between the windows of two unlinked halves
@@ -120,7 +124,6 @@ __global__ __launch_bounds__(64 * LZ4_G_LANES, 4) void k_lz4_lanes2(const uint8_
     uint32_t* shr = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(smem) + data_bytes + 16u + (size_t)G * TAB * 2);
     constexpr uint32_t SH_BYTES = 4u << SH;
     const uint32_t* items = worklist + lz4_items_off(ngroups);
-    const uint32_t nitems = worklist[2u * ngroups + 2u];
     const uint32_t half_bytes = (uint32_t)(G / 2) * sub_bytes;
     K5P_DECL
     uint32_t sh_gen = 0;
@@ -350,6 +353,8 @@ __global__ __launch_bounds__(64 * LZ4_G_LANES, 4) void k_lz4_lanes2(const uint8_
                 m.first_lit_len = st.first_lit;
                 m.first_hdr_bytes = st.first_hdr;
                 meta[unit] = m;
+                if (st.op != 0u) // (the block's count of units with a sequence: k_lz4.hip, lz4_seq_units)
+                    (void)__hip_atomic_fetch_add(lz4_seq_units(worklist, blk.grp_base), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         K5P(8);

@@ -26,8 +26,9 @@ __global__ __launch_bounds__(64) void k_lz4_stitch_scan(const Lz4Block* __restri
                                                         const Lz4Meta* __restrict__ meta, Lz4Plan* __restrict__ plan,
                                                         uint32_t* __restrict__ runs, Lz4BlockOut* __restrict__ bout,
                                                         uint32_t* __restrict__ out_sizes, uint8_t* __restrict__ dst, uint32_t spec,
-                                                        uint32_t* __restrict__ worklist /* [0] = count, then group ids, then (from 1 + wl_cap) their blocks */,
-                                                        uint32_t wl_cap)
+                                                        uint32_t* __restrict__ worklist /* from [1]: group ids, then (from 1 + wl_cap) their blocks */,
+                                                        uint32_t wl_cap, uint32_t* wl_count /* how many */,
+                                                        const uint32_t* seq_units /* lz4_seq_units, or null: every block is walked */)
 {
     const uint32_t b = blockIdx.x + b0;
     if (b >= nblocks)
@@ -38,15 +39,22 @@ __global__ __launch_bounds__(64) void k_lz4_stitch_scan(const Lz4Block* __restri
     uint64_t out_pos = 0; // 64-bit: pathological inputs are caught against dst_cap at the end
     uint32_t carry = 0;
     uint32_t run = 0;
+    // A block none of whose units holds a sequence (incompressible data) was laid out by the match finder (spec) and is one literal run:
+    // what the walk would end with -- no run closed, nothing put out, every byte carried -- is known without it, and its units' records
+    // are not even loaded.  Such a block's plan[] is not written; nobody reads it (the copy kernel visits listed groups only).
+    const bool plain = seq_units && spec && blk.nseg != 0u && seq_units[blk.grp_base] == 0u;
+    const uint32_t nwalk = plain ? 0u : blk.nseg;
+    if (plain)
+        carry = blk.size;
     // The walk is a recurrence over (literal carry, output position, run count), restated as three wave scans per 64
     // units so that no step is serial:  a unit WITH a match resets the carry to its tail literals, one without adds its
     // length (segmented inclusive scan);  only units with a match advance the output (prefix sum of token + length
     // bytes + literals + body, all functions of the carry that reaches them) and close a run (prefix count).
     Lz4Meta m;
     m.seq_bytes = m.tail_lits = m.first_lit_len = m.first_hdr_bytes = 0;
-    if ((uint32_t)lane < blk.nseg)
+    if ((uint32_t)lane < nwalk)
         m = meta[blk.seg_base + (uint32_t)lane];
-    for (uint32_t i0 = 0; i0 < blk.nseg; i0 += 64)
+    for (uint32_t i0 = 0; i0 < nwalk; i0 += 64)
     {
         const uint32_t i = i0 + (uint32_t)lane;
         const Lz4Meta cur = m;
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(64) void k_lz4_stitch_scan(const Lz4Block* __restri
         {
             uint32_t base = 0;
             if (lane == 0)
-                base = atomicAdd(worklist, blk.ngrp);
+                base = atomicAdd(wl_count, blk.ngrp);
             base = __builtin_amdgcn_readfirstlane(base);
             for (uint32_t k = lane; k < blk.ngrp; k += 64)
             {
@@ -175,10 +183,14 @@ __global__ __launch_bounds__(K6_THREADS) void k_lz4_stitch_copy(const uint8_t* _
                                                                  const uint32_t* __restrict__ runs,
                                                                  const Lz4BlockOut* __restrict__ bout,
                                                                  uint8_t* __restrict__ dst, const uint32_t* __restrict__ worklist,
-                                                                 uint32_t gunits /* units per window group */, uint32_t wl_cap)
+                                                                 uint32_t gunits /* units per window group */, uint32_t wl_cap,
+                                                                 const uint32_t* __restrict__ wl_count)
 {
+    // nothing listed (no block of the batch has a match): every workgroup leaves on this one scalar load
+    const uint32_t nwork = *wl_count;
+    if (nwork == 0u)
+        return;
     const int tid = threadIdx.x;
-    const uint32_t nwork = worklist[0];
     (void)nblocks;
   for (uint32_t wi = blockIdx.x; wi < nwork; wi += gridDim.x)
   {
