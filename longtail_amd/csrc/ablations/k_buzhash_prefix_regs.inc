@@ -14,13 +14,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_buzhash_prefix(const uint8_t*
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    uint32_t* rows = smem + 256 * TAB_REP + wave * (WROWS * ROW_DW + HALO_DW); // this wave's [WROWS][ROW_DW] + halo suffixes
+    uint32_t* rows = smem + TAB_DW + wave * (WROWS * ROW_DW + HALO_DW); // this wave's [WROWS][ROW_DW] + halo suffixes
     uint32_t* halo = rows + WROWS * ROW_DW;
     prefix_table_init(smem, tid, 64 * WAVES);
 
     const uint32_t rows_byte = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)rows;
     PrefixConsts pc;
-    pc.lane4 = (uint32_t)lane * 4u;
     pc.hj = 63u - (uint32_t)lane;
     pc.halo_byte = rows_byte + WROWS * ROW_DW * 4u;
     pc.thr = MODE == 1 ? 0u : 0xFFFFFFFFu / (dv.d >> dv.k2);

@@ -1,6 +1,8 @@
 // k_buzhash_roll.inc -- part of k_buzhash.hip, compiled by the ablation build only (-DLTHIP_ABLATIONS, `make ablations`):
 // an earlier formulation kept as a second implementation for differential tests and A/B runs; not in the product library.
 
+constexpr int TAB_REP = 64;                  // this kernel's own table: T[v] replicated once per lane, 256 bytes apart: a lookup address is
+                                             // {byte, lane * 4} = ONE v_perm_b32 of the data dword, and never conflicts
 constexpr int K1_WAVES = 12;                 // one workgroup per CU: 3 waves per SIMD, <= 168 VGPRs each (16 waves at 128 VGPRs spill and gain nothing: measured; the rolling-window kernel)
 constexpr int K1_THREADS = 64 * K1_WAVES;
 constexpr int WVECS = WROWS * 4;         // 260 16-byte vectors per wave-tile

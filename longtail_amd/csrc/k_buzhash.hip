@@ -8,8 +8,13 @@
 //                           straight from global memory into the wave's LDS buffer (global_load_lds_dwordx4), every lane
 //                           keeps the SUFFIX XORs of its own 64-byte run in registers (prefix-XOR formulation: one table
 //                           look-up per byte, no 48-byte warm-up; the neighbour's suffixes through one v_xor_b32_dpp).
-//                           T[256] is replicated 64x in LDS with a 256-byte stride (one copy per lane): the LDS address of
-//                           T[b] is {lane*4, b} = ONE v_perm_b32 of the data dword, and lookups never conflict.
+//                           The LDS table holds T[256] in all 32 rotations, R[r][v] = rotr(T[v], r) at byte r * 1024 + v * 4
+//                           (32 KiB): the look-up of the byte at run position j reads R[j mod 32] -- the address is ONE SDWA
+//                           shift of the data dword (byte << 2), the row is the instruction's offset field, and the word
+//                           arrives rotated into the de-rotated frame.  One copy means bank = v mod 32: look-ups of
+//                           different bytes can conflict (random bytes: ~3.2 LDS cycles per 32 lanes instead of 1, at
+//                           most 8), which the LDS array has the room for; the rotate they save was a VALU instruction
+//                           per byte of an issue-bound kernel (profiles/buzhash_rot_table_ab.txt).
 //                           `H % d == d-1` is a necessary test on the odd part of d accumulated over eight steps, the exact
 //                           multiply-add + rotate + compare only in the rare wave-uniform branch.  Output is a two level
 //                           bitmap: level 0 one bit per byte (only non-zero words are stored), level 1 one bit per 64-byte
@@ -35,8 +40,8 @@ __constant__ uint32_t c_buztab[256] = {
 constexpr int RUN = 64;                      // bytes per thread
 constexpr int TILE = 256 * RUN;              // 16 KiB: the plan's tile (four wave-tiles)
 constexpr int ROW_DW = 17;                   // 16 data dwords + 1 pad: thread-strided ds_read_b32 hits 32 distinct banks
-constexpr int TAB_REP = 64;                  // T[v] replicated once per lane, 256 bytes apart: a lookup address is
-                                             // {byte, lane * 4} = ONE v_perm_b32 of the data dword, and never conflicts
+constexpr int TAB_ROT = 32;                  // the table holds every rotation: R[r][v] = rotr(T[v], r) at LDS dword r * 256 + v
+constexpr int TAB_DW = TAB_ROT * 256;        // 32 KiB, one copy: bank = v mod 32, so a look-up can conflict (at most 8 values a bank)
 
 // 32-bit load from a raw LDS byte address (the device pass only: LDS pointers are 32 bits wide there)
 __device__ __forceinline__ uint32_t lds_load_u32(uint32_t byte_addr)
@@ -125,7 +130,13 @@ constexpr int WTILE = 64 * RUN;          // 4 KiB
 // k = 63 down, so a register's own use (step j-1) precedes its use by the neighbour (step j-17) -- where wave_ror:1
 // hands them to lane 0.  The cut test is accumulated: y = H*inv + inv (<= qodd iff the odd part of d divides H+1) of
 // eight steps goes through v_min3_u32, one compare and one scalar branch per eight bytes; the exact test only in the
-// rare branch.  ~8.4 VALU instructions per byte and lane instead of 11.5, 64 + 16 live values instead of 112 + 28.
+// rare branch.  U[q] is not computed: q0 is a multiple of 64 in the tile's frame, so the rotation of the byte at run position j is the
+// constant j mod 32, and the LDS table holds T in all 32 rotations, R[r][v] = rotr(T[v], r) at byte r * 1024 + v * 4 -- the
+// look-up's address is byte << 2 (one SDWA shift of the data dword), its row the offset field of the ds_read_b32, and pass A is
+// one XOR per byte.  (A tile of the walking scans starts at a multiple of 16 of its part, not of 64: the frame is the tile's, and
+// H comes out the same, since rotl(U[p-1-j], p-1) = rotl(T[b], j) whatever q0 is counted from.)
+// ~7.4 VALU instructions per byte and lane (8.4 with the rotate of the look-up in pass A, 11.5 for the rolling window), 64 + 16
+// live values instead of 112 + 28.
 // ---------------------------------------------------------------------------------------------------
 #ifndef K1_MAD64
 #define K1_MAD64 0 // measured: 5.88 against 5.76 ms per 16 GiB -- not kept
@@ -134,12 +145,34 @@ constexpr int HALO_DW = 64; // per wave: suffix XORs of the halo row, dword j = 
 
 struct PrefixConsts
 {
-    uint32_t lane4;     // lane * 4: low byte of a look-up address
     uint32_t hj;        // the halo byte this lane looks up (63 - lane)
     uint32_t halo_byte; // LDS byte address of the wave's halo[] array
     uint32_t thr;       // y <= thr is necessary for a cut
     uint32_t exact_add; // H*inv + addc = y + exact_add
 };
+
+// LDS byte address of R[j mod 32][byte j of the run]: byte << 2 is ONE SDWA shift of the data dword (left to the compiler, byte 0 of
+// a dword costs a shift and an and), the row is a constant that the load takes into its offset field
+// (j is a constant of the caller's unrolled loop)
+__device__ __forceinline__ uint32_t prefix_lookup(uint32_t w, int j)
+{
+    uint32_t a = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LT_BYTE4(n) asm("v_lshlrev_b32_sdwa %0, 2, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_" #n : "=v"(a) : "v"(w))
+    if ((j & 3) == 0)
+        LT_BYTE4(0);
+    else if ((j & 3) == 1)
+        LT_BYTE4(1);
+    else if ((j & 3) == 2)
+        LT_BYTE4(2);
+    else
+        LT_BYTE4(3);
+#undef LT_BYTE4
+#else
+    (void)w;
+#endif
+    return lds_load_u32(a + (uint32_t)(j & 31) * 1024u);
+}
 
 // One wave-tile: win[] = the lane's own 64-byte run, hb = the lane's halo byte (byte 63 - lane of the 64 bytes before the
 // tile; lanes >= 47 are ignored).  Returns the 64 candidate bits of the run, bit k <=> cut position q0 + k + 1.
@@ -149,8 +182,7 @@ __device__ __forceinline__ uint64_t prefix_tile(const uint32_t (&win)[16], uint3
 {
     // ---- halo: S'[j] for j = 17..63 by a wave scan, to LDS ----
     {
-        uint32_t x = lds_load_u32((hb << 8) | pc.lane4);
-        x = rotr32(x, pc.hj);
+        uint32_t x = lds_load_u32(((pc.hj & 31u) << 10) + (hb << 2)); // R[hj mod 32][hb]
         if (lane >= 47)
             x = 0u;
         // inclusive XOR scan over the lanes: lane i gets the bytes 63-i .. 63 = S'[63 - i]
@@ -165,16 +197,14 @@ __device__ __forceinline__ uint64_t prefix_tile(const uint32_t (&win)[16], uint3
 
     // ---- pass A: suffix XORs of the lane's own run ----
     uint32_t S[65];
-#define LT_LOOKUP(j) S[j] = lds_load_u32(__builtin_amdgcn_perm(win[(j) >> 2], pc.lane4, 0x0c0c0400u | ((uint32_t)((j) & 3) << 8)))
 #pragma unroll
     for (int j = 63; j >= 0; --j)
-        LT_LOOKUP(j);
-#undef LT_LOOKUP
+        S[j] = prefix_lookup(win[j >> 2], j); // R[j mod 32][b_j] = U[q0 + j]
     __builtin_amdgcn_sched_barrier(0);
     S[64] = 0u;
 #pragma unroll
     for (int j = 63; j >= 0; --j)
-        S[j] = S[j + 1] ^ ((j & 31) ? rotr32(S[j], (uint32_t)(j & 31)) : S[j]);
+        S[j] ^= S[j + 1]; // the words come rotated: no rotate here
     __builtin_amdgcn_wave_barrier(); // halo[] written by all lanes, read by lane 63 below
 
     // ---- pass B: eight steps per group, from the top ----
@@ -324,18 +354,11 @@ __device__ __forceinline__ uint64_t prefix_legal(uint64_t m, uint64_t q0, uint64
 
 __device__ __forceinline__ void prefix_table_init(uint32_t* tab, int tid, int nthreads)
 {
-    for (int v = tid; v < 256; v += nthreads)
-    {
-        const uint32_t tv = c_buztab[v];
-        uint4 q = make_uint4(tv, tv, tv, tv);
-        uint4* dst = reinterpret_cast<uint4*>(tab + v * TAB_REP);
-#pragma unroll
-        for (int j = 0; j < TAB_REP / 4; ++j)
-            dst[j] = q;
-    }
+    for (int i = tid; i < TAB_DW; i += nthreads) // R[r][v] = rotr(T[v], r) at dword r * 256 + v
+        tab[i] = rotr32(c_buztab[i & 255], (uint32_t)i >> 8);
     __syncthreads(); // the only barrier: table visible to every wave
     if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t*)tab != 0u)
-        __builtin_trap(); // a look-up address is the v_perm result itself (see k_buzhash_candidates)
+        __builtin_trap(); // a look-up address is byte * 4 plus the row in the offset field: no base add
 }
 
 #ifdef LTHIP_ABLATIONS
@@ -355,7 +378,6 @@ constexpr int DMA_BUF_B = WROWS * 64; // 4160 bytes, linear
 
 // The dynamic LDS of the kernels fed by LDS-DMA, in dwords: the table, then per wave its tile buffer and its halo[]; behind them, in the
 // walking scan that hashes, per wave a pending list of PEND_CAP chunks (uint4 each).  Kernels and launchers read the layout from here.
-constexpr int TAB_DW = 256 * TAB_REP;
 constexpr int DMA_WAVE_DW = (DMA_BUF_B >> 2) + HALO_DW;
 constexpr int PEND_CAP = 64;
 constexpr size_t lds_tiles_dw(int waves) { return TAB_DW + (size_t)waves * DMA_WAVE_DW; }
@@ -404,7 +426,6 @@ struct TileDma
     __device__ __forceinline__ PrefixConsts consts(const DivTest& dv) const
     {
         PrefixConsts pc;
-        pc.lane4 = (uint32_t)lane * 4u;
         pc.hj = 63u - (uint32_t)lane;
         pc.halo_byte = buf_byte + DMA_BUF_B;
         pc.thr = MODE == 1 ? 0u : 0xFFFFFFFFu / (dv.d >> dv.k2);
@@ -1202,7 +1223,7 @@ static int launch_buzhash_prefix(lthip_ctx* ctx, const lthip_plan* plan, const u
 {
     static_assert(DMA || K1_HAS_REG_FLAVOUR, "the register-staged flavour is compiled by the ablation build only");
     // (the register-staged flavour: padded rows in place of the linear buffer, ablations/k_buzhash_prefix_regs.inc)
-    constexpr size_t lds = DMA ? lds_bytes(WAVES, false) : sizeof(uint32_t) * (256 * TAB_REP + WAVES * (WROWS * ROW_DW + HALO_DW));
+    constexpr size_t lds = DMA ? lds_bytes(WAVES, false) : sizeof(uint32_t) * (TAB_DW + WAVES * (WROWS * ROW_DW + HALO_DW));
     static_assert(lds <= 160 * 1024, "LDS budget: one workgroup per CU");
 #ifdef LTHIP_ABLATIONS
     auto k0 = DMA ? &k_buzhash_prefix_dma<0, WAVES> : &k_buzhash_prefix<0, WAVES>;
